@@ -2,18 +2,23 @@
 """bench.py -- SR training images/sec of the MI355X-native hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload g_only|gan|aesrgan_gan] [--batch B] [--lr-size S]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one training iteration of the reference (``train()`` body) on one synthetic batch that is
-already resident in HBM.  Default run = BASELINE.json configs[1] AND configs[2] in one process: the headline fields are the
-BSRGAN RRDBNet x4 (23 RRDB) generator-only step (L1 pixel loss, batch 32 per GPU, 128x128 -> 512x512, 16-bit MFMA with fp32 master
-weights, Adam + EMA inside the timed region); the object under ``"gan"`` is the full GAN step of train_bsrgan.py:387-483 (U-Net
-discriminator + VGG-19 content loss, same batch) timed the same way right after it (``--workload g_only`` / ``gan`` time one only).
+already resident in HBM.  Default run = BASELINE.json configs[1]: the headline fields are the BSRGAN RRDBNet x4 (23 RRDB)
+generator-only step (L1 pixel loss, batch 32 per GPU, 128x128 -> 512x512, 16-bit MFMA with fp32 master weights, Adam + EMA inside
+the timed region), and nothing else is measured.  ``--full`` adds everything else the benchmark measures: configs[2] in the same
+process -- the object under ``"gan"`` is the full GAN step of train_bsrgan.py:387-483 (U-Net discriminator + VGG-19 content loss,
+same batch) timed the same way right after the headline -- plus the per-kernel roofline, the module-level and bf16 legs, the SR
+parity figure and the CPU baseline listed below (``--workload g_only`` / ``gan`` time one only, ``--workload both`` both).
+``--dump-outputs DIR`` writes what the headline's last timed step computed (step output, SR batch, updated weights and EMA copy;
+a fixed seeded sample of each large array) as DIR/<name>.npy in float32, for output-by-output comparisons of two builds.
 N > 1: one process per GPU, weak scaling (batch 32 per GPU), one RCCL all-reduce of the flat gradient per network and step.  Under
 torchrun (RANK / WORLD_SIZE set) the process is one rank; WITHOUT them ``--gpus N`` starts the N ranks itself -- fresh child
 processes through torch.distributed.run, before this process has touched a GPU -- and exits non-zero if fewer than N GPUs are
 visible.  ``--workload aesrgan_gan`` = configs[4] per GPU (RRDBNet + A-ESRGAN attention U-Net discriminator, 192 -> 768).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields plus, with ``--full``,
   roofline     -- dominant kernel class (largest total time) from HIP-event brackets around its launches in the timed
                   region, against the roof its arithmetic intensity puts it under: algorithmic bytes / time vs the
                   8 TB/s HBM peak when FLOP/byte is below the ridge (312), else algorithmic FLOP / time vs the dense
@@ -180,8 +185,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--workload", default="both", choices=["both", "g_only", "gan", "aesrgan_gan", "esrgan_gan", "realesrgan_gan"],
-                    help="both (default) = configs[1] generator-only as the headline + configs[2] full GAN step under \"gan\"")
+    ap.add_argument("--workload", default=None, choices=["both", "g_only", "gan", "aesrgan_gan", "esrgan_gan", "realesrgan_gan"],
+                    help="default g_only (configs[1]); with --full, both = configs[1] generator-only as the headline + configs[2] full GAN "
+                         "step under \"gan\"")
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
     ap.add_argument("--esrgan-module-loop", action="store_true", help="esrgan_gan: run the script's own autograd loop over the drop-in modules instead of the fused trainer")
     ap.add_argument("--lr-size", type=int, default=0, help="LR image side (default 128; 192 for aesrgan_gan)")
@@ -193,15 +199,24 @@ def main():
                          "reference's amp.autocast() computes in and the mode whose SR meets the 1e-3 tolerance (with its GradScaler)")
     ap.add_argument("--module-loop", action="store_true",
                     help="g_only / gan: time the reference's own loop statements (torch.optim.Adam, AveragedModel, amp.autocast + GradScaler, "
-                         "autograd) over the drop-in modules instead of the fused trainer; the default run reports both")
-    ap.add_argument("--no-module-loop", action="store_true", help="default run: skip the module-level legs under \"extra\"")
+                         "autograd) over the drop-in modules instead of the fused trainer; the --full run reports both")
+    ap.add_argument("--no-module-loop", action="store_true", help="--full run: skip the module-level legs under \"extra\"")
     ap.add_argument("--dropin-optim", action="store_true", help="--module-loop with sr_gan_fd_amd.optim.Adam / swa_utils.AveragedModel behind the scripts' names")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bf16", action="store_true", help="default run: skip the bf16 leg (\"bf16\" sub-object)")
+    ap.add_argument("--no-bf16", action="store_true", help="--full run: skip the bf16 leg (\"bf16\" sub-object)")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (nccl = RCCL; gloo only to rehearse the multi-rank path on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the GAN step (default workload both), per-kernel roofline, "
+                         "module-level and bf16 legs, SR parity and CPU baseline (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed as DIR/<name>.npy (float32; seeded sample of large arrays)")
     args = ap.parse_args()
+    if args.workload is None:
+        args.workload = "both" if args.full else "g_only"
+    if not args.full:
+        args.no_kernel_events = True     # the per-kernel event brackets feed the roofline object only
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -234,13 +249,15 @@ def main():
             raise SystemExit("bench.py: all-reduce of ones gave %d, world size %d" % (int(ones.item()), world))
 
     workloads = ["g_only", "gan"] if args.workload == "both" else [args.workload]
-    results = [run_workload(args, wl, rank, world, dev, pg, module_loop=args.module_loop, dropin_optim=args.dropin_optim) for wl in workloads]
+    # --dump-outputs: the headline (first) workload's last timed step only
+    results = [run_workload(args, wl, rank, world, dev, pg, module_loop=args.module_loop, dropin_optim=args.dropin_optim,
+                            dump_dir=args.dump_outputs if i == 0 else None) for i, wl in enumerate(workloads)]
     out = results[0]
     if len(results) > 1 and rank == 0:
         out["gan"] = {k: results[1][k] for k in ("value", "unit", "ms_per_step", "config", "step_tflops_per_gpu", "loss_scale", "last_step_scalars", "roofline", "kernel_classes",
                                                  "exposed_comm_ms_per_step")
                       if k in results[1]}
-    if args.workload == "both" and world == 1 and not args.module_loop and not args.no_module_loop:
+    if args.full and args.workload == "both" and world == 1 and not args.module_loop and not args.no_module_loop:
         # the module-level (drop-in) path next to the fused trainers: the reference's loop statements over the mirror modules, a short
         # timed region of its own (train_bsrnet.py:244-272, train_bsrgan.py:387-483)
         import copy
@@ -267,7 +284,7 @@ def main():
                         "what": "the reference's loop statements (amp.autocast + GradScaler, torch.optim.Adam, AveragedModel, autograd) over the drop-in "
                                 "modules with nothing set on them; with_dropin_optim_and_ema = the same statements with sr_gan_fd_amd.optim.Adam / "
                                 "sr_gan_fd_amd.swa_utils.AveragedModel behind the scripts' names; the headline fields are the fused trainers"}
-    if args.workload == "both" and world == 1 and not args.module_loop and args.dtype == "f16" and not args.no_bf16:
+    if args.full and args.workload == "both" and world == 1 and not args.module_loop and args.dtype == "f16" and not args.no_bf16:
         # BASELINE.json's metric string names bf16; the reference's autocast computes in f16, which is what the headline runs (bf16 misses the
         # 1e-3 SR tolerance).  The same generator-only step in bf16, a short timed region of its own, with its own SR parity figure.
         import copy
@@ -281,7 +298,7 @@ def main():
             out["bf16"]["sr_parity"] = sr_parity(args.lr_size or BASE_LR_SIZE["g_only"], args.num_rrdb, dev, "bf16")
     if rank == 0:
         h = args.lr_size or BASE_LR_SIZE[workloads[0]]
-        if not args.no_cpu_baseline and world == 1:      # host-side legs: rank 0 of the single-GPU run only
+        if args.full and not args.no_cpu_baseline and world == 1:      # host-side legs: rank 0 of the single-GPU run only
             out["sr_parity"] = sr_parity(h, args.num_rrdb, dev, args.dtype)
             out["cpu_baseline"] = cpu_baseline(workloads[0], h, args.num_rrdb)
             if len(results) > 1:
@@ -294,8 +311,9 @@ def main():
 DTYPES = {"f16": "float16", "bf16": "bfloat16", "f32": "float32"}
 
 
-def run_workload(args, workload, rank, world, dev, pg, module_loop=False, dropin_optim=False):
-    """W warm-up steps, then exactly K timed steps between barrier + synchronize on both sides; max over ranks."""
+def run_workload(args, workload, rank, world, dev, pg, module_loop=False, dropin_optim=False, dump_dir=None):
+    """W warm-up steps, then exactly K timed steps between barrier + synchronize on both sides; max over ranks.  ``dump_dir``: rank 0
+    writes the last timed step's outputs there (dump_outputs), before anything else runs on the trainer."""
     import torch
     import torch.distributed as dist
     from sr_gan_fd_amd import model as M
@@ -406,6 +424,8 @@ def run_workload(args, workload, rank, world, dev, pg, module_loop=False, dropin
         dt = t.item()
     ms_per_step = dt / args.steps * 1e3
     value = B * world * args.steps / dt
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, last, trainer, g)
 
     out = {
         "metric": "SR training images/sec (%d->%d x%d, %s)" % (h, S * h, S, args.dtype), "value": round(value, 3), "unit": "img/s",
@@ -480,6 +500,47 @@ def run_workload(args, workload, rank, world, dev, pg, module_loop=False, dropin
     gc.collect()
     torch.cuda.empty_cache()
     return out
+
+
+DUMP_MAX_ELEMS = 1 << 21     # per array (8 MB in float32): at most five arrays per workload keeps a dump under 64 MB
+
+
+def dump_outputs(out_dir: str, last, trainer, g) -> None:
+    """What a caller of the timed path holds after its last step, as ``out_dir/<name>.npy`` (float32; float64 stays float64):
+    ``step_output`` (the step's return: the loss, or the GAN step's logged scalars), ``sr`` (the step's SR batch), ``g_params`` /
+    ``g_ema`` / ``d_params`` (the flat fp32 parameter buffers the optimizers updated, and the generator's EMA copy).  An array of more
+    than DUMP_MAX_ELEMS elements is replaced by a fixed sample of that many: positions drawn (sorted, with replacement) from a CPU
+    generator seeded by the array's name, so the same arguments give the same positions in every run and every build."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = {}
+    if torch.is_tensor(last):
+        arrays["step_output"] = last
+    if torch.is_tensor(getattr(trainer, "sr", None)):
+        arrays["sr"] = trainer.sr
+    for attr, net in (("opt", "g"), ("g_opt", "g"), ("d_opt", "d")):
+        opt = getattr(trainer, attr, None)
+        if opt is not None:
+            arrays[net + "_params"] = opt.flat
+            if opt.ema is not None:
+                arrays[net + "_ema"] = opt.ema
+    if trainer is None:          # the module-level loops: the generator's parameters in named_parameters() order
+        arrays["g_params"] = torch.cat([p.detach().reshape(-1).float() for p in g.parameters()])
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(n, (DUMP_MAX_ELEMS,), generator=gen).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+        log("dumped %s: %d of %d elements" % (name, a.size, n))
+    assert total <= 64 << 20, total
 
 
 def module_level_loop(workload, M, g, dev, cdt, dropin_optim=False):

@@ -1,10 +1,12 @@
 """bench.py end to end on the GPU box: the self-launch path (--gpus N without torchrun's environment starts N ranks before any
-GPU call), the JSON contract of the single line rank 0 prints, and the refusal to report n_gpus it does not have."""
+GPU call), the JSON contract of the single line rank 0 prints, the refusal to report n_gpus it does not have, the lean plain run
+(the headline only) against --full, and --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +29,7 @@ def _line(out):
 def test_bench_self_launches_two_ranks_over_gloo():
     """--gpus 2 with no WORLD_SIZE: two child ranks (sharing the box's one GPU, gloo collectives), one line, n_gpus == 2,
     both workloads in it, weak scaling (global batch = 2 x per-GPU batch)."""
-    out = _run(["--gpus", "2", "--dist-backend", "gloo"] + SMALL)
+    out = _run(["--gpus", "2", "--dist-backend", "gloo", "--full"] + SMALL)
     assert out.returncode == 0, out.stderr[-3000:]
     r = _line(out)
     assert r["n_gpus"] == 2 and r["config"]["global_batch"] == 4 and r["config"]["parallelism"] == "dp2" and r["scaling"] == "weak"
@@ -52,7 +54,7 @@ def test_bench_two_ranks_over_rccl_through_the_driver_command():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + SMALL
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     r = _line(out)
@@ -84,8 +86,8 @@ def test_bench_single_gpu_line():
 
 
 def test_bench_default_line_carries_the_module_level_legs():
-    """the default run times the reference's loop statements over the drop-in modules beside the fused trainers"""
-    out = _run(SMALL)
+    """the --full run times the reference's loop statements over the drop-in modules beside the fused trainers"""
+    out = _run(["--full"] + SMALL)
     assert out.returncode == 0, out.stderr[-3000:]
     r = _line(out)
     ml = r["extra"]["module_loop"]
@@ -105,3 +107,33 @@ def test_bench_default_line_carries_the_module_level_legs():
     out = _run(["--workload", "gan", "--module-loop"] + SMALL)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "module-level" in _line(out)["config"]["loop"]
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain run times the generator-only headline and measures nothing else; --dump-outputs writes what its last timed step computed
+    (float arrays, under 64 MB), and the same arguments give the same inputs: the step is bitwise reproducible, so a second run dumps
+    identical arrays."""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    lines = []
+    plain = [a for a in SMALL if a != "--no-cpu-baseline"]
+    for d in dirs:
+        out = _run(plain + ["--dump-outputs", str(d)])
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(_line(out))
+    r = lines[0]
+    assert r["n_gpus"] == 1 and r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["unit"] == "img/s" and r["higher_is_better"] is True and r["dtype"] == "f16" and r["metric"].startswith("SR training images/sec")
+    assert r["config"]["workload"].startswith("BSRGAN RRDBNet x4 generator-only")
+    for k in ("gan", "roofline", "kernel_classes", "module_loop", "extra", "bf16", "sr_parity", "cpu_baseline"):
+        assert k not in r, k
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == ["g_ema.npy", "g_params.npy", "sr.npy", "step_output.npy"], names
+    total = 0
+    for name in names:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+        assert np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(dirs[0] / "sr.npy").shape == (2, 3, 64, 64)
+    assert abs(float(np.load(dirs[0] / "step_output.npy")[0]) - r["last_step_scalars"][0]) <= 1e-6

@@ -2,7 +2,7 @@
 # round-3 session 1: box baseline, workgroup-stagger experiment on the dense-block convs, L2 hit rate of the weight-gradient launch
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3_exp1; mkdir -p $O
 cd $R
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_g_only.json 2> $O/bench_g_only.err || exit 1
+python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_g_only.json 2> $O/bench_g_only.err || exit 1
 tail -c 600 $O/bench_g_only.json
 SRGANFD_LIB=$R/build_exp/libsrganfd_exp.so python tools/kbench.py --dtype f16 --modes 8 --dbg 0,384,640,1152,2176 --rounds 4 --reps 20 > $O/kbench_stagger.txt 2>&1 || { tail -5 $O/kbench_stagger.txt; exit 1; }
 cat $O/kbench_stagger.txt

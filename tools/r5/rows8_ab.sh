@@ -20,6 +20,6 @@ done
 # per-kernel view (HIP events per launch), once each
 for r8 in 0 auto; do
   echo "== layer classes, g_only batch 16 72 -> 288, CONV_ROWS8=$r8" >> $out
-  SRGANFD_CONV_ROWS8=$r8 timeout -k 10 300 python bench.py --workload g_only --batch 16 --lr-size 72 --steps 10 --warmup 3 --no-cpu-baseline --no-module-loop --no-bf16 2>/dev/null | line 6 >> $out || exit 1
+  SRGANFD_CONV_ROWS8=$r8 timeout -k 10 300 python bench.py --full --workload g_only --batch 16 --lr-size 72 --steps 10 --warmup 3 --no-cpu-baseline --no-module-loop --no-bf16 2>/dev/null | line 6 >> $out || exit 1
 done
 cat $out

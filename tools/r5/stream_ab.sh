@@ -2,7 +2,7 @@
 # conv_stream (LDS-DMA streaming conv, one persistent workgroup per CU) against conv_igemm at the reference-default shapes
 #   tools/r5/stream_ab.sh <out file>
 out=$1; : > $out
-run() { echo "== SRGANFD_USE_STREAM=$S $*" >> $out; SRGANFD_USE_STREAM=$S python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-module-loop --no-bf16 "$@" 2>/dev/null | python -c "
+run() { echo "== SRGANFD_USE_STREAM=$S $*" >> $out; SRGANFD_USE_STREAM=$S python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-module-loop --no-bf16 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('  %.3f ms/step  %.1f img/s' % (d['ms_per_step'], d['value']))

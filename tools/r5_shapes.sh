@@ -6,7 +6,7 @@
 # usage: tools/r5_shapes.sh <out file under gpurun_out>
 out=$1
 : > $out
-run() { echo "== $*" >> $out; python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-module-loop "$@" 2>/dev/null | python -c "
+run() { echo "== $*" >> $out; python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-module-loop "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({k:d[k] for k in ('metric','value','ms_per_step','step_tflops_per_gpu','config')}))
