@@ -363,12 +363,13 @@ def d_param_names(P: Params) -> List[str]:
 
 
 def g_only_step(G: Params, opt: AdamState, lr_img: Tensor, gt: Tensor, *, upscale: int, lr: float,
-                betas: Tuple[float, float], eps: float, loss_weight: float = 1.0) -> Tuple[float, Tensor]:
+                betas: Tuple[float, float], eps: float, loss_weight: float = 1.0, unshuffle: int = 1) -> Tuple[float, Tensor]:
     """Generator-only iteration -- ESRGAN/train_rrdbnet.py:244-267, BSRGAN/train_bsrnet.py:244-272.
-    (autocast / GradScaler are inert on CPU: SURVEY 8 preamble.)  Returns (loss, sr)."""
+    (autocast / GradScaler are inert on CPU: SURVEY 8 preamble.)  ``unshuffle``: rrdbnet_forward's (Real-ESRGAN below x4).
+    Returns (loss, sr)."""
     names = g_param_names(G)
     _leafify(G, names)
-    sr = rrdbnet_forward(lr_img, G, upscale)
+    sr = rrdbnet_forward(lr_img, G, upscale, unshuffle=unshuffle)
     loss = loss_weight * l1_mean(sr, gt)
     grads = torch.autograd.grad(loss, [G[k] for k in names])
     with torch.no_grad():
@@ -381,12 +382,12 @@ def g_only_step(G: Params, opt: AdamState, lr_img: Tensor, gt: Tensor, *, upscal
 def gan_step(G: Params, D: Params, g_opt: AdamState, d_opt: AdamState, lr_img: Tensor, gt: Tensor, *,
              upscale: int, g_lr: float, d_lr: float, betas: Tuple[float, float], eps: float,
              pixel_weight: float, content_weight: float, adversarial_weight: float,
-             content_fn=None, train_generator: bool = True, d_forward=None) -> Dict[str, float]:
+             content_fn=None, train_generator: bool = True, d_forward=None, unshuffle: int = 1) -> Dict[str, float]:
     """One GAN iteration -- BSRGAN/train_bsrgan.py:387-483 (same statements in A-ESRGAN/train_aesrgan.py:396-483;
     ``d_forward(x, D, training=True)`` selects the discriminator, default DiscriminatorUNet), exact order:
     D(gt) fwd+bwd, G fwd, D(sr.detach()) fwd+bwd (accumulate), D step, freeze D, pixel/content/adv
     with the UPDATED D (SN u/v advance a third time), G bwd + step.  content_fn(sr, gt) returns the
-    detached (1,5) tensor or None (-> 0)."""
+    detached (1,5) tensor or None (-> 0).  ``unshuffle``: rrdbnet_forward's (Real-ESRGAN below x4)."""
     gn, dn = g_param_names(G), d_param_names(D)
     discriminator_unet_forward = d_forward or globals()["discriminator_unet_forward"]
     _leafify(D, dn)
@@ -395,7 +396,7 @@ def gan_step(G: Params, D: Params, g_opt: AdamState, d_opt: AdamState, lr_img: T
     gt_out = discriminator_unet_forward(gt, D, training=True)
     d_loss_hr = bce_with_logits_mean(gt_out, 1.0)
     g_hr = torch.autograd.grad(d_loss_hr, [D[k] for k in dn])
-    sr = rrdbnet_forward(lr_img, G, upscale)
+    sr = rrdbnet_forward(lr_img, G, upscale, unshuffle=unshuffle)
     sr_out = discriminator_unet_forward(sr.detach().clone(), D, training=True)
     d_loss_sr = bce_with_logits_mean(sr_out, 0.0)
     g_sr = torch.autograd.grad(d_loss_sr, [D[k] for k in dn])
@@ -420,23 +421,23 @@ def gan_step(G: Params, D: Params, g_opt: AdamState, d_opt: AdamState, lr_img: T
         "d_loss": float(d_loss_hr + d_loss_sr), "pixel_loss": float(pixel), "content_loss": float(content),
         "adversarial_loss": float(adv),
         "d_gt_probability": float(torch.sigmoid(gt_out.detach()).mean()),
-        "d_sr_probability": float(torch.sigmoid(sr_out.detach()).mean()),
+        "d_sr_probability": float(torch.sigmoid(sr_out.detach()).mean()), "sr": sr.detach(),
     }
 
 
 def realesrgan_gan_step(G: Params, D: Params, g_opt: AdamState, d_opt: AdamState, lr_img: Tensor, gt: Tensor, gt_usm: Tensor, *,
                         upscale: int = 4, lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.99), eps: float = 1e-4,
                         pixel_weight: float = 1.0, content_weight=(0.1, 0.1, 1.0, 1.0, 1.0), adversarial_weight: float = 0.1,
-                        content_fn=None) -> Dict[str, float]:
+                        content_fn=None, unshuffle: int = 1) -> Dict[str, float]:
     """One iteration of Real_ESRGAN/train_realesrgan.py:407-476 (realesrgan_config.py:138-151): GENERATOR first -- pixel and
     (detached, logged-only) content loss against the USM-sharpened GT, adversarial BCE vs ones through the frozen D -- Adam
     step; then D(gt) and D(sr.detach()) forward+backward (gradients accumulate), Adam step.  Probabilities are
-    sigmoid(mean(logits)) (:475-476)."""
+    sigmoid(mean(logits)) (:475-476).  ``unshuffle``: rrdbnet_forward's (Real-ESRGAN below x4: 2 at x2, 4 at x1)."""
     gn, dn = g_param_names(G), d_param_names(D)
     _leafify(G, gn)
     for k in dn:
         D[k] = D[k].detach()
-    sr = rrdbnet_forward(lr_img, G, upscale)
+    sr = rrdbnet_forward(lr_img, G, upscale, unshuffle=unshuffle)
     pixel = pixel_weight * l1_mean(sr, gt_usm)
     content = content_fn(sr.detach(), gt_usm) if content_fn is not None else torch.zeros(1, 5)
     content = (torch.tensor(content_weight) * content).sum()
@@ -594,16 +595,16 @@ def content_loss_single(sr: Tensor, gt: Tensor, P: Params, node: str, mean: Sequ
 
 def esrgan_gan_step(G: Params, D: Params, g_opt: AdamState, d_opt: AdamState, lr_img: Tensor, gt: Tensor, *, upscale: int = 4,
                     lr: float = 1e-4, betas: Tuple[float, float] = (0.9, 0.99), eps: float = 1e-8, pixel_weight: float = 0.01,
-                    content_weight: float = 1.0, adversarial_weight: float = 0.005, content_fn=None) -> Dict[str, float]:
+                    content_weight: float = 1.0, adversarial_weight: float = 0.005, content_fn=None, unshuffle: int = 1) -> Dict[str, float]:
     """One iteration of ESRGAN/train_esrgan.py:364-431: GENERATOR first (D frozen; relativistic-average adversarial term
     built from D(gt.detach()) and D(sr), both in training mode so BatchNorm statistics advance), Adam step; then the
     discriminator: D(gt), D(sr.detach()), loss on gt_output - mean(sr_output) (backward with retain_graph), a THIRD forward
-    D(sr.detach()), loss on sr_output - mean(gt_output) (backward), Adam step."""
+    D(sr.detach()), loss on sr_output - mean(gt_output) (backward), Adam step.  ``unshuffle``: rrdbnet_forward's (Real-ESRGAN below x4)."""
     gn, dn = g_param_names(G), [k for k in D if k.endswith((".weight", ".bias"))]
     _leafify(G, gn)
     for k in dn:
         D[k] = D[k].detach()
-    sr = rrdbnet_forward(lr_img, G, upscale)
+    sr = rrdbnet_forward(lr_img, G, upscale, unshuffle=unshuffle)
     gt_output = esrgan_discriminator_forward(gt.detach().clone(), D, training=True)
     sr_output = esrgan_discriminator_forward(sr, D, training=True)
     pixel = pixel_weight * l1_mean(sr, gt)

@@ -40,6 +40,13 @@ def _require_gpu(x: Tensor) -> None:
     A.lib()
 
 
+def check_channels(what: str, x: Tensor, channels: int) -> None:
+    """Host-side input contract of an image-side engine, checked before anything is planned, allocated or launched: a 4-D NCHW tensor
+    with the channel count its first convolution reads (the boundary kernel reads N * channels * H * W elements of it)."""
+    if x.dim() != 4 or x.shape[1] != channels:
+        raise A.SrganfdError(f"{what} expects (N, {channels}, H, W) inputs, got shape {tuple(x.shape)}")
+
+
 def resolve_compute_dtype(module) -> torch.dtype:
     """The reference's precision contract for its modules: a forward issued inside ``torch.autocast("cuda")`` (the training loops'
     ``amp.autocast()``, train_bsrgan.py:415-427,450-457; ESRGAN's validation too, train_rrdbnet.py:324-325) computes in the autocast
@@ -199,10 +206,14 @@ class TrunkEngine:
         if self.Cc % 32 or self.G % 32:
             raise A.SrganfdError("channels and growth_channels must be multiples of 32 for the MFMA path")
         self.Ccat = self.Cc + 4 * self.G
+        self.unshuffle = 1
         if full:
             self.n_up = owner.n_upsample()
             self.in_ch = owner.conv1.weight.shape[1]
             self.out_ch = owner.conv4.weight.shape[0]
+            # Real-ESRGAN below x4 (Real_ESRGAN/model.py:190-204,248): PixelUnshuffle(2 / 4) in front of conv1, applied in forward() so
+            # that the module path and the fused trainers share it
+            self.unshuffle = getattr(owner, "unshuffle", 1)
         self.fp = FlatParams(list(owner.named_parameters()))
         self.shapes = PlanCache()
         self.packed: Dict[int, dict] = {}
@@ -512,14 +523,43 @@ class TrunkEngine:
         sp.wg_ws4 = [torch.empty(dense_ws, dtype=torch.uint8, device=device) for _ in range(_BATCH_REDUCE)] if (dense_ws and _BATCH_REDUCE > 1) else None
 
     # -- execution ----------------------------------------------------------------------------
+    def trunk_size(self, shape) -> Tuple[int, int, int]:
+        """The input shape contract, checked on the host before anything is planned, allocated or launched: the full generator takes
+        (N, in_ch / unshuffle^2, H, W) images with H and W multiples of the unshuffle factor, a stand-alone dense block (N, Cc, H, W)
+        feature maps.  Returns the (N, H, W) the dense blocks run at."""
+        shape = tuple(shape)
+        u = self.unshuffle
+        want_c = self.in_ch // (u * u) if self.full else self.Cc
+        what = "generator" if self.full else "dense block"
+        if len(shape) != 4:
+            raise A.SrganfdError(f"{what} expects a 4-D (N, {want_c}, H, W) input, got shape {shape}")
+        N, c, H, W = shape
+        if c != want_c:
+            raise A.SrganfdError(f"{what} expects (N, {want_c}, H, W) inputs, got shape {shape}")
+        if H % u or W % u:
+            raise A.SrganfdError(f"generator with PixelUnshuffle({u}) expects H and W divisible by {u}: (N, {want_c}, {u}k, {u}m), "
+                                 f"got shape {shape}")
+        return N, H // u, W // u
+
+    def output_shape(self, shape) -> Tuple[int, int, int, int]:
+        """Shape of what forward() returns for an input of ``shape`` (checked as trunk_size() does)."""
+        N, H, W = self.trunk_size(shape)
+        if not self.full:
+            return (N, self.Cc, H, W)
+        return (N, self.out_ch, H << self.n_up, W << self.n_up)
+
     def forward(self, x: Tensor, train: bool) -> Tensor:
         """x: NCHW fp32 (generator: image; trunk-only: feature map).  Returns NCHW fp32."""
+        N, H, W = self.trunk_size(x.shape)
         _require_gpu(x)
         dt, dtc = _dt(self.owner)
         dev = x.device
         pk = self._ensure_packed(dtc, dev)
-        N, _, H, W = x.shape
         sp = self._plan(N, H, W, dt, dtc, dev, train, pk)
+        if self.unshuffle > 1:
+            # a pure re-indexing of the image (no parameters, no arithmetic; the image needs no gradient): conv1 then reads 12 / 48
+            # channels (padded to 32 / 64 for the MFMA path) at the trunk's size
+            x = torch.nn.functional.pixel_unshuffle(x, self.unshuffle)
         x = x.contiguous().float()
         L, st = A.lib(), A.stream_ptr()
         if self.full:

@@ -25,7 +25,7 @@ from torch import Tensor, nn
 from . import _abi as A
 from . import ops
 from . import profiling
-from .engine import FlatParams, _dt, _engine, _require_gpu, _Shape, PlanCache
+from .engine import FlatParams, _dt, _engine, _require_gpu, _Shape, PlanCache, check_channels
 
 # (name, ksize, stride, pad) of the spectral-normalised convs, in forward order
 SN_LAYERS = [("conv1", 3, 2, 1), ("conv2", 3, 2, 1), ("conv3", 3, 2, 1), ("gating", 1, 1, 1), ("cat_1.convU", 3, 1, 1),
@@ -401,6 +401,7 @@ class AesrganDiscriminatorEngine:
             rec.bracket(profiling.conv_label(a), profiling.conv_work(a), lambda: A.check(L.srganfd_conv2d(C.byref(a), st), what))
 
     def forward(self, x: Tensor, training: bool) -> Tensor:
+        check_channels("UNetDiscriminatorAesrgan", x, self.in_ch)
         _require_gpu(x)
         dt, dtc = _dt(self.owner)
         dev = x.device

@@ -23,7 +23,7 @@ from torch import Tensor, nn
 from . import _abi as A
 from . import ops
 from . import profiling
-from .engine import FlatParams, _ENGINES, _dt, _engine, _require_gpu, _Shape, PlanCache
+from .engine import FlatParams, _ENGINES, _dt, _engine, _require_gpu, _Shape, PlanCache, check_channels
 
 SN_LAYERS = [("down_block1", 4, 2), ("down_block2", 4, 2), ("down_block3", 4, 2), ("up_block1", 3, 1),
              ("up_block2", 3, 1), ("up_block3", 3, 1), ("conv2", 3, 1), ("conv3", 3, 1)]
@@ -268,6 +268,7 @@ class DiscriminatorEngine:
 
     # ---- execution ----
     def forward(self, x: Tensor, training: bool) -> Tensor:
+        check_channels("DiscriminatorUNet", x, self.in_ch)
         _require_gpu(x)
         dt, dtc = _dt(self.owner)
         dev = x.device

@@ -25,7 +25,7 @@ from torch import Tensor, nn
 from . import _abi as A
 from . import ops
 from . import profiling
-from .engine import FlatParams, _dt, _engine, _require_gpu, _Shape, PlanCache
+from .engine import FlatParams, _dt, _engine, _require_gpu, _Shape, PlanCache, check_channels
 
 CONV_IDX = (0, 2, 5, 8, 11, 14, 17, 20, 23, 26)          # positions of the convs inside `features`
 SLOPE = 0.2
@@ -92,8 +92,6 @@ class EsrganDiscriminatorEngine:
         sp = self.shapes.get(key)
         if sp is not None:
             return sp
-        if H != 128 or W != 128:
-            raise A.SrganfdError("Discriminator expects 3x128x128 inputs: its classifier is Linear(512*4*4, 100) (ESRGAN/model.py:129)")
         sp = _Shape()
         sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
         V = A.view
@@ -217,6 +215,10 @@ class EsrganDiscriminatorEngine:
             rec.bracket(profiling.conv_label(a), profiling.conv_work(a), lambda: A.check(L.srganfd_conv2d(C.byref(a), st), what))
 
     def forward(self, x: Tensor, training: bool) -> Tensor:
+        check_channels("Discriminator", x, 3)
+        if tuple(x.shape[2:]) != (128, 128):
+            raise A.SrganfdError(f"Discriminator expects 3x128x128 inputs: its classifier is Linear(512*4*4, 100) (ESRGAN/model.py:129); "
+                                 f"got shape {tuple(x.shape)}")
         _require_gpu(x)
         dt, dtc = _dt(self.owner)
         dev = x.device

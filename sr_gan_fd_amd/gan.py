@@ -21,7 +21,8 @@ from .engine import generator_engine
 from .engine_a import aesrgan_engine
 from .engine_d import discriminator_engine
 from .parallel import BucketReducer, SideStreamReducer, SyncBatchNormReduce, allreduce_sum_
-from .trainer import FlatAdamEMA, GanCheckpointMixin, LossScaler, check_loss_scaling, needs_loss_scaling, pin_training_dtype
+from .trainer import (FlatAdamEMA, GanCheckpointMixin, LossScaler, check_loss_scaling, check_targets, needs_loss_scaling,
+                      pin_training_dtype)
 
 
 class GanTrainer(GanCheckpointMixin):
@@ -128,6 +129,7 @@ class GanTrainer(GanCheckpointMixin):
         """One iteration; returns the device tensor [d_loss_hr, d_loss_sr, pixel, adversarial, D(gt), D(sr), 0, 0]
         (no host synchronisation inside; content-loss values are in ``self.content_vals``).  ``gt_usm`` (generator-first
         mode): the sharpened GT the generator's pixel / content losses compare against; the discriminator sees ``gt``."""
+        check_targets("GanTrainer.step", self.ge, lr_img, gt=gt, gt_usm=gt_usm)
         if self.generator_first:
             return self._step_generator_first(lr_img, gt, gt_usm)
         if gt_usm is not None:

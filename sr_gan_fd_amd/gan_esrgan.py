@@ -26,7 +26,8 @@ from .engine import _engine, generator_engine
 from .engine_e import esrgan_discriminator_engine
 from .engine_v import ContentLossGradEngine
 from .parallel import BucketReducer, allreduce_sum_
-from .trainer import FlatAdamEMA, GanCheckpointMixin, LossScaler, check_loss_scaling, needs_loss_scaling, pin_training_dtype
+from .trainer import (FlatAdamEMA, GanCheckpointMixin, LossScaler, check_loss_scaling, check_targets, needs_loss_scaling,
+                      pin_training_dtype)
 
 
 class EsrganGanTrainer(GanCheckpointMixin):
@@ -73,6 +74,7 @@ class EsrganGanTrainer(GanCheckpointMixin):
 
     def step(self, lr_img: Tensor, gt: Tensor) -> Tensor:
         """One iteration; returns the device tensor [d_loss, pixel, content, adversarial, D(gt), D(sr), 0, 0] (no host synchronisation)."""
+        check_targets("EsrganGanTrainer.step", self.ge, lr_img, gt=gt)
         L, st = A.lib(), A.stream_ptr()
         ge, de = self.ge, self.de
         gt = gt.contiguous().float()

@@ -117,10 +117,7 @@ class _RRDBGenerator(nn.Module):
 
     def _forward_impl(self, x: Tensor) -> Tensor:
         from .engine import generator_apply
-        if getattr(self, "unshuffle", 1) > 1:
-            # a pure re-indexing of the input image (no parameters, no arithmetic; the input needs no gradient): torch's op, then the
-            # engine's conv1 reads 12 / 48 channels (padded to 32 / 64 for the MFMA path)
-            x = torch.nn.functional.pixel_unshuffle(x, self.unshuffle)
+        # below x4 the engine applies the PixelUnshuffle itself (engine.TrunkEngine.forward), for this path and the fused trainers alike
         return generator_apply(self, x)
 
 

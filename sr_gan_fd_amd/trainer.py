@@ -188,6 +188,17 @@ def check_loss_scaling(scaler: "LossScaler", *modules) -> None:
                              "its loss scaler is disabled (gradients would underflow) -- set the dtype first, then build the trainer")
 
 
+def check_targets(what: str, eng, lr_img: Tensor, **targets: Optional[Tensor]) -> None:
+    """The fused trainers' shape contract, checked on the host before the generator runs: every target (gt, gt_usm) has exactly the
+    shape the generator ``eng`` produces from ``lr_img`` (which output_shape() checks in turn).  The loss kernels read sr.numel()
+    elements of each target whatever its size."""
+    want = eng.output_shape(lr_img.shape)
+    for name, t in targets.items():
+        if t is not None and tuple(t.shape) != want:
+            raise A.SrganfdError(f"{what}: {name} has shape {tuple(t.shape)}, the generator produces {want} from lr_img of shape "
+                                 f"{tuple(lr_img.shape)}")
+
+
 class FlatAdamEMA:
     """torch.optim.Adam maths (amsgrad=False) + AveragedModel(avg_fn=(1-d)*ema + d*p) over one flat buffer."""
 
@@ -380,6 +391,7 @@ class GeneratorTrainer:
     def step(self, lr_img: Tensor, gt: Tensor) -> Tensor:
         """Returns the (device, 1-element) loss tensor; no host sync inside."""
         eng = self.eng
+        check_targets("GeneratorTrainer.step", eng, lr_img, gt=gt)
         sr = eng.forward(lr_img, True)
         sp, token = eng._last, eng.token
         if self.dsr is None or self.dsr.shape != sr.shape:

@@ -406,3 +406,191 @@ def test_multistep_lr_mirror_follows_torch_and_exchanges_state():
             mine2.step()
             ref2.step()
             assert abs(fused2.lr - fused.lr) < 1e-18 and abs(ref_opt2.param_groups[0]["lr"] - fused.lr) < 1e-18, epoch
+
+
+# ------------------------------------------------------------------------------------------------
+# Input shape contracts (dry run): every entry point refuses a wrong shape on the host, before a plan is built or anything launches.
+# On a GPU each refused call below would be an out-of-bounds read (a boundary kernel or a loss kernel sized by the other operand).
+# ------------------------------------------------------------------------------------------------
+_NODES5 = ["features.2", "features.7", "features.16", "features.25", "features.34"]
+_MEAN, _STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
+
+
+def _unet():
+    from sr_gan_fd_amd import model as M
+    return M.discriminator_unet(in_channels=3, out_channels=1, channels=64)
+
+
+def _engines_of(*modules):
+    from sr_gan_fd_amd import engine as E
+    return [E._ENGINES[m] for m in modules if m in E._ENGINES]
+
+
+def _nothing_planned(*modules):
+    """no engine of these modules has built a plan or run a forward (shape checks come first)"""
+    return all(len(e.shapes) == 0 and e.token == 0 for e in _engines_of(*modules))
+
+
+def _refused_calls():
+    """(id, call) pairs: each call must raise SrganfdError before anything is planned; the modules it touches are returned by the call
+    through the list it is given, so the test can check that nothing was planned for them"""
+    from sr_gan_fd_amd import model as M
+    from sr_gan_fd_amd.gan import GanTrainer
+    from sr_gan_fd_amd.gan_esrgan import EsrganGanTrainer
+    from sr_gan_fd_amd.trainer import GeneratorTrainer
+    r = torch.rand
+
+    def g_trainer_gt_too_small(mods):
+        g = M.bsrgan_x4(num_rrdb=1)
+        mods += [g]
+        GeneratorTrainer(g, lr=1e-4).step(r(2, 3, 16, 16), r(2, 3, 32, 32))           # sr would be 2x3x64x64
+
+    def gan_trainer_gt_too_small(mods):
+        g, d = M.bsrgan_x4(num_rrdb=1), M.uNetDiscriminatorAesrgan()
+        mods += [g, d]
+        GanTrainer(g, d).step(r(2, 3, 16, 16), r(2, 3, 32, 32))
+
+    def gan_trainer_generator_first_gt_usm_wrong(mods):
+        g, d = M.RRDBNet(num_rrdb=1, upscale_factor=2), _unet()
+        mods += [g, d]
+        GanTrainer(g, d, generator_first=True).step(r(2, 3, 16, 16), r(2, 3, 32, 32), r(2, 3, 64, 64))
+
+    def gan_trainer_generator_first_gt_wrong(mods):
+        g, d = M.RRDBNet(num_rrdb=1, upscale_factor=1), _unet()
+        mods += [g, d]
+        GanTrainer(g, d, generator_first=True).step(r(2, 3, 16, 16), r(2, 3, 64, 64), r(2, 3, 16, 16))
+
+    def esrgan_trainer_x2_gt_of_x4(mods):
+        g, d = M.RRDBNet(num_rrdb=1, upscale_factor=2), M.discriminator()
+        mods += [g, d]
+        EsrganGanTrainer(g, d).step(r(2, 3, 32, 32), r(2, 3, 128, 128))             # x2 from 32: sr is 64x64
+
+    def generator_four_channel_image(mods):
+        g = M.bsrgan_x4(num_rrdb=1)
+        mods += [g]
+        g(r(2, 4, 16, 16))
+
+    def generator_x2_channels_after_unshuffle(mods):
+        g = M.RRDBNet(num_rrdb=1, upscale_factor=2)
+        mods += [g]
+        g(r(2, 12, 8, 8))                                                          # an already unshuffled input is not an image
+
+    def generator_x1_size_not_divisible(mods):
+        g = M.RRDBNet(num_rrdb=1, upscale_factor=1)
+        mods += [g]
+        g(r(2, 3, 16, 18))                                                         # PixelUnshuffle(4) needs multiples of 4
+
+    def generator_trainer_x2_odd_size(mods):
+        g = M.RRDBNet(num_rrdb=1, upscale_factor=2)
+        mods += [g]
+        GeneratorTrainer(g, lr=1e-4).step(r(2, 3, 15, 16), r(2, 3, 30, 32))
+
+    def generator_not_4d(mods):
+        g = M.bsrgan_x4(num_rrdb=1)
+        mods += [g]
+        g(r(3, 16, 16))
+
+    def unet_one_channel(mods):
+        d = _unet()
+        mods += [d]
+        d(r(2, 1, 32, 32))
+
+    def aesrgan_d_one_channel(mods):
+        d = M.uNetDiscriminatorAesrgan()
+        mods += [d]
+        d(r(2, 1, 32, 32))
+
+    def esrgan_d_one_channel(mods):
+        d = M.discriminator()
+        mods += [d]
+        d(r(2, 1, 128, 128))
+
+    def esrgan_d_64(mods):
+        d = M.discriminator()
+        mods += [d]
+        d(r(2, 3, 64, 64))
+
+    def rrdb_block_half_channels(mods):
+        blk = M.BSRGAN(num_rrdb=1).trunk[0]
+        mods += [blk]
+        blk(r(1, 32, 16, 16))                                                      # a 64-channel block
+
+    def rdb_block_not_4d(mods):
+        blk = M.BSRGAN(num_rrdb=1).trunk[0].rdb1
+        mods += [blk]
+        blk(r(64, 16, 16))
+    return [(f.__name__, f) for f in (g_trainer_gt_too_small, gan_trainer_gt_too_small, gan_trainer_generator_first_gt_usm_wrong,
+                                      gan_trainer_generator_first_gt_wrong, esrgan_trainer_x2_gt_of_x4, generator_four_channel_image,
+                                      generator_x2_channels_after_unshuffle, generator_x1_size_not_divisible, generator_trainer_x2_odd_size,
+                                      generator_not_4d, unet_one_channel, aesrgan_d_one_channel, esrgan_d_one_channel, esrgan_d_64,
+                                      rrdb_block_half_channels, rdb_block_not_4d)]
+
+
+@pytest.mark.parametrize("name", [n for n, _ in _refused_calls()])
+def test_wrong_shapes_are_refused_before_any_launch(name):
+    """Each of these returned normally before the shape contracts existed (and on a GPU read past the end of an input or target
+    buffer), except the ESRGAN discriminator at 64x64, which was refused only after its weights were packed.  Now each raises
+    SrganfdError naming the shape it got, and no engine involved has built a plan or run a forward."""
+    from sr_gan_fd_amd import _abi as A
+    call = dict(_refused_calls())[name]
+    A.set_dry_run(True)
+    try:
+        mods = []
+        with pytest.raises(A.SrganfdError, match=r"got shape|has shape"):
+            call(mods)
+        assert _nothing_planned(*mods), name
+    finally:
+        A.set_dry_run(False)
+
+
+@pytest.mark.parametrize("s", [2, 1])
+def test_real_esrgan_below_x4_fused_trainers_produce_the_gt_shape(s):
+    """Real-ESRGAN's RRDBNet at x2 / x1 (Real_ESRGAN/model.py:190-204,248): the fused trainers go through the same PixelUnshuffle as the
+    module path, so SR has the GT's shape and the dense blocks run at 1 / unshuffle of the LR size.  (The trainers used to hand the
+    3-channel image to a conv1 that reads 12 / 48 channels and return a 4x-sized SR.)"""
+    from sr_gan_fd_amd import _abi as A, model as M
+    from sr_gan_fd_amd.gan import GanTrainer
+    from sr_gan_fd_amd.gan_esrgan import EsrganGanTrainer
+    from sr_gan_fd_amd.trainer import GeneratorTrainer
+    u = 4 // s
+    A.set_dry_run(True)
+    try:
+        lr, gt = torch.rand(2, 3, 16, 24), torch.rand(2, 3, 16 * s, 24 * s)
+        tr = GeneratorTrainer(M.RRDBNet(num_rrdb=1, upscale_factor=s), lr=1e-4)
+        tr.step(lr, gt)
+        assert tr.sr.shape == gt.shape
+        assert (tr.eng._last.H, tr.eng._last.W) == (16 // u, 24 // u)
+        for order in (False, True):
+            tr = GanTrainer(M.RRDBNet(num_rrdb=1, upscale_factor=s), _unet(), M.ContentLoss(_NODES5, _MEAN, _STD), generator_first=order)
+            assert tr.step(lr, gt, gt.clone() if order else None).shape == (8,)
+            assert tr.sr.shape == gt.shape and tr.content_vals.shape == (1, 5)
+        lr_e = torch.rand(2, 3, 128 // s, 128 // s)                 # the ESRGAN discriminator takes 128x128 only
+        tr = EsrganGanTrainer(M.RRDBNet(num_rrdb=1, upscale_factor=s), M.discriminator(), M.ContentLoss("features.34", _MEAN, _STD))
+        assert tr.step(lr_e, torch.rand(2, 3, 128, 128)).shape == (8,)
+        assert tr.sr.shape == (2, 3, 128, 128)
+    finally:
+        A.set_dry_run(False)
+
+
+@pytest.mark.parametrize("s", [2, 1])
+def test_real_esrgan_below_x4_module_forward_unshuffles_once(s):
+    """The module path still returns 4 / unshuffle times the input size, with the unshuffle applied once (by the engine): the plan
+    is built at the trunk's size, and the training and inference forwards agree on shapes."""
+    from sr_gan_fd_amd import _abi as A, engine as E, model as M
+    u = 4 // s
+    A.set_dry_run(True)
+    try:
+        net = M.RRDBNet(num_rrdb=1, upscale_factor=s)
+        net.compute_dtype = torch.float32
+        x = torch.rand(2, 3, 16, 24)
+        sr = net(x)
+        assert sr.shape == (2, 3, 16 * s, 24 * s)
+        eng = E.generator_engine(net)
+        assert (eng._last.N, eng._last.H, eng._last.W) == (2, 16 // u, 24 // u)
+        assert eng.output_shape(x.shape) == tuple(sr.shape)
+        sr.sum().backward()
+        assert net.conv1.weight.grad.shape == (64, 3 * u * u, 3, 3)
+        with torch.no_grad():
+            assert net(x).shape == sr.shape
+    finally:
+        A.set_dry_run(False)

@@ -94,6 +94,42 @@ def test_realesrgan_rrdbnet_below_x4(golden_dir, name, s):
         _close(P[k].grad, g[f"{name}/grad/{k}"], tol=2e-4, what=f"grad {k}")
 
 
+@pytest.mark.parametrize("name,s", [("x2_r2_s3", 2), ("x1_r2_s3", 1), ("x2_r2_s3_odd", 2)])
+def test_realesrgan_below_x4_oracle_steps_take_unshuffle(golden_dir, name, s):
+    """The oracle's step functions forward ``unshuffle`` to rrdbnet_forward (the GPU tests of the fused trainers below x4 rest on it):
+    g_only_step from the fixture's weights returns the reference class's loss and SR, and each GAN step function's SR has the GT's
+    shape (a step that dropped the keyword would produce a 4 / s times larger SR, or fail on conv1's 12 / 48 input channels)."""
+    from oracle import srgan_oracle as O
+    from sr_gan_fd_amd import model as M
+    g = load_golden(golden_dir, "realesrgan_rrdbnet.npz")
+    torch.manual_seed(0)
+    net = M.RRDBNet(in_channels=3, out_channels=3, channels=64, growth_channels=32, num_rrdb=2, upscale_factor=s)
+    scaled_init(net, 3.0, 0.5)
+    _check_table(table(g, f"{name}/wsum"), net.state_dict(), what=name)
+    G = sd_to_params(net.state_dict())
+    x, gt = torch.tensor(g[f"{name}/x"]), torch.tensor(g[f"{name}/gt"])
+    loss, sr = O.g_only_step(G, O.AdamState(G, O.g_param_names(G)), x, gt, upscale=4, lr=1e-4, betas=(0.9, 0.99), eps=1e-4,
+                             unshuffle=4 // s)
+    _close(sr, g[f"{name}/sr"], what="sr")
+    assert abs(loss - float(g[f"{name}/loss"])) < 1e-6
+    assert not torch.equal(G["conv1.weight"], net.conv1.weight)          # and the step did update the weights
+    # the GAN step functions: a U-Net discriminator needs sides that are multiples of 8 (the odd fixture has none)
+    if name.endswith("odd"):
+        return
+    torch.manual_seed(1)
+    D0 = sd_to_params(M.discriminator_unet(in_channels=3, out_channels=1, channels=64).state_dict(), d=True)
+    for step in ("gan_step", "realesrgan_gan_step"):
+        G, D = sd_to_params(net.state_dict()), {k: v.clone() for k, v in D0.items()}
+        opts = (O.AdamState(G, O.g_param_names(G)), O.AdamState(D, O.d_param_names(D)))
+        if step == "gan_step":
+            out = O.gan_step(G, D, *opts, x, gt, upscale=4, g_lr=1e-4, d_lr=1e-4, betas=(0.9, 0.99), eps=1e-4, pixel_weight=1.0,
+                             content_weight=1.0, adversarial_weight=0.1, unshuffle=4 // s)
+        else:
+            out = O.realesrgan_gan_step(G, D, *opts, x, gt, gt, unshuffle=4 // s)
+        _close(out["sr"], g[f"{name}/sr"], what=f"{step} sr")
+        assert abs(out["pixel_loss"] - float(g[f"{name}/loss"])) < 1e-6, step
+
+
 def test_discriminator(golden_dir):
     from oracle import srgan_oracle as O
     from sr_gan_fd_amd import model as M
