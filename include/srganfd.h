@@ -433,6 +433,34 @@ int64_t srganfd_ssim_workspace_doubles(int32_t n, int32_t c, int32_t h, int32_t 
 int srganfd_ssim(const float* a, const float* b, int32_t n, int32_t c, int32_t h, int32_t w, int32_t crop_border,
                  int32_t y_only, const double* window, int32_t window_size, float* out, double* workspace, void* stream);
 
+/* NIQE features (image_quality_assessment.py:1138-1333; the NIQE module of sr_gan_fd_amd/image_quality_assessment.py finishes
+ * the score from them).  rgb: NCHW fp32 in [0,1], c == 3.  crop_border pixels are dropped on every side, the BT.601 luma
+ * (fp32, x255, rounded half to even) is cut to whole block_h x block_w blocks: lh = floor(hc / block_h) * block_h,
+ * lw likewise.  Per block and scale (the luma, and its 0.5x antialiased-cubic copy with blocks of half the size) 18 AGGD
+ * features of the MSCN map, fp64.
+ *   table: (4, table_len) fp64 in device memory, rows = shape values (rising), their r_gam (rising strictly),
+ *          sqrt(exp(lgamma(1/a) - lgamma(3/a))), exp(lgamma(2/a) - lgamma(1/a)); the reference's grid is
+ *          float32 arange(0.2, 10.001, 0.001) widened to fp64, 9801 entries.
+ *   feat:  (n, blocks, 36) fp64 out, blocks in the reference's column-major order (index = bx * blocks_y + by),
+ *          features 0..17 at scale 1, 18..35 at scale 2.
+ *   workspace: srganfd_niqe_workspace_doubles() doubles; on return it holds the luma plane (n, lh, lw) followed by the
+ *          half-size plane (n, lh/2, lw/2), the latter in [0,1] and holding float32 values as the reference's resize does.
+ * SRGANFD_EINVAL (the query returns -1): c != 3, an odd block size, a block larger than the cropped image, fewer than
+ * 2 blocks per image (the covariance over blocks is undefined), a block whose fp64 image + halo + MSCN map exceed the
+ * CU's 160 KB of LDS (96 x 96 fits; 100 x 100 does not). */
+int64_t srganfd_niqe_workspace_doubles(int32_t n, int32_t c, int32_t h, int32_t w, int32_t crop_border, int32_t block_h,
+                                       int32_t block_w);
+int srganfd_niqe_features(const float* rgb, int32_t n, int32_t c, int32_t h, int32_t w, int32_t crop_border, int32_t block_h,
+                          int32_t block_w, const double* table, int32_t table_len, double* feat, double* workspace,
+                          void* stream);
+/* The same from an fp64 luma plane (n, h, w) with h, w whole multiples of the block; half: (n, h/2, w/2) fp64 out. */
+int srganfd_niqe_features_luma(const double* luma, int32_t n, int32_t h, int32_t w, int32_t block_h, int32_t block_w,
+                               const double* table, int32_t table_len, double* feat, double* half, void* stream);
+/* The half-size resize on its own (image_quality_assessment.py:718-921 at scale 0.5: cubic a = -0.5 stretched by 2, 10
+ * taps, MATLAB symmetric padding, rows then columns): fp64 planes (planes, h, w) -> (planes, ceil(h/2), ceil(w/2)).
+ * Like the reference's, the arithmetic is float32 (inputs rounded to float32, outputs are float32 values widened). */
+int srganfd_resize_half(const double* src, int32_t planes, int32_t h, int32_t w, double* dst, void* stream);
+
 /* ---- Real-ESRGAN on-device degradation (Real_ESRGAN/imgproc.py) ----
  * filter2d_torch (imgproc.py:1092-1124): NCHW fp32 image (b,c,h,w), reflect padding k/2, cross-correlation of every
  * channel of image n with kernels[n] (kernel_batch == b) or the one shared kernel (kernel_batch == 1); k odd, <= 51

@@ -83,6 +83,12 @@ int poisson_apply_impl(const float* image, const float* img_q, const float* gray
 int64_t ssim_workspace_doubles(int n, int c, int h, int w, int crop_border, int y_only, int ws);
 int ssim_impl(const float* a, const float* b, int n, int c, int h, int w, int crop_border, int y_only, const double* window, int ws, float* out,
               double* wsp, hipStream_t s);
+int64_t niqe_workspace_doubles(int n, int c, int h, int w, int crop_border, int bh, int bw);
+int niqe_features_impl(const float* rgb, int n, int c, int h, int w, int crop_border, int bh, int bw, const double* table, int table_len, double* feat,
+                       double* ws, hipStream_t s);
+int niqe_features_luma_impl(const double* luma, int n, int h, int w, int bh, int bw, const double* table, int table_len, double* feat, double* half,
+                            hipStream_t s);
+int resize_half_impl(const double* src, int planes, int h, int w, double div, double* dst, hipStream_t s);
 int sigmoid_impl(float* x, size_t n, hipStream_t s);
 int sigmoid_bwd_impl(const float* ds, const float* sg, float* out, size_t n, hipStream_t s);
 int gate_mul_impl(int bwd, srganfd_view x, const float* gate, srganfd_view y, srganfd_view dx, float* dgate, int dtype, size_t npix, int c, hipStream_t s);
@@ -274,6 +280,20 @@ int64_t srganfd_ssim_workspace_doubles(int32_t n, int32_t c, int32_t h, int32_t 
 int srganfd_ssim(const float* a, const float* b, int32_t n, int32_t c, int32_t h, int32_t w, int32_t crop_border, int32_t y_only, const double* window,
                  int32_t window_size, float* out, double* workspace, void* stream) {
   return ssim_impl(a, b, n, c, h, w, crop_border, y_only, window, window_size, out, workspace, (hipStream_t)stream);
+}
+int64_t srganfd_niqe_workspace_doubles(int32_t n, int32_t c, int32_t h, int32_t w, int32_t crop_border, int32_t block_h, int32_t block_w) {
+  return niqe_workspace_doubles(n, c, h, w, crop_border, block_h, block_w);
+}
+int srganfd_niqe_features(const float* rgb, int32_t n, int32_t c, int32_t h, int32_t w, int32_t crop_border, int32_t block_h, int32_t block_w,
+                          const double* table, int32_t table_len, double* feat, double* workspace, void* stream) {
+  return niqe_features_impl(rgb, n, c, h, w, crop_border, block_h, block_w, table, table_len, feat, workspace, (hipStream_t)stream);
+}
+int srganfd_niqe_features_luma(const double* luma, int32_t n, int32_t h, int32_t w, int32_t block_h, int32_t block_w, const double* table,
+                               int32_t table_len, double* feat, double* half, void* stream) {
+  return niqe_features_luma_impl(luma, n, h, w, block_h, block_w, table, table_len, feat, half, (hipStream_t)stream);
+}
+int srganfd_resize_half(const double* src, int32_t planes, int32_t h, int32_t w, double* dst, void* stream) {
+  return resize_half_impl(src, planes, h, w, 1.0, dst, (hipStream_t)stream);
 }
 int srganfd_filter2d(const float* image, const float* kernels, int32_t kernel_batch, int32_t b, int32_t c, int32_t h, int32_t w, int32_t k, float* out,
                      void* stream) {
