@@ -94,8 +94,9 @@ typedef struct {
    * launch (16-bit dtypes, ksize 2 or 1, stride 1, out_sy = out_sx = 2): class (py,px) = (c >> 1, c & 1) uses out_oy = py, out_ox = px,
    * pad_y - py * class_pad_step, pad_x - px * class_pad_step (pad_y / pad_x = class (0,0)'s) and the packed operand at
    * w_packed + c * ksize^2 * cin * cout * 2 bytes -- the four packs follow each other; out_oy / out_ox are ignored.
-   * class_pad_step = 1: data gradient of a 4x4 stride-2 pad-1 conv (pad 1 - p); 0: the 3x3 stride-2 / 2x2 stride-2 forms whose classes
-   * share one window.  The four workgroups that read one patch of x are neighbours on one XCD, so x comes from HBM once, not four times. */
+   * class_pad_step = 1: data gradient of a 4x4 stride-2 pad-1 conv (pad 1 - p), or the FORWARD of a nearest-x2 upsample + 3x3 pad-1
+   * conv (ksize 2, pad 1, pack codes 14..17: class (py,px) reads the 2x2 low-res window at (oy + py - 1, ox + px - 1)); 0: the
+   * 3x3 stride-2 / 2x2 stride-2 forms whose classes share one window.  The four workgroups that read one patch of x are neighbours on one XCD, so x comes from HBM once, not four times. */
   int32_t out_classes, class_pad_step;
 } srganfd_conv_args;
 
@@ -145,7 +146,13 @@ typedef struct {
                              2+2*py+px: parity class (py,px) of a 4x4 stride-2 data gradient, packed as a
                              2x2-tap operand: tap (a,b) <- source tap (ty,tx), ty = py ? 2-2a : 3-2a;
                              6+2*py+px: same for a 3x3 stride-2 pad-1 conv (A-ESRGAN/model.py:287-291);
-                             10+2*a+b: tap (a,b) of a 2x2 stride-2 conv (:236) as a 1x1 operand */
+                             10+2*a+b: tap (a,b) of a 2x2 stride-2 conv (:236) as a 1x1 operand;
+                             14+2*py+px: FORWARD operand of parity class (py,px) of a nearest-x2 upsample followed by a
+                             3x3 pad-1 conv (BSRGAN/model.py:372-374), as 2x2 taps over the low-res input: per axis
+                             class 0 taps (W0, W1+W2), class 1 taps (W0+W1, W2);
+                             18: data gradient of that nearest-x2 + 3x3 conv as a 4x4 stride-2 pad-1 operand over the
+                             high-res gradient (channels swapped): per axis taps (W2, W1+W2, W0+W1, W0).
+                             The two nearest-x2 codes sum their (up to 4) source taps in fp32 and round once. */
   float scale;
 } srganfd_pack_seg;
 

@@ -4,7 +4,8 @@
 // :102-135 discriminator, :325-355 generator head/tail) together with the element-wise work the
 // reference runs as separate ATen ops around it: bias, LeakyReLU (:48), `mul 0.2 + identity`
 // (:59-60, :85-86), torch.cat (:55-58 -- the output goes straight into a channel slice of the
-// dense-block buffer), nearest x2 upsample (:372-374 -- folded into the gather).  With weights
+// dense-block buffer), nearest x2 upsample (:372-374 -- folded into the gather (up = 1), or in the 16-bit modes the layer as four
+// 2x2-tap parity classes over the low-res input, pack.hip codes 14..17).  With weights
 // packed in data-gradient orientation the same kernel is the dgrad pass (mask = LeakyReLU').
 //
 // Mapping (MI355X-first, not a cuDNN tiling):
@@ -153,7 +154,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
     const int t0 = (int)fast_div((unsigned)bid, (unsigned)a.nNb, a.m_nNb);
     nb_ = __builtin_amdgcn_readfirstlane(bid - t0 * a.nNb);
     if constexpr (kCls) {
-      // all four output-parity classes of a stride-2 data gradient in one launch (srganfd_conv_args.out_classes): the class is the
+      // all four output-parity classes of a stride-2 data gradient (or of a nearest-x2 + 3x3 forward) in one launch (srganfd_conv_args.out_classes): the class is the
       // slow half of the tile's channel-block index, so the 4 x nNb workgroups that read one dy patch are consecutive blocks of one
       // XCD and three of the four reads hit its L2
       if (a.cls_sh >= 0) { cls = nb_ >> a.cls_sh; nb_ &= (1 << a.cls_sh) - 1; }
@@ -168,7 +169,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
 
   const int Hl = a.Hin << a.up, Wl = a.Win << a.up;
   // a class launch derives the class's padding and output offset from its index: class (py, px) produces the output pixels
-  // (2 oy + py, 2 ox + px); 4x4 stride-2 gradient (cls_pad 1): from the 2 x 2 window of dy that starts at (oy + py - 1, ox + px - 1)
+  // (2 oy + py, 2 ox + px); 4x4 stride-2 gradient (cls_pad 1): from the 2 x 2 window of dy that starts at (oy + py - 1, ox + px - 1);
+  // nearest-x2 + 3x3 forward (cls_pad 1): the same window of the low-res input
   auto pad_y = [&]() { return kCls && a.cls_sh >= 0 ? a.pad_y - (cls >> 1) * a.cls_pad : a.pad_y; };
   auto pad_x = [&]() { return kCls && a.cls_sh >= 0 ? a.pad_x - (cls & 1) * a.cls_pad : a.pad_x; };
   auto ooy = [&]() { return kCls && a.cls_sh >= 0 ? (cls >> 1) : a.ooy; };
@@ -923,7 +925,13 @@ static int dispatch_conv(const srganfd_conv_args* a, const ConvK& k, hipStream_t
         return launch_conv<T, 3, 1, 2, 8, 1, true>(k, a->cout, s);
       }
       if (a->ksize == 3 && a->stride == 2) return wide ? launch_conv<T, 3, 2, 1, 4, 2, true>(k, a->cout, s) : launch_conv<T, 3, 2, 1, 4, 1, true>(k, a->cout, s);
-      if (a->ksize == 2 && a->stride == 1) return wide ? launch_conv<T, 2, 1, 2, 4, 2, true>(k, a->cout, s) : launch_conv<T, 2, 1, 2, 8, 1, true>(k, a->cout, s);
+      if (a->ksize == 2 && a->stride == 1) {
+        // the nearest-x2 + 3x3 forward as four parity classes (the class launch with a bias; the data-gradient ones have none and keep
+        // plain stores) writes the upsampled layer (1.07 GB at batch 32, 512^2): the same non-temporal rule as the 3x3 kernels
+        if (wide && g_conv_nt && k.cls_sh >= 0 && a->bias && (size_t)a->n * (size_t)k.HoutF * (size_t)k.WoutF * (size_t)a->cout_store * 2 >= ((size_t)192 << 20))
+          return launch_conv<T, 2, 1, 2, 4, 2, true, 1, -1, true>(k, a->cout, s);
+        return wide ? launch_conv<T, 2, 1, 2, 4, 2, true>(k, a->cout, s) : launch_conv<T, 2, 1, 2, 8, 1, true>(k, a->cout, s);
+      }
       // 4x4 stride 2, 64-channel tiles: weights staged in two halves of two kernel rows -> 73 KiB of LDS, two workgroups per CU
       if (a->ksize == 4 && a->stride == 2) return wide ? launch_conv<T, 4, 2, 1, 4, 2, true, 2>(k, a->cout, s) : launch_conv<T, 4, 2, 1, 4, 1, true>(k, a->cout, s);
       if (a->ksize == 2 && a->stride == 2) return wide ? launch_conv<T, 2, 2, 1, 4, 2, true>(k, a->cout, s) : launch_conv<T, 2, 2, 1, 4, 1, true>(k, a->cout, s);
@@ -958,7 +966,8 @@ int conv_fill_k(const srganfd_conv_args* a, ConvK& k) {
   if (a->out_classes != 0 && a->out_classes != 1 && !allcls) return set_err(SRGANFD_EINVAL, "conv2d: out_classes is 0, 1 or 4");
   if (allcls && (a->out_sy != 2 || a->out_sx != 2 || (a->ksize != 2 && a->ksize != 1) || a->stride != 1 || a->dtype == SRGANFD_F32 || a->up ||
                  (a->class_pad_step != 0 && a->class_pad_step != 1)))
-    return set_err(SRGANFD_EINVAL, "conv2d: out_classes = 4 is the 16-bit data gradient of a stride-2 conv (ksize 2 or 1, stride 1, out_sy = out_sx = 2, class_pad_step 0 / 1)");
+    return set_err(SRGANFD_EINVAL, "conv2d: out_classes = 4 is the 16-bit data gradient of a stride-2 conv or the forward of a nearest-x2 + 3x3 conv "
+                                   "(ksize 2 or 1, stride 1, up 0, out_sy = out_sx = 2, class_pad_step 0 / 1)");
   if (!sub) {
     const int ho = (hl + 2 * a->pad - a->ksize) / a->stride + 1, wo = (wl + 2 * a->pad - a->ksize) / a->stride + 1;
     if (ho != a->h_out || wo != a->w_out)

@@ -39,8 +39,9 @@ __global__ __launch_bounds__(256) void pack_kernel(const srganfd_pack_job* __res
       const srganfd_pack_seg& S = J.seg[g];
       if (k >= S.k_lo && k < S.k_lo + S.k_len) {
         const int kk = k - S.k_lo;
-        int co, ci, t;
+        int co, ci, t = 0;
         int KTs = KT;
+        int ym = 0, xm = 0;   // nearest-x2 + 3x3 forms: this tap is the sum of the source taps in kernel rows ym x columns xm (bit sets)
         if (!S.transposed) { co = n + S.co_off; ci = kk + S.ci_off; t = tap; }
         else if (S.transposed == 1) { co = kk + S.co_off; ci = n + S.ci_off; t = KT - 1 - tap; }
         else if (S.transposed < 6) {  // parity class of the 4x4 stride-2 data gradient: this operand has 2x2 taps, the source 4x4
@@ -54,12 +55,35 @@ __global__ __launch_bounds__(256) void pack_kernel(const srganfd_pack_job* __res
           co = kk + S.co_off; ci = n + S.ci_off; KTs = 9;
           t = ty * 3 + tx;
           if (ty < 0 || tx < 0) co = S.co_src;   // unused tap -> zero
-        } else {  // 10 + 2a + b: tap (a,b) of a 2x2 stride-2 conv as a 1x1 data-gradient operand
+        } else if (S.transposed < 14) {  // 10 + 2a + b: tap (a,b) of a 2x2 stride-2 conv as a 1x1 data-gradient operand
           const int ab = S.transposed - 10;
           co = kk + S.co_off; ci = n + S.ci_off; t = ab; KTs = 4;
+        } else if (S.transposed < 18) {  // 14 + 2py + px: class (py,px) of a nearest-x2 + 3x3 pad-1 conv as a 2x2-tap forward operand
+          // high-res row 2 oy + py reads low-res rows (2 oy + py + dy) >> 1; the class window starts at oy + py - 1:
+          // py = 0: a=0 <- W0, a=1 <- W1 + W2;  py = 1: a=0 <- W0 + W1, a=1 <- W2
+          const int py = (S.transposed - 14) >> 1, px = (S.transposed - 14) & 1, ta = tap >> 1, tb = tap & 1;
+          co = n + S.co_off; ci = kk + S.ci_off; KTs = 9;
+          ym = py ? (ta ? 4 : 3) : (ta ? 6 : 1);
+          xm = px ? (tb ? 4 : 3) : (tb ? 6 : 1);
+        } else {  // 18: data gradient of a nearest-x2 + 3x3 pad-1 conv as a 4x4 stride-2 pad-1 operand over the high-res gradient,
+          // tap u <- K[u] = W2, W1 + W2, W0 + W1, W0 (per axis; channels swapped)
+          const int u = tap >> 2, w = tap & 3;
+          co = kk + S.co_off; ci = n + S.ci_off; KTs = 9;
+          ym = (0x1364 >> (4 * u)) & 7;
+          xm = (0x1364 >> (4 * w)) & 7;
         }
         if (co < S.co_src && ci < S.ci_src) {
-          v = params[S.src_off + ((long long)co * S.ci_src + ci) * KTs + t] * S.scale;
+          const float* src = params + S.src_off + ((long long)co * S.ci_src + ci) * KTs;
+          if (ym) {
+            // up to four source taps, summed in fp32 and rounded once below
+            float sum = 0.f;
+            for (int ty = 0; ty < 3; ++ty)
+              for (int tx = 0; tx < 3; ++tx)
+                if ((ym >> ty) & (xm >> tx) & 1) sum += src[ty * 3 + tx];
+            v = sum * S.scale;
+          } else {
+            v = src[t] * S.scale;
+          }
           if (S.scale_off >= 0) v *= scalars[S.scale_off];
         }
         break;

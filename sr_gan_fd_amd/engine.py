@@ -207,6 +207,10 @@ class TrunkEngine:
             raise A.SrganfdError("channels and growth_channels must be multiples of 32 for the MFMA path")
         self.Ccat = self.Cc + 4 * self.G
         self.unshuffle = 1
+        # nearest-x2 + 3x3 upsampling layers in parity form (16-bit modes): the forward as four 2x2-tap classes over the low-res input, the data
+        # gradient as one 4x4 stride-2 conv over the high-res gradient.  0: the up=1 gather forward, the high-res data gradient and the
+        # nearest adjoint (same-process A/B: the switch is read when the engine is built)
+        self.up_parity = os.environ.get("SRGANFD_UPSAMPLE_PARITY", "1") != "0"
         if full:
             self.n_up = owner.n_upsample()
             self.in_ch = owner.conv1.weight.shape[1]
@@ -231,6 +235,10 @@ class TrunkEngine:
 
     def _poff(self, name: str) -> int:
         return self.fp.off(name)
+
+    def _parity(self, dtc: int) -> bool:
+        """do the upsampling layers run in parity form?  (16-bit modes: the class launch has no fp32 kernel)"""
+        return self.full and self.up_parity and dtc != A.F32
 
     def _build_pack(self, dtc: int, device) -> dict:
         """Pack-job tables + offsets of every packed operand (forward and data-gradient)."""
@@ -268,7 +276,15 @@ class TrunkEngine:
                 add(("b", i, step), 3, kdim, n, segs)
         if self.full:
             fwd(("f", "conv1"), "conv1.weight", Cc, self.in_ch)
-            for nm in ["conv2"] + [f"upsampling{u}.0" for u in range(1, self.n_up + 1)] + ["conv3.0"]:
+            ups = [f"upsampling{u}.0" for u in range(1, self.n_up + 1)]
+            for nm in ["conv2"] + ups + ["conv3.0"]:
+                if nm in ups and self._parity(dtc):
+                    # forward: four 2x2-tap class operands back to back (pack codes 14..17); data gradient: one 4x4 operand (code 18)
+                    src = self._poff(nm + ".weight")
+                    for c in range(4):
+                        add(("fc", nm, c), 2, Cc, Cc, [dict(src_off=src, co_src=Cc, ci_src=Cc, k_len=Cc, transposed=14 + c)])
+                    add(("b4", nm), 4, Cc, Cc, [dict(src_off=src, co_src=Cc, ci_src=Cc, k_len=Cc, transposed=18)])
+                    continue
                 fwd(("f", nm), nm + ".weight", Cc, Cc)
                 bwd(("b", nm), nm + ".weight", Cc, Cc)
             fwd(("f", "conv4"), "conv4.weight", self.out_ch, Cc)
@@ -360,8 +376,11 @@ class TrunkEngine:
             src, h, w = sp.f0, H, W
             for u in range(1, self.n_up + 1):
                 nm = f"upsampling{u}.0"
-                fw.append(ops.conv_args(dtc, V(src), V(sp.ups[u - 1]), wptr + pk["offs"][("f", nm)], N, h, w, Cc, Cc, up=1,
-                                        bias=bias(nm + ".bias"), act=A.ACT_LRELU, slope=0.2))
+                if self._parity(dtc):
+                    fw.extend(self._up_forward(dtc, pk, V(src), V(sp.ups[u - 1]), N, h, w, bias(nm + ".bias"), nm))
+                else:
+                    fw.append(ops.conv_args(dtc, V(src), V(sp.ups[u - 1]), wptr + pk["offs"][("f", nm)], N, h, w, Cc, Cc, up=1,
+                                            bias=bias(nm + ".bias"), act=A.ACT_LRELU, slope=0.2))
                 src, h, w = sp.ups[u - 1], h * 2, w * 2
             fw.append(ops.conv_args(dtc, V(src), V(sp.c3), wptr + pk["offs"][("f", "conv3.0")], N, h, w, Cc, Cc, bias=bias("conv3.0.bias"),
                                     act=A.ACT_LRELU, slope=0.2))
@@ -378,6 +397,25 @@ class TrunkEngine:
             self._plan_backward(sp, pk)
         self.shapes.put(key, sp, pinned=train)
         return sp
+
+    def _up_forward(self, dtc: int, pk: dict, x: A.View, y: A.View, N: int, h: int, w: int, bias: int, nm: str) -> List[A.ConvArgs]:
+        """nearest x2 + 3x3 pad-1 conv + LeakyReLU (BSRGAN/model.py:372-374) as its four output-parity classes: 2x2-tap convs over the
+        low-res input x (pack codes 14..17), written into the high-res y.  One launch when the library takes the four classes together
+        (ops.class4_ok), else one launch per class."""
+        Cc, O, wptr = self.Cc, pk["offs"], pk["buf"].data_ptr()
+        one = ops.class4_ok(dtc, Cc, [O[("fc", nm, c)] for c in range(4)], ops.packed_bytes(dtc, 2, Cc, Cc))
+        out = []
+        for par in range(1 if one else 4):
+            py, px = par >> 1, par & 1
+            a = ops.conv_args(dtc, x, y, wptr + O[("fc", nm, par)], N, h, w, Cc, Cc, ksize=2, stride=1, pad=0, bias=bias, act=A.ACT_LRELU, slope=0.2)
+            a.h_out, a.w_out = h, w
+            a.out_sy, a.out_sx, a.out_oy, a.out_ox = 2, 2, py, px
+            a.out_h_full, a.out_w_full = 2 * h, 2 * w
+            a.pad_y, a.pad_x = (1, 1) if one else (1 - py, 1 - px)      # class (py, px) reads the window at (oy + py - 1, ox + px - 1)
+            a.out_classes, a.class_pad_step = (4, 1) if one else (0, 0)
+            a._label_tag = " nearest-x2 fwd"
+            out.append(a)
+        return out
 
     def _plan_backward(self, sp: _Shape, pk: dict) -> None:
         N, H, W, dt, dtc, device = sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device
@@ -443,13 +481,22 @@ class TrunkEngine:
                 cur_v = V(cur.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
                 oth_v = V(other.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
                 bw.append(("wgrad", wplan(N, hin, win, Cc, Cc, one(nm, Cc, Cc), up=1), V(xin_t), cur_v, 0))
-                bw.append(("conv", ops.conv_args(dtc, cur_v, oth_v, wptr + pk["offs"][("b", nm)], N, hin * 2, win * 2, Cc, Cc)))
                 glo = sp.glo[u - 1]
-                bw.append(("call", (lambda a=oth_v, b=V(glo), hh=hin, ww=win: A.check(
-                    A.lib().srganfd_resample(0, a, b, dtc, N, hh, ww, Cc, A.stream_ptr()), "nearest_bwd"))))
-                if u >= 2:   # input of this stage is the LeakyReLU output of the previous upsampling conv
-                    bw.append(("call", (lambda d=V(glo), act=V(xin_t), npx2=N * hin * win: A.check(
-                        A.lib().srganfd_lrelu_bwd(d, act, A.NULL_VIEW, d, dtc, npx2, Cc, 0.2, A.stream_ptr()), "lrelu_bwd"))))
+                if self._parity(dtc):
+                    # data gradient, nearest adjoint and (u >= 2: the input is the previous upsampling conv's LeakyReLU output) LeakyReLU' as
+                    # ONE 4x4 stride-2 pad-1 conv over the high-res gradient, written at the low resolution
+                    a = ops.conv_args(dtc, cur_v, V(glo), wptr + pk["offs"][("b4", nm)], N, hin * 2, win * 2, Cc, Cc, ksize=4, stride=2, pad=1,
+                                      mask=V(xin_t) if u >= 2 else A.NULL_VIEW, mask_slope=0.2)
+                    a._label_tag = " nearest-x2 dgrad"
+                    bw.append(("conv", a))
+                else:
+                    bw.append(("conv", ops.conv_args(dtc, cur_v, oth_v, wptr + pk["offs"][("b", nm)], N, hin * 2, win * 2, Cc, Cc)))
+                    bw.append(("call", (lambda a=oth_v, b=V(glo), hh=hin, ww=win: A.check(
+                        A.lib().srganfd_resample(0, a, b, dtc, N, hh, ww, Cc, A.stream_ptr()), "nearest_bwd"))))
+                    if u >= 2:   # input of this stage is the LeakyReLU output of the previous upsampling conv
+                        bw.append(("call", (lambda d=V(glo), act=V(xin_t), npx2=N * hin * win: A.check(
+                            A.lib().srganfd_lrelu_bwd(d, act, A.NULL_VIEW, d, dtc, npx2, Cc, 0.2, A.stream_ptr()), "lrelu_bwd"))))
+                if u >= 2:
                     # next stage works at (hin, win): reuse gA/gB as scratch, the gradient lives in glo
                     cur, other = glo, sp.gA
                     # make cur the full buffer view expected above

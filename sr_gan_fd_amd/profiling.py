@@ -54,14 +54,15 @@ def disable() -> None:
 
 
 def conv_label(a) -> str:
-    """kernel template the launch dispatches to (asked from the library: srganfd_conv2d_describe)"""
+    """kernel template the launch dispatches to (asked from the library: srganfd_conv2d_describe), plus the layer form an engine tagged
+    the launch with (``_label_tag``: the nearest-x2 upsampling layers in parity form share their kernels with the discriminator's)"""
     lab = getattr(a, "_kernel_label", None)      # launch structs live in the engines' plans: ask once
     if lab is None:
         import ctypes as C
         from . import _abi as A
         buf = C.create_string_buffer(160)
         A.check(A.lib().srganfd_conv2d_describe(C.byref(a), buf, 160), "conv2d_describe")
-        lab = a._kernel_label = buf.value.decode()
+        lab = a._kernel_label = buf.value.decode() + getattr(a, "_label_tag", "")
     return lab
 
 
