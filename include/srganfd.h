@@ -468,6 +468,22 @@ int srganfd_niqe_features_luma(const double* luma, int32_t n, int32_t h, int32_t
  * Like the reference's, the arithmetic is float32 (inputs rounded to float32, outputs are float32 values widened). */
 int srganfd_resize_half(const double* src, int32_t planes, int32_t h, int32_t w, double* dst, void* stream);
 
+/* MATLAB's imresize as the reference's imgproc.image_resize runs it (ESRGAN/imgproc.py:202-288): a separable weighted sum, rows
+ * (H) first, then columns (W), float32 throughout, the intermediate rounded to float32 between the passes (it stays in LDS).
+ *   src: (planes, h, w) fp32, contiguous; dst: (planes, out_h, out_w) fp32.
+ *   wt_h (out_h, taps_h) fp32 and first_h (out_h) int32, wt_w (out_w, taps_w) and first_w (out_w) likewise: device tables the
+ *   caller builds (sr_gan_fd_amd/imgproc.py).  Output i of a side sums wt[i][k] * sample(first[i] + k), k = 0 .. taps - 1;
+ *   first[i] is a 0-based source index that may be negative or run past the end: index j is read at -1 - j when j < 0 and at
+ *   2n - 1 - j when j >= n (MATLAB's symmetric padding).  first[] does not decrease; anything further out than one reflection is
+ *   clamped into the image, so a tap of weight 0 is never read out of range.
+ * One launch; one workgroup per output tile, whose input footprint is staged in LDS.  The tile (32, 16, 8, ... outputs a side) is
+ * the largest whose footprint -- sized from in / out, which bounds the scale when out = ceil(in * scale) -- intermediate and
+ * weights fit 64 KB: every scale in [1/8, 8] with the cubic's 4 / scale-wide kernel runs.
+ * SRGANFD_EINVAL: null pointer, non-positive size, taps < 1, more than 65535 planes, a footprint that fits no tile. */
+int srganfd_imresize(const float* src, int32_t planes, int32_t h, int32_t w, int32_t out_h, int32_t out_w, const float* wt_h,
+                     const int32_t* first_h, int32_t taps_h, const float* wt_w, const int32_t* first_w, int32_t taps_w,
+                     float* dst, void* stream);
+
 /* ---- Real-ESRGAN on-device degradation (Real_ESRGAN/imgproc.py) ----
  * filter2d_torch (imgproc.py:1092-1124): NCHW fp32 image (b,c,h,w), reflect padding k/2, cross-correlation of every
  * channel of image n with kernels[n] (kernel_batch == b) or the one shared kernel (kernel_batch == 1); k odd, <= 51

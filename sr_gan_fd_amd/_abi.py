@@ -186,6 +186,7 @@ SYMBOLS = {
     "srganfd_niqe_features": (C.c_int, [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "srganfd_niqe_features_luma": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "srganfd_resize_half": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p]),
+    "srganfd_imresize": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32] * 2 + [C.c_void_p, C.c_void_p]),
     "srganfd_gate_mul": (C.c_int, [C.c_int32, View, C.c_void_p, View, View, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "srganfd_batchnorm_fwd": (C.c_int, [View, View, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                         C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -89,6 +89,8 @@ int niqe_features_impl(const float* rgb, int n, int c, int h, int w, int crop_bo
 int niqe_features_luma_impl(const double* luma, int n, int h, int w, int bh, int bw, const double* table, int table_len, double* feat, double* half,
                             hipStream_t s);
 int resize_half_impl(const double* src, int planes, int h, int w, double div, double* dst, hipStream_t s);
+int imresize_impl(const float* src, int planes, int h, int w, int oh, int ow, const float* wt_h, const int* first_h, int taps_h,
+                  const float* wt_w, const int* first_w, int taps_w, float* dst, hipStream_t s);
 int sigmoid_impl(float* x, size_t n, hipStream_t s);
 int sigmoid_bwd_impl(const float* ds, const float* sg, float* out, size_t n, hipStream_t s);
 int gate_mul_impl(int bwd, srganfd_view x, const float* gate, srganfd_view y, srganfd_view dx, float* dgate, int dtype, size_t npix, int c, hipStream_t s);
@@ -294,6 +296,11 @@ int srganfd_niqe_features_luma(const double* luma, int32_t n, int32_t h, int32_t
 }
 int srganfd_resize_half(const double* src, int32_t planes, int32_t h, int32_t w, double* dst, void* stream) {
   return resize_half_impl(src, planes, h, w, 1.0, dst, (hipStream_t)stream);
+}
+int srganfd_imresize(const float* src, int32_t planes, int32_t h, int32_t w, int32_t out_h, int32_t out_w, const float* wt_h,
+                     const int32_t* first_h, int32_t taps_h, const float* wt_w, const int32_t* first_w, int32_t taps_w,
+                     float* dst, void* stream) {
+  return imresize_impl(src, planes, h, w, out_h, out_w, wt_h, first_h, taps_h, wt_w, first_w, taps_w, dst, (hipStream_t)stream);
 }
 int srganfd_filter2d(const float* image, const float* kernels, int32_t kernel_batch, int32_t b, int32_t c, int32_t h, int32_t w, int32_t k, float* out,
                      void* stream) {

@@ -14,11 +14,20 @@ import torch
 class CUDAPrefetcher:
     """``ingest_u8`` (an addition; the reference's loader hands out fp32 CHW tensors): a batch entry that is a uint8 (N, H, W, 3) tensor -- decoded
     images as cv2.imread returns them -- is copied as bytes and converted on the device on the copy stream (imgproc.image_to_tensor_u8:
-    / 255, BGR -> RGB, HWC -> CHW), so the consumer sees the same fp32 (N, 3, H, W) batch at a quarter of the PCIe traffic."""
+    / 255, BGR -> RGB, HWC -> CHW), so the consumer sees the same fp32 (N, 3, H, W) batch at a quarter of the PCIe traffic.
 
-    def __init__(self, dataloader, device: torch.device, ingest_u8: bool = False, bgr: bool = True):
+    ``synthesize_lr`` (an addition; ESRGAN/dataset.py:73 makes the LR image per sample on the host with ``imgproc.image_resize(gt_image,
+    1 / upscale_factor)``): with an upscale factor, a batch that has ``"gt"`` and no ``"lr"`` gets ``batch["lr"] = image_resize(batch["gt"],
+    1 / factor)`` on the copy stream, after the u8 ingest, so the resize of batch i+1 overlaps iteration i like the copy does.  A batch that
+    brings its own ``"lr"`` keeps it; the default ``None`` changes nothing.  (The reference resizes in BGR and swaps channels afterwards; the
+    resize is per channel, so the order does not matter.)"""
+
+    def __init__(self, dataloader, device: torch.device, ingest_u8: bool = False, bgr: bool = True, synthesize_lr: int | None = None):
         self.original_dataloader = dataloader
         self.ingest_u8, self.bgr = ingest_u8, bgr
+        if synthesize_lr is not None and not synthesize_lr >= 1:
+            raise ValueError(f"CUDAPrefetcher: synthesize_lr is the upscale factor (>= 1) or None, got {synthesize_lr}")
+        self.synthesize_lr = synthesize_lr
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.batch_data = None
@@ -38,6 +47,9 @@ class CUDAPrefetcher:
                 for k, v in self.batch_data.items():
                     if torch.is_tensor(v) and v.dtype == torch.uint8 and v.dim() == 4 and v.shape[-1] == 3:
                         self.batch_data[k] = image_to_tensor_u8(v, bgr=self.bgr)      # launched on the copy stream (A.stream_ptr() = current stream)
+            if self.synthesize_lr is not None and "lr" not in self.batch_data and torch.is_tensor(self.batch_data.get("gt")):
+                from .imgproc import image_resize
+                self.batch_data["lr"] = image_resize(self.batch_data["gt"], 1 / self.synthesize_lr)
 
     def next(self):
         """the staged batch (or None at the end of the epoch); starts staging the following one"""

@@ -4,6 +4,7 @@
 stay the reference's own."""
 from __future__ import annotations
 
+import math
 import random
 from typing import Tuple, Union
 
@@ -54,6 +55,101 @@ def image_to_tensor_u8(images_u8: Tensor, top: int = 0, left: int = 0, size=None
 def _need_gpu(t: Tensor, what: str) -> None:
     if not t.is_cuda:
         raise A.SrganfdError(f"{what}: tensors must be on the GPU (the HIP library is the product; no CPU fallback)")
+
+
+# ---- MATLAB imresize (ESRGAN/imgproc.py:34-127, 202-288; the same text in every imgproc.py of the reference) --------------------
+def _cubic_f32(x: Tensor) -> Tensor:
+    """Keys' cubic with a = -0.5 on a float32 tensor: the two polynomial pieces, each masked by its interval"""
+    ax = torch.abs(x)
+    ax2, ax3 = ax ** 2, ax ** 3
+    inner = (1.5 * ax3 - 2.5 * ax2 + 1) * (ax <= 1).type_as(ax)
+    outer = (-0.5 * ax3 + 2.5 * ax2 - 4 * ax + 2) * ((ax > 1) * (ax <= 2)).type_as(ax)
+    return inner + outer
+
+
+def _resize_tables_host(in_length: int, out_length: int, scale: float, antialiasing: bool):
+    """Weights and first source indices of one side, as ``_calculate_weights_indices`` (imgproc.py:53-127) makes them: computed in
+    FLOAT32 with torch's CPU ops in the reference's order of operations (output coordinates, their inverse map, the left-most
+    contributing sample, the kernel -- stretched and scaled when it shrinks with antialiasing -- and the row normalisation), so the
+    weights carry the reference's bits; fp64 tables would differ from it by up to 3.6e-6 in the result at scales like 0.3 or 3.0.
+    Returns ``(weights (out, taps) float32, first (out,) int32, pad_start, pad_end)``: ``first`` is the 0-based source index of tap 0
+    (negative / past the end where the symmetric padding is read), ``pad_*`` the reference's ``sym_len_s`` / ``sym_len_e``.  The
+    edge columns are dropped exactly where the reference drops them (it drops the outermost pair whenever the first column holds a
+    zero, which it always does: that sample lies half a kernel width or more from the centre)."""
+    width = 4.0
+    shrink = scale < 1 and antialiasing
+    if shrink:
+        width = width / scale
+    x = torch.linspace(1, out_length, out_length)
+    u = x / scale + 0.5 * (1 - 1 / scale)
+    left = torch.floor(u - width / 2)
+    p = math.ceil(width) + 2
+    idx = left.view(out_length, 1) + torch.linspace(0, p - 1, p).view(1, p)          # 1-based sample numbers, float32 (exact)
+    dist = u.view(out_length, 1) - idx
+    w = scale * _cubic_f32(dist * scale) if shrink else _cubic_f32(dist)
+    w = w / torch.sum(w, 1).view(out_length, 1)
+    zeros = torch.sum(w == 0, 0)
+    if int(zeros[0]) != 0:
+        idx, w = idx[:, 1:p - 1], w[:, 1:p - 1]
+    if int(zeros[-1]) != 0:
+        idx, w = idx[:, :p - 2], w[:, :p - 2]
+    pad_start = int(-idx.min() + 1)
+    pad_end = int(idx.max() - in_length)
+    first = (idx[:, 0] - 1).to(torch.int32)
+    return w.contiguous(), first.contiguous(), pad_start, pad_end
+
+
+_RESIZE_TABLES = {}          # (in, out, scale, antialiasing) -> host tables; (..., device) -> their device copies.  Never evicted: a
+                             # training run resizes a handful of lengths, and a copy freed here could still be read by a launch in flight
+
+
+def _resize_tables(in_length: int, out_length: int, scale: float, antialiasing: bool, side: str, device=None):
+    """one side's tables, cached: on the host (``device`` None), where the reference's failure on padding longer than the image becomes
+    a ValueError, or as device copies ``(weights, first, taps)``"""
+    key = (in_length, out_length, float(scale), bool(antialiasing))
+    host = _RESIZE_TABLES.get(key)
+    if host is None:
+        host = _RESIZE_TABLES[key] = _resize_tables_host(in_length, out_length, scale, antialiasing)
+    if max(host[2], host[3]) > in_length:
+        raise ValueError(f"image_resize: the {side} of {in_length} pixels is shorter than the symmetric padding the kernel needs "
+                         f"({host[2]} before, {host[3]} after) at scale {scale}")
+    if device is None:
+        return host
+    dev = _RESIZE_TABLES.get(key + (str(device),))
+    if dev is None:
+        dev = _RESIZE_TABLES[key + (str(device),)] = (host[0].to(device), host[1].to(device), host[0].shape[1])
+    return dev
+
+
+def image_resize(image: Tensor, scale_factor: float, antialiasing: bool = True) -> Tensor:
+    """imgproc.image_resize (ESRGAN/imgproc.py:202-288; dataset.py:73 makes every LR image with it): MATLAB's ``imresize`` -- cubic
+    a = -0.5, widened by 1 / scale when it shrinks with ``antialiasing``, symmetric padding, rows then columns, float32.  ``image``:
+    a GPU tensor ``(H, W)`` or ``(C, H, W)`` (the reference's forms) or a batch ``(N, C, H, W)``; returns float32 of the same rank,
+    ``math.ceil(in * scale_factor)`` per side.  One HIP launch for the whole batch (srganfd_imresize) instead of the reference's
+    Python loop over output rows and columns; no autograd (the reference calls it on data).  CPU tensors and numpy arrays raise
+    ``SrganfdError``; ``scale_factor <= 0`` raises ``ValueError``.  Differences from the reference, both where it cannot run as
+    written: a side shorter than its padding (4 x 4 at 1/4 needs 7 rows) raises ``ValueError`` naming the side before anything is
+    launched (the reference dies in a ``copy_`` size mismatch), and a side that needs no padding at its end (64 x 64 at 1/4 without
+    antialiasing: ``image[:, -0:, :]`` is the whole image there and the reference raises) returns the defined result -- there is
+    nothing to reflect on that side."""
+    if not torch.is_tensor(image):
+        raise A.SrganfdError("image_resize: takes GPU tensors (the HIP library is the product; no CPU fallback)")
+    if image.dim() not in (2, 3, 4):
+        raise A.SrganfdError("image_resize takes (H, W), (C, H, W) or (N, C, H, W) tensors")
+    if not scale_factor > 0:
+        raise ValueError(f"image_resize: scale_factor must be positive, got {scale_factor}")
+    h, w = image.shape[-2:]
+    oh, ow = math.ceil(h * scale_factor), math.ceil(w * scale_factor)
+    for args in ((h, oh, "height"), (w, ow, "width")):             # the argument errors come first, whatever the device
+        _resize_tables(args[0], args[1], scale_factor, antialiasing, args[2])
+    _need_gpu(image, "image_resize")
+    wt_h, first_h, taps_h = _resize_tables(h, oh, scale_factor, antialiasing, "height", image.device)
+    wt_w, first_w, taps_w = _resize_tables(w, ow, scale_factor, antialiasing, "width", image.device)
+    x = image.detach().contiguous().float()
+    out = torch.empty(*x.shape[:-2], oh, ow, dtype=torch.float32, device=x.device)
+    A.check(A.lib().srganfd_imresize(x.data_ptr(), x.numel() // (h * w), h, w, oh, ow, wt_h.data_ptr(), first_h.data_ptr(), taps_h,
+                                     wt_w.data_ptr(), first_w.data_ptr(), taps_w, out.data_ptr(), A.stream_ptr()), "imresize")
+    return out
 
 
 def filter2d_torch(image: Tensor, kernel: Tensor) -> Tensor:

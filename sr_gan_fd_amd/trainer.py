@@ -158,6 +158,45 @@ class MultiStepLR:
         self.optimizer.lr = self._last_lr[0]
 
 
+class StepLR:
+    """``torch.optim.lr_scheduler.StepLR`` for the fused optimizers, built like ``MultiStepLR`` above.  The reference's generator
+    pre-training builds one from ``lr_scheduler_step_size`` / ``lr_scheduler_gamma`` (ESRGAN/rrdbnet_config.py:77-78: epochs // 5, 0.5;
+    train_rrdbnet.py:205-210) and steps it once per epoch.  ``state_dict()`` carries torch's keys, so the two resume from each other's
+    checkpoints."""
+
+    def __init__(self, optimizer: "FlatAdamEMA", step_size: int, gamma: float = 0.1, last_epoch: int = -1):
+        self.optimizer = optimizer
+        self.step_size = int(step_size)
+        if self.step_size < 1:
+            raise ValueError(f"StepLR: step_size must be at least 1, got {step_size}")
+        self.gamma = gamma
+        self.base_lrs = [optimizer.lr]
+        self.last_epoch = last_epoch
+        self._step_count = 0
+        self._last_lr = [optimizer.lr]
+        self.step()                                   # torch's constructor performs the initial step (last_epoch -> 0)
+
+    def get_last_lr(self):
+        return list(self._last_lr)
+
+    def step(self) -> None:
+        self._step_count += 1
+        self.last_epoch += 1
+        if self.last_epoch > 0 and self.last_epoch % self.step_size == 0:      # torch's chained form: multiply the CURRENT rate
+            self.optimizer.lr = self.optimizer.lr * self.gamma
+        self._last_lr = [self.optimizer.lr]
+
+    def state_dict(self) -> dict:
+        return {"step_size": self.step_size, "gamma": self.gamma, "base_lrs": list(self.base_lrs), "last_epoch": self.last_epoch,
+                "verbose": False, "_step_count": self._step_count, "_get_lr_called_within_step": False, "_last_lr": list(self._last_lr)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.step_size, self.gamma, self.base_lrs = int(sd["step_size"]), sd["gamma"], list(sd["base_lrs"])
+        self.last_epoch, self._step_count = int(sd["last_epoch"]), int(sd["_step_count"])
+        self._last_lr = list(sd["_last_lr"])
+        self.optimizer.lr = self._last_lr[0]
+
+
 def pin_training_dtype(*modules) -> torch.dtype:
     """The fused trainers ARE the reference's training loops, and those run every forward under ``amp.autocast()`` (train_bsrgan.py:415-427,
     450-457; train_bsrnet.py:252-254): float16 + GradScaler.  A module whose ``compute_dtype`` is still None (the default: follow autocast)
