@@ -187,7 +187,39 @@ class PlanCache:
         self.d.clear()
 
 
-class TrunkEngine:
+class EngineBase:
+    """What every engine owns: the module's parameters as one flat buffer, the per-shape plans, one packed-weight record per compute
+    dtype (built by the subclass's ``_build_pack``) and the token that ties a backward pass to its forward."""
+
+    def __init__(self, owner: nn.Module, named_params: Sequence[Tuple[str, nn.Parameter]]):
+        self.owner = owner
+        self.fp = FlatParams(named_params)
+        self.shapes = PlanCache()
+        self.packed: Dict[int, dict] = {}
+        self.token = 0
+
+    def _poff(self, name: str) -> int:
+        return self.fp.off(name)
+
+    def _packed(self, dtc: int, device) -> dict:
+        """the packed-weight record of a dtype, rebuilt when the parameters moved to another device or flat buffer"""
+        flat = self.fp.sync(device)
+        pk = self.packed.get(dtc)
+        if pk is None or pk["buf"].device != device or pk.get("flat_ptr") != flat.data_ptr():
+            pk = self._build_pack(dtc, device)
+            pk["flat_ptr"] = flat.data_ptr()
+            self.packed[dtc] = pk
+        return pk
+
+    def _ensure_packed(self, dtc: int, device) -> dict:
+        """... and packed again when the parameter values changed since this record was last packed"""
+        pk = self._packed(dtc, device)
+        if self.fp.stale(pk):
+            pk["table"].run(self.fp.flat, pk["buf"])
+        return pk
+
+
+class TrunkEngine(EngineBase):
     """Forward/backward of a chain of residual dense blocks, optionally wrapped by the generator's
     head (conv1) and tail (conv2, upsampling, conv3, conv4, clamp).
 
@@ -195,7 +227,7 @@ class TrunkEngine:
     :79-88, BSRGAN._forward_impl :366-381 (RRDBNet: ESRGAN/model.py:208-229)."""
 
     def __init__(self, owner: nn.Module, rdbs: Sequence[nn.Module], rrdb: bool, full: bool):
-        self.owner = owner
+        super().__init__(owner, list(owner.named_parameters()))
         self.rdbs = list(rdbs)
         self.rrdb = rrdb
         self.full = full
@@ -218,10 +250,6 @@ class TrunkEngine:
             # Real-ESRGAN below x4 (Real_ESRGAN/model.py:190-204,248): PixelUnshuffle(2 / 4) in front of conv1, applied in forward() so
             # that the module path and the fused trainers share it
             self.unshuffle = getattr(owner, "unshuffle", 1)
-        self.fp = FlatParams(list(owner.named_parameters()))
-        self.shapes = PlanCache()
-        self.packed: Dict[int, dict] = {}
-        self.token = 0
         self._rdb_prefix = self._find_prefixes()
 
     # -- parameter bookkeeping ----------------------------------------------------------------
@@ -233,9 +261,6 @@ class TrunkEngine:
             out.append(n + "." if n else "")
         return out
 
-    def _poff(self, name: str) -> int:
-        return self.fp.off(name)
-
     def _parity(self, dtc: int) -> bool:
         """do the upsampling layers run in parity form?  (16-bit modes: the class launch has no fp32 kernel)"""
         return self.full and self.up_parity and dtc != A.F32
@@ -243,19 +268,9 @@ class TrunkEngine:
     def _build_pack(self, dtc: int, device) -> dict:
         """Pack-job tables + offsets of every packed operand (forward and data-gradient)."""
         Cc, G, Ccat = self.Cc, self.G, self.Ccat
-        jobs, offs, cur = [], {}, 0
-
-        def add(key, ksize, k, n, segs):
-            nonlocal cur
-            offs[key] = cur
-            jobs.append(ops.pack_job(cur, dtc, ksize, k, n, segs))
-            cur += (ops.packed_bytes(dtc, ksize, k, n) + 255) // 256 * 256
-
-        def fwd(key, wname, co, ci):
-            add(key, 3, ops.pad32(ci), ops.pad32(co), [dict(src_off=self._poff(wname), co_src=co, ci_src=ci, k_len=ops.pad32(ci))])
-
-        def bwd(key, wname, co, ci):
-            add(key, 3, ops.pad32(co), ops.pad32(ci), [dict(src_off=self._poff(wname), co_src=co, ci_src=ci, k_len=ops.pad32(co), transposed=1)])
+        pb = ops.PackBuilder(dtc)
+        fwd = lambda key, wname, co, ci: pb.fwd(key, self._poff(wname), co, ci)
+        bwd = lambda key, wname, co, ci: pb.bwd(key, self._poff(wname), co, ci)
 
         for i, pre in enumerate(self._rdb_prefix):
             for k in range(1, 6):
@@ -273,36 +288,21 @@ class TrunkEngine:
                     cin_j, cout_j = Cc + (j - 1) * G, (Cc if j == 5 else G)
                     segs.append(dict(src_off=self._poff(f"{pre}conv{j}.weight"), co_src=cout_j, ci_src=cin_j, k_lo=dyoff[j],
                                      k_len=cout_j, ci_off=c_lo, transposed=1, scale=(s5 if j == 5 else 1.0)))
-                add(("b", i, step), 3, kdim, n, segs)
+                pb.add(("b", i, step), 3, kdim, n, segs)
         if self.full:
             fwd(("f", "conv1"), "conv1.weight", Cc, self.in_ch)
             ups = [f"upsampling{u}.0" for u in range(1, self.n_up + 1)]
             for nm in ["conv2"] + ups + ["conv3.0"]:
                 if nm in ups and self._parity(dtc):
                     # forward: four 2x2-tap class operands back to back (pack codes 14..17); data gradient: one 4x4 operand (code 18)
-                    src = self._poff(nm + ".weight")
-                    for c in range(4):
-                        add(("fc", nm, c), 2, Cc, Cc, [dict(src_off=src, co_src=Cc, ci_src=Cc, k_len=Cc, transposed=14 + c)])
-                    add(("b4", nm), 4, Cc, Cc, [dict(src_off=src, co_src=Cc, ci_src=Cc, k_len=Cc, transposed=18)])
+                    pb.classes(("fc", nm), self._poff(nm + ".weight"), Cc, Cc, 2, 14)
+                    pb.bwd(("b4", nm), self._poff(nm + ".weight"), Cc, Cc, 4, transposed=18)
                     continue
                 fwd(("f", nm), nm + ".weight", Cc, Cc)
                 bwd(("b", nm), nm + ".weight", Cc, Cc)
             fwd(("f", "conv4"), "conv4.weight", self.out_ch, Cc)
             bwd(("b", "conv4"), "conv4.weight", self.out_ch, Cc)
-        table = ops.PackTable(jobs, device)
-        buf = torch.empty(cur, dtype=torch.uint8, device=device)
-        return dict(table=table, offs=offs, buf=buf)
-
-    def _ensure_packed(self, dtc: int, device) -> dict:
-        flat = self.fp.sync(device)
-        pk = self.packed.get(dtc)
-        if pk is None or pk["buf"].device != device or pk.get("flat_ptr") != flat.data_ptr():
-            pk = self._build_pack(dtc, device)
-            pk["flat_ptr"] = flat.data_ptr()
-            self.packed[dtc] = pk
-        if self.fp.stale(pk):
-            pk["table"].run(flat, pk["buf"])
-        return pk
+        return pb.finish(device)
 
     # -- per-shape plan -----------------------------------------------------------------------
     def _plan(self, N: int, H: int, W: int, dt: torch.dtype, dtc: int, device, train: bool, pk: dict) -> _Shape:
@@ -351,11 +351,8 @@ class TrunkEngine:
             sp.ups = [new(N, H << u, W << u, Cc) for u in range(1, self.n_up + 1)]
             sp.c3 = new(N, H * s, W * s, Cc)
             sp.srp = new(N, H * s, W * s, 4, dtype=torch.float32)
-            if sp.thin_i:
-                fw.append(ops.ThinLaunch("thin_in", ops.thin_args(dtc, N, H, W, self.in_ch, bias("conv1.weight"), VC(catb(0)), w_big_is_cout=True,
-                                                                  bias=bias("conv1.bias"), thin=sp.xin)))
-            else:
-                fw.append(ops.conv_args(dtc, V(sp.xin), VC(catb(0)), wptr + pk["offs"][("f", "conv1")], N, H, W, cin1, Cc, bias=bias("conv1.bias")))
+            fw.append(ops.image_to_features(dtc, sp.thin_i, sp.xin, VC(catb(0)), bias("conv1.weight"), wptr + pk["offs"][("f", "conv1")], N, H, W,
+                                            self.in_ch, Cc, True, bias=bias("conv1.bias"))[1])
         for i, pre in enumerate(self._rdb_prefix):
             ci = catb(i)
             blk = []
@@ -384,12 +381,8 @@ class TrunkEngine:
                 src, h, w = sp.ups[u - 1], h * 2, w * 2
             fw.append(ops.conv_args(dtc, V(src), V(sp.c3), wptr + pk["offs"][("f", "conv3.0")], N, h, w, Cc, Cc, bias=bias("conv3.0.bias"),
                                     act=A.ACT_LRELU, slope=0.2))
-            if sp.thin_o:
-                fw.append(ops.ThinLaunch("thin_out", ops.thin_args(dtc, N, h, w, self.out_ch, bias("conv4.weight"), V(sp.c3), w_big_is_cout=False,
-                                                                   bias=bias("conv4.bias"), thin_out=sp.srp, thin_out_pitch=4)))
-            else:
-                fw.append(ops.conv_args(dtc, V(sp.c3), V(sp.srp), wptr + pk["offs"][("f", "conv4")], N, h, w, Cc, 32, cout_store=self.out_ch,
-                                        bias=bias("conv4.bias"), y_f32=True))
+            fw.append(ops.features_to_image(dtc, sp.thin_o, V(sp.c3), sp.srp, 4, bias("conv4.weight"), wptr + pk["offs"][("f", "conv4")], N, h, w,
+                                            self.out_ch, Cc, False, bias=bias("conv4.bias"))[1])
             sp.hs, sp.ws = h, w
         sp.fw = fw
         sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
@@ -402,19 +395,11 @@ class TrunkEngine:
         """nearest x2 + 3x3 pad-1 conv + LeakyReLU (BSRGAN/model.py:372-374) as its four output-parity classes: 2x2-tap convs over the
         low-res input x (pack codes 14..17), written into the high-res y.  One launch when the library takes the four classes together
         (ops.class4_ok), else one launch per class."""
-        Cc, O, wptr = self.Cc, pk["offs"], pk["buf"].data_ptr()
-        one = ops.class4_ok(dtc, Cc, [O[("fc", nm, c)] for c in range(4)], ops.packed_bytes(dtc, 2, Cc, Cc))
-        out = []
-        for par in range(1 if one else 4):
-            py, px = par >> 1, par & 1
-            a = ops.conv_args(dtc, x, y, wptr + O[("fc", nm, par)], N, h, w, Cc, Cc, ksize=2, stride=1, pad=0, bias=bias, act=A.ACT_LRELU, slope=0.2)
-            a.h_out, a.w_out = h, w
-            a.out_sy, a.out_sx, a.out_oy, a.out_ox = 2, 2, py, px
-            a.out_h_full, a.out_w_full = 2 * h, 2 * w
-            a.pad_y, a.pad_x = (1, 1) if one else (1 - py, 1 - px)      # class (py, px) reads the window at (oy + py - 1, ox + px - 1)
-            a.out_classes, a.class_pad_step = (4, 1) if one else (0, 0)
+        Cc, O = self.Cc, pk["offs"]
+        out = ops.parity_class_launches(dtc, x, y, pk["buf"].data_ptr(), [O[("fc", nm, c)] for c in range(4)], N, h, w, Cc, Cc, 2, 1,
+                                        bias=bias, act=A.ACT_LRELU, slope=0.2)      # class (py, px) reads the window at (oy + py - 1, ox + px - 1)
+        for a in out:
             a._label_tag = " nearest-x2 fwd"
-            out.append(a)
         return out
 
     def _plan_backward(self, sp: _Shape, pk: dict) -> None:
@@ -433,13 +418,7 @@ class TrunkEngine:
         sp.dx0 = new(N, H, W, Cc)           # gradient w.r.t. the trunk input
         dyb = lambda i: sp.dy[i % 4]
         bw: List[tuple] = []                 # ("conv", args) | ("wgrad", plan, xview, dyview, grad_off) | ("call", fn)
-        ws_bytes = 0
-
-        def wplan(n, h, w, xch, dych, convs, up=0):
-            nonlocal ws_bytes
-            p = ops.WgradPlan(device, dtc, n, h, w, xch, dych, convs, up=up)
-            ws_bytes = max(ws_bytes, p.workspace_bytes)
-            return p
+        wplans = ops.WgradPlans(device, dtc, N)
 
         if self.full:
             s = 1 << self.n_up
@@ -447,8 +426,7 @@ class TrunkEngine:
             sp.dsrp = new(N, hs, ws_, 4 if sp.thin_o else 32)
             sp.gA = new(N, hs, ws_, Cc)
             fptr = self.fp.flat.data_ptr()
-            if sp.thin_i or sp.thin_o:
-                sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device)
+            sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device) if (sp.thin_i or sp.thin_o) else None
             sp.gB = new(N, hs, ws_, Cc)
             sp.glo = [new(N, H << u, W << u, Cc) for u in range(0, self.n_up)]   # grads at the input res of upsampling u+1
 
@@ -456,18 +434,14 @@ class TrunkEngine:
                 return [dict(cin=ops.pad32(cin), cout=ops.pad32(cout), dw_off=self._poff(name + ".weight"), db_off=self._poff(name + ".bias"),
                              co_dst=cout, ci_dst=cin)]
             # conv4
-            if sp.thin_o:
-                w4 = fptr + 4 * self._poff("conv4.weight")
-                bw.append(("thin", ops.ThinLaunch("thin_wgrad", ops.thin_args(dtc, N, hs, ws_, self.out_ch, w4, V(sp.c3), w_big_is_cout=False, thin=sp.dsrp),
-                                                  dw_off=self._poff("conv4.weight"), db_off=self._poff("conv4.bias"), ws=sp.thin_ws)))
-                bw.append(("thin", ops.ThinLaunch("thin_in", ops.thin_args(dtc, N, hs, ws_, self.out_ch, w4, V(sp.gA), w_big_is_cout=False, flip=True,
-                                                                           mask=V(sp.c3), mask_slope=0.2, thin=sp.dsrp))))
-            else:
-                bw.append(("wgrad", wplan(N, hs, ws_, Cc, 32, one("conv4", self.out_ch, Cc)), V(sp.c3), V(sp.dsrp), 0))
-                bw.append(("conv", ops.conv_args(dtc, V(sp.dsrp), V(sp.gA), wptr + pk["offs"][("b", "conv4")], N, hs, ws_, 32, Cc, mask=V(sp.c3), mask_slope=0.2)))
+            w4 = fptr + 4 * self._poff("conv4.weight")
+            bw.append(ops.image_wgrad(dtc, sp.thin_o, wplans, sp.dsrp, sp.c3, w4, self._poff("conv4.weight"), self._poff("conv4.bias"), sp.thin_ws,
+                                      N, hs, ws_, self.out_ch, Cc, False, extra=(0,)))
+            bw.append(ops.image_to_features(dtc, sp.thin_o, sp.dsrp, V(sp.gA), w4, wptr + pk["offs"][("b", "conv4")], N, hs, ws_, self.out_ch, Cc, False,
+                                            flip=True, mask=V(sp.c3), mask_slope=0.2))
             # conv3
             src3 = sp.ups[-1] if self.n_up else sp.f0
-            bw.append(("wgrad", wplan(N, hs, ws_, Cc, Cc, one("conv3.0", Cc, Cc)), V(src3), V(sp.gA), 0))
+            bw.append(("wgrad", wplans.plan(hs, ws_, Cc, Cc, one("conv3.0", Cc, Cc)), V(src3), V(sp.gA), 0))
             if self.n_up:
                 bw.append(("conv", ops.conv_args(dtc, V(sp.gA), V(sp.gB), wptr + pk["offs"][("b", "conv3.0")], N, hs, ws_, Cc, Cc, mask=V(src3), mask_slope=0.2)))
             else:
@@ -480,7 +454,7 @@ class TrunkEngine:
                 npx = N * (hin * 2) * (win * 2)
                 cur_v = V(cur.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
                 oth_v = V(other.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
-                bw.append(("wgrad", wplan(N, hin, win, Cc, Cc, one(nm, Cc, Cc), up=1), V(xin_t), cur_v, 0))
+                bw.append(("wgrad", wplans.plan(hin, win, Cc, Cc, one(nm, Cc, Cc), up=1), V(xin_t), cur_v, 0))
                 glo = sp.glo[u - 1]
                 if self._parity(dtc):
                     # data gradient, nearest adjoint and (u >= 2: the input is the previous upsampling conv's LeakyReLU output) LeakyReLU' as
@@ -505,7 +479,7 @@ class TrunkEngine:
             d_f0 = cur if self.n_up else sp.gB
             sp.d_f0 = d_f0
             # conv2: f0 = out1 + conv2(trunk_out)
-            bw.append(("wgrad", wplan(N, H, W, Cc, Cc, one("conv2", Cc, Cc)), VC(sp.catb(R)), V(d_f0), 0))
+            bw.append(("wgrad", wplans.plan(H, W, Cc, Cc, one("conv2", Cc, Cc)), VC(sp.catb(R)), V(d_f0), 0))
             bw.append(("conv", ops.conv_args(dtc, V(d_f0), VD(dyb(R - 1)), wptr + pk["offs"][("b", "conv2")], N, H, W, Cc, Cc)))
             # gradient buckets for the data-parallel exchange (parallel.BucketReducer): parameters sit in named_parameters() order --
             # conv1, the dense blocks, conv2 and the tail -- so "everything from conv2 on" is one contiguous range, final here
@@ -528,7 +502,7 @@ class TrunkEngine:
                     convs.append(dict(ci_lo=0, cin=cin, co_lo=(0 if k == 5 else Cc + (4 - k) * G), cout=cout,
                                       dw_off=self._poff(pre + f"conv{k}.weight") - base, db_off=self._poff(pre + f"conv{k}.bias") - base,
                                       co_dst=cout, ci_dst=cin, alpha=(s5 if k == 5 else 1.0)))
-                plans[s5] = wplan(N, H, W, Ccat, Ccat, convs)
+                plans[s5] = wplans.plan(H, W, Ccat, Ccat, convs)
             blk = []
             for step in range(4):
                 kdim = Cc + step * G
@@ -552,19 +526,13 @@ class TrunkEngine:
         if self.full:
             bw.append(("call", (lambda x=V(sp.d_f0), y=V(sp.dx0): A.check(
                 A.lib().srganfd_axpby(x, y, dtc, N * H * W, Cc, 1.0, 1.0, A.stream_ptr()), "axpby"))))
-            if sp.thin_i:
-                bw.append(("thin", ops.ThinLaunch("thin_wgrad", ops.thin_args(dtc, N, H, W, self.in_ch, self.fp.flat.data_ptr() + 4 * self._poff("conv1.weight"),
-                                                                              V(sp.dx0), w_big_is_cout=True, thin=sp.xin),
-                                                  dw_off=self._poff("conv1.weight"), db_off=self._poff("conv1.bias"), ws=sp.thin_ws)))
-            else:
-                cin1 = ops.pad32(self.in_ch)
-                convs = [dict(cin=cin1, cout=Cc, dw_off=self._poff("conv1.weight"), db_off=self._poff("conv1.bias"), co_dst=Cc, ci_dst=self.in_ch)]
-                bw.append(("wgrad", wplan(N, H, W, cin1, Cc, convs), V(sp.xin), V(sp.dx0), 0))
+            bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, sp.xin, sp.dx0, fptr + 4 * self._poff("conv1.weight"), self._poff("conv1.weight"),
+                                      self._poff("conv1.bias"), sp.thin_ws, N, H, W, self.in_ch, Cc, True, extra=(0,)))
         # last bucket: whatever the earlier markers did not cover
         covered = min([it[1] for it in bw if it[0] == "ready"], default=self.fp.total)
         bw.append(("ready", 0, covered))
         sp.bw = bw
-        sp.wg_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        sp.wg_ws = wplans.workspace()
         # four more workspaces of the dense-block plan's size for the batched slab reduction (34 MB each at B=32, 128x128)
         dense_ws = max((p_.workspace_bytes for p_ in plans.values()), default=0)
         sp.wg_ws4 = [torch.empty(dense_ws, dtype=torch.uint8, device=device) for _ in range(_BATCH_REDUCE)] if (dense_ws and _BATCH_REDUCE > 1) else None
@@ -819,5 +787,5 @@ def discriminator_apply(owner: nn.Module, x: Tensor) -> Tensor:
 
 
 def content_loss_apply(owner: nn.Module, sr: Tensor, gt: Tensor) -> Tensor:
-    from .engine_d import content_loss_apply as f
+    from .engine_v import content_loss_apply as f
     return f(owner, sr, gt)

@@ -14,18 +14,16 @@ as 4 output-parity classes of 2x2-tap convs, the 2x2 stride-2 ones as 4 classes 
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional, Tuple
-
 import weakref
+from typing import List
 
 import torch
 from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
-from . import profiling
-from .engine import FlatParams, _dt, _engine, _require_gpu, _Shape, PlanCache, check_channels
+from .engine import _engine, _Shape
+from .engine_core import DiscriminatorEngineCore, discriminator_forward
 
 # (name, ksize, stride, pad) of the spectral-normalised convs, in forward order
 SN_LAYERS = [("conv1", 3, 2, 1), ("conv2", 3, 2, 1), ("conv3", 3, 2, 1), ("gating", 1, 1, 1), ("cat_1.convU", 3, 1, 1),
@@ -41,21 +39,16 @@ def _mod(owner: nn.Module, name: str) -> nn.Module:
     return m
 
 
-class AesrganDiscriminatorEngine:
+class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
+    what = "UNetDiscriminatorAesrgan"
+    batch_stats = True
+
     def __init__(self, owner: nn.Module):
-        self.owner = owner
-        self.fp = FlatParams(list(owner.named_parameters()))
+        super().__init__(owner, owner.conv0.weight.shape[1], [n + ".weight_orig" for n, _, _, _ in SN_LAYERS])
         self.nf = owner.conv0.weight.shape[0]
-        self.in_ch = owner.conv0.weight.shape[1]
         if self.nf != 64:
             raise A.SrganfdError("UNetDiscriminatorAesrgan: num_feat must be 64 (channel counts are multiples of 32, BatchNorm <= 256 channels)")
-        self.shapes = PlanCache()
-        self.packed: Dict[int, dict] = {}
-        self.token = 0
         self.sync_bn = None   # data parallel: SyncBatchNormReduce -- batch statistics over all ranks (set by GanTrainer(sync_batchnorm=True))
-
-    def _poff(self, n):
-        return self.fp.off(n)
 
     def _wshape(self, name):
         w = _mod(self.owner, name)
@@ -64,33 +57,23 @@ class AesrganDiscriminatorEngine:
 
     # ---- packing ----
     def _build_pack(self, dtc, device):
-        jobs, offs, cur = [], {}, 0
+        pb = ops.PackBuilder(dtc)
 
-        def add(key, ksize, k, n, seg):
-            nonlocal cur
-            offs[key] = cur
-            jobs.append(ops.pack_job(cur, dtc, ksize, k, n, [seg]))
-            cur += (ops.packed_bytes(dtc, ksize, k, n) + 255) // 256 * 256
-
-        def plain(name, ks, fwd=True, bwd=True):
+        def plain(name, ks):
             co, ci = self._wshape(name)
-            src = self._poff(name + ".weight")
-            if fwd:
-                add(("f", name), ks, ops.pad32(ci), ops.pad32(co), dict(src_off=src, co_src=co, ci_src=ci, k_len=ops.pad32(ci)))
-            if bwd:
-                add(("b", name), ks, ops.pad32(co), ops.pad32(ci), dict(src_off=src, co_src=co, ci_src=ci, k_len=ops.pad32(co), transposed=1))
+            pb.fwd(("f", name), self._poff(name + ".weight"), co, ci, ks)
+            pb.bwd(("b", name), self._poff(name + ".weight"), co, ci, ks)
         plain("conv0", 3)
         plain("conv9", 3)
         for l, (name, ks, st, _) in enumerate(SN_LAYERS):
             co, ci = self._wshape(name)
             src = self._poff(name + ".weight_orig")
             sc = 2 * l + 1
-            add(("f", name), ks, ci, co, dict(src_off=src, co_src=co, ci_src=ci, k_len=ci, scale_off=sc))
+            pb.fwd(("f", name), src, co, ci, ks, scale_off=sc)
             if st == 1:
-                add(("b", name), ks, co, ci, dict(src_off=src, co_src=co, ci_src=ci, k_len=co, transposed=1, scale_off=sc))
-            else:
-                for par in range(4):   # 3x3 stride-2 data gradient: 4 parity classes of 2x2-tap convs
-                    add(("b", name, par), 2, co, ci, dict(src_off=src, co_src=co, ci_src=ci, k_len=co, transposed=6 + par, scale_off=sc))
+                pb.bwd(("b", name), src, co, ci, ks, scale_off=sc)
+            else:                      # 3x3 stride-2 data gradient: 4 parity classes of 2x2-tap convs
+                pb.classes(("b", name), src, co, ci, 2, 6, scale_off=sc)
         for k in (1, 2, 3):
             pre = f"attn_{k}"
             plain(pre + ".W.0", 1)
@@ -98,34 +81,9 @@ class AesrganDiscriminatorEngine:
             plain(pre + ".psi", 1)
             co, ci = self._wshape(pre + ".theta")
             src = self._poff(pre + ".theta.weight")
-            add(("f", pre + ".theta"), 2, ci, co, dict(src_off=src, co_src=co, ci_src=ci, k_len=ci))
-            for ab in range(4):        # 2x2 stride-2 data gradient: 4 classes of 1x1 convs
-                add(("b", pre + ".theta", ab), 1, co, ci, dict(src_off=src, co_src=co, ci_src=ci, k_len=co, transposed=10 + ab))
-        return dict(table=ops.PackTable(jobs, device), offs=offs, buf=torch.empty(cur, dtype=torch.uint8, device=device))
-
-    def _ensure_packed(self, dtc, device):
-        flat = self.fp.sync(device)
-        pk = self.packed.get(dtc)
-        if pk is None or pk["buf"].device != device or pk.get("flat_ptr") != flat.data_ptr():
-            pk = self._build_pack(dtc, device)
-            pk["flat_ptr"] = flat.data_ptr()
-            pk["scalars"] = torch.ones(2 * len(SN_LAYERS), dtype=torch.float32, device=device)
-            pk["sn_ws"] = torch.empty(sum(A.sn_ws_floats(self._wshape(n)[0], self._wshape(n)[1] * ks * ks) for n, ks, _, _ in SN_LAYERS),
-                                      dtype=torch.float32, device=device)
-            self.packed[dtc] = pk
-        return pk
-
-    def _spectral_norm_and_pack(self, pk, training):
-        flat = self.fp.flat
-        sc = pk["scalars"].data_ptr()
-        layers = []
-        for l, (name, ks, _, _) in enumerate(SN_LAYERS):
-            co, ci = self._wshape(name)
-            m = _mod(self.owner, name)
-            layers.append((flat.data_ptr() + 4 * self._poff(name + ".weight_orig"), m.weight_u.data_ptr(), m.weight_v.data_ptr(), co, ci * ks * ks,
-                           sc + 8 * l, sc + 8 * l + 4))
-        ops.spectral_norm_batch(layers, training, pk["sn_ws"])
-        pk["table"].run(flat, pk["buf"], pk["scalars"])
+            pb.fwd(("f", pre + ".theta"), src, co, ci, 2)
+            pb.classes(("b", pre + ".theta"), src, co, ci, 1, 10)      # 2x2 stride-2 data gradient: 4 classes of 1x1 convs
+        return pb.finish(device)
 
     # ---- plan ----
     def _plan(self, N, H, W, dt, dtc, device, pk):
@@ -152,7 +110,7 @@ class AesrganDiscriminatorEngine:
         B = sp.B = {}
         # conv0 (in_ch -> nf) and conv9 (nf -> 1) on the thin-side kernels in the 16-bit modes (csrc/conv_thin.hip): 4-channel pitch
         sp.thin_i, sp.thin_o = ops.thin_ok(dtc, nf, self.in_ch), ops.thin_ok(dtc, nf, 1)
-        B["xin"] = new(H, W, 4 if sp.thin_i else 32)
+        B["xin"] = sp.xin = new(H, W, 4 if sp.thin_i else 32)
         B["x0"], B["x1"], B["x2"], B["x3"] = new(*R[0], nf), new(*R[1], 2 * nf), new(*R[2], 4 * nf), new(*R[3], 8 * nf)
         B["gated"] = new(Hg, Wg, 4 * nf)
         B["cat1"], B["cat2"], B["cat3"] = new(*R[2], 8 * nf), new(*R[1], 4 * nf), new(*R[0], 2 * nf)
@@ -166,9 +124,8 @@ class AesrganDiscriminatorEngine:
         st = A.stream_ptr
         rs = lambda op, a, b, h, w, c, dtype=dtc: call(lambda: A.check(L.srganfd_resample(op, a, b, dtype, N, h, w, c, st()), "resample"))
         fw: List[tuple] = [
-            ("thin", ops.ThinLaunch("thin_in", ops.thin_args(dtc, N, H, W, self.in_ch, P("conv0.weight"), V(B["x0"]), w_big_is_cout=True, bias=P("conv0.bias"),
-                                                             thin=B["xin"], **lre)))
-            if sp.thin_i else cv(V(B["xin"]), V(B["x0"]), Wp("f", "conv0"), N, H, W, 32, nf, bias=P("conv0.bias"), **lre),
+            ops.image_to_features(dtc, sp.thin_i, B["xin"], V(B["x0"]), P("conv0.weight"), Wp("f", "conv0"), N, H, W, self.in_ch, nf, True,
+                                  bias=P("conv0.bias"), **lre),
             cv(V(B["x0"]), V(B["x1"]), Wp("f", "conv1"), N, *R[0], nf, 2 * nf, stride=2, **lre),
             cv(V(B["x1"]), V(B["x2"]), Wp("f", "conv2"), N, *R[1], 2 * nf, 4 * nf, stride=2, **lre),
             cv(V(B["x2"]), V(B["x3"]), Wp("f", "conv3"), N, *R[2], 4 * nf, 8 * nf, stride=2, **lre),
@@ -217,12 +174,9 @@ class AesrganDiscriminatorEngine:
             cv(V(B["c7"]), V(B["c8"]), Wp("f", "conv8"), N, *R[0], nf, nf, **lre),
         ]
         sp.fw = fw
-        if sp.thin_o:
-            sp.conv9 = lambda logits: ("thin", ops.ThinLaunch("thin_out", ops.thin_args(dtc, N, H, W, 1, P("conv9.weight"), V(B["c8"]), w_big_is_cout=False,
-                                                                                        bias=P("conv9.bias"), thin_out=logits.data_ptr(), thin_out_pitch=1)))
-        else:
-            sp.conv9 = lambda logits: ("conv", ops.conv_args(dtc, V(B["c8"]), A.View(logits.data_ptr(), 1, 0), Wp("f", "conv9"), N, H, W, nf, 32,
-                                                             cout_store=1, bias=P("conv9.bias"), y_f32=True))
+        thin_o = sp.thin_o
+        sp.logits_conv = lambda logits: ops.features_to_image(dtc, thin_o, V(B["c8"]), logits.data_ptr(), 1, P("conv9.weight"), Wp("f", "conv9"),
+                                                              N, H, W, 1, nf, False, bias=P("conv9.bias"))
         sp.R, sp.Rg = R, (Hg, Wg)
         self._plan_backward(sp, pk)
         self.shapes[key] = sp
@@ -240,43 +194,27 @@ class AesrganDiscriminatorEngine:
 
         def new(h, w, c, dtype=dt):
             return torch.empty(N, h, w, c, dtype=dtype, device=device)
-        ws_bytes = 0
+        wplans = ops.WgradPlans(device, dtc, N)
 
-        def wg(name, x, dy, h, w, cin, cout, k=3, s=1, pad=1, sn=False, cin_real=None, cout_real=None, bias=False, x_c0=0, dy_c0=0):
-            nonlocal ws_bytes
-            pname = name + (".weight_orig" if sn else ".weight")
-            conv = dict(cin=cin, cout=cout, dw_off=self._poff(pname), db_off=(self._poff(name + ".bias") if bias else -1),
-                        co_dst=cout_real or cout, ci_dst=cin_real or cin)
-            plan = ops.WgradPlan(device, dtc, N, h, w, cin, cout, [conv], ksize=k, stride=s, pad=pad)
-            ws_bytes = max(ws_bytes, plan.workspace_bytes)
-            return ("wgrad", plan, V(x, c0=x_c0), V(dy, c0=dy_c0), SN_INDEX[name] if sn else None, name, k)
+        def wg(name, x, dy, h, w, cin, cout, k=3, s=1, pad=1, sn=False, cin_real=None, cout_real=None, bias=False, dy_c0=0):
+            plan = wplans.conv(h, w, cin, cout, self._poff(name + (".weight_orig" if sn else ".weight")), self._poff(name + ".bias") if bias else -1,
+                               cin_real, cout_real, ksize=k, stride=s, pad=pad)
+            return ("wgrad", plan, V(x), V(dy, c0=dy_c0), SN_INDEX[name] if sn else None)
 
         cv = lambda *a, **k: ("conv", ops.conv_args(dtc, *a, **k))
         call = lambda fn: ("call", fn)
         rs = lambda op, a, b, h, w, c, dtype=dtc: call(lambda: A.check(L.srganfd_resample(op, a, b, dtype, N, h, w, c, st()), "resample"))
         lb = lambda dy, act, out, npix, c, slope=0.2: call(lambda: A.check(L.srganfd_lrelu_bwd(dy, act, A.NULL_VIEW, out, dtc, npix, c, slope, st()), "lrelu_bwd"))
 
-        def strided_dgrad(key_fn, ks, dy, dx, hd, wd, cin_op, cout_op, r1=None, r2=None, mask=None):
+        def strided_dgrad(key, ks, dy, dx, hd, wd, cin_op, cout_op, r1=None, r2=None, mask=None):
             """4 parity classes writing a (2hd x 2wd) image: ks=2 (3x3 s2 conv) or ks=1 (2x2 s2 conv)"""
-            items = []
-            one = ops.class4_ok(dtc, cout_op, [O[key_fn(c)] for c in range(4)], ops.packed_bytes(dtc, ks, cin_op, cout_op), ksize=ks)
-            for par in range(1 if one else 4):
-                py, px = par >> 1, par & 1
-                a = ops.conv_args(dtc, V(dy), V(dx), Wp(*key_fn(par)), N, hd, wd, cin_op, cout_op, ksize=ks, stride=1, pad=0,
-                                  r1=V(r1) if r1 is not None else A.NULL_VIEW, r1_scale=1.0 if r1 is not None else 0.0,
-                                  r2=V(r2) if r2 is not None else A.NULL_VIEW, r2_scale=1.0 if r2 is not None else 0.0,
-                                  mask=V(mask) if mask is not None else A.NULL_VIEW, mask_slope=0.2)
-                a.h_out, a.w_out = hd, wd
-                a.out_sy, a.out_sx, a.out_oy, a.out_ox = 2, 2, py, px
-                a.out_h_full, a.out_w_full = 2 * hd, 2 * wd
-                a.pad_y, a.pad_x = 0, 0
-                a.out_classes, a.class_pad_step = (4, 0) if one else (0, 0)     # one launch: every class reads the same window of dy
-                items.append(("conv", a))
-            return items
+            view = lambda t: None if t is None else V(t)
+            return [("conv", a) for a in ops.parity_class_launches(      # class_pad 0: every class reads the same window of dy
+                dtc, V(dy), V(dx), wptr, [O[key + (c,)] for c in range(4)], N, hd, wd, cin_op, cout_op, ks, 0,
+                **ops.dgrad_epilogue(view(r1), view(r2), view(mask)))]
 
         sp.dl = new(H, W, 4 if sp.thin_o else 32)
-        if sp.thin_i or sp.thin_o:
-            sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device)
+        sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device) if (sp.thin_i or sp.thin_o) else None
         G = sp.G = {}
         G["g8"], G["g7"], G["g6"] = new(*R[0], nf), new(*R[0], nf), new(*R[0], nf)
         G["dc3"], G["db5"], G["dx5"] = new(*R[0], 2 * nf), new(*R[0], 2 * nf), new(*R[1], 2 * nf)
@@ -296,7 +234,6 @@ class AesrganDiscriminatorEngine:
             D["dsigup"] = torch.empty(N, h, w, 1, dtype=torch.float32, device=device)
             D["dsig"] = torch.empty(N, hh, wh, 1, dtype=torch.float32, device=device)
             D["dpsip"], D["df"], D["dxt"], D["dphi"] = new(hh, wh, 32), new(hh, wh, Ck), new(h, w, Ck), new(Hg, Wg, Ck)
-            bn = _mod(self.owner, pre + ".W.1")
             items = [
                 ("bn_bwd", (V(T["wy"]), V(dcat), V(D["dwy"]), N * h * w, Ck, pre, T["save"])),
                 wg(pre + ".W.0", T["y"], D["dwy"], h, w, Ck, Ck, k=1, pad=0, bias=True),
@@ -311,7 +248,7 @@ class AesrganDiscriminatorEngine:
                 cv(V(D["dpsip"]), V(D["df"]), Wp("b", pre + ".psi"), N, hh, wh, 32, Ck, ksize=1, pad=0, mask=V(T["f"]), mask_slope=0.0),
                 wg(pre + ".theta", B[xname], D["df"], h, w, Ck, Ck, k=2, s=2, pad=0),
             ]
-            items += strided_dgrad(lambda par: ("b", pre + ".theta", par), 1, D["df"], D["dxt"], hh, wh, Ck, Ck)
+            items += strided_dgrad(("b", pre + ".theta"), 1, D["df"], D["dxt"], hh, wh, Ck, Ck)
             items += [
                 call(lambda a=V(D["df"]), b=V(D["dphi"]), hh=hh, wh=wh, Ck=Ck: A.check(
                     L.srganfd_resize_bilinear(1, a, b, dtc, N, Hg, Wg, hh, wh, Ck, st()), "resize_bwd")),
@@ -322,15 +259,11 @@ class AesrganDiscriminatorEngine:
             ]
             return items
 
-        if sp.thin_o:
-            head = [("thin", ops.ThinLaunch("thin_wgrad", ops.thin_args(dtc, N, H, W, 1, P("conv9.weight"), V(B["c8"]), w_big_is_cout=False, thin=sp.dl),
-                                            dw_off=self._poff("conv9.weight"), db_off=self._poff("conv9.bias"), ws=sp.thin_ws)),
-                    ("thin", ops.ThinLaunch("thin_in", ops.thin_args(dtc, N, H, W, 1, P("conv9.weight"), V(G["g8"]), w_big_is_cout=False, flip=True,
-                                                                     mask=V(B["c8"]), mask_slope=0.2, thin=sp.dl)))]
-        else:
-            head = [wg("conv9", B["c8"], sp.dl, H, W, nf, 32, cout_real=1, bias=True),
-                    cv(V(sp.dl), V(G["g8"]), Wp("b", "conv9"), N, H, W, 32, nf, mask=V(B["c8"]), mask_slope=0.2)]
-        bw: List[tuple] = head + [
+        bw: List[tuple] = [
+            ops.image_wgrad(dtc, sp.thin_o, wplans, sp.dl, B["c8"], P("conv9.weight"), self._poff("conv9.weight"), self._poff("conv9.bias"), sp.thin_ws,
+                            N, H, W, 1, nf, False, extra=(None,)),
+            ops.image_to_features(dtc, sp.thin_o, sp.dl, V(G["g8"]), P("conv9.weight"), Wp("b", "conv9"), N, H, W, 1, nf, False, flip=True,
+                                  mask=V(B["c8"]), mask_slope=0.2),
             wg("conv8", B["c7"], G["g8"], H, W, nf, nf, sn=True),
             cv(V(G["g8"]), V(G["g7"]), Wp("b", "conv8"), N, H, W, nf, nf, mask=V(B["c7"]), mask_slope=0.2),
             wg("conv7", B["x6"], G["g7"], H, W, nf, nf, sn=True),
@@ -370,170 +303,68 @@ class AesrganDiscriminatorEngine:
                mask=V(B["x3"]), mask_slope=0.2),
             wg("conv3", B["x2"], G["dx3"], *R[2], 4 * nf, 8 * nf, s=2, sn=True),
         ]
-        bw += strided_dgrad(lambda par: ("b", "conv3", par), 2, G["dx3"], G["dx2"], *R[3], 8 * nf, 4 * nf,
+        bw += strided_dgrad(("b", "conv3"), 2, G["dx3"], G["dx2"], *R[3], 8 * nf, 4 * nf,
                             r1=sp.attn[1]["grad"]["dxg"], r2=sp.attn[1]["grad"]["dxt"], mask=B["x2"])
         bw.append(wg("conv2", B["x1"], G["dx2"], *R[1], 2 * nf, 4 * nf, s=2, sn=True))
-        bw += strided_dgrad(lambda par: ("b", "conv2", par), 2, G["dx2"], G["dx1"], *R[2], 4 * nf, 2 * nf,
+        bw += strided_dgrad(("b", "conv2"), 2, G["dx2"], G["dx1"], *R[2], 4 * nf, 2 * nf,
                             r1=sp.attn[2]["grad"]["dxg"], r2=sp.attn[2]["grad"]["dxt"], mask=B["x1"])
         bw.append(wg("conv1", B["x0"], G["dx1"], *R[0], nf, 2 * nf, s=2, sn=True))
-        bw += strided_dgrad(lambda par: ("b", "conv1", par), 2, G["dx1"], G["dx0"], *R[1], 2 * nf, nf,
+        bw += strided_dgrad(("b", "conv1"), 2, G["dx1"], G["dx0"], *R[1], 2 * nf, nf,
                             r1=sp.attn[3]["grad"]["dxg"], r2=sp.attn[3]["grad"]["dxt"], mask=B["x0"])
-        if sp.thin_i:
-            bw.append(("thin", ops.ThinLaunch("thin_wgrad", ops.thin_args(dtc, N, H, W, self.in_ch, P("conv0.weight"), V(G["dx0"]), w_big_is_cout=True, thin=B["xin"]),
-                                              dw_off=self._poff("conv0.weight"), db_off=self._poff("conv0.bias"), ws=sp.thin_ws)))
-            sp.dx_conv = ops.ThinLaunch("thin_out", ops.thin_args(dtc, N, H, W, self.in_ch, P("conv0.weight"), V(G["dx0"]), w_big_is_cout=True, flip=True,
-                                                                  thin_out=sp.dxp, thin_out_pitch=4))
-        else:
-            bw.append(wg("conv0", B["xin"], G["dx0"], H, W, 32, nf, cin_real=self.in_ch, bias=True))
-            sp.dx_conv = ops.conv_args(dtc, V(G["dx0"]), V(sp.dxp), Wp("b", "conv0"), N, H, W, nf, 32, cout_store=self.in_ch, y_f32=True)
+        bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, B["xin"], G["dx0"], P("conv0.weight"), self._poff("conv0.weight"), self._poff("conv0.bias"),
+                                  sp.thin_ws, N, H, W, self.in_ch, nf, True, extra=(None,)))
+        sp.dx_conv = ops.features_to_image(dtc, sp.thin_i, V(G["dx0"]), sp.dxp, 4, P("conv0.weight"), Wp("b", "conv0"), N, H, W, self.in_ch, nf, True, flip=True)
         sp.bw = bw
-        sp.wg_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-        sp.gtmp = torch.zeros(self.fp.total, dtype=torch.float32, device=device)
-        sp.sn_ws = torch.empty(len(SN_LAYERS) * A.SN_GRAD_WS_FLOATS, dtype=torch.float32, device=device)
+        self._backward_workspaces(sp, wplans)
 
-    # ---- execution ----
-    def _run_conv(self, L, st, a, rec, what):
-        if rec is None:
-            rc = L.srganfd_conv2d(C.byref(a), st)
-            if rc:
-                A.check(rc, what)
+    # ---- execution: the core's loops, plus the attention gates' BatchNorm ----
+    def _forward_item(self, kind, item, sp, training, L, st) -> None:
+        """("bn", ...): BatchNorm2d of an attention gate's W branch, written into its half of the concatenation buffer"""
+        k, xv, yv, npix, Ck, gamma, beta, bn, save = item
+        dtc = sp.dtc
+        if bn.running_mean.device != sp.device:
+            raise A.SrganfdError("BatchNorm buffers must live on the module's GPU")
+        if training and self.sync_bn is not None:
+            # (sum x, sum x^2) of this rank's pixels -> summed over the ranks -> statistics of the whole batch (pixel count = ranks * npix)
+            sb, ws = self.sync_bn, sp.bn_ws
+            args = (xv, yv, dtc, npix, Ck, gamma, beta, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.momentum, bn.eps,
+                    save.data_ptr(), ws.data_ptr(), 1.0)
+            A.check(L.srganfd_batchnorm_fwd_sync(*args, 1, 0, st), "batchnorm_fwd_sync")
+            sb.all_reduce(ws[:L.srganfd_batchnorm_partial_floats(Ck)])
+            A.check(L.srganfd_batchnorm_fwd_sync(*args, 2, npix * sb.world, st), "batchnorm_fwd_sync")
         else:
-            rec.bracket(profiling.conv_label(a), profiling.conv_work(a), lambda: A.check(L.srganfd_conv2d(C.byref(a), st), what))
+            A.check(L.srganfd_batchnorm_fwd(xv, yv, dtc, npix, Ck, gamma, beta, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                                            bn.momentum, bn.eps, 1 if training else 0, save.data_ptr(), sp.bn_ws.data_ptr(), st), "batchnorm_fwd")
+        if training:
+            bn.num_batches_tracked += 1
 
     def forward(self, x: Tensor, training: bool) -> Tensor:
-        check_channels("UNetDiscriminatorAesrgan", x, self.in_ch)
-        _require_gpu(x)
-        dt, dtc = _dt(self.owner)
-        dev = x.device
-        pk = self._ensure_packed(dtc, dev)
-        self._spectral_norm_and_pack(pk, training)
-        N, _, H, W = x.shape
-        sp = self._plan(N, H, W, dt, dtc, dev, pk)
-        L, st = A.lib(), A.stream_ptr()
-        x = x.contiguous().float()
-        A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.in_ch, H, W, A.view(sp.B["xin"]), dtc, sp.B["xin"].shape[-1], None, None, st), "nchw_to_nhwc")
-        logits = torch.empty(N, 1, H, W, dtype=torch.float32, device=dev)
-        rec = profiling.REC
-        for kind, item in sp.fw + [sp.conv9(logits)]:
-            if kind == "thin":
-                item.launch(rec)
-            elif kind == "conv":
-                self._run_conv(L, st, item, rec, "conv2d")
-            elif kind == "bn":
-                k, xv, yv, npix, Ck, gamma, beta, bn, save = item
-                if bn.running_mean.device != dev:
-                    raise A.SrganfdError("BatchNorm buffers must live on the module's GPU")
-                if training and self.sync_bn is not None:
-                    # (sum x, sum x^2) of this rank's pixels -> summed over the ranks -> statistics of the whole batch (pixel count = ranks * npix)
-                    sb, ws = self.sync_bn, sp.bn_ws
-                    args = (xv, yv, dtc, npix, Ck, gamma, beta, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.momentum, bn.eps,
-                            save.data_ptr(), ws.data_ptr(), 1.0)
-                    A.check(L.srganfd_batchnorm_fwd_sync(*args, 1, 0, st), "batchnorm_fwd_sync")
-                    sb.all_reduce(ws[:L.srganfd_batchnorm_partial_floats(Ck)])
-                    A.check(L.srganfd_batchnorm_fwd_sync(*args, 2, npix * sb.world, st), "batchnorm_fwd_sync")
-                else:
-                    A.check(L.srganfd_batchnorm_fwd(xv, yv, dtc, npix, Ck, gamma, beta, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                                    bn.momentum, bn.eps, 1 if training else 0, save.data_ptr(), sp.bn_ws.data_ptr(), st), "batchnorm_fwd")
-                if training:
-                    bn.num_batches_tracked += 1
-            else:
-                item()
-        o = self.owner
-        o.ly1, o.ly2, o.ly3 = (sp.attn[k]["sigup"].view(N, 1, *sp.attn[k]["dims"][:2]).clone() for k in (1, 2, 3))
-        self.token += 1
-        sp.token = self.token
-        sp.inv_sigma = pk["scalars"]
-        sp.training = training
-        self._last = sp
+        logits = super().forward(x, training)
+        sp, o = self._last, self.owner
+        o.ly1, o.ly2, o.ly3 = (sp.attn[k]["sigup"].view(sp.N, 1, *sp.attn[k]["dims"][:2]).clone() for k in (1, 2, 3))
         return logits
 
-    def backward(self, sp, token, dlogits, need_wgrad, need_dx):
-        if getattr(sp, "token", None) != token:
-            raise A.SrganfdError("discriminator activations / spectral-norm state were overwritten by a later forward before backward ran")
-        if not sp.training:
-            raise A.SrganfdError("UNetDiscriminatorAesrgan backward is implemented for training-mode forwards (BatchNorm batch statistics)")
-        L, st = A.lib(), A.stream_ptr()
-        N, H, W, dtc = sp.N, sp.H, sp.W, sp.dtc
-        dlogits = dlogits.contiguous().float()
-        A.check(L.srganfd_nchw_to_nhwc(dlogits.data_ptr(), N, 1, H, W, A.view(sp.dl), dtc, sp.dl.shape[-1], None, None, st), "nchw_to_nhwc")
-        flat = self.fp.flat
-        # the flat gradient also receives BatchNorm's dgamma/dbeta; frozen-parameter passes write them to scratch
-        flat_grad = self.fp.new_grad(sp.device) if need_wgrad else sp.gtmp
-        rec = profiling.REC
-        sn_grads = []
-        for item in sp.bw:
-            kind = item[0]
-            if kind == "conv":
-                self._run_conv(L, st, item[1], rec, "conv2d(dgrad)")
-            elif kind == "thin":
-                if item[1].is_wgrad and not need_wgrad:
-                    continue
-                item[1].launch(rec, flat_grad.data_ptr())
-            elif kind == "wgrad":
-                if not need_wgrad:
-                    continue
-                _, plan, xv, dyv, sn_index, name, ks = item
-                dst = flat_grad if sn_index is None else sp.gtmp
-                run = lambda: A.check(L.srganfd_conv2d_wgrad(plan.host, plan.dev.data_ptr(), xv, dyv, dst.data_ptr(), None, sp.wg_ws.data_ptr(),
-                                                             sp.wg_ws.numel(), st), "conv2d_wgrad")
-                if rec is None:
-                    run()
-                else:
-                    rec.bracket(plan.label, (plan.flops, plan.nbytes), run)
-                if sn_index is not None:
-                    co, ci = self._wshape(name)
-                    off = 4 * self._poff(name + ".weight_orig")
-                    m = _mod(self.owner, name)
-                    sn_grads.append((sp.gtmp.data_ptr() + off, flat.data_ptr() + off, m.weight_u.data_ptr(), m.weight_v.data_ptr(),
-                                     sp.inv_sigma.data_ptr() + 4 * (2 * sn_index + 1), flat_grad.data_ptr() + off, co, ci * ks * ks))
-            elif kind == "bn_bwd":
-                xv, dyv, dxv, npix, Ck, pre, save = item[1]
-                if self.sync_bn is not None:
-                    # dgamma/dbeta stay this rank's sums (the flat-gradient all-reduce averages them with everything else); the
-                    # dx coefficients need (sum dy, sum dy*xhat) over the whole batch
-                    sb, ws = self.sync_bn, sp.bn_ws
-                    nfl = L.srganfd_batchnorm_partial_floats(Ck)
-                    if sp.bn_ws_global is None:
-                        sp.bn_ws_global = torch.empty(L.srganfd_batchnorm_partial_floats(256), dtype=torch.float32, device=ws.device)
-                    args = (xv, dyv, dxv, dtc, npix, Ck, flat.data_ptr() + 4 * self._poff(pre + ".W.1.weight"), save.data_ptr(),
-                            flat_grad.data_ptr() + 4 * self._poff(pre + ".W.1.weight"), flat_grad.data_ptr() + 4 * self._poff(pre + ".W.1.bias"),
-                            0.0, ws.data_ptr(), sp.bn_ws_global.data_ptr(), A.NULL_VIEW, 1.0)
-                    A.check(L.srganfd_batchnorm_bwd_sync(*args, 1, 0, st), "batchnorm_bwd_sync")
-                    sp.bn_ws_global[:nfl].copy_(ws[:nfl])
-                    sb.all_reduce(sp.bn_ws_global[:nfl])
-                    A.check(L.srganfd_batchnorm_bwd_sync(*args, 2, npix * sb.world, st), "batchnorm_bwd_sync")
-                else:
-                    A.check(L.srganfd_batchnorm_bwd(xv, dyv, dxv, dtc, npix, Ck, flat.data_ptr() + 4 * self._poff(pre + ".W.1.weight"), save.data_ptr(),
-                                                    flat_grad.data_ptr() + 4 * self._poff(pre + ".W.1.weight"),
-                                                    flat_grad.data_ptr() + 4 * self._poff(pre + ".W.1.bias"), 0.0, sp.bn_ws.data_ptr(), st), "batchnorm_bwd")
-            else:
-                item[1]()
-        ops.spectral_norm_grad_batch(sn_grads, sp.sn_ws)       # dL/d(W/sigma) -> dL/dW_orig for every normalised layer, batched
-        dx = None
-        if need_dx:
-            if type(sp.dx_conv) is ops.ThinLaunch:
-                sp.dx_conv.launch(rec)
-            else:
-                A.check(L.srganfd_conv2d(C.byref(sp.dx_conv), st), "conv2d(dgrad conv0)")
-            dx = torch.empty(N, self.in_ch, H, W, dtype=torch.float32, device=sp.device)
-            A.check(L.srganfd_nhwc_to_nchw(A.view(sp.dxp), A.F32, N, self.in_ch, H, W, dx.data_ptr(), 0, st), "nhwc_to_nchw")
-        return (flat_grad if need_wgrad else None), dx
-
-
-class _AesrganFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, eng, training, *params):
-        out = eng.forward(x, training)
-        ctx.eng, ctx.sp, ctx.token = eng, eng._last, eng.token
-        ctx.need_dx = ctx.needs_input_grad[0]
-        ctx.need_w = any(ctx.needs_input_grad[3:])
-        return out
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        g, dx = ctx.eng.backward(ctx.sp, ctx.token, dlogits, ctx.need_w, ctx.need_dx)
-        grads = tuple(ctx.eng.fp.grad_views(g)) if g is not None else tuple(None for _ in ctx.eng.fp.params)
-        return (dx, None, None) + grads
+    def _backward_item(self, item, sp, flat_grad, L, st) -> None:
+        """("bn_bwd", ...): the flat gradient receives dgamma / dbeta"""
+        xv, dyv, dxv, npix, Ck, pre, save = item[1]
+        dtc, flat = sp.dtc, self.fp.flat
+        gamma, beta = 4 * self._poff(pre + ".W.1.weight"), 4 * self._poff(pre + ".W.1.bias")
+        if self.sync_bn is not None:
+            # dgamma/dbeta stay this rank's sums (the flat-gradient all-reduce averages them with everything else); the
+            # dx coefficients need (sum dy, sum dy*xhat) over the whole batch
+            sb, ws = self.sync_bn, sp.bn_ws
+            nfl = L.srganfd_batchnorm_partial_floats(Ck)
+            if sp.bn_ws_global is None:
+                sp.bn_ws_global = torch.empty(L.srganfd_batchnorm_partial_floats(256), dtype=torch.float32, device=ws.device)
+            args = (xv, dyv, dxv, dtc, npix, Ck, flat.data_ptr() + gamma, save.data_ptr(), flat_grad.data_ptr() + gamma, flat_grad.data_ptr() + beta,
+                    0.0, ws.data_ptr(), sp.bn_ws_global.data_ptr(), A.NULL_VIEW, 1.0)
+            A.check(L.srganfd_batchnorm_bwd_sync(*args, 1, 0, st), "batchnorm_bwd_sync")
+            sp.bn_ws_global[:nfl].copy_(ws[:nfl])
+            sb.all_reduce(sp.bn_ws_global[:nfl])
+            A.check(L.srganfd_batchnorm_bwd_sync(*args, 2, npix * sb.world, st), "batchnorm_bwd_sync")
+        else:
+            A.check(L.srganfd_batchnorm_bwd(xv, dyv, dxv, dtc, npix, Ck, flat.data_ptr() + gamma, save.data_ptr(), flat_grad.data_ptr() + gamma,
+                                            flat_grad.data_ptr() + beta, 0.0, sp.bn_ws.data_ptr(), st), "batchnorm_bwd")
 
 
 def aesrgan_engine(owner: nn.Module) -> AesrganDiscriminatorEngine:
@@ -541,7 +372,4 @@ def aesrgan_engine(owner: nn.Module) -> AesrganDiscriminatorEngine:
 
 
 def aesrgan_discriminator_apply(owner: nn.Module, x: Tensor) -> Tensor:
-    eng = aesrgan_engine(owner)
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in eng.fp.params)):
-        return _AesrganFn.apply(x, eng, owner.training, *eng.fp.params)
-    return eng.forward(x, owner.training)
+    return discriminator_forward(aesrgan_engine(owner), owner, x)

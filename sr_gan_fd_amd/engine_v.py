@@ -1,6 +1,10 @@
-"""Differentiable single-node VGG-19 content loss: ESRGAN/model.py:258-292.
+"""The two VGG-19 content losses: BSRGAN's five-node, forward-only one (ContentLossEngine) and ESRGAN's differentiable single-node
+one (ContentLossGradEngine).  Both run SR and GT through the extractor as one 2N batch of normalised NHWC images, pack
+``features.*`` the same way and put ``features.0`` (3 -> 64) on the thin-side kernel in the 16-bit modes (VggEngineBase).
 
-ESRGAN's ContentLoss is ``F.l1_loss(vgg(sr)[node], vgg(gt)[node])`` with ONE node (``features.34`` in esrgan_config) and,
+ContentLossEngine: ContentLoss.forward BSRGAN/model.py:536-554 (the reference detaches the result, :552).
+
+ContentLossGradEngine: ESRGAN/model.py:258-292.  ESRGAN's ContentLoss is ``F.l1_loss(vgg(sr)[node], vgg(gt)[node])`` with ONE node (``features.34`` in esrgan_config) and,
 unlike BSRGAN's five-node version, it stays in the autograd graph: the generator receives its gradient, so the frozen
 VGG needs a backward pass.  SR and GT run through the extractor as one 2N batch; every ReLU output of the SR half is kept.
 Backward = sign(sr_f - gt_f) / numel at the node, then per conv the data-gradient launch of the implicit-GEMM kernel with
@@ -9,8 +13,7 @@ final relayout that undoes the normalisation's 1/std.  No weight gradients (the 
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 from torch import Tensor, nn
@@ -18,41 +21,141 @@ from torch import Tensor, nn
 from . import _abi as A
 from . import ops
 from . import profiling
-from .engine import FlatParams, _dt, _engine, _require_gpu, _Shape, PlanCache
+from .engine import EngineBase, _dt, _engine, _require_gpu, _Shape
 
 
-class ContentLossGradEngine:
+class VggEngineBase(EngineBase):
+    """the convs of ``owner.features[:layers]`` as one flat parameter buffer, packed for the forward pass and, with ``dgrad``, for the
+    data gradient; the 2N-batch input; the launch of one feature conv"""
+    dgrad = False
+
+    def __init__(self, owner: nn.Module, layers: int):
+        self.convs = [(i, m) for i, m in enumerate(owner.features[:layers]) if isinstance(m, nn.Conv2d)]
+        super().__init__(owner, [(f"features.{i}.{k}", getattr(m, k)) for i, m in self.convs for k in ("weight", "bias")])
+
+    def _fkey(self, i: int):
+        """key of features.i's forward operand in the pack record (the forward-only engine has no other operands)"""
+        return ("f", i) if self.dgrad else i
+
+    def _build_pack(self, dtc: int, device) -> dict:
+        pb = ops.PackBuilder(dtc)
+        for i, m in self.convs:
+            co, ci = m.weight.shape[:2]
+            pb.fwd(self._fkey(i), self._poff(f"features.{i}.weight"), co, ci)
+            if self.dgrad:
+                pb.bwd(("b", i), self._poff(f"features.{i}.weight"), co, ci)
+        return pb.finish(device)
+
+    def _new_input(self, sp: _Shape, N: int, H: int, W: int, cin: int, dt, dtc: int, device) -> None:
+        # features.0 (3 -> 64) on the thin-side kernels in the 16-bit modes (csrc/conv_thin.hip): the normalised image is NHWC with a
+        # 4-channel pitch
+        sp.thin = ops.thin_ok(dtc, self.owner.features[0].weight.shape[0], cin)
+        sp.xin = torch.empty(2 * N, H, W, 4 if sp.thin else 32, dtype=dt, device=device)
+
+    def _load_input(self, sp: _Shape, sr: Tensor, gt: Tensor, dtc: int, L, st) -> None:
+        """SR into the first N images of sp.xin, GT into the other N, normalised with the module's mean / std"""
+        N, cin, H, W = sr.shape
+        mean, std = self.owner.mean, self.owner.std
+        cpad = sp.xin.shape[-1]
+        for img, half in ((sr, 0), (gt, 1)):
+            img = img.detach().contiguous().float()
+            dst = A.View(sp.xin.data_ptr() + half * N * H * W * cpad * sp.xin.element_size(), cpad, 0)
+            A.check(L.srganfd_nchw_to_nhwc(img.data_ptr(), N, cin, H, W, dst, dtc, cpad, mean.data_ptr(), std.data_ptr(), st), "nchw_to_nhwc")
+
+    def _feature_conv(self, sp: _Shape, pk: dict, dtc: int, idx: int, x: Tensor, y: Tensor, cin: int, act: int) -> tuple:
+        """launch item of features.idx + activation over the 2N batch: x (its padded channel count is cin) -> y"""
+        n, h, w, co = y.shape
+        fptr = self.fp.flat.data_ptr()
+        bias = fptr + 4 * self._poff(f"features.{idx}.bias")
+        if idx == 0 and sp.thin:
+            return ("thin", ops.ThinLaunch("thin_in", ops.thin_args(dtc, n, h, w, self.convs[0][1].weight.shape[1], fptr + 4 * self._poff("features.0.weight"),
+                                                                    A.view(y), w_big_is_cout=True, bias=bias, act=act, thin=sp.xin)))
+        return ("conv", ops.conv_args(dtc, A.view(x), A.view(y), pk["buf"].data_ptr() + pk["offs"][self._fkey(idx)], n, h, w, cin, co, bias=bias, act=act))
+
+
+def _launch(kind: str, item, rec, what: str, L, st) -> None:
+    if kind == "thin":
+        item.launch(rec)
+    else:
+        ops.conv2d(item, rec, what, L, st)
+
+
+class ContentLossEngine(VggEngineBase):
     def __init__(self, owner: nn.Module):
-        self.owner = owner
-        self.last = int(owner.feature_model_extractor_nodes[0].split(".")[1])
-        feats = owner.features
-        if not isinstance(feats[self.last], nn.Conv2d):
-            raise A.SrganfdError("differentiable ContentLoss: the node must be a conv of vgg19.features (esrgan_config uses features.34)")
-        self.convs = [(i, feats[i]) for i in range(self.last + 1) if isinstance(feats[i], nn.Conv2d)]
-        self.fp = FlatParams([(f"features.{i}.{k}", getattr(m, k)) for i, m in self.convs for k in ("weight", "bias")])
-        self.shapes = PlanCache()
-        self.packed: Dict[int, dict] = {}
-        self.token = 0
+        super().__init__(owner, len(owner.features))
+        self.want = [int(n.split(".")[1]) for n in owner.feature_model_extractor_nodes]
 
-    def _ensure_packed(self, dtc, device):
-        flat = self.fp.sync(device)
-        pk = self.packed.get(dtc)
-        if pk is None or pk["buf"].device != device or pk.get("flat_ptr") != flat.data_ptr():
-            jobs, offs, cur = [], {}, 0
-            for i, m in self.convs:
-                co, ci = m.weight.shape[:2]
-                cip = ops.pad32(ci)
-                src = self.fp.off(f"features.{i}.weight")
-                for key, k, n, seg in ((("f", i), cip, co, dict(src_off=src, co_src=co, ci_src=ci, k_len=cip)),
-                                       (("b", i), co, cip, dict(src_off=src, co_src=co, ci_src=ci, k_len=co, transposed=1))):
-                    offs[key] = cur
-                    jobs.append(ops.pack_job(cur, dtc, 3, k, n, [seg]))
-                    cur += (ops.packed_bytes(dtc, 3, k, n) + 255) // 256 * 256
-            pk = dict(table=ops.PackTable(jobs, device), offs=offs, buf=torch.empty(cur, dtype=torch.uint8, device=device), flat_ptr=flat.data_ptr())
-            self.packed[dtc] = pk
-        if self.fp.stale(pk):
-            pk["table"].run(flat, pk["buf"])
-        return pk
+    def forward(self, sr: Tensor, gt: Tensor) -> Tensor:
+        _require_gpu(sr)
+        dt, dtc = _dt(self.owner)
+        dev = sr.device
+        pk = self._ensure_packed(dtc, dev)
+        N, Cin, H, W = sr.shape
+        if H < 16 or W < 16:
+            raise A.SrganfdError("ContentLoss input height/width must be at least 16 (four 2x2 max-pools; odd sizes floor like torch)")
+        L, st = A.lib(), A.stream_ptr()
+        key = (N, H, W, dtc, str(dev), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
+        sp = self.shapes.get(key)
+        if sp is None:
+            sp = _Shape()
+            self._new_input(sp, N, H, W, Cin, dt, dtc, dev)
+            sp.bufs = {}
+            sp.ws = torch.empty(A.LOSS_WS_FLOATS, dtype=torch.float32, device=dev)
+            sp.dt, sp.dtc = dt, dtc
+            self.shapes[key] = sp
+        self._last = sp
+        self._load_input(sp, sr, gt, dtc, L, st)
+        losses = torch.zeros(len(self.want), dtype=torch.float32, device=dev)
+        last = max(self.want)
+        post = self.owner.taps_post_relu
+        cur, ch, h, w = sp.xin, 32, H, W
+        rec = profiling.REC
+
+        def buf(tag, hh, ww, cc):
+            b = sp.bufs.get((tag, hh, ww, cc))
+            if b is None:
+                b = torch.empty(2 * N, hh, ww, cc, dtype=dt, device=dev)
+                sp.bufs[(tag, hh, ww, cc)] = b
+            return b
+        flip = 0
+        for idx in range(last + 1):
+            m = self.owner.features[idx]
+            if isinstance(m, nn.Conv2d):
+                co = m.weight.shape[0]
+                out = buf(flip, h, w, co)
+                flip ^= 1
+                tap = idx in self.want
+                # taps are observed after the in-place ReLU unless they are the last requested node
+                relu_in_conv = not (tap and (idx == last or not post))
+                _launch(*self._feature_conv(sp, pk, dtc, idx, cur, out, ch, A.ACT_RELU if relu_in_conv else A.ACT_NONE), rec, "conv2d(vgg)", L, st)
+                if tap:
+                    half_b = N * h * w * co * out.element_size()
+                    A.check(L.srganfd_l1_loss_views(A.View(out.data_ptr(), co, 0), A.View(out.data_ptr() + half_b, co, 0), dtc, N * h * w, co, 0, 1.0,
+                                                    losses.data_ptr() + 4 * self.want.index(idx), 0, sp.ws.data_ptr(), st), "l1_views")
+                    if not relu_in_conv and idx != last:
+                        A.check(L.srganfd_resample(4, A.view(out), A.view(out), dtc, 2 * N, h, w, co, st), "relu")
+                cur, ch = out, co
+            elif isinstance(m, nn.MaxPool2d):
+                out = buf("p", h // 2, w // 2, ch)
+                A.check(L.srganfd_resample(3, A.view(cur), A.view(out), dtc, 2 * N, h, w, ch, st), "maxpool")
+                cur, h, w = out, h // 2, w // 2
+        return losses.view(1, -1)
+
+
+def content_loss_apply(owner: nn.Module, sr: Tensor, gt: Tensor) -> Tensor:
+    eng = _engine(owner, lambda: ContentLossEngine(owner))
+    with torch.no_grad():
+        return eng.forward(sr, gt)
+
+
+class ContentLossGradEngine(VggEngineBase):
+    dgrad = True
+
+    def __init__(self, owner: nn.Module):
+        self.last = int(owner.feature_model_extractor_nodes[0].split(".")[1])
+        if not isinstance(owner.features[self.last], nn.Conv2d):
+            raise A.SrganfdError("differentiable ContentLoss: the node must be a conv of vgg19.features (esrgan_config uses features.34)")
+        super().__init__(owner, self.last + 1)
 
     def _plan(self, N, H, W, dt, dtc, dev, pk):
         key = (N, H, W, dtc, str(dev), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
@@ -63,9 +166,7 @@ class ContentLossGradEngine:
         sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, dev
         es = torch.empty(0, dtype=dt).element_size()
         fptr, wptr, O = self.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
-        # features.0 (3 -> 64) and its data gradient on the thin-side kernels in the 16-bit modes (csrc/conv_thin.hip): 4-channel pitch
-        sp.thin = ops.thin_ok(dtc, self.owner.features[0].weight.shape[0], 3)
-        sp.xin = torch.empty(2 * N, H, W, 4 if sp.thin else 32, dtype=dt, device=dev)
+        self._new_input(sp, N, H, W, 3, dt, dtc, dev)      # (thin: features.0's data gradient runs on the thin-side kernel too)
         half = lambda t: A.View(t.data_ptr(), t.shape[3], 0)                     # SR half (first N images)
         other = lambda t: A.View(t.data_ptr() + t[:N].numel() * es, t.shape[3], 0)   # GT half
         fw, chain = [], []          # chain: (kind, index, tensor, h, w, c) in forward order
@@ -76,14 +177,7 @@ class ContentLossGradEngine:
             if isinstance(m, nn.Conv2d):
                 co = m.weight.shape[0]
                 out = torch.empty(2 * N, h, w, co, dtype=dt, device=dev)
-                if idx == 0 and sp.thin:
-                    fw.append(("thin", ops.ThinLaunch("thin_in", ops.thin_args(dtc, 2 * N, h, w, 3, fptr + 4 * self.fp.off("features.0.weight"), A.view(out),
-                                                                               w_big_is_cout=True, bias=fptr + 4 * self.fp.off("features.0.bias"),
-                                                                               act=A.ACT_NONE if idx == self.last else A.ACT_RELU, thin=sp.xin))))
-                else:
-                    fw.append(("conv", ops.conv_args(dtc, A.view(cur), A.view(out), wptr + O[("f", idx)], 2 * N, h, w, ch, co,
-                                                     bias=fptr + 4 * self.fp.off(f"features.{idx}.bias"),
-                                                     act=A.ACT_NONE if idx == self.last else A.ACT_RELU)))
+                fw.append(self._feature_conv(sp, pk, dtc, idx, cur, out, ch, A.ACT_NONE if idx == self.last else A.ACT_RELU))
                 chain.append(("conv", idx, cur, out, h, w, ch, co))
                 cur, ch = out, co
             elif isinstance(m, nn.MaxPool2d):
@@ -138,21 +232,11 @@ class ContentLossGradEngine:
             raise A.SrganfdError("ContentLoss needs 3-channel inputs with height/width multiples of 16 (four 2x2 max-pools)")
         sp = self._plan(N, H, W, dt, dtc, dev, pk)
         L, st = A.lib(), A.stream_ptr()
-        mean, std = self.owner.mean, self.owner.std
-        for img, hf in ((sr, 0), (gt, 1)):
-            img = img.detach().contiguous().float()
-            cpad = sp.xin.shape[-1]
-            dst = A.View(sp.xin.data_ptr() + hf * N * H * W * cpad * sp.xin.element_size(), cpad, 0)
-            A.check(L.srganfd_nchw_to_nhwc(img.data_ptr(), N, 3, H, W, dst, dtc, cpad, mean.data_ptr(), std.data_ptr(), st), "nchw_to_nhwc")
+        self._load_input(sp, sr, gt, dtc, L, st)
         rec = profiling.REC
         for kind, item in sp.fw:
-            if kind == "thin":
-                item.launch(rec)
-            elif kind == "conv":
-                if rec is None:
-                    A.check(L.srganfd_conv2d(C.byref(item), st), "conv2d(vgg)")
-                else:
-                    rec.bracket(profiling.conv_label(item), profiling.conv_work(item), lambda: A.check(L.srganfd_conv2d(C.byref(item), st), "conv2d(vgg)"))
+            if kind != "pool":
+                _launch(kind, item, rec, "conv2d(vgg)", L, st)
             else:
                 xv, yv, h, w, c = item
                 A.check(L.srganfd_resample(3, xv, yv, dtc, 2 * N, h, w, c, st), "maxpool")
@@ -179,13 +263,8 @@ class ContentLossGradEngine:
                                         weight / float(N * h * w * c), st), "l1_grad_views")
         rec = profiling.REC
         for kind, item in sp.bw:
-            if kind == "thin":
-                item.launch(rec)
-            elif kind == "conv":
-                if rec is None:
-                    A.check(L.srganfd_conv2d(C.byref(item), st), "conv2d(vgg dgrad)")
-                else:
-                    rec.bracket(profiling.conv_label(item), profiling.conv_work(item), lambda: A.check(L.srganfd_conv2d(C.byref(item), st), "conv2d(vgg dgrad)"))
+            if kind != "poolbwd":
+                _launch(kind, item, rec, "conv2d(vgg dgrad)", L, st)
             else:
                 xv, dyv, dxv, hh, ww, cc = item
                 A.check(L.srganfd_maxpool2_relu_bwd(xv, dyv, dxv, dtc, N, hh, ww, cc, st), "maxpool2_relu_bwd")

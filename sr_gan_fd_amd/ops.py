@@ -11,6 +11,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _abi as A
+from . import profiling
 
 DT = {torch.bfloat16: A.BF16, torch.float32: A.F32, torch.float16: A.F16}
 
@@ -64,6 +65,37 @@ def pad32(c: int) -> int:
     return (c + 31) // 32 * 32
 
 
+class PackBuilder:
+    """Accumulates the pack jobs of one engine and compute dtype: every operand gets the next 256-byte aligned offset of one packed
+    buffer under a key of the engine's choice.  ``finish`` returns the record the engines keep per dtype: the device-resident job
+    table, the offsets and the (still unwritten) packed buffer."""
+
+    def __init__(self, dtc: int):
+        self.dtc, self.jobs, self.offs, self.cur = dtc, [], {}, 0
+
+    def add(self, key, ksize: int, k: int, n: int, segs) -> None:
+        self.offs[key] = self.cur
+        self.jobs.append(pack_job(self.cur, self.dtc, ksize, k, n, [segs] if isinstance(segs, dict) else segs))
+        self.cur += (packed_bytes(self.dtc, ksize, k, n) + 255) // 256 * 256
+
+    def fwd(self, key, src_off: int, co: int, ci: int, ksize: int = 3, **seg) -> None:
+        """forward operand of a (co, ci, ksize, ksize) weight at element ``src_off`` of the flat parameters, both sides padded to 32"""
+        self.add(key, ksize, pad32(ci), pad32(co), dict(src_off=src_off, co_src=co, ci_src=ci, k_len=pad32(ci), **seg))
+
+    def bwd(self, key, src_off: int, co: int, ci: int, ksize: int = 3, transposed: int = 1, **seg) -> None:
+        """data-gradient operand of the same weight (``transposed``: the pack code, 1 = plain transpose with flipped taps)"""
+        self.add(key, ksize, pad32(co), pad32(ci), dict(src_off=src_off, co_src=co, ci_src=ci, k_len=pad32(co), transposed=transposed, **seg))
+
+    def classes(self, key: tuple, src_off: int, co: int, ci: int, ksize: int, code: int, **seg) -> None:
+        """the four output-parity class operands of a strided conv's data gradient (or of a nearest-x2 forward), back to back under
+        ``key + (class,)``: pack codes ``code .. code + 3``, ``ksize`` the classes' tap size"""
+        for par in range(4):
+            self.bwd(key + (par,), src_off, co, ci, ksize, transposed=code + par, **seg)
+
+    def finish(self, device) -> dict:
+        return dict(table=PackTable(self.jobs, device), offs=self.offs, buf=torch.empty(self.cur, dtype=torch.uint8, device=device))
+
+
 def pack_single(weight: torch.Tensor, dtype: int, transposed: bool = False, scale: float = 1.0) -> torch.Tensor:
     """Pack one (Cout, Cin, k, k) fp32 weight for conv2d (forward) or for its data gradient."""
     co, ci, kh, kw = weight.shape
@@ -111,8 +143,53 @@ def class4_ok(dtype: int, n_out: int, offsets: Sequence[int], pack_bytes: int, k
             and all(offsets[c] == offsets[0] + c * pack_bytes for c in range(4)))
 
 
-def conv2d(args: A.ConvArgs) -> None:
-    A.check(A.lib().srganfd_conv2d(C.byref(args), A.stream_ptr()), "conv2d")
+def parity_class_launches(dtc: int, x: A.View, y: A.View, wptr: int, offs4: Sequence[int], n: int, h: int, w: int, kdim: int, ndim: int,
+                          ksize: int, class_pad: int, valid: bool = False, **epilogue) -> List[A.ConvArgs]:
+    """A strided conv's data gradient, or a nearest-x2 conv's forward, as its four output-parity classes: stride-1 ``ksize``-tap
+    convs over the (h, w) input ``x``, class (py, px) writing the pixels (2i + py, 2j + px) of ``y``.  ``offs4``: byte offsets of the
+    four packed operands behind ``wptr``.  ``class_pad`` 1: class (py, px) reads the window one row / column earlier where py / px is
+    0 (3x3 and 4x4 pad-1 kernels); 0: every class reads the same window (2x2 stride-2 kernels).  ``valid``: the strided conv had no
+    padding (4x4 stride 2 over an even size) -- each class then has one more row and column of outputs, takes the tap pairs of the
+    opposite parity and one row / column of zero padding on the low side.  ONE launch when the library takes the four classes
+    together (class4_ok), else one per class.  ``epilogue``: conv_args' bias / act / slope / r1 / r2 / mask keywords."""
+    one = not valid and class4_ok(dtc, ndim, offs4, packed_bytes(dtc, ksize, kdim, ndim), ksize)
+    ext = 1 if valid else 0
+    out = []
+    for par in range(1 if one else 4):
+        py, px = par >> 1, par & 1
+        a = conv_args(dtc, x, y, wptr + offs4[3 - par if valid else par], n, h, w, kdim, ndim, ksize=ksize, stride=1, pad=0, **epilogue)
+        a.h_out, a.w_out = h + ext, w + ext
+        a.out_sy, a.out_sx, a.out_oy, a.out_ox = 2, 2, py, px
+        a.out_h_full, a.out_w_full = 2 * (h + ext), 2 * (w + ext)
+        a.pad_y, a.pad_x = (1, 1) if valid else (class_pad * (1 - py), class_pad * (1 - px))
+        a.out_classes, a.class_pad_step = (4, class_pad) if one else (0, 0)     # one launch: the classes' workgroups share each input patch through L2
+        out.append(a)
+    return out
+
+
+def dgrad_epilogue(r1: Optional[A.View] = None, r2: Optional[A.View] = None, mask: Optional[A.View] = None, mask_slope: float = 0.2) -> dict:
+    """conv_args' keywords of a data-gradient epilogue: up to two gradients added at scale 1 and the activation derivative of ``mask``"""
+    kw = {}
+    if r1 is not None:
+        kw.update(r1=r1, r1_scale=1.0)
+    if r2 is not None:
+        kw.update(r2=r2, r2_scale=1.0)
+    if mask is not None:
+        kw.update(mask=mask, mask_slope=mask_slope)
+    return kw
+
+
+def conv2d(args: A.ConvArgs, rec=None, what: str = "conv2d", L=None, st=None) -> None:
+    """Issue one conv launch on the current stream; ``rec`` (profiling.REC) brackets it with its label and algorithmic work.  A loop
+    over many launches passes the library handle and the stream it already holds."""
+    if L is None:
+        L, st = A.lib(), A.stream_ptr()
+    if rec is None:
+        rc = L.srganfd_conv2d(C.byref(args), st)
+        if rc:
+            A.check(rc, what)
+    else:
+        rec.bracket(profiling.conv_label(args), profiling.conv_work(args), lambda: A.check(L.srganfd_conv2d(C.byref(args), st), what))
 
 
 # ---- LDS-resident dense-block launch (csrc/dense_chain.hip): the five convs of a dense block, or of its data-gradient pass, as one launch ----
@@ -273,6 +350,40 @@ class ThinLaunch:
             rec.bracket(self.label, self.work, lambda: self.run(grad_ptr))
 
 
+# ---- image-side layers: a 3x3 conv between an image-like tensor (``cs`` = 1..4 real channels) and ``big_ch`` feature channels.  In the
+# 16-bit modes with 64 feature channels (thin_ok) the image side is NHWC with a 4-channel pitch and the thin kernels read the layer's
+# raw fp32 ``weight`` (an address in the flat parameters); otherwise it is padded to 32 channels for conv2d and the packed operand.
+# ``w_big_is_cout``: the weight's output channels are the feature side (a network's first layer; False: its last).  Each returns one
+# launch item: ("thin", ThinLaunch) or ("conv", ConvArgs) / ("wgrad", plan, x view, dy view) + extra.
+def image_to_features(dtc: int, thin: bool, image: torch.Tensor, big: A.View, weight: int, w_packed: int, n: int, h: int, w: int, cs: int,
+                      big_ch: int, w_big_is_cout: bool, flip: bool = False, **epilogue) -> tuple:
+    """a first layer's forward, or (flip) a last layer's data gradient; epilogue: bias / act / slope / mask / mask_slope"""
+    if thin:
+        return ("thin", ThinLaunch("thin_in", thin_args(dtc, n, h, w, cs, weight, big, w_big_is_cout=w_big_is_cout, flip=flip, thin=image, **epilogue)))
+    return ("conv", conv_args(dtc, A.view(image), big, w_packed, n, h, w, image.shape[-1], big_ch, **epilogue))
+
+
+def features_to_image(dtc: int, thin: bool, big: A.View, out, out_pitch: int, weight: int, w_packed: int, n: int, h: int, w: int, cs: int,
+                      big_ch: int, w_big_is_cout: bool, flip: bool = False, bias=None) -> tuple:
+    """a last layer's forward, or (flip) a first layer's data gradient, written as fp32 at ``out`` (tensor or address) with a pitch of
+    ``out_pitch`` channels"""
+    if thin:
+        return ("thin", ThinLaunch("thin_out", thin_args(dtc, n, h, w, cs, weight, big, w_big_is_cout=w_big_is_cout, flip=flip, bias=bias,
+                                                         thin_out=out, thin_out_pitch=out_pitch)))
+    return ("conv", conv_args(dtc, big, A.View(_ptr(out), out_pitch, 0), w_packed, n, h, w, big_ch, 32, cout_store=cs, bias=bias, y_f32=True))
+
+
+def image_wgrad(dtc: int, thin: bool, wplans: "WgradPlans", image: torch.Tensor, big: torch.Tensor, weight: int, dw_off: int, db_off: int,
+                thin_ws: Optional[torch.Tensor], n: int, h: int, w: int, cs: int, big_ch: int, w_big_is_cout: bool, extra: tuple = ()) -> tuple:
+    """weight and bias gradient of either layer, at elements dw_off / db_off of the flat gradient"""
+    if thin:
+        return ("thin", ThinLaunch("thin_wgrad", thin_args(dtc, n, h, w, cs, weight, A.view(big), w_big_is_cout=w_big_is_cout, thin=image),
+                                   dw_off=dw_off, db_off=db_off, ws=thin_ws))
+    if w_big_is_cout:
+        return ("wgrad", wplans.conv(h, w, image.shape[-1], big_ch, dw_off, db_off, cin_real=cs), A.view(image), A.view(big)) + extra
+    return ("wgrad", wplans.conv(h, w, big_ch, 32, dw_off, db_off, cout_real=cs), A.view(big), A.view(image)) + extra
+
+
 class WgradPlan:
     """Host+device plan of one weight-gradient launch (several convs sharing x and dy)."""
 
@@ -312,6 +423,40 @@ class WgradPlan:
                                              scalars.data_ptr() if scalars is not None else None,
                                              workspace.data_ptr(), workspace.numel() * workspace.element_size(),
                                              A.stream_ptr()), "conv2d_wgrad")
+
+
+def conv2d_wgrad(plan: WgradPlan, x: A.View, dy: A.View, grad_ptr: int, workspace: torch.Tensor, rec=None, L=None, st=None) -> None:
+    """Issue one weight-gradient launch (MFMA kernel + slab reduction) writing at ``grad_ptr``; ``rec`` brackets it as conv2d's does."""
+    if L is None:
+        L, st = A.lib(), A.stream_ptr()
+    run = lambda: A.check(L.srganfd_conv2d_wgrad(plan.host, plan.dev.data_ptr(), x, dy, grad_ptr, None, workspace.data_ptr(), workspace.numel(), st),
+                          "conv2d_wgrad")
+    if rec is None:
+        run()
+    else:
+        rec.bracket(plan.label, (plan.flops, plan.nbytes), run)
+
+
+class WgradPlans:
+    """Builds the weight-gradient plans of one launch list and keeps the largest workspace any of them needs (they run one after the
+    other and share it)."""
+
+    def __init__(self, device, dtc: int, n: int):
+        self.device, self.dtc, self.n, self.ws_bytes = device, dtc, n, 0
+
+    def plan(self, h: int, w: int, x_channels: int, dy_channels: int, convs: Sequence[dict], **kw) -> WgradPlan:
+        p = WgradPlan(self.device, self.dtc, self.n, h, w, x_channels, dy_channels, convs, **kw)
+        self.ws_bytes = max(self.ws_bytes, p.workspace_bytes)
+        return p
+
+    def conv(self, h: int, w: int, cin: int, cout: int, dw_off: int, db_off: int = -1, cin_real: Optional[int] = None,
+             cout_real: Optional[int] = None, **kw) -> WgradPlan:
+        """plan of ONE conv whose x / dy carry cin / cout (padded) channels; the gradient of the real (cout_real, cin_real) weight goes
+        to element ``dw_off`` of the flat gradient, the bias gradient to ``db_off``"""
+        return self.plan(h, w, cin, cout, [dict(cin=cin, cout=cout, dw_off=dw_off, db_off=db_off, co_dst=cout_real or cout, ci_dst=cin_real or cin)], **kw)
+
+    def workspace(self) -> torch.Tensor:
+        return torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
 
 
 # same-box A/B switch (0: one group of launches per layer, the round-1 form); both forms run in the HIP library and agree to the bit

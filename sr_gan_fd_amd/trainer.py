@@ -2,7 +2,7 @@
 
   * ``GeneratorTrainer.step``  = ESRGAN/train_rrdbnet.py:244-272 / BSRGAN/train_bsrnet.py:244-272
     (zero_grad, G forward, L1 * weight, backward, Adam step, EMA update).
-  * ``GanTrainer.step``        = BSRGAN/train_bsrgan.py:387-483 (see engine_d.py / gan.py).
+  * ``GanTrainer.step``        = BSRGAN/train_bsrgan.py:387-483 (see engine_d.py, engine_core.py / gan.py).
 
 They call the same engines as the ``nn.Module`` surface (``model.py``) but skip the autograd
 bookkeeping: loss + dLoss/dSR come from one HIP kernel, the flat gradient goes straight to the fused
