@@ -468,6 +468,53 @@ int srganfd_niqe_features_luma(const double* luma, int32_t n, int32_t h, int32_t
  * Like the reference's, the arithmetic is float32 (inputs rounded to float32, outputs are float32 values widened). */
 int srganfd_resize_half(const double* src, int32_t planes, int32_t h, int32_t w, double* dst, void* stream);
 
+/* ---- LPIPS v0.1 on AlexNet (the `lpips` package's LPIPS(net='alex') as validate() calls it: train_bsrgan.py:115,571,
+ * train_aesrgan.py:133,583, train_esrgan.py:101,526, train_realesrgan.py:96,592), fp32, forward only (csrc/lpips.hip) ----
+ * One convolution of the AlexNet trunk with bias and ReLU, implicit GEMM on v_mfma_f32_32x32x2_f32, output NHWC fp32
+ * (n, h_out, w_out, cout) with cout a multiple of 64.  Three forms:
+ *   first != 0  ksize 11, stride 4, pad 2, cin 3: reads the caller's two NCHW fp32 batches in0 and in1 (n / 2 images each,
+ *               element strides stride0 / stride1 in (image, channel, row, column) order, so slices need no copy) as one
+ *               batch of n, in0's images first.  In-bounds taps become ((normalize ? 2 x - 1 : x) - shift[c]) / scale[c];
+ *               padded taps are 0.  w is [363][cout] with rows in (c, ky, kx) order.
+ *   else        ksize 5, stride 1, pad 2 or ksize 3, stride 1, pad 1 over x = (n, h_in, w_in, cin) NHWC fp32, cin a multiple
+ *               of 32; w is [ksize * ksize * cin][cout] with rows in (ky, kx, c) order.
+ *   pool != 0   (not with first) x first passes through MaxPool2d(3, 2) without padding (floor): the conv's input is
+ *               ((h_in - 3) / 2 + 1) x ((w_in - 3) / 2 + 1), each value the 3 x 3 maximum taken while the tile is staged.
+ * h_out / w_out must be what these rules give.  x and w 16-byte aligned. */
+typedef struct srganfd_lpips_conv_args {
+  int32_t n, h_in, w_in;      /* stored input (before the pool) */
+  int32_t cin, cout, ksize, stride, pad;
+  int32_t pool, first, normalize;
+  int32_t h_out, w_out;
+  int32_t pad_;
+  const float* x;
+  const float* in0;
+  const float* in1;
+  int64_t stride0[4], stride1[4];
+  const float* w;
+  const float* bias;          /* [cout] */
+  float* y;
+  float shift[3], scale[3];
+  int32_t pad2_[2];
+} srganfd_lpips_conv_args;
+int srganfd_lpips_conv(const srganfd_lpips_conv_args* a, void* stream);
+/* The LPIPS head over 1..5 tap maps in two launches.  maps: (2 n, h, w, c) NHWC fp32, image i of the first input at i and of
+ * the second at n + i; c a multiple of 64 up to 384; lin: [c] weights of the bias-free 1 x 1 conv.  Per pixel
+ * v = sum_c lin[c] * (f0[c] / (|f0| + 1e-10) - f1[c] / (|f1| + 1e-10))^2 (an all-zero vector gives 0), per tap and image the
+ * mean of v over the pixels.  out: (ntaps + 1, n) fp32, the per-tap values then their sum over the taps.  Fixed summation order,
+ * no atomics: equal inputs give equal bits.  workspace: n * sum(h * w) floats. */
+typedef struct srganfd_lpips_tap {
+  const float* maps;
+  const float* lin;
+  int32_t h, w, c, pad_;
+} srganfd_lpips_tap;
+int srganfd_lpips_head(const srganfd_lpips_tap* taps, int32_t ntaps, int32_t n, float* out, float* workspace, void* stream);
+/* Bytes of the module's workspace for two (n, 3, h, w) inputs: the five tap maps (2 n, h_k, w_k, {64, 192, 384, 256, 256})
+ * followed by the head's n * sum(h_k * w_k) floats, where tap 1 is ((h - 7) / 4 + 1) x ((w - 7) / 4 + 1), tap 2 a
+ * MaxPool(3, 2) of it, taps 3..5 a MaxPool(3, 2) of tap 2.  -1 (SRGANFD_EINVAL) when h or w is below 31: the second pool
+ * then has no full window. */
+int64_t srganfd_lpips_workspace_bytes(int32_t n, int32_t h, int32_t w);
+
 /* MATLAB's imresize as the reference's imgproc.image_resize runs it (ESRGAN/imgproc.py:202-288): a separable weighted sum, rows
  * (H) first, then columns (W), float32 throughout, the intermediate rounded to float32 between the passes (it stays in LDS).
  *   src: (planes, h, w) fp32, contiguous; dst: (planes, out_h, out_w) fp32.

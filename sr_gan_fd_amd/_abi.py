@@ -110,6 +110,21 @@ class WgradShape(C.Structure):
     ]
 
 
+class LpipsConvArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
+        ("ksize", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("pool", C.c_int32), ("first", C.c_int32),
+        ("normalize", C.c_int32), ("h_out", C.c_int32), ("w_out", C.c_int32), ("pad_", C.c_int32),
+        ("x", C.c_void_p), ("in0", C.c_void_p), ("in1", C.c_void_p), ("stride0", C.c_int64 * 4), ("stride1", C.c_int64 * 4),
+        ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("shift", C.c_float * 3), ("scale", C.c_float * 3),
+        ("pad2_", C.c_int32 * 2),
+    ]
+
+
+class LpipsTap(C.Structure):
+    _fields_ = [("maps", C.c_void_p), ("lin", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("pad_", C.c_int32)]
+
+
 # symbol -> (restype, argtypes); tests check that the library exports every one of these
 SYMBOLS = {
     "srganfd_last_error": (C.c_char_p, []),
@@ -185,6 +200,9 @@ SYMBOLS = {
     "srganfd_niqe_workspace_doubles": (C.c_int64, [C.c_int32] * 7),
     "srganfd_niqe_features": (C.c_int, [C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "srganfd_niqe_features_luma": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "srganfd_lpips_conv": (C.c_int, [C.POINTER(LpipsConvArgs), C.c_void_p]),
+    "srganfd_lpips_head": (C.c_int, [C.POINTER(LpipsTap), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "srganfd_lpips_workspace_bytes": (C.c_int64, [C.c_int32] * 3),
     "srganfd_resize_half": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p]),
     "srganfd_imresize": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32] * 2 + [C.c_void_p, C.c_void_p]),
     "srganfd_gate_mul": (C.c_int, [C.c_int32, View, C.c_void_p, View, View, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),

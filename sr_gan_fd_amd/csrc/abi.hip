@@ -91,6 +91,9 @@ int niqe_features_luma_impl(const double* luma, int n, int h, int w, int bh, int
 int resize_half_impl(const double* src, int planes, int h, int w, double div, double* dst, hipStream_t s);
 int imresize_impl(const float* src, int planes, int h, int w, int oh, int ow, const float* wt_h, const int* first_h, int taps_h,
                   const float* wt_w, const int* first_w, int taps_w, float* dst, hipStream_t s);
+int lpips_conv_impl(const srganfd_lpips_conv_args* a, hipStream_t s);
+int lpips_head_impl(const srganfd_lpips_tap* taps, int ntaps, int n, float* out, float* ws, hipStream_t s);
+int64_t lpips_workspace_bytes_impl(int n, int h, int w);
 int sigmoid_impl(float* x, size_t n, hipStream_t s);
 int sigmoid_bwd_impl(const float* ds, const float* sg, float* out, size_t n, hipStream_t s);
 int gate_mul_impl(int bwd, srganfd_view x, const float* gate, srganfd_view y, srganfd_view dx, float* dgate, int dtype, size_t npix, int c, hipStream_t s);
@@ -294,6 +297,11 @@ int srganfd_niqe_features_luma(const double* luma, int32_t n, int32_t h, int32_t
                                int32_t table_len, double* feat, double* half, void* stream) {
   return niqe_features_luma_impl(luma, n, h, w, block_h, block_w, table, table_len, feat, half, (hipStream_t)stream);
 }
+int srganfd_lpips_conv(const srganfd_lpips_conv_args* a, void* stream) { return lpips_conv_impl(a, (hipStream_t)stream); }
+int srganfd_lpips_head(const srganfd_lpips_tap* taps, int32_t ntaps, int32_t n, float* out, float* workspace, void* stream) {
+  return lpips_head_impl(taps, ntaps, n, out, workspace, (hipStream_t)stream);
+}
+int64_t srganfd_lpips_workspace_bytes(int32_t n, int32_t h, int32_t w) { return lpips_workspace_bytes_impl(n, h, w); }
 int srganfd_resize_half(const double* src, int32_t planes, int32_t h, int32_t w, double* dst, void* stream) {
   return resize_half_impl(src, planes, h, w, 1.0, dst, (hipStream_t)stream);
 }

@@ -1,5 +1,6 @@
 """PSNR, SSIM and NIQE of the validation loop (reference: BSRGAN/image_quality_assessment.py:361-418, :420-532 and
-:1138-1333, used at train_bsrgan.py:545-590)."""
+:1138-1333, used at train_bsrgan.py:545-590), and LPIPS (the `lpips` package's ``LPIPS(net='alex')`` of train_bsrgan.py:115,571;
+sr_gan_fd_amd/lpips.py), re-exported here so that one import binds all four validation metrics."""
 from __future__ import annotations
 
 import numpy as np
@@ -7,6 +8,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _abi as A
+from .lpips import LPIPS  # noqa: F401
 
 
 class PSNR(nn.Module):
