@@ -554,6 +554,34 @@ int32_t srganfd_diff_jpeg_table_floats(void);
 int srganfd_diff_jpeg_tables(float* host_out);
 int srganfd_diff_jpeg(const float* image, int32_t b, int32_t c, int32_t h, int32_t w, float* quality,
                       int32_t quality_is_factor, int32_t differentiable, const float* tables, float* out, void* stream);
+/* ---- BSRGAN / A-ESRGAN blind degradation (BSRGAN/imgproc.py:492-562) ----
+ * A real baseline JPEG round trip, as cv2.imencode(".jpg", quality) + cv2.imdecode run it through libjpeg's defaults (imgproc.py:284-293):
+ * 4:2:0, integer colour conversion, the accurate integer DCT, (|c| + 4 q) / (8 q) quantisation, fancy chroma upsampling.  Integer
+ * arithmetic in int32 throughout; not differentiable.  The result equals the library's bytes.
+ *   image: (b, 3, h, w) fp32 RGB in any range, quantised as rintf(clamp(x, 0, 1) * 255.f); out (may not alias image): (float)u8 / 255.0f.
+ *   quality: b int32 in DEVICE memory, 1..100 (the quantiser tables are scaled from it in the kernel); 0 leaves that image's three
+ *   planes as they are, bit for bit.  quality_host: the same b values in host memory, or NULL; where given they are validated.  Values
+ *   outside 1..100 that only the device sees are clamped into it as the library clamps them (0 still skips).
+ *   workspace: srganfd_jpeg_workspace_bytes(b, h, w) bytes (the decoded Y, Cb, Cr planes as bytes, padded to whole 16 x 16 MCUs), 4-byte aligned.
+ * Two launches: one wave per MCU up to the decoded planes, then upsampling + colour conversion per pixel.  Any h, w >= 1.
+ * SRGANFD_EINVAL (the query returns -1): null pointer, c != 3, non-positive size, out == image, a quality_host entry outside 0..100. */
+int64_t srganfd_jpeg_workspace_bytes(int32_t b, int32_t h, int32_t w);
+int srganfd_jpeg_roundtrip(const float* image, int32_t b, int32_t c, int32_t h, int32_t w, const int32_t* quality,
+                           const int32_t* quality_host, void* workspace, float* out, void* stream);
+/* The blur of the same degradation (imgproc.py:212-225: ndimage.convolve(image, k[:, :, None], mode='mirror')) for a batch in which
+ * every image has its own kernel: fp64 fused multiply-adds on the fp32 samples, one rounding to fp32 at the end -- scipy's arithmetic
+ * for a float32 image and a float64 kernel.
+ *   image: (b, c, h, w) fp32; out (may not alias image) likewise.
+ *   kernels: (b, kmax, kmax) fp64 in device memory, image n's own ksize[n] x ksize[n] kernel CENTRED in its kmax x kmax array (kmax odd,
+ *   3..25); ksize: b int32 in DEVICE memory, odd sizes from 3 to kmax, 0 = copy the image through.  ksize_host: the same values in
+ *   host memory, or NULL; where given they are validated and h, w > max(ksize) / 2 is required, without them h, w > kmax / 2.
+ *   Mirror padding (no repeat of the edge sample: scipy 'mirror', torch 'reflect').
+ * Computes the CROSS-CORRELATION out[y][x] = sum k[i][j] * image[y + i - r][x + j - r], like srganfd_filter2d; scipy's convolve flips
+ * the kernel, which changes nothing for the point-symmetric Gaussians of the reference.  A workgroup loops over its image's k x k taps only.
+ * SRGANFD_EINVAL: null pointer, non-positive size, bad kmax, out == image, a bad ksize_host entry, an image too small to mirror,
+ * more than 65535 planes. */
+int srganfd_filter2d_mirror_f64(const float* image, const double* kernels, int32_t kmax, const int32_t* ksize,
+                                const int32_t* ksize_host, int32_t b, int32_t c, int32_t h, int32_t w, float* out, void* stream);
 /* F.interpolate as degradation_process calls it (imgproc.py:2374, :2415-2418, :2440-2442, :2454-2456): mode 0 "area"
  * (adaptive average pooling), 1 "bilinear", 2 "bicubic" (A = -0.75), align_corners unset.  `planes` = b*c NCHW fp32 planes.
  * rscale_h/w: 1 / scale_factor when the caller passed scale_factor= (torch maps coordinates with it), 0 = in / out. */

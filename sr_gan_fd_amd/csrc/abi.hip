@@ -92,6 +92,11 @@ int resize_half_impl(const double* src, int planes, int h, int w, double div, do
 int imresize_impl(const float* src, int planes, int h, int w, int oh, int ow, const float* wt_h, const int* first_h, int taps_h,
                   const float* wt_w, const int* first_w, int taps_w, float* dst, hipStream_t s);
 int lpips_conv_impl(const srganfd_lpips_conv_args* a, hipStream_t s);
+long long jpeg_workspace_bytes(int b, int h, int w);
+int jpeg_roundtrip_impl(const float* src, int b, int c, int h, int w, const int* quality, const int* quality_host, void* workspace, float* dst,
+                        hipStream_t s);
+int filter2d_mirror_f64_impl(const float* src, const double* kernels, int kmax, const int* ksize, const int* ksize_host, int b, int c, int h, int w,
+                             float* out, hipStream_t s);
 int lpips_head_impl(const srganfd_lpips_tap* taps, int ntaps, int n, float* out, float* ws, hipStream_t s);
 int64_t lpips_workspace_bytes_impl(int n, int h, int w);
 int sigmoid_impl(float* x, size_t n, hipStream_t s);
@@ -337,6 +342,15 @@ int srganfd_diff_jpeg_tables(float* host_out) {
 int srganfd_diff_jpeg(const float* image, int32_t b, int32_t c, int32_t h, int32_t w, float* quality, int32_t quality_is_factor,
                       int32_t differentiable, const float* tables, float* out, void* stream) {
   return diff_jpeg_impl(image, b, c, h, w, quality, quality_is_factor, differentiable, tables, out, (hipStream_t)stream);
+}
+int64_t srganfd_jpeg_workspace_bytes(int32_t b, int32_t h, int32_t w) { return jpeg_workspace_bytes(b, h, w); }
+int srganfd_jpeg_roundtrip(const float* image, int32_t b, int32_t c, int32_t h, int32_t w, const int32_t* quality, const int32_t* quality_host,
+                           void* workspace, float* out, void* stream) {
+  return jpeg_roundtrip_impl(image, b, c, h, w, quality, quality_host, workspace, out, (hipStream_t)stream);
+}
+int srganfd_filter2d_mirror_f64(const float* image, const double* kernels, int32_t kmax, const int32_t* ksize, const int32_t* ksize_host, int32_t b,
+                                int32_t c, int32_t h, int32_t w, float* out, void* stream) {
+  return filter2d_mirror_f64_impl(image, kernels, kmax, ksize, ksize_host, b, c, h, w, out, (hipStream_t)stream);
 }
 int srganfd_resize(const float* src, int32_t planes, int32_t h, int32_t w, int32_t out_h, int32_t out_w, int32_t mode, float rscale_h, float rscale_w,
                    float* dst, void* stream) {

@@ -20,14 +20,30 @@ class CUDAPrefetcher:
     1 / upscale_factor)``): with an upscale factor, a batch that has ``"gt"`` and no ``"lr"`` gets ``batch["lr"] = image_resize(batch["gt"],
     1 / factor)`` on the copy stream, after the u8 ingest, so the resize of batch i+1 overlaps iteration i like the copy does.  A batch that
     brings its own ``"lr"`` keeps it; the default ``None`` changes nothing.  (The reference resizes in BGR and swaps channels afterwards; the
-    resize is per channel, so the order does not matter.)"""
+    resize is per channel, so the order does not matter.)
 
-    def __init__(self, dataloader, device: torch.device, ingest_u8: bool = False, bgr: bool = True, synthesize_lr: int | None = None):
+    ``synthesize_lr_bsrgan`` (an addition; BSRGAN/dataset.py:83 and A-ESRGAN's make the LR image per sample on the host with
+    ``imgproc.degradation_process(gt, upscale_factor, jpeg_prob, scale2_prob)`` in cv2, scipy and numpy): a dict with ``upscale_factor`` and
+    optionally ``jpeg_prob`` / ``scale2_prob``; a batch that has ``"gt"`` and no ``"lr"`` gets ``batch["lr"] =
+    imgproc.degradation_process_bsrgan(batch["gt"], **dict)`` on the copy stream, the random draws taken from the global ``random`` /
+    ``np.random`` streams when the batch is staged.  It excludes ``synthesize_lr`` (``ValueError``): a batch gets one LR."""
+
+    def __init__(self, dataloader, device: torch.device, ingest_u8: bool = False, bgr: bool = True, synthesize_lr: int | None = None,
+                 synthesize_lr_bsrgan: dict | None = None):
         self.original_dataloader = dataloader
         self.ingest_u8, self.bgr = ingest_u8, bgr
         if synthesize_lr is not None and not synthesize_lr >= 1:
             raise ValueError(f"CUDAPrefetcher: synthesize_lr is the upscale factor (>= 1) or None, got {synthesize_lr}")
         self.synthesize_lr = synthesize_lr
+        if synthesize_lr_bsrgan is not None:
+            if synthesize_lr is not None:
+                raise ValueError("CUDAPrefetcher: synthesize_lr and synthesize_lr_bsrgan both make batch['lr']; pass one of them")
+            unknown = set(synthesize_lr_bsrgan) - {"upscale_factor", "jpeg_prob", "scale2_prob"}
+            if "upscale_factor" not in synthesize_lr_bsrgan or unknown:
+                raise ValueError("CUDAPrefetcher: synthesize_lr_bsrgan is dict(upscale_factor=..., jpeg_prob=..., scale2_prob=...), got "
+                                 f"{sorted(synthesize_lr_bsrgan)}")
+            synthesize_lr_bsrgan = dict(synthesize_lr_bsrgan)
+        self.synthesize_lr_bsrgan = synthesize_lr_bsrgan
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.batch_data = None
@@ -50,6 +66,9 @@ class CUDAPrefetcher:
             if self.synthesize_lr is not None and "lr" not in self.batch_data and torch.is_tensor(self.batch_data.get("gt")):
                 from .imgproc import image_resize
                 self.batch_data["lr"] = image_resize(self.batch_data["gt"], 1 / self.synthesize_lr)
+            if self.synthesize_lr_bsrgan is not None and "lr" not in self.batch_data and torch.is_tensor(self.batch_data.get("gt")):
+                from .imgproc import degradation_process_bsrgan
+                self.batch_data["lr"] = degradation_process_bsrgan(self.batch_data["gt"], **self.synthesize_lr_bsrgan)
 
     def next(self):
         """the staged batch (or None at the end of the epoch); starts staging the following one"""

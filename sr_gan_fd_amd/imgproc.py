@@ -1,6 +1,7 @@
 """Device-side mirror of the data-side helpers the train loops call on GPU tensors (reference: BSRGAN/imgproc.py for
 ``random_crop``; Real_ESRGAN/imgproc.py for the on-device degradation stages -- SURVEY 8f N4: ``filter2d_torch``,
-``USMSharp``, ``DiffJPEG``, the noise stages, ``degradation_process``).  The CPU-side pieces of that file (kernel synthesis with numpy / scipy, cv2 image I/O)
+``USMSharp``, ``DiffJPEG``, the noise stages, ``degradation_process``; BSRGAN/imgproc.py:492-562 for the blind degradation,
+``degradation_process_bsrgan``, with its real JPEG round trip and fp64 blur).  The CPU-side pieces of that file (kernel synthesis with numpy / scipy, cv2 image I/O)
 stay the reference's own."""
 from __future__ import annotations
 
@@ -465,6 +466,263 @@ def degradation_process(gt: Tensor, gaussian_kernel1: Tensor, gaussian_kernel2: 
         out = filter2d_torch(out, sinc_kernel)
     lr = quantize_u8(out)
     return gt_usm, gt, lr
+
+
+# ---- BSRGAN / A-ESRGAN blind degradation (BSRGAN/imgproc.py:161-225, 284-293, 492-562; the same text in A-ESRGAN/imgproc.py) ------
+def jpeg_compression(image: Tensor, quality) -> Tensor:
+    """imgproc._add_jpeg_compression (BSRGAN/imgproc.py:284-293) for a batch, at given qualities: ``uint8(round(clip(x, 0, 1) * 255))``,
+    a real baseline JPEG encode and decode (what ``cv2.imencode`` / ``cv2.imdecode`` run through libjpeg: 4:2:0, integer DCT, fancy
+    upsampling -- srganfd_jpeg_roundtrip computes the library's bytes), ``float32(u8) / 255``.  ``image``: (B, 3, H, W) or (3, H, W) RGB
+    on the GPU; ``quality``: an int, a sequence or an integer tensor with one entry per image, 1..100, where 0 returns that image
+    unchanged bit for bit (a ``jpeg_prob`` miss inside a batch).  Values that live on the host are validated; an integer tensor already
+    on the GPU is used as it is (no synchronisation; the kernel clamps 1..100).  Not differentiable: ``DiffJPEG`` is the other one."""
+    if not torch.is_tensor(image) or image.dim() not in (3, 4):
+        raise A.SrganfdError("jpeg_compression takes (3, H, W) or (B, 3, H, W) tensors")
+    _need_gpu(image, "jpeg_compression")
+    x = image.detach().contiguous().float()
+    x4 = x if x.dim() == 4 else x.unsqueeze(0)
+    b, c, h, w = x4.shape
+    q_host = None
+    if torch.is_tensor(quality) and quality.is_cuda:
+        if quality.dtype not in (torch.int32, torch.int64) or quality.numel() != b:
+            raise A.SrganfdError("jpeg_compression: a quality tensor holds one integer per image")
+        q_dev = quality.to(torch.int32).contiguous()
+    else:
+        q_host = _per_image_int(quality, b, "jpeg_compression: quality")
+        q_dev = torch.from_numpy(q_host).to(x.device)
+    return _jpeg_roundtrip(x4, q_dev, q_host).view(x.shape)
+
+
+def _per_image_int(v, b: int, what: str) -> np.ndarray:
+    if isinstance(v, (int, np.integer)):
+        return np.full(b, int(v), dtype=np.int32)
+    a = np.asarray(v.cpu() if torch.is_tensor(v) else v)
+    if a.dtype.kind not in "iu" or a.size != b:
+        raise A.SrganfdError(f"{what} holds one integer per image ({b}), got {a.dtype} x {a.size}")
+    return np.ascontiguousarray(a.reshape(b), dtype=np.int32)
+
+
+def _jpeg_roundtrip(x: Tensor, q_dev: Tensor, q_host) -> Tensor:
+    b, c, h, w = x.shape
+    L = A.lib()
+    nbytes = L.srganfd_jpeg_workspace_bytes(b, h, w)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=x.device)
+    out = torch.empty_like(x)
+    A.check(L.srganfd_jpeg_roundtrip(x.data_ptr(), b, c, h, w, q_dev.data_ptr(), q_host.ctypes.data if q_host is not None else None, ws.data_ptr(),
+                                     out.data_ptr(), A.stream_ptr()), "jpeg_roundtrip")
+    return out
+
+
+def _filter2d_mirror_f64(x: Tensor, kernels: Tensor, ksize_dev: Tensor, ksize_host: np.ndarray) -> Tensor:
+    """srganfd_filter2d_mirror_f64: image n of ``x`` with its own ``ksize[n]``-sized kernel (0: copied through), centred in ``kernels[n]``"""
+    b, c, h, w = x.shape
+    out = torch.empty_like(x)
+    A.check(A.lib().srganfd_filter2d_mirror_f64(x.data_ptr(), kernels.data_ptr(), kernels.shape[-1], ksize_dev.data_ptr(), ksize_host.ctypes.data,
+                                                b, c, h, w, out.data_ptr(), A.stream_ptr()), "filter2d_mirror_f64")
+    return out
+
+
+def filter2d_mirror_f64(image: Tensor, kernels, ksize) -> Tensor:
+    """``ndimage.convolve(image, k[:, :, None], mode='mirror')`` (BSRGAN/imgproc.py:223) for a batch whose images each have a kernel of
+    their own: ``image`` (B, C, H, W) on the GPU, ``kernels`` (B, kmax, kmax) float64 (array or tensor) with image n's ``ksize[n]``-sized
+    kernel centred in its array, ``ksize`` B odd sizes from 3 to kmax <= 25 or 0 (that image is returned unchanged).  fp64 multiply-adds,
+    one rounding to float32: scipy's values.  Cross-correlation, which for point-symmetric kernels is scipy's convolution."""
+    if not torch.is_tensor(image) or image.dim() != 4:
+        raise A.SrganfdError("filter2d_mirror_f64 takes a (B, C, H, W) tensor")
+    _need_gpu(image, "filter2d_mirror_f64")
+    x = image.detach().contiguous().float()
+    ks = _per_image_int(ksize, x.shape[0], "filter2d_mirror_f64: ksize")
+    kk = torch.as_tensor(kernels).to(device=x.device, dtype=torch.float64).contiguous()
+    if kk.dim() != 3 or kk.shape[0] != x.shape[0] or kk.shape[1] != kk.shape[2]:
+        raise A.SrganfdError(f"filter2d_mirror_f64: kernels are (B, kmax, kmax), got {tuple(kk.shape)} for {x.shape[0]} images")
+    return _filter2d_mirror_f64(x, kk, torch.from_numpy(ks).to(x.device), ks)
+
+
+BSRGAN_KMAX = 25             # _add_blur draws 2 * randint(2, 11) + 3: 7 .. 25
+_CV2_INTERP = {1: "bilinear", 2: "bicubic", 3: "area"}      # cv2.INTER_LINEAR / INTER_CUBIC / INTER_AREA
+
+
+def _fspecial_gaussian(hsize: int, sigma: float) -> np.ndarray:
+    """imgproc._fspecial_gaussian (BSRGAN/imgproc.py:161-172; ``np.finfo`` for the ``scipy.finfo`` that scipy no longer has)"""
+    half = (hsize - 1.0) / 2.0
+    x, y = np.meshgrid(np.arange(-half, half + 1), np.arange(-half, half + 1))
+    h = np.exp(-(x * x + y * y) / (2 * sigma * sigma))
+    h[h < np.finfo(float).eps * h.max()] = 0
+    sumh = h.sum()
+    if sumh != 0:
+        h = h / sumh
+    return h
+
+
+def _gm_blur_kernel(cov: np.ndarray, size: int) -> np.ndarray:
+    """imgproc._gm_blur_kernel (:186-197) at mean 0: the bivariate normal density on the centred grid, normalised to sum 1.  The density is
+    written out (scipy is not a dependency): exp(-x' inv(cov) x / 2) / (2 pi sqrt(det cov))"""
+    c = np.arange(size) - size / 2.0 - 0.5 + 1
+    cx, cy = np.meshgrid(c, c)                                # k[y, x] = pdf([cx, cy])
+    cov = (cov + cov.T) / 2
+    inv = np.linalg.inv(cov)
+    maha = inv[0, 0] * cx * cx + (inv[0, 1] + inv[1, 0]) * cx * cy + inv[1, 1] * cy * cy
+    k = np.exp(-0.5 * maha) / (2 * np.pi * np.sqrt(np.linalg.det(cov)))
+    return k / np.sum(k)
+
+
+def _anisotropic_gaussian(ksize: int, theta: float, l1: float, l2: float) -> np.ndarray:
+    """imgproc._anisotropic_gaussian (:201-208)"""
+    v = np.dot(np.array([[np.cos(theta), -np.sin(theta)], [np.sin(theta), np.cos(theta)]]), np.array([1., 0.]))
+    V = np.array([[v[0], v[1]], [v[1], -v[0]]])
+    D = np.array([[l1, 0], [0, l2]])
+    return _gm_blur_kernel(np.dot(np.dot(V, D), np.linalg.inv(V)), ksize)
+
+
+def bsrgan_degradation_draws(batch: int, upscale_factor: int, jpeg_prob: float = 0.9, scale2_prob: float = 0.25) -> list:
+    """Every random decision of ``degradation_process`` (BSRGAN/imgproc.py:492-562) for ``batch`` images, drawn image by image from the
+    global ``random`` and ``np.random`` streams in exactly the reference's order, so that a seeded run degrades as the reference's loader
+    would: [factor 4 only: ``random.random() < scale2_prob``; if so ``np.random.rand() < 0.5`` and, for the cv2 branch,
+    ``random.choice([1, 2, 3])``], ``random.sample(range(6), 6)``, then per live op in the shuffled order -- a blur: ``random.random() <
+    0.5``, then ``l1``, ``l2``, ``randint(2, 11)``, ``random.random() * pi`` (anisotropic) or ``randint(2, 11)``, ``wd * random.random()``
+    (isotropic); the JPEG: ``random.random() < jpeg_prob`` and ``randint(30, 95)`` on a hit -- and the final ``randint(30, 95)``.  Ops 2,
+    3 and 4 (the two resizes and the noise) begin with ``continue`` in the reference and draw nothing.
+    One plain dict per image: ``upscale_factor`` (as passed), ``half`` (None, "imresize" or "cv2"), ``interp`` (cv2's code 1 / 2 / 3 =
+    bilinear / bicubic / area, or None), ``sf`` (2 after a half-step), ``order`` (the shuffle), ``ops`` (the live ops in order:
+    ``("blur", {"kind": "aniso", "ksize", "theta", "l1", "l2"})``, ``("blur", {"kind": "iso", "ksize", "sigma"})``, ``("jpeg", quality or
+    0 on a miss)``) and ``final_quality``."""
+    out = []
+    for _ in range(batch):
+        rec = {"upscale_factor": upscale_factor, "half": None, "interp": None, "sf": upscale_factor}
+        if upscale_factor == 4 and random.random() < scale2_prob:
+            if np.random.rand() < 0.5:
+                rec["half"], rec["interp"] = "cv2", random.choice([1, 2, 3])
+            else:
+                rec["half"] = "imresize"
+            rec["sf"] = 2
+        order = random.sample(range(6), 6)
+        idx1, idx2 = order.index(2), order.index(3)
+        if idx1 > idx2:
+            order[idx1], order[idx2] = order[idx2], order[idx1]
+        rec["order"] = order
+        wd, wd2 = 2.0 + 0.2 * rec["sf"], 4.0 + rec["sf"]
+        ops = []
+        for i in order:
+            if i in (0, 1):
+                if random.random() < 0.5:
+                    l1 = wd2 * random.random()
+                    l2 = wd2 * random.random()
+                    ksize = 2 * random.randint(2, 11) + 3
+                    ops.append(("blur", {"kind": "aniso", "ksize": ksize, "theta": random.random() * np.pi, "l1": l1, "l2": l2}))
+                else:
+                    ksize = 2 * random.randint(2, 11) + 3
+                    ops.append(("blur", {"kind": "iso", "ksize": ksize, "sigma": wd * random.random()}))
+            elif i == 5:
+                ops.append(("jpeg", random.randint(30, 95) if random.random() < jpeg_prob else 0))
+        rec["ops"] = ops
+        rec["final_quality"] = random.randint(30, 95)
+        out.append(rec)
+    return out
+
+
+def bsrgan_blur_kernels(draws: list, upscale_factor: int):
+    """The two blur kernels of every image of ``draws`` (``_add_blur``, BSRGAN/imgproc.py:212-225), on the host in float64: ``(kernels
+    (B, 2, 25, 25)`` with each k x k kernel centred in its 25 x 25 array and zeros around it, ``ksize (B, 2) int32)``, the blurs in the
+    order the image runs them.  ``upscale_factor`` is the one the draws were made for (the widths ``wd``, ``wd2`` of an image that took the
+    half-step come from its updated factor and are already in its draws)."""
+    kernels = np.zeros((len(draws), 2, BSRGAN_KMAX, BSRGAN_KMAX), dtype=np.float64)
+    ksize = np.zeros((len(draws), 2), dtype=np.int32)
+    for n, rec in enumerate(draws):
+        if rec["upscale_factor"] != upscale_factor:
+            raise ValueError(f"bsrgan_blur_kernels: image {n} was drawn for factor {rec['upscale_factor']}, not {upscale_factor}")
+        blurs = [p for kind, p in rec["ops"] if kind == "blur"]
+        for j, p in enumerate(blurs):
+            k = _anisotropic_gaussian(p["ksize"], p["theta"], p["l1"], p["l2"]) if p["kind"] == "aniso" else _fspecial_gaussian(p["ksize"], p["sigma"])
+            o = (BSRGAN_KMAX - p["ksize"]) // 2
+            kernels[n, j, o:o + p["ksize"], o:o + p["ksize"]] = k
+            ksize[n, j] = p["ksize"]
+    return kernels, ksize
+
+
+def _bsrgan_programs(draws: list, kernels: np.ndarray, ksize: np.ndarray, idx: list):
+    """the images ``idx`` as three rounds of (blur | JPEG): per round the kernel array, the blur sizes (0: no blur this round) and the
+    JPEG qualities (0: none), plus the final qualities"""
+    n = len(idx)
+    kr = np.zeros((3, n, BSRGAN_KMAX, BSRGAN_KMAX), dtype=np.float64)
+    ks = np.zeros((3, n), dtype=np.int32)
+    qs = np.zeros((4, n), dtype=np.int32)
+    for j, i in enumerate(idx):
+        nb = 0
+        for r, (kind, p) in enumerate(draws[i]["ops"]):
+            if kind == "blur":
+                kr[r, j], ks[r, j] = kernels[i, nb], ksize[i, nb]
+                nb += 1
+            else:
+                qs[r, j] = p
+        qs[3, j] = draws[i]["final_quality"]
+    return kr, ks, qs
+
+
+def degradation_process_bsrgan(gt: Tensor, upscale_factor: int, jpeg_prob: float = 0.9, scale2_prob: float = 0.25, draws: list = None) -> Tensor:
+    """imgproc.degradation_process (BSRGAN/imgproc.py:492-562, dataset.py:83; A-ESRGAN's is the same text) for a whole GT batch on the GPU:
+    per image an optional half-size step (factor 4 only), two Gaussian blurs and an optional JPEG round trip in a shuffled order, a final
+    JPEG round trip and ``image_resize(1 / factor)``.  ``gt``: (B, 3, H, W) fp32 RGB in [0, 1]; returns (B, 3, H / factor, W / factor).
+    ``draws``: the per-image records of ``bsrgan_degradation_draws``; None draws them here, consuming the global ``random`` /
+    ``np.random`` streams exactly as the reference does image by image.
+    Images that took the half-step form a second sub-batch at (H / 2, W / 2) that runs with factor 2.  Each image's program is at most
+    three ops, run in three rounds; a round is one batched blur launch (srganfd_filter2d_mirror_f64, sizes 0 copy through) and one
+    batched JPEG launch (srganfd_jpeg_roundtrip, quality 0 copies through) per sub-batch, so nothing is gathered per image.  The blur
+    accumulates in fp64 like scipy's and the JPEG is the library's integer pipeline, so everything before the last ``image_resize`` lands on
+    the reference's float32 values.  The reference's ops 2, 3, 4 are dead code (they begin with ``continue``) and are not here.
+    ``ValueError``: a factor below 1, sizes the factor does not divide (odd sizes at factor 4 included), images whose shorter side -- after
+    the possible half-step -- is 12 or less (a 25-tap mirror does not fit), draws that do not match the batch."""
+    if not torch.is_tensor(gt) or gt.dim() != 4 or gt.shape[1] != 3:
+        raise A.SrganfdError("degradation_process_bsrgan takes a (B, 3, H, W) tensor")
+    b, _, h, w = gt.shape
+    if not (isinstance(upscale_factor, int) and upscale_factor >= 1):
+        raise ValueError(f"degradation_process_bsrgan: upscale_factor must be a positive integer, got {upscale_factor}")
+    if upscale_factor == 4 and (h % 2 or w % 2):
+        raise ValueError(f"degradation_process_bsrgan: {h} x {w} is odd; factor 4 may halve the image first")
+    if h % upscale_factor or w % upscale_factor:
+        raise ValueError(f"degradation_process_bsrgan: {h} x {w} is not divisible by the factor {upscale_factor}")
+    if (min(h, w) / 2 if upscale_factor == 4 else min(h, w)) <= BSRGAN_KMAX // 2:
+        raise ValueError(f"degradation_process_bsrgan: {h} x {w} is too small at factor {upscale_factor}: the 25-tap blur mirrors 12 samples "
+                         "of the image (of its half-size copy at factor 4)")
+    if draws is not None and (len(draws) != b or any(r["upscale_factor"] != upscale_factor for r in draws)):
+        raise ValueError(f"degradation_process_bsrgan: draws are for {len(draws)} images"
+                         f" at factor {sorted(set(r['upscale_factor'] for r in draws))}, the batch is {b} at factor {upscale_factor}")
+    _need_gpu(gt, "degradation_process_bsrgan")
+    if draws is None:
+        draws = bsrgan_degradation_draws(b, upscale_factor, jpeg_prob, scale2_prob)
+    kernels, ksize = bsrgan_blur_kernels(draws, upscale_factor)
+    x = gt.detach().contiguous().float()
+    dev = x.device
+    out = torch.empty(b, 3, h // upscale_factor, w // upscale_factor, dtype=torch.float32, device=dev)
+    full = [i for i, r in enumerate(draws) if r["half"] is None]
+    half = [i for i, r in enumerate(draws) if r["half"] is not None]
+    batches = []
+    if full:
+        batches.append((full, x if len(full) == b else x[torch.as_tensor(full, device=dev)], upscale_factor))
+    if half:
+        xh = torch.empty(len(half), 3, h // 2, w // 2, dtype=torch.float32, device=dev)
+        groups = {}
+        for j, i in enumerate(half):
+            groups.setdefault(draws[i]["interp"], []).append((j, i))
+        for interp, members in groups.items():
+            src = x[torch.as_tensor([i for _, i in members], device=dev)]
+            y = image_resize(src, 1 / 2, True) if interp is None else interpolate(src, scale_factor=0.5, mode=_CV2_INTERP[interp])
+            xh[torch.as_tensor([j for j, _ in members], device=dev)] = torch.clamp(y, 0.0, 1.0)
+        batches.append((half, xh, 2))
+    for idx, y, sf in batches:
+        kr, ks, qs = _bsrgan_programs(draws, kernels, ksize, idx)
+        ks_dev, qs_dev = torch.from_numpy(ks).to(dev), torch.from_numpy(qs).to(dev)
+        kr_dev = torch.from_numpy(kr).to(dev) if ks.any() else None
+        for r in range(3):
+            if ks[r].any():
+                y = _filter2d_mirror_f64(y, kr_dev[r], ks_dev[r], ks[r])
+            if qs[r].any():
+                y = _jpeg_roundtrip(y, qs_dev[r], qs[r])
+        y = _jpeg_roundtrip(y, qs_dev[3], qs[3])
+        y = image_resize(y, 1 / sf)
+        if len(idx) == b:
+            return y
+        out[torch.as_tensor(idx, device=dev)] = y
+    return out
 
 
 # ---- batch augmentation of the Real-ESRGAN loop (train_realesrgan.py:400-404) ------------------------------------------------
