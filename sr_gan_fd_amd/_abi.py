@@ -38,10 +38,12 @@ ACT_NONE, ACT_LRELU, ACT_RELU = 0, 1, 2
 
 
 class View(C.Structure):
+    C_NAME = "srganfd_view"
     _fields_ = [("ptr", C.c_void_p), ("cstride", C.c_int32), ("c0", C.c_int32), ("planar", C.c_int32), ("pad_", C.c_int32)]
 
 
 class ConvArgs(C.Structure):
+    C_NAME = "srganfd_conv_args"
     _fields_ = [
         ("dtype", C.c_int32), ("n", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("up", C.c_int32),
         ("ksize", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
@@ -57,6 +59,7 @@ class ConvArgs(C.Structure):
 
 
 class ThinArgs(C.Structure):
+    C_NAME = "srganfd_thin_args"
     _fields_ = [
         ("dtype", C.c_int32), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cs", C.c_int32), ("w_big_is_cout", C.c_int32),
         ("flip", C.c_int32), ("act", C.c_int32), ("slope", C.c_float), ("mask_slope", C.c_float),
@@ -66,20 +69,24 @@ class ThinArgs(C.Structure):
 
 
 class WgradReduceJob(C.Structure):
+    C_NAME = "srganfd_wgrad_reduce_job"
     _fields_ = [("plan_host", C.c_void_p), ("plan_dev", C.c_void_p), ("grads", C.c_void_p), ("scalars", C.c_void_p), ("workspace", C.c_void_p)]
 
 
 class SnJob(C.Structure):
+    C_NAME = "srganfd_sn_job"
     _fields_ = [("w_orig", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("sigma_out", C.c_void_p), ("inv_sigma_out", C.c_void_p),
                 ("workspace", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]
 
 
 class SnGradJob(C.Structure):
+    C_NAME = "srganfd_sn_grad_job"
     _fields_ = [("g_weight", C.c_void_p), ("w_orig", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("inv_sigma", C.c_void_p),
                 ("dw_orig", C.c_void_p), ("workspace", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]
 
 
 class PackSeg(C.Structure):
+    C_NAME = "srganfd_pack_seg"
     _fields_ = [
         ("src_off", C.c_int64), ("scale_off", C.c_int64), ("co_src", C.c_int32), ("ci_src", C.c_int32),
         ("k_lo", C.c_int32), ("k_len", C.c_int32), ("co_off", C.c_int32), ("ci_off", C.c_int32),
@@ -88,6 +95,7 @@ class PackSeg(C.Structure):
 
 
 class PackJob(C.Structure):
+    C_NAME = "srganfd_pack_job"
     _fields_ = [
         ("dst_off", C.c_int64), ("dtype", C.c_int32), ("ksize", C.c_int32), ("k", C.c_int32), ("n", C.c_int32),
         ("nseg", C.c_int32), ("layout", C.c_int32), ("seg", PackSeg * 5),
@@ -95,6 +103,7 @@ class PackJob(C.Structure):
 
 
 class WgradConv(C.Structure):
+    C_NAME = "srganfd_wgrad_conv"
     _fields_ = [
         ("ci_lo", C.c_int32), ("cin", C.c_int32), ("co_lo", C.c_int32), ("cout", C.c_int32),
         ("dw_off", C.c_int64), ("db_off", C.c_int64), ("co_dst", C.c_int32), ("ci_dst", C.c_int32),
@@ -103,6 +112,7 @@ class WgradConv(C.Structure):
 
 
 class WgradShape(C.Structure):
+    C_NAME = "srganfd_wgrad_shape"
     _fields_ = [
         ("dtype", C.c_int32), ("n", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("up", C.c_int32),
         ("ksize", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("h_out", C.c_int32), ("w_out", C.c_int32),
@@ -111,6 +121,7 @@ class WgradShape(C.Structure):
 
 
 class LpipsConvArgs(C.Structure):
+    C_NAME = "srganfd_lpips_conv_args"
     _fields_ = [
         ("n", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
         ("ksize", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("pool", C.c_int32), ("first", C.c_int32),
@@ -122,10 +133,13 @@ class LpipsConvArgs(C.Structure):
 
 
 class LpipsTap(C.Structure):
+    C_NAME = "srganfd_lpips_tap"
     _fields_ = [("maps", C.c_void_p), ("lin", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("pad_", C.c_int32)]
 
 
-# symbol -> (restype, argtypes); tests check that the library exports every one of these
+# symbol -> (restype, argtypes).  tests/test_host_logic.py checks that the library exports every one of these, and has a C++ compiler
+# check each entry's argument and return classes, every Structure above (C_NAME: the header's struct; size, field offsets and sizes) and
+# the constants this file repeats against include/srganfd.h
 SYMBOLS = {
     "srganfd_last_error": (C.c_char_p, []),
     "srganfd_abi_version": (C.c_int, []),

@@ -81,8 +81,9 @@ __global__ __launch_bounds__(256) void filter2d_mirror_f64_kernel(const float* _
   }
 }
 
-int filter2d_mirror_f64_impl(const float* src, const double* kernels, int kmax, const int* ksize, const int* ksize_host, int b, int c, int h, int w,
-                             float* out, hipStream_t s) {
+extern "C" int srganfd_filter2d_mirror_f64(const float* src, const double* kernels, int32_t kmax, const int32_t* ksize, const int32_t* ksize_host, int32_t b,
+                                           int32_t c, int32_t h, int32_t w, float* out, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!src || !kernels || !ksize || !out) return set_err(SRGANFD_EINVAL, "filter2d_mirror_f64: null pointer");
   if (b <= 0 || c <= 0 || h <= 0 || w <= 0) return set_err(SRGANFD_EINVAL, "filter2d_mirror_f64: bad args (b %d, c %d, %d x %d: all must be positive)", b, c, h, w);
   if (kmax < 3 || kmax > kB64MaxK || kmax % 2 == 0) return set_err(SRGANFD_EINVAL, "filter2d_mirror_f64: kmax %d is not an odd size from 3 to %d", kmax, kB64MaxK);

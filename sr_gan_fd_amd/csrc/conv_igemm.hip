@@ -888,6 +888,7 @@ static int launch_conv(const ConvK& k, int cout, hipStream_t stream) {
 // steps power-limited (1.2 kW, clock at 2.06 of 2.4 GHz) and holds a higher clock on this form.  The 32x32x16 instantiations of the
 // 16-bit kernels and the level switch live in the experiment sources (tools/experiments/r3_src).
 int g_mfma16 = 3;
+extern "C" int srganfd_get_mfma16(void) { return g_mfma16; }
 // non-temporal stores for outputs > 192 MB (same-box A/B switch: SRGANFD_CONV_NT=0 in the environment of the process that loads the library)
 static const bool g_conv_nt = [] { const char* e = getenv("SRGANFD_CONV_NT"); return !(e && e[0] == '0'); }();
 
@@ -896,6 +897,7 @@ bool conv_uses_m16(int dtype, int ksize, int cout) {
   (void)ksize; (void)cout;
   return dtype != SRGANFD_F32;
 }
+extern "C" int srganfd_pack_layout(int32_t dtype, int32_t ksize, int32_t n) { return conv_uses_m16(dtype, ksize, n) ? 1 : 0; }
 
 template <typename T>
 static int dispatch_conv(const srganfd_conv_args* a, const ConvK& k, hipStream_t s) {
@@ -1019,7 +1021,8 @@ int conv_fill_k(const srganfd_conv_args* a, ConvK& k) {
   return SRGANFD_OK;
 }
 
-int conv2d_impl(const srganfd_conv_args* a, hipStream_t stream) {
+// shared by srganfd_conv2d and srganfd_conv2d_describe (which launches nothing: dispatch_conv writes the kernel's label instead)
+static int conv2d_impl(const srganfd_conv_args* a, hipStream_t stream) {
   ConvK k;
   {
     const int rc = conv_fill_k(a, k);
@@ -1029,6 +1032,15 @@ int conv2d_impl(const srganfd_conv_args* a, hipStream_t stream) {
   if (a->dtype == SRGANFD_F16) return dispatch_conv<f16_t>(a, k, stream);
   if (a->dtype == SRGANFD_F32) return dispatch_conv<float>(a, k, stream);
   return set_err(SRGANFD_EINVAL, "conv2d: bad dtype %d", a->dtype);
+}
+extern "C" int srganfd_conv2d(const srganfd_conv_args* a, void* stream) { return conv2d_impl(a, (hipStream_t)stream); }
+extern "C" int srganfd_conv2d_describe(const srganfd_conv_args* a, char* out, size_t out_len) {
+  if (!out || !out_len) return set_err(SRGANFD_EINVAL, "conv2d_describe: no buffer");
+  out[0] = 0;
+  g_describe = out; g_describe_len = out_len;
+  const int rc = conv2d_impl(a, nullptr);
+  g_describe = nullptr; g_describe_len = 0;
+  return rc;
 }
 
 }  // namespace srganfd

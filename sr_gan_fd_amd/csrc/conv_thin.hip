@@ -590,7 +590,8 @@ static void thin_fill(const srganfd_thin_args* a, ThinK& k) {
   k.nt = (long long)a->n * ipix * a->big.cstride * 2 >= (192LL << 20) ? 1 : 0;
 }
 
-int conv2d_thin_in_impl(const srganfd_thin_args* a, hipStream_t s) {
+extern "C" int srganfd_conv2d_thin_in(const srganfd_thin_args* a, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   const int rc = thin_check(a, "conv2d_thin_in", true, false);
   if (rc != SRGANFD_OK) return rc;
   ThinK k;
@@ -611,7 +612,8 @@ int conv2d_thin_in_impl(const srganfd_thin_args* a, hipStream_t s) {
   return SRGANFD_OK;
 }
 
-int conv2d_thin_out_impl(const srganfd_thin_args* a, hipStream_t s) {
+extern "C" int srganfd_conv2d_thin_out(const srganfd_thin_args* a, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   const int rc = thin_check(a, "conv2d_thin_out", false, true);
   if (rc != SRGANFD_OK) return rc;
   if (a->big.planar) return set_err(SRGANFD_EINVAL, "conv2d_thin_out: NHWC input views only");
@@ -628,12 +630,13 @@ int conv2d_thin_out_impl(const srganfd_thin_args* a, hipStream_t s) {
 }
 
 static int thin_wgrad_grid() { return 2 * conv_device_cus(); }
-size_t conv2d_thin_wgrad_workspace_impl() { return (size_t)thin_wgrad_grid() * kTwSlab * sizeof(float); }
+extern "C" size_t srganfd_conv2d_thin_wgrad_workspace(void) { return (size_t)thin_wgrad_grid() * kTwSlab * sizeof(float); }
 
-int conv2d_thin_wgrad_impl(const srganfd_thin_args* a, float* dw, float* db, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int srganfd_conv2d_thin_wgrad(const srganfd_thin_args* a, float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   const int rc = thin_check(a, "conv2d_thin_wgrad", true, false);
   if (rc != SRGANFD_OK) return rc;
-  if (!dw || !ws || ws_bytes < conv2d_thin_wgrad_workspace_impl()) return set_err(SRGANFD_EINVAL, "conv2d_thin_wgrad: null gradient / workspace below srganfd_conv2d_thin_wgrad_workspace()");
+  if (!dw || !ws || ws_bytes < srganfd_conv2d_thin_wgrad_workspace()) return set_err(SRGANFD_EINVAL, "conv2d_thin_wgrad: null gradient / workspace below srganfd_conv2d_thin_wgrad_workspace()");
   ThinWgK k;
   const long long ipix = (long long)a->h * a->w;
   k.big = a->big.ptr; k.thin = a->thin; k.slabs = (float*)ws;

@@ -102,8 +102,9 @@ __global__ __launch_bounds__(256) void filter2d_kernel(const float* __restrict__
   }
 }
 
-int filter2d_impl(const float* src, const float* kernels, int kernel_batch, int b, int c, int h, int w, int k, int mode, const float* x_in,
-                  const float* res_in, float weight, float threshold, float* out, float* out2, hipStream_t s, bool separable = false) {
+// shared by srganfd_filter2d, srganfd_filter2d_separable and the two passes of srganfd_usm_sharp
+static int filter2d_impl(const float* src, const float* kernels, int kernel_batch, int b, int c, int h, int w, int k, int mode, const float* x_in,
+                         const float* res_in, float weight, float threshold, float* out, float* out2, hipStream_t s, bool separable) {
   if (!src || !kernels || !out || b <= 0 || c <= 0 || h <= 0 || w <= 0) return set_err(SRGANFD_EINVAL, "filter2d: null / empty argument");
   if (k % 2 == 0 || k < 1) return set_err(SRGANFD_EINVAL, "Wrong kernel size.");                     // the reference's ValueError text
   if (k > kF2dMaxK) return set_err(SRGANFD_EINVAL, "filter2d: kernel size %d above the LDS tile's %d", k, kF2dMaxK);
@@ -121,6 +122,24 @@ int filter2d_impl(const float* src, const float* kernels, int kernel_batch, int 
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
+extern "C" int srganfd_filter2d(const float* image, const float* kernels, int32_t kernel_batch, int32_t b, int32_t c, int32_t h, int32_t w, int32_t k, float* out,
+                                void* stream) {
+  return filter2d_impl(image, kernels, kernel_batch, b, c, h, w, k, 0, nullptr, nullptr, 0.f, 0.f, out, nullptr, (hipStream_t)stream, false);
+}
+extern "C" int srganfd_usm_sharp(const float* image, const float* kernel, int32_t separable, int32_t b, int32_t c, int32_t h, int32_t w, int32_t k, float weight,
+                                 float threshold, float* out, float* workspace, void* stream) {
+  if (!workspace) return set_err(SRGANFD_EINVAL, "usm_sharp: workspace of 2 * b*c*h*w floats needed");
+  const size_t n = (size_t)b * c * h * w;
+  float* residual = workspace;
+  float* mask = workspace + n;
+  int rc = filter2d_impl(image, kernel, 1, b, c, h, w, k, 1, nullptr, nullptr, weight, threshold, residual, mask, (hipStream_t)stream, separable != 0);
+  if (rc != SRGANFD_OK) return rc;
+  return filter2d_impl(mask, kernel, 1, b, c, h, w, k, 2, image, residual, weight, threshold, out, nullptr, (hipStream_t)stream, separable != 0);
+}
+extern "C" int srganfd_filter2d_separable(const float* image, const float* taps, int32_t kernel_batch, int32_t b, int32_t c, int32_t h, int32_t w, int32_t k,
+                                          float* out, void* stream) {
+  return filter2d_impl(image, taps, kernel_batch, b, c, h, w, k, 0, nullptr, nullptr, 0.f, 0.f, out, nullptr, (hipStream_t)stream, true);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // DiffJPEG (imgproc.py:1198-1497): x255, RGB -> YCbCr, 2x2 chroma average, per 8x8 block DCT -> divide by
@@ -133,8 +152,9 @@ int filter2d_impl(const float* src, const float* kernels, int kernel_batch, int 
 // tables: [dct 4096 | idct 4096 | dct scale 64 | idct alpha 64 | y_table 64 | c_table 64] floats.
 // ---------------------------------------------------------------------------------------------------------------
 static constexpr int kJpegTableFloats = 4096 * 2 + 64 * 4;
+extern "C" int32_t srganfd_diff_jpeg_table_floats(void) { return kJpegTableFloats; }
 
-void diff_jpeg_tables_host(float* t) {
+static void diff_jpeg_tables_host(float* t) {
   static const float y_std[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
                                   14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
                                   49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
@@ -161,6 +181,11 @@ void diff_jpeg_tables_host(float* t) {
       ytab[u * 8 + v] = y_std[v * 8 + u];                                    // the reference transposes the standard table (:43-48)
       ctab[u * 8 + v] = (u < 4 && v < 4) ? c_small[v * 4 + u] : 99.f;
     }
+}
+extern "C" int srganfd_diff_jpeg_tables(float* host_out) {
+  if (!host_out) return set_err(SRGANFD_EINVAL, "diff_jpeg_tables: null output");
+  diff_jpeg_tables_host(host_out);
+  return SRGANFD_OK;
 }
 
 __global__ __launch_bounds__(256) void diff_jpeg_kernel(const float* __restrict__ src, int b, int h, int w, int mcus_x, int mcus_y,
@@ -284,8 +309,9 @@ __global__ void jpeg_quality_factor_kernel(float* q, int n) {
   }
 }
 
-int diff_jpeg_impl(const float* src, int b, int c, int h, int w, float* quality, int quality_is_factor, int differentiable, const float* tables,
-                   float* dst, hipStream_t s) {
+extern "C" int srganfd_diff_jpeg(const float* src, int32_t b, int32_t c, int32_t h, int32_t w, float* quality, int32_t quality_is_factor,
+                                 int32_t differentiable, const float* tables, float* dst, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!src || !dst || !quality || !tables || b <= 0 || h <= 0 || w <= 0) return set_err(SRGANFD_EINVAL, "diff_jpeg: null / empty argument");
   if (c != 3) return set_err(SRGANFD_EINVAL, "diff_jpeg: needs 3-channel RGB input, got %d channels", c);
   const int mcus_x = ceil_div(w, 16), mcus_y = ceil_div(h, 16);
@@ -303,7 +329,9 @@ __global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restric
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
     dst[i] = fminf(fmaxf(rintf(src[i] * 255.f), 0.f), 255.f) / 255.f;
 }
-int quantize_u8_impl(const float* src, float* dst, size_t n, hipStream_t s) {
+extern "C" int srganfd_quantize_u8(const float* src, float* dst, int64_t numel, void* stream) {
+  const size_t n = numel > 0 ? (size_t)numel : 0;
+  const hipStream_t s = (hipStream_t)stream;
   if (!src || !dst || n == 0) return set_err(SRGANFD_EINVAL, "quantize_u8: null / empty argument");
   const size_t blocks = (n + 255) / 256;
   SRGANFD_LAUNCH(quantize_u8_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, s, src, dst, n);
@@ -367,7 +395,9 @@ __global__ __launch_bounds__(256) void resize_kernel(const float* __restrict__ s
   }
 }
 
-int resize_impl(const float* src, int planes, int h, int w, int oh, int ow, int mode, float rscale_h, float rscale_w, float* dst, hipStream_t s) {
+extern "C" int srganfd_resize(const float* src, int32_t planes, int32_t h, int32_t w, int32_t oh, int32_t ow, int32_t mode, float rscale_h, float rscale_w,
+                              float* dst, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!src || !dst || planes <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) return set_err(SRGANFD_EINVAL, "resize: null / empty argument");
   if (mode < 0 || mode > 2) return set_err(SRGANFD_EINVAL, "resize: mode %d (0 area, 1 bilinear, 2 bicubic)", mode);
   const float rh = rscale_h > 0.f ? rscale_h : (float)h / (float)oh, rw = rscale_w > 0.f ? rscale_w : (float)w / (float)ow;
@@ -482,8 +512,9 @@ static inline dim3 ew_grid(size_t total) {
   const size_t blocks = (total + 255) / 256;
   return dim3((unsigned)(blocks < 32768 ? blocks : 32768));
 }
-int gaussian_noise_impl(const float* image, const float* n_color, const float* n_gray, const float* sigma, const float* gray, int b, int c, int h, int w,
-                        int clip, int rounds, float* out, hipStream_t s) {
+extern "C" int srganfd_gaussian_noise(const float* image, const float* n_color, const float* n_gray, const float* sigma, const float* gray, int32_t b,
+                                      int32_t c, int32_t h, int32_t w, int32_t clip, int32_t rounds, float* out, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!image || !n_color || !sigma || !out || b <= 0 || c <= 0 || h <= 0 || w <= 0 || (n_gray && !gray))
     return set_err(SRGANFD_EINVAL, "gaussian_noise: null / empty argument (a gray field needs the per-image gray flags)");
   const size_t hw = (size_t)h * w, total = hw * c * b;
@@ -491,8 +522,10 @@ int gaussian_noise_impl(const float* image, const float* n_color, const float* n
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
-int poisson_prepare_impl(const float* image, int b, int c, int h, int w, int want_gray, float* img_q, float* gray_q, float* vals, float* vals_gray,
-                         unsigned int* presence, hipStream_t s) {
+extern "C" int srganfd_poisson_prepare(const float* image, int32_t b, int32_t c, int32_t h, int32_t w, int32_t want_gray, float* img_q, float* gray_q,
+                                       float* vals, float* vals_gray, void* workspace, void* stream) {
+  unsigned int* presence = (unsigned int*)workspace;
+  const hipStream_t s = (hipStream_t)stream;
   if (!image || !img_q || !vals || !presence || b <= 0 || c <= 0 || h <= 0 || w <= 0 || b > 65535)
     return set_err(SRGANFD_EINVAL, "poisson_prepare: null / empty argument");
   if (want_gray && (c != 3 || !gray_q || !vals_gray)) return set_err(SRGANFD_EINVAL, "poisson_prepare: gray noise needs 3-channel RGB and its outputs");
@@ -504,9 +537,10 @@ int poisson_prepare_impl(const float* image, int b, int c, int h, int w, int wan
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
-int poisson_apply_impl(const float* image, const float* img_q, const float* gray_q, const float* pois, const float* pois_gray, const float* vals,
-                       const float* vals_gray, const float* scale, const float* gray, int b, int c, int h, int w, int clip, int rounds, float* out,
-                       hipStream_t s) {
+extern "C" int srganfd_poisson_apply(const float* image, const float* img_q, const float* gray_q, const float* pois, const float* pois_gray,
+                                     const float* vals, const float* vals_gray, const float* scale, const float* gray, int32_t b, int32_t c, int32_t h,
+                                     int32_t w, int32_t clip, int32_t rounds, float* out, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!image || !img_q || !pois || !vals || !scale || !out || b <= 0 || c <= 0 || h <= 0 || w <= 0)
     return set_err(SRGANFD_EINVAL, "poisson_apply: null / empty argument");
   if (pois_gray && (!gray_q || !vals_gray || !gray)) return set_err(SRGANFD_EINVAL, "poisson_apply: gray noise needs gray_q, vals_gray and the gray flags");
@@ -540,7 +574,9 @@ __global__ __launch_bounds__(256) void crop_rot_flip_kernel(const float* __restr
     dst[i] = src[(pl * h + top + sy) * w + left + sx];
   }
 }
-int crop_rot_flip_impl(const float* src, float* dst, int planes, int h, int w, int top, int left, int ph, int pw, int op, hipStream_t s) {
+extern "C" int srganfd_crop_rot_flip(const float* src, float* dst, int32_t planes, int32_t h, int32_t w, int32_t top, int32_t left, int32_t ph, int32_t pw,
+                                     int32_t op, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!src || !dst || planes <= 0 || top < 0 || left < 0 || ph <= 0 || pw <= 0 || top + ph > h || left + pw > w)
     return set_err(SRGANFD_EINVAL, "crop_rot_flip: window %dx%d at (%d,%d) outside %dx%d", ph, pw, top, left, h, w);
   if (op < 0 || op > 5) return set_err(SRGANFD_EINVAL, "crop_rot_flip: op %d", op);
@@ -549,7 +585,5 @@ int crop_rot_flip_impl(const float* src, float* dst, int planes, int h, int w, i
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
-
-int jpeg_table_floats() { return kJpegTableFloats; }
 
 }  // namespace srganfd

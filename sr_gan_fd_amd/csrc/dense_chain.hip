@@ -622,7 +622,7 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-size_t dense_chain_workspace_bytes_impl() { return 64 + sizeof(int) * 4 * kDcMaxTiles; }      // header + flags of 4 growth layers x tiles of one call
+extern "C" size_t srganfd_dense_chain_workspace_bytes(void) { return 64 + sizeof(int) * 4 * kDcMaxTiles; }      // header + flags of 4 growth layers x tiles of one call
 
 // Validates that `layers` are the convs of one dense chain and fills the kernel arguments at image 0's bases.
 static int dense_chain_fill(const srganfd_conv_args* layers, int n, DcK& K) {
@@ -698,18 +698,18 @@ static int dense_chain_limits(const DcK& K) {
   return SRGANFD_OK;
 }
 
-int dense_chain_check_impl(const srganfd_conv_args* layers, int n) {
+extern "C" int srganfd_dense_chain_check(const srganfd_conv_args* layers, int32_t n) {
   DcK K;
   const int rc = dense_chain_fill(layers, n, K);
   return rc != SRGANFD_OK ? rc : dense_chain_limits(K);
 }
 
-int dense_chain_impl(const srganfd_conv_args* layers, int n, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+extern "C" int srganfd_dense_chain(const srganfd_conv_args* layers, int32_t n, void* workspace, size_t workspace_bytes, void* stream) {
   DcK K;
   int rc = dense_chain_fill(layers, n, K);
   if (rc != SRGANFD_OK) return rc;
   if ((rc = dense_chain_limits(K)) != SRGANFD_OK) return rc;
-  if (!workspace || workspace_bytes < dense_chain_workspace_bytes_impl()) return set_err(SRGANFD_ENOSPC, "dense_chain: workspace too small");
+  if (!workspace || workspace_bytes < srganfd_dense_chain_workspace_bytes()) return set_err(SRGANFD_ENOSPC, "dense_chain: workspace too small");
   if (g_describe) { snprintf(g_describe, g_describe_len, "dense_chain_kernel<%s,%d layers>", layers[0].dtype == SRGANFD_F16 ? "f16" : "bf16", n); return SRGANFD_OK; }
   K.hdr = (int*)workspace;
   K.flags = (int*)((char*)workspace + 64);
@@ -729,12 +729,12 @@ int dense_chain_impl(const srganfd_conv_args* layers, int n, void* workspace, si
   }
   const unsigned grid = (unsigned)(K.ipl * K.tpi);
   switch (variant) {
-    case 0: SRGANFD_LAUNCH((dense_chain_kernel<bf16_t, 4>), dim3(grid), dim3(kDcThreads), lds, stream, K); break;
-    case 1: SRGANFD_LAUNCH((dense_chain_kernel<f16_t, 4>), dim3(grid), dim3(kDcThreads), lds, stream, K); break;
-    case 2: SRGANFD_LAUNCH((dense_chain_kernel<bf16_t, 3>), dim3(grid), dim3(kDcThreads), lds, stream, K); break;
-    case 3: SRGANFD_LAUNCH((dense_chain_kernel<f16_t, 3>), dim3(grid), dim3(kDcThreads), lds, stream, K); break;
-    case 4: SRGANFD_LAUNCH((dense_chain_kernel<bf16_t, 2>), dim3(grid), dim3(kDcThreads), lds, stream, K); break;
-    default: SRGANFD_LAUNCH((dense_chain_kernel<f16_t, 2>), dim3(grid), dim3(kDcThreads), lds, stream, K); break;
+    case 0: SRGANFD_LAUNCH((dense_chain_kernel<bf16_t, 4>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
+    case 1: SRGANFD_LAUNCH((dense_chain_kernel<f16_t, 4>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
+    case 2: SRGANFD_LAUNCH((dense_chain_kernel<bf16_t, 3>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
+    case 3: SRGANFD_LAUNCH((dense_chain_kernel<f16_t, 3>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
+    case 4: SRGANFD_LAUNCH((dense_chain_kernel<bf16_t, 2>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
+    default: SRGANFD_LAUNCH((dense_chain_kernel<f16_t, 2>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
   }
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;

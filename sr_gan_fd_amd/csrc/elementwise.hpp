@@ -1,0 +1,90 @@
+// elementwise.hpp -- what the bandwidth-bound kernel files share (elementwise, layout, resample, loss, norm, optim): typed scalar
+// and 16-byte vector access to channel-slice views, the block reduction, and the host side's grid sizing and dtype dispatch.
+// Those kernels are grid-stride, vectorised where the layout allows, and accumulate in fp32.
+// Reductions are two-stage (per-block partials, then one block) -> bitwise reproducible, no atomics.
+#pragma once
+#include "common.hpp"
+#include <initializer_list>
+
+namespace srganfd {
+
+template <typename T> __device__ __forceinline__ float ld(const void* p, size_t i) { return Elem<T>::to_f(((const T*)p)[i]); }
+template <typename T> __device__ __forceinline__ void st(void* p, size_t i, float v) { ((T*)p)[i] = Elem<T>::from_f(v); }
+
+__device__ __forceinline__ float block_reduce_sum(float v, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  float r = 0.f;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
+  return r;  // valid on thread 0
+}
+
+// ---- 16-byte vector access (8 bf16 / 4 f32 channels per lane): every view-to-view kernel below has a
+// vector form used whenever channel count, view offset and buffer stride are multiples of VecN<T>.
+template <typename T> struct VecN { static constexpr int N = 16 / (int)sizeof(T); };
+template <typename T> __device__ __forceinline__ void ldv(const void* p, size_t i, float* o) {
+  if constexpr (sizeof(T) == 2) {
+    unpack8<T>(*(const u32x4*)((const T*)p + i), o);
+  } else {
+    const f32x4 r = *(const f32x4*)((const float*)p + i);
+    o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3];
+  }
+}
+// non-temporal form: outputs that are written once and are far larger than the caches (the upsampled U-Net tensors: 0.5-2 GB)
+template <typename T> __device__ __forceinline__ void stv_nt(void* p, size_t i, const float* v) {
+  if constexpr (sizeof(T) == 2) {
+    __builtin_nontemporal_store(pack8<T>(v), (u32x4*)((T*)p + i));
+  } else {
+    const f32x4 o = {v[0], v[1], v[2], v[3]};
+    __builtin_nontemporal_store(o, (f32x4*)((float*)p + i));
+  }
+}
+template <typename T> __device__ __forceinline__ void stv(void* p, size_t i, const float* v) {
+  if constexpr (sizeof(T) == 2) {
+    *(u32x4*)((T*)p + i) = pack8<T>(v);
+  } else {
+    const f32x4 o = {v[0], v[1], v[2], v[3]};
+    *(f32x4*)((float*)p + i) = o;
+  }
+}
+
+// raw 16-byte vector (8 halves or 4 floats), widened to floats where it is used
+template <typename T> __device__ __forceinline__ u32x4 ldraw(const void* p, size_t i) { return *(const u32x4*)((const T*)p + i); }
+template <typename T> __device__ __forceinline__ void widen(const u32x4 raw, float* o) {
+  if constexpr (sizeof(T) == 2) unpack8<T>(raw, o);
+  else { o[0] = __uint_as_float(raw[0]); o[1] = __uint_as_float(raw[1]); o[2] = __uint_as_float(raw[2]); o[3] = __uint_as_float(raw[3]); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+inline unsigned grid_for(size_t total, int block = 256, unsigned cap = 8192) {
+  size_t g = (total + block - 1) / block;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (unsigned)g;
+}
+// CALL names the element type as TT
+#define DISPATCH_T(dtype, CALL)                                                              \
+  if ((dtype) == SRGANFD_BF16) { using TT = bf16_t; CALL; } else if ((dtype) == SRGANFD_F16) { using TT = f16_t; CALL; } \
+  else if ((dtype) == SRGANFD_F32) { using TT = float; CALL; }                               \
+  else return set_err(SRGANFD_EINVAL, "bad dtype %d", (int)(dtype));
+
+static constexpr int kRedBlocks = 1024;  // partial sums of a two-stage reduction; workspace floats needed by the loss entry points: 2 * kRedBlocks
+
+// may every view be read and written as 16-byte vectors of `dtype` over c channels?  (a null view passes)
+inline bool vec_ok(int dtype, int c, std::initializer_list<srganfd_view> vs) {
+  const int vn = dtype == SRGANFD_F32 ? 4 : 8;
+  if (c % vn) return false;
+  for (const auto& v : vs)
+    if (v.ptr && (v.c0 % vn || v.cstride % vn || ((uintptr_t)v.ptr & 15))) return false;
+  return true;
+}
+// the same view, cb channels further on
+inline srganfd_view sub_view(srganfd_view v, int cb) { if (v.ptr) v.c0 += cb; return v; }
+
+}  // namespace srganfd

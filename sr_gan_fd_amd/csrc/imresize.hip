@@ -218,8 +218,9 @@ static bool imresize_plan(int T, int h, int w, int oh, int ow, int taps_h, int t
   return true;
 }
 
-int imresize_impl(const float* src, int planes, int h, int w, int oh, int ow, const float* wt_h, const int* first_h, int taps_h,
-                  const float* wt_w, const int* first_w, int taps_w, float* dst, hipStream_t s) {
+extern "C" int srganfd_imresize(const float* src, int32_t planes, int32_t h, int32_t w, int32_t oh, int32_t ow, const float* wt_h, const int32_t* first_h,
+                                int32_t taps_h, const float* wt_w, const int32_t* first_w, int32_t taps_w, float* dst, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!src || !dst || !wt_h || !first_h || !wt_w || !first_w) return set_err(SRGANFD_EINVAL, "imresize: null pointer");
   if (planes <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || taps_h < 1 || taps_w < 1)
     return set_err(SRGANFD_EINVAL, "imresize: bad args (planes %d, %d x %d -> %d x %d, taps %d / %d: all must be positive)", planes, h, w, oh, ow,

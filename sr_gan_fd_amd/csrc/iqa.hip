@@ -7,7 +7,7 @@
 //                       in a fixed order, the AGGD fits and the 18 features by the first lanes of wave 0
 // Launch plan per batch: luma, block kernel (scale 1), resize, block kernel (scale 2).  fp64 vector arithmetic throughout (no MFMA),
 // except the resize, which the reference runs in float32 (see resize_half_kernel).
-// PSNR and SSIM stay in elementwise.hip.
+// PSNR and SSIM are in psnr_ssim.hip: this file compiles with floating-point contraction off (below), they were validated with it on.
 #include "common.hpp"
 #include <math.h>
 
@@ -250,7 +250,7 @@ static int niqe_geometry(const char* who, int n, int hc, int wc, int bh, int bw,
   return SRGANFD_OK;
 }
 
-int64_t niqe_workspace_doubles(int n, int c, int h, int w, int crop_border, int bh, int bw) {
+extern "C" int64_t srganfd_niqe_workspace_doubles(int32_t n, int32_t c, int32_t h, int32_t w, int32_t crop_border, int32_t bh, int32_t bw) {
   int lh = 0, lw = 0;
   if (c != 3) { set_err(SRGANFD_EINVAL, "niqe: needs 3-channel RGB input, have %d channels", c); return -1; }
   if (crop_border < 0 || niqe_geometry("niqe", n, h - 2 * crop_border, w - 2 * crop_border, bh, bw, &lh, &lw) != SRGANFD_OK) {
@@ -260,13 +260,17 @@ int64_t niqe_workspace_doubles(int n, int c, int h, int w, int crop_border, int 
   return (int64_t)n * lh * lw + (int64_t)n * (lh / 2) * (lw / 2);
 }
 
-int resize_half_impl(const double* src, int planes, int h, int w, double div, double* dst, hipStream_t s) {
+// shared by srganfd_resize_half (div 1) and srganfd_niqe_features_luma (div 255: the second scale works on [0, 1])
+static int resize_half_impl(const double* src, int planes, int h, int w, double div, double* dst, hipStream_t s) {
   if (!src || !dst || planes <= 0 || planes > 65535 || h < 4 + (h & 1) || w < 4 + (w & 1))
     return set_err(SRGANFD_EINVAL, "resize_half: bad args (planes 1..65535 of at least 4 x 4 pixels, 5 along an odd side)");
   const int oh = (h + 1) / 2, ow = (w + 1) / 2;
   SRGANFD_LAUNCH(resize_half_kernel, dim3(ceil_div(ow, kHalfTile), ceil_div(oh, kHalfTile), planes), dim3(256), 0, s, src, h, w, oh, ow, div, dst);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
+}
+extern "C" int srganfd_resize_half(const double* src, int32_t planes, int32_t h, int32_t w, double* dst, void* stream) {
+  return resize_half_impl(src, planes, h, w, 1.0, dst, (hipStream_t)stream);
 }
 
 static int niqe_block_launch(const double* plane, int n, int ph, int pw, int bh, int bw, double mult, const double* table, int table_len,
@@ -292,8 +296,9 @@ static int niqe_block_launch(const double* plane, int n, int ph, int pw, int bh,
 }
 
 // luma (n, h, w) with h, w whole multiples of the block -> feat (n, blocks, 36), half (n, h/2, w/2) in [0,1]
-int niqe_features_luma_impl(const double* luma, int n, int h, int w, int bh, int bw, const double* table, int table_len, double* feat, double* half,
-                            hipStream_t s) {
+extern "C" int srganfd_niqe_features_luma(const double* luma, int32_t n, int32_t h, int32_t w, int32_t bh, int32_t bw, const double* table, int32_t table_len,
+                                          double* feat, double* half, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   int lh = 0, lw = 0;
   if (!luma || !table || !feat || !half || table_len < 2) return set_err(SRGANFD_EINVAL, "niqe_features_luma: null pointer or a table of fewer than 2 entries");
   int rc = niqe_geometry("niqe_features_luma", n, h, w, bh, bw, &lh, &lw);
@@ -304,16 +309,17 @@ int niqe_features_luma_impl(const double* luma, int n, int h, int w, int bh, int
   return niqe_block_launch(half, n, h / 2, w / 2, bh / 2, bw / 2, 255.0, table, table_len, feat + 18, s);
 }
 
-int niqe_features_impl(const float* rgb, int n, int c, int h, int w, int crop_border, int bh, int bw, const double* table, int table_len, double* feat,
-                       double* ws, hipStream_t s) {
+extern "C" int srganfd_niqe_features(const float* rgb, int32_t n, int32_t c, int32_t h, int32_t w, int32_t crop_border, int32_t bh, int32_t bw,
+                                     const double* table, int32_t table_len, double* feat, double* ws, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!rgb || !table || !feat || !ws || table_len < 2) return set_err(SRGANFD_EINVAL, "niqe_features: null pointer or a table of fewer than 2 entries");
-  if (niqe_workspace_doubles(n, c, h, w, crop_border, bh, bw) < 0) return SRGANFD_EINVAL;
+  if (srganfd_niqe_workspace_doubles(n, c, h, w, crop_border, bh, bw) < 0) return SRGANFD_EINVAL;
   const int lh = (h - 2 * crop_border) / bh * bh, lw = (w - 2 * crop_border) / bw * bw;
   const size_t total = (size_t)n * lh * lw;
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   SRGANFD_LAUNCH(niqe_luma_kernel, dim3(grid), dim3(256), 0, s, rgb, h, w, crop_border, lh, lw, total, ws);
   SRGANFD_HIP_CHECK(hipGetLastError());
-  return niqe_features_luma_impl(ws, n, lh, lw, bh, bw, table, table_len, feat, ws + total, s);
+  return srganfd_niqe_features_luma(ws, n, lh, lw, bh, bw, table, table_len, feat, ws + total, stream);
 }
 
 }  // namespace srganfd

@@ -232,13 +232,14 @@ __global__ __launch_bounds__(256) void jpeg_finish_kernel(const float* __restric
   }
 }
 
-long long jpeg_workspace_bytes(int b, int h, int w) {
+extern "C" int64_t srganfd_jpeg_workspace_bytes(int32_t b, int32_t h, int32_t w) {
   if (b <= 0 || h <= 0 || w <= 0) return -1;
   return (long long)b * ceil_div(h, 16) * ceil_div(w, 16) * kJpgMcuBytes;
 }
 
-int jpeg_roundtrip_impl(const float* src, int b, int c, int h, int w, const int* quality, const int* quality_host, void* workspace, float* dst,
-                        hipStream_t s) {
+extern "C" int srganfd_jpeg_roundtrip(const float* src, int32_t b, int32_t c, int32_t h, int32_t w, const int32_t* quality, const int32_t* quality_host,
+                                      void* workspace, float* dst, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!src || !dst || !quality || !workspace) return set_err(SRGANFD_EINVAL, "jpeg_roundtrip: null pointer");
   if (c != 3) return set_err(SRGANFD_EINVAL, "jpeg_roundtrip: needs 3-channel RGB input, got %d channels", c);
   if (b <= 0 || h <= 0 || w <= 0) return set_err(SRGANFD_EINVAL, "jpeg_roundtrip: bad args (b %d, %d x %d: all must be positive)", b, h, w);

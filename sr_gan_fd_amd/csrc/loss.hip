@@ -1,0 +1,297 @@
+// loss.hip -- the scalar losses and what scales them: L1 (flat, on views, its gradient on views), BCE-with-logits and its
+// relativistic-average form, sigmoid(mean), the non-finite flag and the device-resident loss scaler.
+#include "elementwise.hpp"
+
+namespace srganfd {
+
+// ---- losses.  out[slot] (+)= weight * mean(...) ; two-stage deterministic reduction ----
+// L1 (nn.L1Loss, train_bsrgan.py:297,450) on flat fp32 arrays, optional gradient wrt a.
+__global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n, float gscale,
+                                                         const float* __restrict__ gscale_dev, float* __restrict__ grad, float* __restrict__ partial) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  if (gscale_dev) gscale *= *gscale_dev;      // the loss scale lives in device memory (srganfd_loss_scale_update), as torch's GradScaler keeps it
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float d = a[i] - b[i];
+    s += fabsf(d);
+    if (grad) grad[i] = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f);
+  }
+  const float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+// L1 between two NHWC T views (VGG feature taps, model.py:548-550), no gradient (detached in the reference)
+template <typename T>
+__global__ __launch_bounds__(256) void l1_views_partial_kernel(const void* __restrict__ a, int aC, int a0, const void* __restrict__ b, int bC, int b0,
+                                                               size_t npix, int c, int relu, float* __restrict__ partial) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  const size_t total = npix * c;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int ch = (int)(i % c);
+    const size_t p = i / c;
+    float va = ld<T>(a, p * aC + a0 + ch), vb = ld<T>(b, p * bC + b0 + ch);
+    if (relu) { va = fmaxf(va, 0.f); vb = fmaxf(vb, 0.f); }
+    s += fabsf(va - vb);
+  }
+  const float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void l1_views_vec_partial_kernel(const void* __restrict__ a, int aC, int a0, const void* __restrict__ b, int bC, int b0,
+                                                                   size_t npix, int c, int relu, float* __restrict__ partial) {
+  constexpr int N = VecN<T>::N;
+  __shared__ float sh[4];
+  float s = 0.f;
+  const int cv = c / N;
+  const size_t total = npix * cv;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int ch = (int)(i % cv) * N;
+    const size_t p = i / cv;
+    float va[N], vb[N];
+    ldv<T>(a, p * aC + a0 + ch, va);
+    ldv<T>(b, p * bC + b0 + ch, vb);
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      float x = va[q], y = vb[q];
+      if (relu) { x = fmaxf(x, 0.f); y = fmaxf(y, 0.f); }
+      s += fabsf(x - y);
+    }
+  }
+  const float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+// BCE-with-logits against a constant label map (train_bsrgan.py:301,403-404): loss and sigmoid mean
+__global__ __launch_bounds__(256) void bce_partial_kernel(const float* __restrict__ x, size_t n, float target, float gscale,
+                                                          const float* __restrict__ gscale_dev, float* __restrict__ grad, float* __restrict__ partial,
+                                                          float* __restrict__ partial_sig) {
+  __shared__ float sh[4];
+  float s = 0.f, sg = 0.f;
+  if (gscale_dev) gscale *= *gscale_dev;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float v = x[i];
+    s += fmaxf(v, 0.f) - v * target + log1pf(expf(-fabsf(v)));
+    const float sig = 1.f / (1.f + expf(-v));
+    sg += sig;
+    if (grad) grad[i] = (sig - target) * gscale;
+  }
+  float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+  r = block_reduce_sum(sg, sh);
+  if (threadIdx.x == 0) partial_sig[blockIdx.x] = r;
+}
+__global__ __launch_bounds__(256) void finish_sum_kernel(const float* __restrict__ partial, int nblk, float scale, float* out, int accumulate) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
+  const float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) *out = (accumulate ? *out : 0.f) + r * scale;
+}
+// sigmoid(mean(logits)): the D(x) probability as ESRGAN / Real-ESRGAN log it (train_esrgan.py:430-431, train_realesrgan.py:475-476;
+// BSRGAN / A-ESRGAN log mean(sigmoid(logits)) instead -- bce_partial_kernel's second output)
+__global__ __launch_bounds__(256) void sum_partial_kernel(const float* __restrict__ x, size_t n, float* __restrict__ partial) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) s += x[i];
+  const float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+// ---- relativistic-average BCE (ESRGAN/train_esrgan.py:378-380,404,412): mean_i BCE(x_i - mean(other), target) ----
+// stage 0: mean(other) -> ws[2 * kRedBlocks] (sum_partial_kernel + this finish); stage 1: per-element loss, d/dx_i, partial sums of the loss
+// and of (sigmoid - target); stage 2: finishes -- loss, and d/d(other_j) = -(1/n_other) * mean_i(sigmoid_i - target), the same for every j.
+__global__ __launch_bounds__(256) void finish_mean_kernel(const float* __restrict__ partial, int nblk, float inv_n, float* out) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
+  const float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) *out = r * inv_n;
+}
+__global__ __launch_bounds__(256) void bce_rel_partial_kernel(const float* __restrict__ x, size_t n, const float* __restrict__ other_mean, float target,
+                                                              float gscale, const float* __restrict__ gscale_dev, float* __restrict__ grad_x,
+                                                              int accumulate_x, float* __restrict__ partial, float* __restrict__ partial_d) {
+  __shared__ float sh[4];
+  float s = 0.f, sd = 0.f;
+  const float m = *other_mean;
+  if (gscale_dev) gscale *= *gscale_dev;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float v = x[i] - m;
+    s += fmaxf(v, 0.f) - v * target + log1pf(expf(-fabsf(v)));
+    const float d = 1.f / (1.f + expf(-v)) - target;
+    sd += d;
+    if (grad_x) grad_x[i] = (accumulate_x ? grad_x[i] : 0.f) + d * gscale;
+  }
+  float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+  r = block_reduce_sum(sd, sh);
+  if (threadIdx.x == 0) partial_d[blockIdx.x] = r;
+}
+// grad_other[j] (+)= -gscale * sum_d / n_other for every j (gscale already carries weight / n_x)
+__global__ __launch_bounds__(256) void bce_rel_other_kernel(const float* __restrict__ partial_d, int nblk, float gscale, const float* __restrict__ gscale_dev,
+                                                            float* __restrict__ grad_other, size_t n_other, int accumulate) {
+  __shared__ float sh[4];
+  __shared__ float tot;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += 256) s += partial_d[i];      // every block re-reduces the (<= 1024) partials: same order, same value
+  const float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) tot = r;
+  __syncthreads();
+  if (gscale_dev) gscale *= *gscale_dev;
+  const float g = -gscale * tot / (float)n_other;
+  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < n_other; j += (size_t)gridDim.x * 256)
+    grad_other[j] = (accumulate ? grad_other[j] : 0.f) + g;
+}
+__global__ __launch_bounds__(256) void finish_sigmoid_mean_kernel(const float* __restrict__ partial, int nblk, float inv_n, float* out) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
+  const float r = block_reduce_sum(s, sh);
+  if (threadIdx.x == 0) *out = 1.f / (1.f + expf(-r * inv_n));
+}
+
+// ---- differentiable VGG tap (ESRGAN/model.py:281-292): gradient of mean |a - b| w.r.t. a ----
+template <typename T>
+__global__ __launch_bounds__(256) void l1_grad_views_kernel(const void* __restrict__ a, int aC, int a0, const void* __restrict__ b, int bC, int b0,
+                                                            void* out, int oC, int o0, size_t npix, int c, const float* __restrict__ upstream, float scale) {
+  const float sc = scale * (upstream ? *upstream : 1.f);
+  const size_t total = npix * c;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int ch = (int)(i % c);
+    const size_t p = i / c;
+    const float d = ld<T>(a, p * aC + a0 + ch) - ld<T>(b, p * bC + b0 + ch);
+    st<T>(out, p * oC + o0 + ch, d > 0.f ? sc : (d < 0.f ? -sc : 0.f));     // torch: sign(0) = 0
+  }
+}
+
+// flag = 1 if any element of x is inf or NaN (the found_inf of torch.cuda.amp.GradScaler.unscale_, train_bsrgan.py:436,466)
+__global__ __launch_bounds__(256) void nonfinite_flag_kernel(const float* __restrict__ x, size_t n, float* __restrict__ flag) {
+  bool bad = false;
+  const size_t n4 = n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const f32x4 v = ((const f32x4*)x)[i];
+    bad |= !(fabsf(v[0]) <= 3.402823466e38f) | !(fabsf(v[1]) <= 3.402823466e38f) | !(fabsf(v[2]) <= 3.402823466e38f) | !(fabsf(v[3]) <= 3.402823466e38f);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) bad |= !(fabsf(x[n4 * 4 + threadIdx.x]) <= 3.402823466e38f);
+  if (__any(bad) && (threadIdx.x & 63) == 0) *flag = 1.f;      // every writer stores the same value
+}
+
+// torch.amp.GradScaler.update() (torch/amp/grad_scaler.py, _amp_update_scale_) on a device-resident state, so that neither the host nor a
+// captured graph ever carries a stale scale: state = {scale, 1 / scale, growth tracker, optimizer steps, skipped steps}.  The three
+// counters are int32 words of the same 8-word state (a float stops counting at 2^24 steps; torch's tracker is an int32 tensor too).
+__global__ void loss_scale_update_kernel(float* __restrict__ st, const float* __restrict__ found_inf, float growth, float backoff, int interval) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int* sti = reinterpret_cast<int*>(st);
+  float scale = st[0];
+  int tracker = sti[2];
+  sti[3] += 1;
+  if (*found_inf != 0.f) {
+    scale *= backoff; tracker = 0; sti[4] += 1;
+  } else {
+    tracker += 1;
+    if (tracker >= interval) {
+      const float grown = scale * growth;
+      if (fabsf(grown) <= 3.402823466e38f) scale = grown;       // torch keeps the scale when growing it would overflow
+      tracker = 0;
+    }
+  }
+  st[0] = scale; st[1] = 1.f / scale; sti[2] = tracker;
+}
+
+// ------------------------------------------------------------------------------------------------
+extern "C" int srganfd_l1_loss(const float* a, const float* b, int64_t numel, float weight, float* out, int32_t accumulate, float* grad, float grad_scale,
+                               const float* grad_scale_dev, float* ws, void* stream) {
+  const size_t n = (size_t)numel;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!a || !b || !out || !ws || n == 0) return set_err(SRGANFD_EINVAL, "l1_loss: bad args");
+  const unsigned g = grid_for(n, 256, kRedBlocks);
+  SRGANFD_LAUNCH(l1_partial_kernel, dim3(g), dim3(256), 0, s, a, b, n, grad_scale / (float)n, grad_scale_dev, grad, ws);
+  SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, out, accumulate);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+extern "C" int srganfd_l1_loss_views(srganfd_view a, srganfd_view b, int32_t dtype, int64_t npix64, int32_t c, int32_t relu, float weight, float* out,
+                                     int32_t accumulate, float* ws, void* stream) {
+  const size_t npix = (size_t)npix64;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!a.ptr || !b.ptr || !out || !ws) return set_err(SRGANFD_EINVAL, "l1_views: bad args");
+  const size_t n = npix * c;
+  const unsigned g = grid_for(n, 256, kRedBlocks);
+  const int vn = dtype == SRGANFD_F32 ? 4 : 8;
+  if (c % vn == 0 && a.c0 % vn == 0 && b.c0 % vn == 0 && a.cstride % vn == 0 && b.cstride % vn == 0 && ((uintptr_t)a.ptr & 15) == 0 && ((uintptr_t)b.ptr & 15) == 0) {
+    DISPATCH_T(dtype,
+               SRGANFD_LAUNCH(l1_views_vec_partial_kernel<TT>, dim3(g), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, npix, c, relu, ws));
+  } else
+  DISPATCH_T(dtype,
+             SRGANFD_LAUNCH(l1_views_partial_kernel<TT>, dim3(g), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, npix, c, relu, ws));
+  SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, out, accumulate);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+extern "C" int srganfd_l1_grad_views(srganfd_view a, srganfd_view b, srganfd_view out, int32_t dtype, int64_t npix64, int32_t c, const float* upstream,
+                                     float scale, void* stream) {
+  const size_t npix = (size_t)npix64;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!a.ptr || !b.ptr || !out.ptr || npix == 0 || c <= 0) return set_err(SRGANFD_EINVAL, "l1_grad_views: bad args");
+  DISPATCH_T(dtype,
+             SRGANFD_LAUNCH(l1_grad_views_kernel<TT>, dim3(grid_for(npix * c)), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, out.ptr, out.cstride, out.c0, npix, c, upstream, scale));
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+extern "C" int srganfd_bce_logits(const float* x, int64_t numel, float target, float weight, float* loss_out, int32_t accumulate, float* sig_mean_out,
+                                  float* grad, float grad_scale, const float* grad_scale_dev, float* ws, void* stream) {
+  const size_t n = (size_t)numel;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!x || !loss_out || !ws || n == 0) return set_err(SRGANFD_EINVAL, "bce: bad args");
+  const unsigned g = grid_for(n, 256, kRedBlocks);
+  SRGANFD_LAUNCH(bce_partial_kernel, dim3(g), dim3(256), 0, s, x, n, target, grad_scale / (float)n, grad_scale_dev, grad, ws, ws + kRedBlocks);
+  SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, loss_out, accumulate);
+  if (sig_mean_out) SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)(ws + kRedBlocks), (int)g, 1.f / (float)n, sig_mean_out, 0);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+extern "C" int srganfd_sigmoid_of_mean(const float* x, int64_t numel, float* out, float* ws, void* stream) {
+  const size_t n = numel > 0 ? (size_t)numel : 0;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!x || !out || !ws || n == 0) return set_err(SRGANFD_EINVAL, "sigmoid_of_mean: bad args");
+  const unsigned g = grid_for(n, 256, kRedBlocks);
+  SRGANFD_LAUNCH(sum_partial_kernel, dim3(g), dim3(256), 0, s, x, n, ws);
+  SRGANFD_LAUNCH(finish_sigmoid_mean_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, 1.f / (float)n, out);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+// workspace: 2 * kRedBlocks + 1 floats (SRGANFD_LOSS_WS_FLOATS)
+extern "C" int srganfd_bce_logits_relativistic(const float* x, int64_t numel, const float* other, int64_t numel_other, float target, float weight,
+                                               float* loss_out, int32_t accumulate, float* grad_x, int32_t accumulate_x, float* grad_other,
+                                               int32_t accumulate_other, float grad_scale, const float* grad_scale_dev, float* ws, void* stream) {
+  const size_t n = numel > 0 ? (size_t)numel : 0, n_other = numel_other > 0 ? (size_t)numel_other : 0;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!x || !other || !loss_out || !ws || n == 0 || n_other == 0) return set_err(SRGANFD_EINVAL, "bce_relativistic: bad args");
+  float* mean = ws + 2 * kRedBlocks;
+  const unsigned go = grid_for(n_other, 256, kRedBlocks), g = grid_for(n, 256, kRedBlocks);
+  SRGANFD_LAUNCH(sum_partial_kernel, dim3(go), dim3(256), 0, s, other, n_other, ws);
+  SRGANFD_LAUNCH(finish_mean_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)go, 1.f / (float)n_other, mean);
+  SRGANFD_LAUNCH(bce_rel_partial_kernel, dim3(g), dim3(256), 0, s, x, n, (const float*)mean, target, grad_scale / (float)n, grad_scale_dev, grad_x,
+                 accumulate_x, ws, ws + kRedBlocks);
+  SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, loss_out, accumulate);
+  if (grad_other)
+    SRGANFD_LAUNCH(bce_rel_other_kernel, dim3(grid_for(n_other, 256, 256)), dim3(256), 0, s, (const float*)(ws + kRedBlocks), (int)g, grad_scale / (float)n,
+                   grad_scale_dev, grad_other, n_other, accumulate_other);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+extern "C" int srganfd_nonfinite_flag(const float* x, int64_t numel, float* flag, int32_t accumulate, void* stream) {
+  const size_t n = (size_t)numel;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!x || !flag || n == 0 || ((uintptr_t)x & 15)) return set_err(SRGANFD_EINVAL, "nonfinite_flag: bad args");
+  if (!accumulate) SRGANFD_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(float), s));
+  SRGANFD_LAUNCH(nonfinite_flag_kernel, dim3(grid_for(n / 4 + 1, 256, 2048)), dim3(256), 0, s, x, n, flag);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+extern "C" int srganfd_loss_scale_update(float* state, const float* found_inf, float growth, float backoff, int32_t interval, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
+  if (!state || !found_inf || interval < 1 || !(growth >= 1.f) || !(backoff > 0.f && backoff <= 1.f)) return set_err(SRGANFD_EINVAL, "loss_scale_update: bad args");
+  SRGANFD_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), 0, s, state, found_inf, growth, backoff, interval);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+
+}  // namespace srganfd

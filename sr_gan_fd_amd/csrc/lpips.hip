@@ -247,7 +247,7 @@ static bool lpips_maps(int h, int w, int* th, int* tw) {
   return true;
 }
 
-int64_t lpips_workspace_bytes_impl(int n, int h, int w) {
+extern "C" int64_t srganfd_lpips_workspace_bytes(int32_t n, int32_t h, int32_t w) {
   int th[kLpTaps], tw[kLpTaps];
   if (n < 1) { set_err(SRGANFD_EINVAL, "lpips: batch size %d", n); return -1; }
   if (!lpips_maps(h, w, th, tw)) {
@@ -266,7 +266,8 @@ template <int KS, int STRIDE, int PAD, int MODE> static void lpips_conv_launch(c
   SRGANFD_LAUNCH((lpips_conv_kernel<KS, STRIDE, PAD, MODE>), grid, dim3(kLpThreads), 0, s, k);
 }
 
-int lpips_conv_impl(const srganfd_lpips_conv_args* a, hipStream_t s) {
+extern "C" int srganfd_lpips_conv(const srganfd_lpips_conv_args* a, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!a) return set_err(SRGANFD_EINVAL, "lpips_conv: null arguments");
   if (!a->w || !a->bias || !a->y) return set_err(SRGANFD_EINVAL, "lpips_conv: null weight, bias or output pointer");
   if (a->n < 1 || a->h_in < 1 || a->w_in < 1) return set_err(SRGANFD_EINVAL, "lpips_conv: bad input dims n %d, %d x %d", a->n, a->h_in, a->w_in);
@@ -313,7 +314,8 @@ int lpips_conv_impl(const srganfd_lpips_conv_args* a, hipStream_t s) {
   return SRGANFD_OK;
 }
 
-int lpips_head_impl(const srganfd_lpips_tap* taps, int ntaps, int n, float* out, float* ws, hipStream_t s) {
+extern "C" int srganfd_lpips_head(const srganfd_lpips_tap* taps, int32_t ntaps, int32_t n, float* out, float* ws, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
   if (!taps || !out || !ws) return set_err(SRGANFD_EINVAL, "lpips_head: null pointer");
   if (ntaps < 1 || ntaps > kLpTaps || n < 1) return set_err(SRGANFD_EINVAL, "lpips_head: %d taps (1..%d), n %d", ntaps, kLpTaps, n);
   LpipsHeadK k = {};

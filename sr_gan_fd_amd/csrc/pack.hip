@@ -95,12 +95,16 @@ __global__ __launch_bounds__(256) void pack_kernel(const srganfd_pack_job* __res
   }
 }
 
-int pack_weights_impl(const srganfd_pack_job* jobs_dev, int njobs, long long max_elems, const float* params,
-                      const float* scalars, void* packed, hipStream_t stream) {
+extern "C" size_t srganfd_packed_bytes(int32_t dtype, int32_t ksize, int32_t k, int32_t n) {
+  if (k <= 0 || n <= 0 || k % 32 || n % 32) return 0;
+  return (size_t)ksize * ksize * k * n * (dtype == SRGANFD_F32 ? 4 : 2);
+}
+extern "C" int srganfd_pack_weights(const srganfd_pack_job* jobs_dev, int32_t njobs, int64_t max_elems, const float* params,
+                                    const float* scalars, void* packed, void* stream) {
   if (!jobs_dev || njobs <= 0 || max_elems <= 0 || !params || !packed) return set_err(SRGANFD_EINVAL, "pack_weights: bad args");
   long long gx = (max_elems + 255) / 256;
   if (gx > 4096) gx = 4096;
-  SRGANFD_LAUNCH(pack_kernel, dim3((unsigned)gx, (unsigned)njobs), dim3(256), 0, stream, jobs_dev, params, scalars, (char*)packed);
+  SRGANFD_LAUNCH(pack_kernel, dim3((unsigned)gx, (unsigned)njobs), dim3(256), 0, (hipStream_t)stream, jobs_dev, params, scalars, (char*)packed);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }

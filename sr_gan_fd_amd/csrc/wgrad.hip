@@ -718,14 +718,14 @@ static int build_plan(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* co
   return SRGANFD_OK;
 }
 
-size_t wgrad_plan_bytes_impl(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* convs) {
+extern "C" size_t srganfd_wgrad_plan_bytes(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* convs) {
   PlanBuild pb;
   if (build_plan(s, convs, pb) != SRGANFD_OK) return 0;
   return (size_t)pb.hdr.total_bytes;
 }
 
-int wgrad_plan_build_impl(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* convs, void* plan_host, size_t plan_bytes,
-                          size_t* workspace_bytes) {
+extern "C" int srganfd_wgrad_plan_build(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* convs, void* plan_host, size_t plan_bytes,
+                                        size_t* workspace_bytes) {
   PlanBuild pb;
   int rc = build_plan(s, convs, pb);
   if (rc != SRGANFD_OK) return rc;
@@ -778,9 +778,9 @@ static int launch_wgrad(const WgHeader& H, const WgK& k, hipStream_t stream) {
   return H.dy_upad == 2 ? launch_wgrad2<T, KS, STRIDE, 1, 2>(H, k, stream) : launch_wgrad2<T, KS, STRIDE, 1, 1>(H, k, stream);
 }
 
-int wgrad_reduce_batch_impl(const srganfd_wgrad_reduce_job* jobs, int njobs, hipStream_t stream);
-int wgrad_impl(const void* plan_host, const void* plan_dev, srganfd_view x, srganfd_view dy, float* grads, const float* scalars,
-               void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// shared by srganfd_conv2d_wgrad (grads != NULL) and srganfd_conv2d_wgrad_partial (grads == NULL)
+static int wgrad_impl(const void* plan_host, const void* plan_dev, srganfd_view x, srganfd_view dy, float* grads, const float* scalars,
+                      void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!plan_host || !plan_dev || !x.ptr || !dy.ptr || !workspace) return set_err(SRGANFD_EINVAL, "wgrad: null pointer");
   const WgHeader& H = *(const WgHeader*)plan_host;
   if (H.magic != kWgMagic) return set_err(SRGANFD_EINVAL, "wgrad: bad plan");
@@ -809,10 +809,19 @@ int wgrad_impl(const void* plan_host, const void* plan_dev, srganfd_view x, srga
   if (rc != SRGANFD_OK) return rc;
   if (!grads) return SRGANFD_OK;          // srganfd_conv2d_wgrad_partial: the slabs stay in the workspace for srganfd_wgrad_reduce_batch
   srganfd_wgrad_reduce_job job = {plan_host, plan_dev, grads, scalars, workspace};
-  return wgrad_reduce_batch_impl(&job, 1, stream);
+  return srganfd_wgrad_reduce_batch(&job, 1, stream);
+}
+extern "C" int srganfd_conv2d_wgrad_partial(const void* plan_host, const void* plan_dev, srganfd_view x, srganfd_view dy, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  return wgrad_impl(plan_host, plan_dev, x, dy, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int srganfd_conv2d_wgrad(const void* plan_host, const void* plan_dev, srganfd_view x, srganfd_view dy, float* grads,
+                                    const float* scalars, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!grads) return srganfd::set_err(SRGANFD_EINVAL, "wgrad: null gradient pointer (srganfd_conv2d_wgrad_partial is the reduce-later form)");
+  return wgrad_impl(plan_host, plan_dev, x, dy, grads, scalars, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-int wgrad_reduce_batch_impl(const srganfd_wgrad_reduce_job* jobs, int njobs, hipStream_t stream) {
+extern "C" int srganfd_wgrad_reduce_batch(const srganfd_wgrad_reduce_job* jobs, int32_t njobs, void* stream) {
   if (!jobs || njobs <= 0 || njobs > kRedBatch) return set_err(SRGANFD_EINVAL, "wgrad_reduce_batch: 1..%d jobs", kRedBatch);
   WgRedJobs J;
   memset(&J, 0, sizeof(J));
@@ -830,7 +839,7 @@ int wgrad_reduce_batch_impl(const srganfd_wgrad_reduce_job* jobs, int njobs, hip
     J.j[i].bslabs = (const float*)q.workspace + H.bias_slab_off;
     J.j[i].grads = q.grads; J.j[i].scalars = q.scalars; J.j[i].ntasks = H.ntasks;
   }
-  SRGANFD_LAUNCH(wgrad_reduce_kernel, dim3(ntap, maxtasks, njobs), dim3(1024), 0, stream, J, ntap);
+  SRGANFD_LAUNCH(wgrad_reduce_kernel, dim3(ntap, maxtasks, njobs), dim3(1024), 0, (hipStream_t)stream, J, ntap);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }

@@ -28,6 +28,82 @@ def test_library_exports_every_header_symbol():
     assert A.lib().srganfd_get_mfma16() == 3
 
 
+_BINDING_CHECK_PRELUDE = r"""
+#include <stddef.h>
+#include <stdint.h>
+#include "srganfd.h"
+// one class letter per argument / return type; a type outside this table has no K<> and fails to compile
+template <class T> struct K;
+template <> struct K<void> { static constexpr char c = 'v'; };
+template <> struct K<int32_t> { static constexpr char c = 'i'; };
+template <> struct K<int64_t> { static constexpr char c = 'l'; };
+template <> struct K<size_t> { static constexpr char c = 'z'; };
+template <> struct K<float> { static constexpr char c = 'f'; };
+template <> struct K<double> { static constexpr char c = 'd'; };
+template <> struct K<srganfd_view> { static constexpr char c = 'V'; };
+template <class T> struct K<T*> { static constexpr char c = 'p'; };
+template <class F> struct Sig;
+template <class R, class... A> struct Sig<R (*)(A...)> { static constexpr char s[sizeof...(A) + 2] = {K<R>::c, K<A>::c..., 0}; };
+constexpr bool eq(const char* a, const char* b) { return *a == *b && (*a == 0 || eq(a + 1, b + 1)); }
+"""
+
+
+def _ctype_class(t) -> str:
+    from sr_gan_fd_amd import _abi as A
+    if t is None:
+        return "v"
+    if t is A.View:
+        return "V"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "p"
+    return {C.c_int32: "i", C.c_int64: "l", C.c_size_t: "z", C.c_float: "f", C.c_double: "d"}[t]   # c_int is c_int32; anything else: KeyError
+
+
+def binding_check_source(A) -> str:
+    """A translation unit of static_asserts that holds sr_gan_fd_amd/_abi.py against include/srganfd.h: every SYMBOLS entry's return and
+    argument classes, every Structure's size and its fields' offsets and sizes, and the constants the binding repeats."""
+    out = [_BINDING_CHECK_PRELUDE]
+    for name, (res, args) in A.SYMBOLS.items():
+        sig = _ctype_class(res) + "".join(_ctype_class(a) for a in args)
+        out.append(f'static_assert(eq(Sig<decltype(&{name})>::s, "{sig}"), "{name}");')
+    structs = [v for v in vars(A).values() if isinstance(v, type) and issubclass(v, C.Structure) and v.__module__ == A.__name__]
+    assert structs and all("C_NAME" in vars(s) for s in structs), "every Structure of _abi.py names the C struct it mirrors (C_NAME)"
+    for s in structs:
+        out.append(f'static_assert(sizeof({s.C_NAME}) == {C.sizeof(s)}, "sizeof({s.C_NAME}) != sizeof({s.__name__})");')
+        for field, _ in s._fields_:
+            d = getattr(s, field)
+            out.append(f'static_assert(offsetof({s.C_NAME}, {field}) == {d.offset} && sizeof({s.C_NAME}::{field}) == {d.size}, '
+                       f'"{s.C_NAME}.{field} vs {s.__name__}.{field}");')
+    consts = {"SRGANFD_BF16": A.BF16, "SRGANFD_F32": A.F32, "SRGANFD_F16": A.F16, "SRGANFD_ACT_NONE": A.ACT_NONE, "SRGANFD_ACT_LRELU": A.ACT_LRELU,
+              "SRGANFD_ACT_RELU": A.ACT_RELU, "SRGANFD_LOSS_WS_FLOATS": A.LOSS_WS_FLOATS, "SRGANFD_ABI_VERSION": A._ABI_VERSION_BUILT}
+    for cname, val in consts.items():
+        out.append(f'static_assert({cname} == {val}, "{cname} is not the binding\'s {val}");')
+    return "\n".join(out) + "\n"
+
+
+def _cxx_compiler():
+    import shutil
+    rocm = os.environ.get("ROCM_PATH") or "/opt/rocm"
+    for c in (os.environ.get("CXX"), "c++", "g++", "clang++", os.path.join(rocm, "llvm", "bin", "clang++")):
+        if c and shutil.which(c.split()[0]):
+            return c.split()
+    return None
+
+
+def test_binding_matches_header(tmp_path):
+    """The ctypes binding is compiled against the header: a wrong width, a misplaced argument, a field out of order or a stale constant
+    in _abi.py is a failed static_assert that names the symbol or field.  No GPU and no built library are needed."""
+    import subprocess
+    from sr_gan_fd_amd import _abi as A
+    cxx = _cxx_compiler()
+    if cxx is None:
+        pytest.skip("no C++ compiler found ($CXX, c++, g++, clang++, ROCm's clang++)")
+    src = tmp_path / "binding_check.cpp"
+    src.write_text(binding_check_source(A))
+    r = subprocess.run(cxx + ["-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, "sr_gan_fd_amd/_abi.py disagrees with include/srganfd.h:\n" + r.stderr[-4000:]
+
+
 def test_product_path_fails_loudly_without_gpu():
     from sr_gan_fd_amd import _abi as A, model as M
     net = M.bsrgan_x4(num_rrdb=1)
