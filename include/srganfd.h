@@ -609,6 +609,37 @@ int srganfd_crop_rot_flip(const float* src, float* dst, int32_t planes, int32_t 
 /* last line of degradation_process (imgproc.py:2460): dst = clamp(round(src * 255), 0, 255) / 255 (may alias) */
 int srganfd_quantize_u8(const float* src, float* dst, int64_t numel, void* stream);
 
+/* ---- fused multi-head self-attention (the reference's SelfAttention, BSRGAN/model.py:388-402: nn.MultiheadAttention without
+ * masks or dropout), forward and backward (csrc/attention.hip) ----
+ * qkv: the packed in-projection output (batch, seq, 3 C) in `dtype`, token-major, q | k | v within a token's row, head h in
+ * channels [h head_dim, (h + 1) head_dim) of each (torch's in_proj layout); C = heads * head_dim, head_dim 16, 32 or 64, any seq >= 1.
+ *   fwd      S = (q k^T) / sqrt(head_dim), row softmax in fp32, out = P v: out (batch, seq, C) in `dtype` (P is rounded to it once),
+ *            lse (batch, heads, seq) fp32 = log sum exp of a row of S.
+ *   weights  weights (batch, seq, seq) fp32 = the mean over the heads of the fp32 probabilities exp(S - lse) (need_weights).
+ *   bwd      from qkv, out, lse and d_out (batch, seq, C): d_qkv (batch, seq, 3 C) in `dtype`, the gradient in qkv's own layout.
+ *            Two launches (per query block: delta = rowsum(d_out o out) and dq; per key block: dk and dv), every element with one
+ *            owner and a fixed summation order: no atomics, bit-reproducible.  workspace: srganfd_attention_workspace_bytes bytes.
+ * Nothing is read back and nothing waits on the host, so the launches can be captured into a graph.
+ * SRGANFD_EINVAL (the query returns 0): a null pointer among those the entry point uses, head_dim outside {16, 32, 64}, a
+ * non-positive size, a bad dtype, a pointer not 16-byte aligned, out or d_qkv aliasing qkv, a workspace that is too small. */
+typedef struct srganfd_attn_args {
+  int32_t dtype;                 /* SRGANFD_F32 / F16 / BF16 */
+  int32_t batch, seq, heads, head_dim;
+  int32_t pad_;
+  const void* qkv;
+  void* out;
+  float* lse;
+  const void* d_out;
+  void* d_qkv;
+  float* weights;
+  void* workspace;
+  size_t workspace_bytes;
+} srganfd_attn_args;
+size_t srganfd_attention_workspace_bytes(const srganfd_attn_args* a);
+int srganfd_attention_fwd(const srganfd_attn_args* a, void* stream);
+int srganfd_attention_weights(const srganfd_attn_args* a, void* stream);
+int srganfd_attention_bwd(const srganfd_attn_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,15 @@ class LpipsTap(C.Structure):
     _fields_ = [("maps", C.c_void_p), ("lin", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("pad_", C.c_int32)]
 
 
+class AttnArgs(C.Structure):
+    C_NAME = "srganfd_attn_args"
+    _fields_ = [
+        ("dtype", C.c_int32), ("batch", C.c_int32), ("seq", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("pad_", C.c_int32),
+        ("qkv", C.c_void_p), ("out", C.c_void_p), ("lse", C.c_void_p), ("d_out", C.c_void_p), ("d_qkv", C.c_void_p), ("weights", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 # symbol -> (restype, argtypes).  tests/test_host_logic.py checks that the library exports every one of these, and has a C++ compiler
 # check each entry's argument and return classes, every Structure above (C_NAME: the header's struct; size, field offsets and sizes) and
 # the constants this file repeats against include/srganfd.h
@@ -236,6 +245,10 @@ SYMBOLS = {
                                             C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "srganfd_batchnorm_act_bwd": (C.c_int, [View, View, View, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                             C.c_void_p, View, C.c_float, C.c_void_p]),
+    "srganfd_attention_workspace_bytes": (C.c_size_t, [C.POINTER(AttnArgs)]),
+    "srganfd_attention_fwd": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
+    "srganfd_attention_weights": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
+    "srganfd_attention_bwd": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
 }
 
 LOSS_WS_FLOATS = 2049

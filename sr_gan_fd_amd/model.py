@@ -32,6 +32,7 @@ __all__ = [
     "rrdbnet_x1", "rrdbnet_x2", "rrdbnet_x4", "rrdbnet_x8",
     "UNetDiscriminatorAesrgan", "uNetDiscriminatorAesrgan",
     "Discriminator", "discriminator",
+    "SelfAttention", "BSRGANsa", "bsrgansa_x2",
 ]
 
 
@@ -125,6 +126,41 @@ class BSRGAN(_RRDBGenerator):
     def __init__(self, in_channels: int = 3, out_channels: int = 3, channels: int = 64, growth_channels: int = 32,
                  num_rrdb: int = 23, upscale_factor: int = 4) -> None:
         super().__init__(in_channels, out_channels, channels, growth_channels, num_rrdb, upscale_factor, always_up1=True)
+
+
+class BSRGANsa(_RRDBGenerator):
+    """BSRGAN/model.py:405-496: despite its name the class holds no attention layer -- its parameters and its forward are BSRGAN's
+    (``visualize_attention_map`` reads an attribute nothing sets) -- so configs that name ``bsrgansa_x2`` get the same engine."""
+
+    def __init__(self, in_channels: int = 3, out_channels: int = 3, channels: int = 64, growth_channels: int = 32,
+                 num_rrdb: int = 23, upscale_factor: int = 4) -> None:
+        super().__init__(in_channels, out_channels, channels, growth_channels, num_rrdb, upscale_factor, always_up1=True)
+
+
+class SelfAttention(nn.Module):
+    """BSRGAN/model.py:388-402: ``nn.MultiheadAttention(channels, num_heads)`` over the h*w positions of a (b, c, h, w) map, every
+    image its own sequence.  The child module is a parameter container (the reference's state-dict keys, shapes and seeded initial
+    values); ``forward`` runs the fused HIP attention (attention.py, csrc/attention.hip) and returns the reference's pair
+    ``(attn_output (b, c, h, w), attn_output_weights (b, h*w, h*w))``, both fp32.
+
+    Deviations: the weights come back detached (no consumer in the reference differentiates them); ``need_weights = False`` on the
+    module skips the launch that computes them and returns ``None`` in their place; CPU tensors, ``channels % num_heads != 0`` and a
+    head size outside {16, 32, 64} raise ``SrganfdError``."""
+
+    def __init__(self, channels: int, num_heads: int = 8) -> None:
+        super().__init__()
+        if channels % num_heads:
+            from ._abi import SrganfdError
+            raise SrganfdError(f"SelfAttention: channels {channels} is not a multiple of num_heads {num_heads}")
+        self.channels = channels
+        self.num_heads = num_heads
+        self.multihead_attention = nn.MultiheadAttention(channels, num_heads)
+        self.need_weights = True
+        self.compute_dtype = None
+
+    def forward(self, x: Tensor):
+        from .attention import self_attention_apply
+        return self_attention_apply(self, x)
 
 
 class RRDBNet(_RRDBGenerator):
@@ -299,6 +335,11 @@ def uNetDiscriminatorAesrgan() -> UNetDiscriminatorAesrgan:
 
 def discriminator_unet(**kwargs: Any) -> DiscriminatorUNet:
     return DiscriminatorUNet(**kwargs)
+
+
+def bsrgansa_x2(**kwargs: Any) -> BSRGANsa:
+    """BSRGAN/model.py:570-574"""
+    return BSRGANsa(upscale_factor=2, **kwargs)
 
 
 def bsrgan_x2(**kwargs: Any) -> BSRGAN:

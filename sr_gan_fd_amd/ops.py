@@ -459,6 +459,67 @@ class WgradPlans:
         return torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
 
 
+# ---- fused multi-head self-attention (csrc/attention.hip) ----
+ATTN_HEAD_DIMS = (16, 32, 64)
+
+
+def attn_args(dtype: int, batch: int, seq: int, heads: int, head_dim: int, *, qkv=None, out=None, lse=None, d_out=None, d_qkv=None,
+              weights=None, workspace: Optional[torch.Tensor] = None) -> A.AttnArgs:
+    """qkv (batch, seq, 3 * heads * head_dim), out / d_out (batch, seq, heads * head_dim) in ``dtype``; lse (batch, heads, seq) and
+    weights (batch, seq, seq) fp32; tensors or device addresses, None for what the entry point at hand does not use"""
+    a = A.AttnArgs()
+    a.dtype, a.batch, a.seq, a.heads, a.head_dim = dtype, batch, seq, heads, head_dim
+    a.qkv, a.out, a.lse, a.d_out, a.d_qkv, a.weights = _ptr(qkv), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(d_qkv), _ptr(weights)
+    if workspace is not None:
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    return a
+
+
+def attention_workspace_bytes(a: A.AttnArgs) -> int:
+    n = int(A.lib().srganfd_attention_workspace_bytes(C.byref(a)))
+    if n == 0:
+        raise A.SrganfdError("attention_workspace_bytes: " + A.lib().srganfd_last_error().decode())
+    return n
+
+
+def attn_work(a: A.AttnArgs, kind: str):
+    """(algorithmic FLOP, algorithmic bytes): 4 B H L^2 D forward (two products), 2 B H L^2 D for the weights, 10 B H L^2 D backward"""
+    es, c = esize(a.dtype), a.heads * a.head_dim
+    unit = 2.0 * a.batch * a.heads * a.seq * a.seq * a.head_dim
+    tok = float(a.batch) * a.seq
+    if kind == "fwd":
+        return 2 * unit, tok * (4 * c * es + 4 * a.heads)
+    if kind == "weights":
+        return unit, tok * (2 * c * es + 4 * a.heads + 4 * a.seq)
+    return 5 * unit, tok * (8 * c * es + 12 * a.heads)
+
+
+def _attention(kind: str, a: A.AttnArgs, rec, L, st) -> None:
+    if L is None:
+        L, st = A.lib(), A.stream_ptr()
+    what = "attention_" + kind
+    run = lambda: A.check(getattr(L, "srganfd_" + what)(C.byref(a), st), what)
+    if rec is None:
+        run()
+    else:
+        rec.bracket("attn_%s_kernel<%s,D=%d>" % (kind, A.DT_NAME[a.dtype], a.head_dim), attn_work(a, kind), run)
+
+
+def attention_fwd(a: A.AttnArgs, rec=None, L=None, st=None) -> None:
+    """out = softmax(q k^T / sqrt(D)) v and lse, one launch on the current stream"""
+    _attention("fwd", a, rec, L, st)
+
+
+def attention_weights(a: A.AttnArgs, rec=None, L=None, st=None) -> None:
+    """the head-averaged probabilities (nn.MultiheadAttention's second result), a launch of its own"""
+    _attention("weights", a, rec, L, st)
+
+
+def attention_bwd(a: A.AttnArgs, rec=None, L=None, st=None) -> None:
+    """d_qkv from qkv, out, lse and d_out: two launches (dq per query block, dk / dv per key block), bit-reproducible"""
+    _attention("bwd", a, rec, L, st)
+
+
 # same-box A/B switch (0: one group of launches per layer, the round-1 form); both forms run in the HIP library and agree to the bit
 _SN_BATCH = os.environ.get("SRGANFD_SN_BATCH", "1") != "0"
 
