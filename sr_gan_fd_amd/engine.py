@@ -352,7 +352,7 @@ class TrunkEngine(EngineBase):
             sp.c3 = new(N, H * s, W * s, Cc)
             sp.srp = new(N, H * s, W * s, 4, dtype=torch.float32)
             fw.append(ops.image_to_features(dtc, sp.thin_i, sp.xin, VC(catb(0)), bias("conv1.weight"), wptr + pk["offs"][("f", "conv1")], N, H, W,
-                                            self.in_ch, Cc, True, bias=bias("conv1.bias"))[1])
+                                            self.in_ch, Cc, True, bias=bias("conv1.bias")))
         for i, pre in enumerate(self._rdb_prefix):
             ci = catb(i)
             blk = []
@@ -365,24 +365,24 @@ class TrunkEngine(EngineBase):
             blk.append(ops.conv_args(dtc, VC(ci), VC(catb(i + 1)), wptr + pk["offs"][("f", i, 5)], N, H, W, Ccat, Cc,
                                      bias=bias(f"{pre}conv5.bias"), **kw))
             # small batches (the reference's own crop sizes): the five launches as ONE LDS-resident launch (csrc/dense_chain.hip)
-            fw.extend(ops.dense_chain_or_launches(blk, device) if (Cc, G) == (64, 32) else blk)
+            fw.extend(ops.dense_chain_or_launches(blk, device) if (Cc, G) == (64, 32) else [ops.Conv(a) for a in blk])
         if self.full:
             tout = catb(R)
-            fw.append(ops.conv_args(dtc, VC(tout), V(sp.f0), wptr + pk["offs"][("f", "conv2")], N, H, W, Cc, Cc, bias=bias("conv2.bias"),
-                                    r1=VC(catb(0)), r1_scale=1.0))
+            fw.append(ops.Conv(ops.conv_args(dtc, VC(tout), V(sp.f0), wptr + pk["offs"][("f", "conv2")], N, H, W, Cc, Cc, bias=bias("conv2.bias"),
+                                             r1=VC(catb(0)), r1_scale=1.0)))
             src, h, w = sp.f0, H, W
             for u in range(1, self.n_up + 1):
                 nm = f"upsampling{u}.0"
                 if self._parity(dtc):
                     fw.extend(self._up_forward(dtc, pk, V(src), V(sp.ups[u - 1]), N, h, w, bias(nm + ".bias"), nm))
                 else:
-                    fw.append(ops.conv_args(dtc, V(src), V(sp.ups[u - 1]), wptr + pk["offs"][("f", nm)], N, h, w, Cc, Cc, up=1,
-                                            bias=bias(nm + ".bias"), act=A.ACT_LRELU, slope=0.2))
+                    fw.append(ops.Conv(ops.conv_args(dtc, V(src), V(sp.ups[u - 1]), wptr + pk["offs"][("f", nm)], N, h, w, Cc, Cc, up=1,
+                                                     bias=bias(nm + ".bias"), act=A.ACT_LRELU, slope=0.2)))
                 src, h, w = sp.ups[u - 1], h * 2, w * 2
-            fw.append(ops.conv_args(dtc, V(src), V(sp.c3), wptr + pk["offs"][("f", "conv3.0")], N, h, w, Cc, Cc, bias=bias("conv3.0.bias"),
-                                    act=A.ACT_LRELU, slope=0.2))
+            fw.append(ops.Conv(ops.conv_args(dtc, V(src), V(sp.c3), wptr + pk["offs"][("f", "conv3.0")], N, h, w, Cc, Cc, bias=bias("conv3.0.bias"),
+                                             act=A.ACT_LRELU, slope=0.2)))
             fw.append(ops.features_to_image(dtc, sp.thin_o, V(sp.c3), sp.srp, 4, bias("conv4.weight"), wptr + pk["offs"][("f", "conv4")], N, h, w,
-                                            self.out_ch, Cc, False, bias=bias("conv4.bias"))[1])
+                                            self.out_ch, Cc, False, bias=bias("conv4.bias")))
             sp.hs, sp.ws = h, w
         sp.fw = fw
         sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
@@ -391,16 +391,13 @@ class TrunkEngine(EngineBase):
         self.shapes.put(key, sp, pinned=train)
         return sp
 
-    def _up_forward(self, dtc: int, pk: dict, x: A.View, y: A.View, N: int, h: int, w: int, bias: int, nm: str) -> List[A.ConvArgs]:
+    def _up_forward(self, dtc: int, pk: dict, x: A.View, y: A.View, N: int, h: int, w: int, bias: int, nm: str) -> List[ops.Conv]:
         """nearest x2 + 3x3 pad-1 conv + LeakyReLU (BSRGAN/model.py:372-374) as its four output-parity classes: 2x2-tap convs over the
         low-res input x (pack codes 14..17), written into the high-res y.  One launch when the library takes the four classes together
         (ops.class4_ok), else one launch per class."""
         Cc, O = self.Cc, pk["offs"]
-        out = ops.parity_class_launches(dtc, x, y, pk["buf"].data_ptr(), [O[("fc", nm, c)] for c in range(4)], N, h, w, Cc, Cc, 2, 1,
-                                        bias=bias, act=A.ACT_LRELU, slope=0.2)      # class (py, px) reads the window at (oy + py - 1, ox + px - 1)
-        for a in out:
-            a._label_tag = " nearest-x2 fwd"
-        return out
+        return ops.parity_class_launches(dtc, x, y, pk["buf"].data_ptr(), [O[("fc", nm, c)] for c in range(4)], N, h, w, Cc, Cc, 2, 1,
+                                         tag=" nearest-x2 fwd", bias=bias, act=A.ACT_LRELU, slope=0.2)      # class (py, px) reads the window at (oy + py - 1, ox + px - 1)
 
     def _plan_backward(self, sp: _Shape, pk: dict) -> None:
         N, H, W, dt, dtc, device = sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device
@@ -417,7 +414,8 @@ class TrunkEngine(EngineBase):
         sp.dy = [new(N, H, W, Ccat) for _ in range(4)]
         sp.dx0 = new(N, H, W, Cc)           # gradient w.r.t. the trunk input
         dyb = lambda i: sp.dy[i % 4]
-        bw: List[tuple] = []                 # ("conv", args) | ("wgrad", plan, xview, dyview, grad_off) | ("call", fn)
+        bw = []                              # ops.Conv | Wgrad | ThinLaunch | DenseChain | Call and the markers Item("ready", (lo, hi)) | Item("fence", block)
+        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
         wplans = ops.WgradPlans(device, dtc, N)
 
         if self.full:
@@ -436,16 +434,13 @@ class TrunkEngine(EngineBase):
             # conv4
             w4 = fptr + 4 * self._poff("conv4.weight")
             bw.append(ops.image_wgrad(dtc, sp.thin_o, wplans, sp.dsrp, sp.c3, w4, self._poff("conv4.weight"), self._poff("conv4.bias"), sp.thin_ws,
-                                      N, hs, ws_, self.out_ch, Cc, False, extra=(0,)))
+                                      N, hs, ws_, self.out_ch, Cc, False))
             bw.append(ops.image_to_features(dtc, sp.thin_o, sp.dsrp, V(sp.gA), w4, wptr + pk["offs"][("b", "conv4")], N, hs, ws_, self.out_ch, Cc, False,
                                             flip=True, mask=V(sp.c3), mask_slope=0.2))
             # conv3
             src3 = sp.ups[-1] if self.n_up else sp.f0
-            bw.append(("wgrad", wplans.plan(hs, ws_, Cc, Cc, one("conv3.0", Cc, Cc)), V(src3), V(sp.gA), 0))
-            if self.n_up:
-                bw.append(("conv", ops.conv_args(dtc, V(sp.gA), V(sp.gB), wptr + pk["offs"][("b", "conv3.0")], N, hs, ws_, Cc, Cc, mask=V(src3), mask_slope=0.2)))
-            else:
-                bw.append(("conv", ops.conv_args(dtc, V(sp.gA), V(sp.gB), wptr + pk["offs"][("b", "conv3.0")], N, hs, ws_, Cc, Cc)))
+            bw.append(ops.Wgrad(wplans.plan(hs, ws_, Cc, Cc, one("conv3.0", Cc, Cc)), V(src3), V(sp.gA)))
+            bw.append(cv(V(sp.gA), V(sp.gB), wptr + pk["offs"][("b", "conv3.0")], N, hs, ws_, Cc, Cc, mask=V(src3) if self.n_up else A.NULL_VIEW, mask_slope=0.2))
             cur, other = sp.gB, sp.gA        # cur = gradient w.r.t. pre-activation of upsampling{n_up} (at its output res)
             for u in range(self.n_up, 0, -1):
                 nm = f"upsampling{u}.0"
@@ -454,22 +449,20 @@ class TrunkEngine(EngineBase):
                 npx = N * (hin * 2) * (win * 2)
                 cur_v = V(cur.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
                 oth_v = V(other.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
-                bw.append(("wgrad", wplans.plan(hin, win, Cc, Cc, one(nm, Cc, Cc), up=1), V(xin_t), cur_v, 0))
+                bw.append(ops.Wgrad(wplans.plan(hin, win, Cc, Cc, one(nm, Cc, Cc), up=1), V(xin_t), cur_v))
                 glo = sp.glo[u - 1]
                 if self._parity(dtc):
                     # data gradient, nearest adjoint and (u >= 2: the input is the previous upsampling conv's LeakyReLU output) LeakyReLU' as
                     # ONE 4x4 stride-2 pad-1 conv over the high-res gradient, written at the low resolution
-                    a = ops.conv_args(dtc, cur_v, V(glo), wptr + pk["offs"][("b4", nm)], N, hin * 2, win * 2, Cc, Cc, ksize=4, stride=2, pad=1,
-                                      mask=V(xin_t) if u >= 2 else A.NULL_VIEW, mask_slope=0.2)
-                    a._label_tag = " nearest-x2 dgrad"
-                    bw.append(("conv", a))
+                    it = cv(cur_v, V(glo), wptr + pk["offs"][("b4", nm)], N, hin * 2, win * 2, Cc, Cc, ksize=4, stride=2, pad=1,
+                            mask=V(xin_t) if u >= 2 else A.NULL_VIEW, mask_slope=0.2)
+                    it.args._label_tag = " nearest-x2 dgrad"
+                    bw.append(it)
                 else:
-                    bw.append(("conv", ops.conv_args(dtc, cur_v, oth_v, wptr + pk["offs"][("b", nm)], N, hin * 2, win * 2, Cc, Cc)))
-                    bw.append(("call", (lambda a=oth_v, b=V(glo), hh=hin, ww=win: A.check(
-                        A.lib().srganfd_resample(0, a, b, dtc, N, hh, ww, Cc, A.stream_ptr()), "nearest_bwd"))))
+                    bw.append(cv(cur_v, oth_v, wptr + pk["offs"][("b", nm)], N, hin * 2, win * 2, Cc, Cc))
+                    bw.append(ops.Call("srganfd_resample", (0, oth_v, V(glo), dtc, N, hin, win, Cc), "nearest_bwd"))
                     if u >= 2:   # input of this stage is the LeakyReLU output of the previous upsampling conv
-                        bw.append(("call", (lambda d=V(glo), act=V(xin_t), npx2=N * hin * win: A.check(
-                            A.lib().srganfd_lrelu_bwd(d, act, A.NULL_VIEW, d, dtc, npx2, Cc, 0.2, A.stream_ptr()), "lrelu_bwd"))))
+                        bw.append(ops.Call("srganfd_lrelu_bwd", (V(glo), V(xin_t), A.NULL_VIEW, V(glo), dtc, N * hin * win, Cc, 0.2), "lrelu_bwd"))
                 if u >= 2:
                     # next stage works at (hin, win): reuse gA/gB as scratch, the gradient lives in glo
                     cur, other = glo, sp.gA
@@ -479,11 +472,11 @@ class TrunkEngine(EngineBase):
             d_f0 = cur if self.n_up else sp.gB
             sp.d_f0 = d_f0
             # conv2: f0 = out1 + conv2(trunk_out)
-            bw.append(("wgrad", wplans.plan(H, W, Cc, Cc, one("conv2", Cc, Cc)), VC(sp.catb(R)), V(d_f0), 0))
-            bw.append(("conv", ops.conv_args(dtc, V(d_f0), VD(dyb(R - 1)), wptr + pk["offs"][("b", "conv2")], N, H, W, Cc, Cc)))
+            bw.append(ops.Wgrad(wplans.plan(H, W, Cc, Cc, one("conv2", Cc, Cc)), VC(sp.catb(R)), V(d_f0)))
+            bw.append(cv(V(d_f0), VD(dyb(R - 1)), wptr + pk["offs"][("b", "conv2")], N, H, W, Cc, Cc))
             # gradient buckets for the data-parallel exchange (parallel.BucketReducer): parameters sit in named_parameters() order --
             # conv1, the dense blocks, conv2 and the tail -- so "everything from conv2 on" is one contiguous range, final here
-            bw.append(("ready", self._poff("conv2.weight"), self.fp.total))
+            bw.append(ops.Item("ready", (self._poff("conv2.weight"), self.fp.total)))
         # dense blocks, last to first
         rdb_names = ["conv%d" % k for k in range(1, 6)]
         plans = {}
@@ -513,24 +506,23 @@ class TrunkEngine(EngineBase):
             if first:
                 kw.update(r2=VD(dyb(i + 2)), r2_scale=1.0)
             blk.append(ops.conv_args(dtc, VD(di), dst, wptr + pk["offs"][("b", i, 4)], N, H, W, Ccat, Cc, **kw))
-            chain = ops.dense_chain_or_launches(blk, sp.device) if (Cc, G) == (64, 32) else blk
-            wg = ("wgrad", plans[s5], VC(ci), VD(di), self._poff(pre + "conv1.weight"), i)     # 6th field: dense block (batched reduction)
-            fence = [("fence", i + 3)] if i > 0 else []     # dst is the buffer block i + 3's weight gradient read (side-stream mode, see backward())
-            ready = [("ready", self._poff(pre + "conv1.weight"), self._poff("conv2.weight"))] if self.full and R >= 4 and i == R // 2 else []     # upper half of the trunk is final: second bucket
+            chain = ops.dense_chain_or_launches(blk, sp.device) if (Cc, G) == (64, 32) else [ops.Conv(a) for a in blk]
+            wg = ops.Wgrad(plans[s5], VC(ci), VD(di), dw_off=self._poff(pre + "conv1.weight"), block=i)     # the plan's offsets are relative to the block
+            fence = [ops.Item("fence", i + 3)] if i > 0 else []     # dst is the buffer block i + 3's weight gradient read (side-stream mode, see backward())
+            ready = [ops.Item("ready", (self._poff(pre + "conv1.weight"), self._poff("conv2.weight")))] if self.full and R >= 4 and i == R // 2 else []     # upper half of the trunk is final: second bucket
             if len(chain) == 1:
                 # one launch for the five data-gradient convs (it writes dst, so the fence comes first); the weight gradient reads what
                 # the chain's four growth layers wrote and follows it
-                bw.extend(fence + [("chain", chain[0]), wg] + ready)
+                bw.extend(fence + chain + [wg] + ready)
             else:
-                bw.extend([("conv", a_) for a_ in blk[:4]] + [wg] + ready + fence + [("conv", blk[4])])
+                bw.extend(chain[:4] + [wg] + ready + fence + chain[4:])
         if self.full:
-            bw.append(("call", (lambda x=V(sp.d_f0), y=V(sp.dx0): A.check(
-                A.lib().srganfd_axpby(x, y, dtc, N * H * W, Cc, 1.0, 1.0, A.stream_ptr()), "axpby"))))
+            bw.append(ops.Call("srganfd_axpby", (V(sp.d_f0), V(sp.dx0), dtc, N * H * W, Cc, 1.0, 1.0), "axpby"))
             bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, sp.xin, sp.dx0, fptr + 4 * self._poff("conv1.weight"), self._poff("conv1.weight"),
-                                      self._poff("conv1.bias"), sp.thin_ws, N, H, W, self.in_ch, Cc, True, extra=(0,)))
+                                      self._poff("conv1.bias"), sp.thin_ws, N, H, W, self.in_ch, Cc, True))
         # last bucket: whatever the earlier markers did not cover
-        covered = min([it[1] for it in bw if it[0] == "ready"], default=self.fp.total)
-        bw.append(("ready", 0, covered))
+        covered = min([it.payload[0] for it in bw if it.kind == "ready"], default=self.fp.total)
+        bw.append(ops.Item("ready", (0, covered)))
         sp.bw = bw
         sp.wg_ws = wplans.workspace()
         # four more workspaces of the dense-block plan's size for the batched slab reduction (34 MB each at B=32, 128x128)
@@ -582,21 +574,11 @@ class TrunkEngine(EngineBase):
         else:
             A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.Cc, H, W, A.view(sp.catb(0)), dtc, self.Cc, None, None, st), "nchw_to_nhwc")
         rec = profiling.REC
-        Thin, Chain = ops.ThinLaunch, ops.DenseChain
-        if rec is None:
-            for a in sp.fw:
-                if type(a) is Thin or type(a) is Chain:
-                    a.run()
-                    continue
-                rc = L.srganfd_conv2d(C.byref(a), st)
-                if rc:
-                    A.check(rc, "conv2d")
-        else:
-            for a in sp.fw:
-                if type(a) is Thin or type(a) is Chain:
-                    a.launch(rec)
-                    continue
-                rec.bracket(profiling.conv_label(a), profiling.conv_work(a), lambda: A.check(L.srganfd_conv2d(C.byref(a), st), "conv2d"))
+        for item in sp.fw:
+            if item.kind == "conv":
+                ops.conv2d(item.args, rec, "conv2d", L, st)
+            else:                                   # "thin" | "chain"
+                item.launch(rec, L, st)
         if self.full:
             out = torch.empty(N, self.out_ch, sp.hs, sp.ws, dtype=torch.float32, device=dev)
             A.check(L.srganfd_nhwc_to_nchw(A.view(sp.srp), A.F32, N, self.out_ch, sp.hs, sp.ws, out.data_ptr(), 1, st), "nhwc_to_nchw")
@@ -652,66 +634,49 @@ class TrunkEngine(EngineBase):
                 j.grads, j.scalars, j.workspace = gptr + 4 * goff, None, ws.data_ptr()
             n_jobs = len(pend_red)
             run = lambda: A.check(L.srganfd_wgrad_reduce_batch(jobs, n_jobs, A.stream_ptr()), "wgrad_reduce_batch")
-            if rec is None:
-                on_side(run)
-            else:
-                on_side(lambda: rec.bracket("wgrad_reduce_batch", (0.0, float(sum(w.numel() for _, _, w in pend_red))), run))
+            on_side(run if rec is None else lambda: rec.bracket("wgrad_reduce_batch", (0.0, float(sum(w.numel() for _, _, w in pend_red))), run))
             pend_red.clear()
         for item in sp.bw:
-            kind = item[0]
+            kind = item.kind
             if kind == "conv":
-                if rec is None:
-                    rc = L.srganfd_conv2d(C.byref(item[1]), st)
-                    if rc:
-                        A.check(rc, "conv2d(dgrad)")
-                else:
-                    a = item[1]
-                    rec.bracket(profiling.conv_label(a), profiling.conv_work(a), lambda: A.check(L.srganfd_conv2d(C.byref(a), st), "conv2d(dgrad)"))
+                ops.conv2d(item.args, rec, "conv2d(dgrad)", L, st)
             elif kind == "chain":
-                item[1].launch(rec)
+                item.launch(rec, L, st)
             elif kind == "wgrad":
-                plan, xv, dyv, goff = item[1:5]
-                if len(item) > 5 and sp.wg_ws4 is not None:
+                plan = item.plan
+                if item.block is not None and sp.wg_ws4 is not None:
                     # dense block: MFMA kernel now, slabs into one of four workspaces; the slab reduction of up to four blocks is ONE
                     # launch (srganfd_wgrad_reduce_batch: the reduction is latency-bound at ~20 us whatever it reduces)
                     ws = sp.wg_ws4[len(pend_red)]
-                    run = lambda: A.check(L.srganfd_conv2d_wgrad_partial(plan.host, plan.dev.data_ptr(), xv, dyv, ws.data_ptr(), ws.numel(), A.stream_ptr()),
-                                          "conv2d_wgrad_partial")
+                    run = lambda: A.check(L.srganfd_conv2d_wgrad_partial(plan.host, plan.dev.data_ptr(), item.x, item.dy, ws.data_ptr(), ws.numel(),
+                                                                         A.stream_ptr()), "conv2d_wgrad_partial")      # (the side stream's, inside on_side)
                     if side is not None:
                         side.wait_stream(main)          # the block's four data-gradient launches have written its stacked gradient
-                    if rec is None:
-                        on_side(run)
-                    else:
-                        on_side(lambda: rec.bracket(plan.label, (plan.flops, plan.nbytes), run))
+                    on_side(run if rec is None else lambda: rec.bracket(plan.label, (plan.flops, plan.nbytes), run))
                     if side is not None:
                         ev = torch.cuda.Event()
                         ev.record(side)
-                        wg_done[item[5]] = ev
-                    pend_red.append((plan, goff, ws))
+                        wg_done[item.block] = ev
+                    pend_red.append((plan, item.dw_off, ws))
                     if len(pend_red) == len(sp.wg_ws4):
                         flush_reduce()
                 else:
                     flush_reduce()                      # the launches share workspace slot 0
-                    run = lambda: A.check(L.srganfd_conv2d_wgrad(plan.host, plan.dev.data_ptr(), xv, dyv, gptr + 4 * goff, None,
-                                                                 sp.wg_ws.data_ptr(), sp.wg_ws.numel(), st), "conv2d_wgrad")
-                    if rec is None:
-                        run()
-                    else:
-                        rec.bracket(plan.label, (plan.flops, plan.nbytes), run)
+                    ops.conv2d_wgrad(plan, item.x, item.dy, gptr + 4 * item.dw_off, sp.wg_ws, rec, L, st)
             elif kind == "thin":
                 flush_reduce()                          # (keeps the launch order of the padded path: slot-0 workspace users come after pending slabs)
-                item[1].launch(rec, gptr)
+                item.launch(rec, L, st, gptr)
             elif kind == "ready":
                 flush_reduce()
                 if side is not None:
                     main.wait_stream(side)
                 if on_ready is not None:
-                    on_ready(flat_grad, item[1], item[2])
+                    on_ready(flat_grad, *item.payload)
             elif kind == "fence":
-                if side is not None and item[1] in wg_done:
-                    main.wait_event(wg_done.pop(item[1]))
-            else:
-                item[1]()
+                if side is not None and item.payload in wg_done:
+                    main.wait_event(wg_done.pop(item.payload))
+            else:                                       # "call"
+                item.launch(rec, L, st)
         flush_reduce()
         if side is not None:
             main.wait_stream(side)

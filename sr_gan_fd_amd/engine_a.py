@@ -15,8 +15,6 @@ as 4 output-parity classes of 2x2-tap convs, the 2x2 stride-2 ones as 4 classes 
 from __future__ import annotations
 
 import weakref
-from typing import List
-
 import torch
 from torch import Tensor, nn
 
@@ -96,7 +94,6 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
         sp = _Shape()
         sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
         V = A.view
-        L = A.lib()
         fptr, wptr, O = self.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
         me = weakref.proxy(self)                    # closures stored on the plan must not hold the engine (reference cycle)
         P = lambda name: fptr + 4 * me._poff(name)
@@ -119,11 +116,9 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
         sp.bn_ws = torch.empty(2048 * 256 + 3 * 256, dtype=torch.float32, device=device)
         sp.bn_ws_global = None
         lre = dict(act=A.ACT_LRELU, slope=0.2)
-        cv = lambda *a, **k: ("conv", ops.conv_args(dtc, *a, **k))
-        call = lambda fn: ("call", fn)
-        st = A.stream_ptr
-        rs = lambda op, a, b, h, w, c, dtype=dtc: call(lambda: A.check(L.srganfd_resample(op, a, b, dtype, N, h, w, c, st()), "resample"))
-        fw: List[tuple] = [
+        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
+        rs = lambda op, a, b, h, w, c, dtype=dtc: ops.Call("srganfd_resample", (op, a, b, dtype, N, h, w, c), "resample")
+        fw = [
             ops.image_to_features(dtc, sp.thin_i, B["xin"], V(B["x0"]), P("conv0.weight"), Wp("f", "conv0"), N, H, W, self.in_ch, nf, True,
                                   bias=P("conv0.bias"), **lre),
             cv(V(B["x0"]), V(B["x1"]), Wp("f", "conv1"), N, *R[0], nf, 2 * nf, stride=2, **lre),
@@ -149,16 +144,14 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
             fw += [
                 cv(V(B[xname]), V(T["theta"]), Wp("f", pre + ".theta"), N, h, w, Ck, Ck, ksize=2, stride=2, pad=0),
                 cv(V(B["gated"]), V(T["phi"]), Wp("f", pre + ".phi"), N, Hg, Wg, 4 * nf, Ck, ksize=1, pad=0, bias=P(pre + ".phi.bias")),
-                call(lambda a=V(T["phi"]), b=V(T["phiup"]), hh=hh, wh=wh, Ck=Ck: A.check(
-                    L.srganfd_resize_bilinear(0, a, b, dtc, N, Hg, Wg, hh, wh, Ck, st()), "resize")),
-                call(lambda a=V(T["theta"]), b=V(T["phiup"]), o=V(T["f"]), n=N * hh * wh, Ck=Ck: A.check(L.srganfd_add_relu(a, b, o, dtc, n, Ck, st()), "add_relu")),
+                ops.Call("srganfd_resize_bilinear", (0, V(T["phi"]), V(T["phiup"]), dtc, N, Hg, Wg, hh, wh, Ck), "resize"),
+                ops.Call("srganfd_add_relu", (V(T["theta"]), V(T["phiup"]), V(T["f"]), dtc, N * hh * wh, Ck), "add_relu"),
                 cv(V(T["f"]), V(T["sig"]), Wp("f", pre + ".psi"), N, hh, wh, Ck, 32, ksize=1, pad=0, cout_store=1, bias=P(pre + ".psi.bias"), y_f32=True),
-                call(lambda t=T["sig"]: A.check(L.srganfd_sigmoid(t.data_ptr(), t.numel(), st()), "sigmoid")),
+                ops.Call("srganfd_sigmoid", (T["sig"].data_ptr(), T["sig"].numel()), "sigmoid"),
                 rs(1, V(T["sig"]), V(T["sigup"]), hh, wh, 1, A.F32),
-                call(lambda x=V(B[xname]), g=T["sigup"], y=V(T["y"]), n=N * h * w, Ck=Ck: A.check(
-                    L.srganfd_gate_mul(0, x, g.data_ptr(), y, A.NULL_VIEW, None, dtc, n, Ck, st()), "gate_mul")),
+                ops.Call("srganfd_gate_mul", (0, V(B[xname]), T["sigup"].data_ptr(), V(T["y"]), A.NULL_VIEW, None, dtc, N * h * w, Ck), "gate_mul"),
                 cv(V(T["y"]), V(T["wy"]), Wp("f", pre + ".W.0"), N, h, w, Ck, Ck, ksize=1, pad=0, bias=P(pre + ".W.0.bias")),
-                ("bn", (k, V(T["wy"]), V(B[cat]), N * h * w, Ck, P(pre + ".W.1.weight"), P(pre + ".W.1.bias"), bn, T["save"])),
+                ops.Item("bn", (k, V(T["wy"]), V(B[cat]), N * h * w, Ck, P(pre + ".W.1.weight"), P(pre + ".W.1.bias"), bn, T["save"])),
             ]
         fw += [
             rs(1, V(B["x3"]), V(B["b3"]), *R[3], 8 * nf),
@@ -184,13 +177,12 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
 
     def _plan_backward(self, sp, pk):
         N, H, W, dt, dtc, device = sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device
-        V, L, B, R, nf = A.view, A.lib(), sp.B, sp.R, self.nf
+        V, B, R, nf = A.view, sp.B, sp.R, self.nf
         Hg, Wg = sp.Rg
         wptr, O = pk["buf"].data_ptr(), pk["offs"]
         Wp = lambda *key: wptr + O[key]
         fptr = self.fp.flat.data_ptr()
         P = lambda name: fptr + 4 * self.fp.off(name)      # (used while the plan is built only, not stored on it)
-        st = A.stream_ptr
 
         def new(h, w, c, dtype=dt):
             return torch.empty(N, h, w, c, dtype=dtype, device=device)
@@ -199,19 +191,18 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
         def wg(name, x, dy, h, w, cin, cout, k=3, s=1, pad=1, sn=False, cin_real=None, cout_real=None, bias=False, dy_c0=0):
             plan = wplans.conv(h, w, cin, cout, self._poff(name + (".weight_orig" if sn else ".weight")), self._poff(name + ".bias") if bias else -1,
                                cin_real, cout_real, ksize=k, stride=s, pad=pad)
-            return ("wgrad", plan, V(x), V(dy, c0=dy_c0), SN_INDEX[name] if sn else None)
+            return ops.Wgrad(plan, V(x), V(dy, c0=dy_c0), sn=SN_INDEX[name] if sn else None)
 
-        cv = lambda *a, **k: ("conv", ops.conv_args(dtc, *a, **k))
-        call = lambda fn: ("call", fn)
-        rs = lambda op, a, b, h, w, c, dtype=dtc: call(lambda: A.check(L.srganfd_resample(op, a, b, dtype, N, h, w, c, st()), "resample"))
-        lb = lambda dy, act, out, npix, c, slope=0.2: call(lambda: A.check(L.srganfd_lrelu_bwd(dy, act, A.NULL_VIEW, out, dtc, npix, c, slope, st()), "lrelu_bwd"))
+        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
+        rs = lambda op, a, b, h, w, c, dtype=dtc: ops.Call("srganfd_resample", (op, a, b, dtype, N, h, w, c), "resample")
+        lb = lambda dy, act, out, npix, c, slope=0.2: ops.Call("srganfd_lrelu_bwd", (dy, act, A.NULL_VIEW, out, dtc, npix, c, slope), "lrelu_bwd")
 
         def strided_dgrad(key, ks, dy, dx, hd, wd, cin_op, cout_op, r1=None, r2=None, mask=None):
             """4 parity classes writing a (2hd x 2wd) image: ks=2 (3x3 s2 conv) or ks=1 (2x2 s2 conv)"""
             view = lambda t: None if t is None else V(t)
-            return [("conv", a) for a in ops.parity_class_launches(      # class_pad 0: every class reads the same window of dy
+            return ops.parity_class_launches(      # class_pad 0: every class reads the same window of dy
                 dtc, V(dy), V(dx), wptr, [O[key + (c,)] for c in range(4)], N, hd, wd, cin_op, cout_op, ks, 0,
-                **ops.dgrad_epilogue(view(r1), view(r2), view(mask)))]
+                **ops.dgrad_epilogue(view(r1), view(r2), view(mask)))
 
         sp.dl = new(H, W, 4 if sp.thin_o else 32)
         sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device) if (sp.thin_i or sp.thin_o) else None
@@ -235,23 +226,21 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
             D["dsig"] = torch.empty(N, hh, wh, 1, dtype=torch.float32, device=device)
             D["dpsip"], D["df"], D["dxt"], D["dphi"] = new(hh, wh, 32), new(hh, wh, Ck), new(h, w, Ck), new(Hg, Wg, Ck)
             items = [
-                ("bn_bwd", (V(T["wy"]), V(dcat), V(D["dwy"]), N * h * w, Ck, pre, T["save"])),
+                ops.Item("bn_bwd", (V(T["wy"]), V(dcat), V(D["dwy"]), N * h * w, Ck, pre, T["save"])),
                 wg(pre + ".W.0", T["y"], D["dwy"], h, w, Ck, Ck, k=1, pad=0, bias=True),
                 cv(V(D["dwy"]), V(D["dy"]), Wp("b", pre + ".W.0"), N, h, w, Ck, Ck, ksize=1, pad=0),
-                call(lambda x=V(B[xname]), g=T["sigup"], dy=V(D["dy"]), dx=V(D["dxg"]), dg=D["dsigup"], n=N * h * w, Ck=Ck: A.check(
-                    L.srganfd_gate_mul(1, x, g.data_ptr(), dy, dx, dg.data_ptr(), dtc, n, Ck, st()), "gate_mul_bwd")),
+                ops.Call("srganfd_gate_mul", (1, V(B[xname]), T["sigup"].data_ptr(), V(D["dy"]), V(D["dxg"]), D["dsigup"].data_ptr(), dtc, N * h * w, Ck),
+                         "gate_mul_bwd"),
                 rs(2, V(D["dsigup"]), V(D["dsig"]), hh, wh, 1, A.F32),
-                call(lambda ds=D["dsig"], s_=T["sig"]: A.check(L.srganfd_sigmoid_bwd(ds.data_ptr(), s_.data_ptr(), ds.data_ptr(), ds.numel(), st()), "sigmoid_bwd")),
-                call(lambda ds=D["dsig"], o=V(D["dpsip"]), hh=hh, wh=wh: A.check(
-                    L.srganfd_nchw_to_nhwc(ds.data_ptr(), N, 1, hh, wh, o, dtc, 32, None, None, st()), "pad32")),
+                ops.Call("srganfd_sigmoid_bwd", (D["dsig"].data_ptr(), T["sig"].data_ptr(), D["dsig"].data_ptr(), D["dsig"].numel()), "sigmoid_bwd"),
+                ops.Call("srganfd_nchw_to_nhwc", (D["dsig"].data_ptr(), N, 1, hh, wh, V(D["dpsip"]), dtc, 32, None, None), "pad32"),
                 wg(pre + ".psi", T["f"], D["dpsip"], hh, wh, Ck, 32, k=1, pad=0, cout_real=1, bias=True),
                 cv(V(D["dpsip"]), V(D["df"]), Wp("b", pre + ".psi"), N, hh, wh, 32, Ck, ksize=1, pad=0, mask=V(T["f"]), mask_slope=0.0),
                 wg(pre + ".theta", B[xname], D["df"], h, w, Ck, Ck, k=2, s=2, pad=0),
             ]
             items += strided_dgrad(("b", pre + ".theta"), 1, D["df"], D["dxt"], hh, wh, Ck, Ck)
             items += [
-                call(lambda a=V(D["df"]), b=V(D["dphi"]), hh=hh, wh=wh, Ck=Ck: A.check(
-                    L.srganfd_resize_bilinear(1, a, b, dtc, N, Hg, Wg, hh, wh, Ck, st()), "resize_bwd")),
+                ops.Call("srganfd_resize_bilinear", (1, V(D["df"]), V(D["dphi"]), dtc, N, Hg, Wg, hh, wh, Ck), "resize_bwd"),
                 wg(pre + ".phi", B["gated"], D["dphi"], Hg, Wg, 4 * nf, Ck, k=1, pad=0, bias=True),
                 cv(V(D["dphi"]), V(dgated_out), Wp("b", pre + ".phi"), N, Hg, Wg, Ck, 4 * nf, ksize=1, pad=0,
                    r1=V(dgated_prev) if dgated_prev is not None else A.NULL_VIEW, r1_scale=1.0 if dgated_prev is not None else 0.0,
@@ -259,9 +248,9 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
             ]
             return items
 
-        bw: List[tuple] = [
+        bw = [
             ops.image_wgrad(dtc, sp.thin_o, wplans, sp.dl, B["c8"], P("conv9.weight"), self._poff("conv9.weight"), self._poff("conv9.bias"), sp.thin_ws,
-                            N, H, W, 1, nf, False, extra=(None,)),
+                            N, H, W, 1, nf, False),
             ops.image_to_features(dtc, sp.thin_o, sp.dl, V(G["g8"]), P("conv9.weight"), Wp("b", "conv9"), N, H, W, 1, nf, False, flip=True,
                                   mask=V(B["c8"]), mask_slope=0.2),
             wg("conv8", B["c7"], G["g8"], H, W, nf, nf, sn=True),
@@ -312,15 +301,15 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
         bw += strided_dgrad(("b", "conv1"), 2, G["dx1"], G["dx0"], *R[1], 2 * nf, nf,
                             r1=sp.attn[3]["grad"]["dxg"], r2=sp.attn[3]["grad"]["dxt"], mask=B["x0"])
         bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, B["xin"], G["dx0"], P("conv0.weight"), self._poff("conv0.weight"), self._poff("conv0.bias"),
-                                  sp.thin_ws, N, H, W, self.in_ch, nf, True, extra=(None,)))
+                                  sp.thin_ws, N, H, W, self.in_ch, nf, True))
         sp.dx_conv = ops.features_to_image(dtc, sp.thin_i, V(G["dx0"]), sp.dxp, 4, P("conv0.weight"), Wp("b", "conv0"), N, H, W, self.in_ch, nf, True, flip=True)
         sp.bw = bw
         self._backward_workspaces(sp, wplans)
 
     # ---- execution: the core's loops, plus the attention gates' BatchNorm ----
-    def _forward_item(self, kind, item, sp, training, L, st) -> None:
-        """("bn", ...): BatchNorm2d of an attention gate's W branch, written into its half of the concatenation buffer"""
-        k, xv, yv, npix, Ck, gamma, beta, bn, save = item
+    def _forward_item(self, item, sp, training, L, st) -> None:
+        """Item("bn", ...): BatchNorm2d of an attention gate's W branch, written into its half of the concatenation buffer"""
+        k, xv, yv, npix, Ck, gamma, beta, bn, save = item.payload
         dtc = sp.dtc
         if bn.running_mean.device != sp.device:
             raise A.SrganfdError("BatchNorm buffers must live on the module's GPU")
@@ -345,8 +334,8 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
         return logits
 
     def _backward_item(self, item, sp, flat_grad, L, st) -> None:
-        """("bn_bwd", ...): the flat gradient receives dgamma / dbeta"""
-        xv, dyv, dxv, npix, Ck, pre, save = item[1]
+        """Item("bn_bwd", ...): the flat gradient receives dgamma / dbeta"""
+        xv, dyv, dxv, npix, Ck, pre, save = item.payload
         dtc, flat = sp.dtc, self.fp.flat
         gamma, beta = 4 * self._poff(pre + ".W.1.weight"), 4 * self._poff(pre + ".W.1.bias")
         if self.sync_bn is not None:

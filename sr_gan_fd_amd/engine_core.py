@@ -2,13 +2,13 @@
 forward and backward launch loops, and the autograd glue.
 
 A subclass describes its network: the layer tables, ``_build_pack``, ``_plan`` / ``_plan_backward`` (the launch lists) and, for
-launch kinds only it has (BatchNorm), ``_forward_item`` / ``_backward_item``.  A plan ``sp`` carries
+launch kinds only it has (BatchNorm), ``_forward_item`` / ``_backward_item``.  A plan ``sp`` carries (items: ops.py's, by ``kind``)
   sp.xin                 NHWC input buffer (4-channel pitch for the thin kernels, else padded to 32)
-  sp.fw                  forward items: ("conv", ConvArgs) | ("thin", ThinLaunch) | ("call", fn) | (own kind, ...)
+  sp.fw                  forward items: ops.Conv | ops.ThinLaunch | ops.Call | ops.Item(own kind, payload)
   sp.logits_conv(t)      the item of the last layer, which writes the fp32 logits tensor ``t`` (allocated per forward)
   sp.dl                  NHWC buffer of the logits' gradient
-  sp.bw                  backward items: the forward kinds and ("wgrad", plan, x view, dy view, spectral-norm index or None)
-  sp.dx_conv, sp.dxp     the item of the first layer's data gradient and its fp32 NHWC4 output
+  sp.bw                  backward items: the forward kinds and ops.Wgrad (``sn``: the layer's spectral-norm slot, or None)
+  sp.dx_conv, sp.dxp     the item (Conv or ThinLaunch) of the first layer's data gradient and its fp32 NHWC4 output
   sp.wg_ws, sp.gtmp, sp.sn_ws   workspaces (``_backward_workspaces``)
 """
 from __future__ import annotations
@@ -75,11 +75,11 @@ class DiscriminatorEngineCore(EngineBase):
     def _logits(self, N: int, H: int, W: int, device) -> Tensor:
         return torch.empty(N, 1, H, W, dtype=torch.float32, device=device)
 
-    def _forward_item(self, kind, item, sp, training, L, st) -> None:
-        raise A.SrganfdError(f"{self.what}: unknown launch kind {kind!r}")
+    def _forward_item(self, item, sp, training, L, st) -> None:
+        raise A.SrganfdError(f"{self.what}: unknown launch kind {item.kind!r}")
 
     def _backward_item(self, item, sp, flat_grad, L, st) -> None:
-        raise A.SrganfdError(f"{self.what}: unknown launch kind {item[0]!r}")
+        raise A.SrganfdError(f"{self.what}: unknown launch kind {item.kind!r}")
 
     def forward(self, x: Tensor, training: bool) -> Tensor:
         self._check_input(x)                       # the shape contract, before anything is packed, planned or launched
@@ -94,15 +94,14 @@ class DiscriminatorEngineCore(EngineBase):
         A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.in_ch, H, W, A.view(sp.xin), dtc, sp.xin.shape[-1], None, None, st), "nchw_to_nhwc")
         logits = self._logits(N, H, W, dev)
         rec = profiling.REC
-        for kind, item in sp.fw + [sp.logits_conv(logits)]:
+        for item in sp.fw + [sp.logits_conv(logits)]:
+            kind = item.kind
             if kind == "conv":
-                ops.conv2d(item, rec, "conv2d", L, st)
-            elif kind == "thin":
-                item.launch(rec)
-            elif kind == "call":
-                item()
+                ops.conv2d(item.args, rec, "conv2d", L, st)
+            elif kind == "thin" or kind == "call":
+                item.launch(rec, L, st)
             else:
-                self._forward_item(kind, item, sp, training, L, st)
+                self._forward_item(item, sp, training, L, st)
         self.token += 1
         sp.token, sp.training, sp.inv_sigma = self.token, training, pk.get("scalars")
         self._last = sp
@@ -124,17 +123,17 @@ class DiscriminatorEngineCore(EngineBase):
         rec = profiling.REC
         sn_grads = []
         for item in sp.bw:
-            kind = item[0]
+            kind = item.kind
             if kind == "conv":
-                ops.conv2d(item[1], rec, "conv2d(dgrad)", L, st)
+                ops.conv2d(item.args, rec, "conv2d(dgrad)", L, st)
             elif kind == "thin":
-                if need_wgrad or not item[1].is_wgrad:
-                    item[1].launch(rec, flat_grad.data_ptr())
+                if need_wgrad or not item.is_wgrad:
+                    item.launch(rec, L, st, flat_grad.data_ptr())
             elif kind == "wgrad":
                 if not need_wgrad:
                     continue
-                _, plan, xv, dyv, l = item
-                ops.conv2d_wgrad(plan, xv, dyv, (flat_grad if l is None else sp.gtmp).data_ptr(), sp.wg_ws, rec, L, st)
+                l = item.sn
+                ops.conv2d_wgrad(item.plan, item.x, item.dy, (flat_grad if l is None else sp.gtmp).data_ptr(), sp.wg_ws, rec, L, st)
                 if l is not None:
                     name, rows, cols = self.sn[l]
                     off = 4 * self._poff(name)
@@ -142,18 +141,18 @@ class DiscriminatorEngineCore(EngineBase):
                     sn_grads.append((sp.gtmp.data_ptr() + off, flat.data_ptr() + off, u.data_ptr(), v.data_ptr(),
                                      sp.inv_sigma.data_ptr() + 4 * (2 * l + 1), flat_grad.data_ptr() + off, rows, cols))
             elif kind == "call":
-                item[1]()
+                item.launch(rec, L, st)
             else:
                 self._backward_item(item, sp, flat_grad, L, st)
         # dL/d(W/sigma) of every spectral-normalised layer sits in its own range of gtmp: one batched pass turns them into dL/dW_orig
         ops.spectral_norm_grad_batch(sn_grads, sp.sn_ws)
         dx = None
         if need_dx:
-            kind, item = sp.dx_conv
-            if kind == "thin":
-                item.launch(rec)
+            item = sp.dx_conv
+            if item.kind == "thin":
+                item.launch(rec, L, st)
             else:
-                ops.conv2d(item, None, "conv2d(dgrad of the first layer)", L, st)
+                ops.conv2d(item.args, None, "conv2d(dgrad of the first layer)", L, st)
             dx = torch.empty(N, self.in_ch, H, W, dtype=torch.float32, device=sp.device)
             A.check(L.srganfd_nhwc_to_nchw(A.view(sp.dxp), A.F32, N, self.in_ch, H, W, dx.data_ptr(), 0, st), "nhwc_to_nchw")
         return (flat_grad if need_wgrad else None), dx

@@ -82,9 +82,8 @@ class DiscriminatorEngine(DiscriminatorEngineCore):
         sp.c2, sp.c3 = new(H, W, 64), new(H, W, 64)
         # LeakyReLU outputs before the skip adds (exact derivative sign in backward)
         sp.a1, sp.a2, sp.a3 = new(H // 4, W // 4, 256), new(H // 2, W // 2, 128), new(H, W, 64)
-        L = A.lib()
-        cv = lambda *a, **k: ("conv", ops.conv_args(dtc, *a, **k))
-        rs = lambda op, a, b, h, w, c: ("call", lambda: A.check(L.srganfd_resample(op, a, b, dtc, N, h, w, c, A.stream_ptr()), "resample"))
+        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
+        rs = lambda op, a, b, h, w, c: ops.Call("srganfd_resample", (op, a, b, dtc, N, h, w, c), "resample")
         lre = dict(act=A.ACT_LRELU, slope=0.2)
         w1, b1 = fptr + 4 * self._poff("conv1.weight"), fptr + 4 * self._poff("conv1.bias")
         fw = [
@@ -114,7 +113,6 @@ class DiscriminatorEngine(DiscriminatorEngineCore):
         N, H, W, dt, dtc, device = sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device
         V = A.view
         wptr, O = pk["buf"].data_ptr(), pk["offs"]
-        L = A.lib()
 
         def new(h, w, c, dtype=dt):
             return torch.empty(N, h, w, c, dtype=dtype, device=device)
@@ -135,23 +133,22 @@ class DiscriminatorEngine(DiscriminatorEngineCore):
             pname = self.sn[sn_index][0] if sn_index is not None else f"{name}.weight"
             plan = wplans.conv(h, w, cin, cout, self._poff(pname), self._poff(f"{name}.bias") if bias else -1, cin_real, cout_real,
                                ksize=k, stride=s, pad=1)
-            return ("wgrad", plan, V(x), V(dy), sn_index)
+            return ops.Wgrad(plan, V(x), V(dy), sn=sn_index)
 
-        cv = lambda *a, **k: ("conv", ops.conv_args(dtc, *a, **k))
+        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
         # bilinear-x2 backward + LeakyReLU' of the upsampled layer in one pass: raw gradient (the skip connection's share) and masked one
-        rsl = lambda dy, raw, act, masked, h, w, c: ("call", lambda: A.check(
-            L.srganfd_resample_bwd_lrelu(dy, raw, act, masked, dtc, N, h, w, c, 0.2, A.stream_ptr()), "resample_bwd_lrelu"))
+        rsl = lambda dy, raw, act, masked, h, w, c: ops.Call("srganfd_resample_bwd_lrelu", (dy, raw, act, masked, dtc, N, h, w, c, 0.2), "resample_bwd_lrelu")
 
         def s2_dgrad(name, dy, dx, hd, wd, cout, cin, r1, mask):
             """data gradient of a 4x4 stride-2 conv: 4 output-parity classes (2x2-tap convs over dy)"""
-            return [("conv", a) for a in ops.parity_class_launches(
+            return ops.parity_class_launches(
                 dtc, V(dy), V(dx), wptr, [O[("b", name, c)] for c in range(4)], N, hd, wd, cout, cin, 2, 1,
-                **ops.dgrad_epilogue(r1=None if r1 is None else V(r1), mask=None if mask is None else V(mask)))]
+                **ops.dgrad_epilogue(r1=None if r1 is None else V(r1), mask=None if mask is None else V(mask)))
 
         w4raw, w1raw = fptr + 4 * self._poff("conv4.weight"), fptr + 4 * self._poff("conv1.weight")
         bw = [
             ops.image_wgrad(dtc, sp.thin_o, wplans, sp.dl, sp.c3, w4raw, self._poff("conv4.weight"), self._poff("conv4.bias"), sp.thin_ws,
-                            N, H, W, 1, 64, False, extra=(None,)),
+                            N, H, W, 1, 64, False),
             ops.image_to_features(dtc, sp.thin_o, sp.dl, V(gA), w4raw, wptr + O[("b", "conv4")], N, H, W, 1, 64, False, flip=True,
                                   mask=V(sp.c3), mask_slope=0.2),
             wg("conv3", sp.c2, gA, H, W, 64, 64, sn_index=7),
@@ -177,7 +174,7 @@ class DiscriminatorEngine(DiscriminatorEngineCore):
         bw.append(wg("down_block1", sp.out1, h4, H, W, 64, 128, sn_index=0, k=4, s=2))
         bw += s2_dgrad("down_block1", h4, gD, H // 2, W // 2, 128, 64, gA, None)         # gD = d out1 (+ skip d u3)
         bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, sp.xin, gD, w1raw, self._poff("conv1.weight"), self._poff("conv1.bias"), sp.thin_ws,
-                                  N, H, W, self.in_ch, 64, True, extra=(None,)))
+                                  N, H, W, self.in_ch, 64, True))
         sp.dx_conv = ops.features_to_image(dtc, sp.thin_i, V(gD), sp.dxp, 4, w1raw, wptr + O[("b", "conv1")], N, H, W, self.in_ch, 64, True, flip=True)
         sp.bw = bw
         self._backward_workspaces(sp, wplans)

@@ -79,7 +79,7 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
         sp.y, sp.a, sp.save, sp.hw = {}, {}, {}, {}
         h, w = H, W
         fw = []
-        cv = lambda *a, **k: ("conv", ops.conv_args(dtc, *a, **k))
+        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
         prev = sp.xin
         for i, (fi, ci, co, ks, st) in enumerate(self.convs):
             ho, wo = h // st, w // st
@@ -92,15 +92,14 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
                 sp.y[i] = new(ho, wo, co)
                 sp.save[i] = torch.empty(4 * co, dtype=torch.float32, device=device)
                 fw.append(cv(V(prev), V(sp.y[i]), wptr + O[("f", fi)], N, h, w, ci, co, ksize=ks, stride=st))
-                fw.append(("bn", i))
+                fw.append(ops.Item("bn", i))
             prev, h, w = sp.a[i], ho, wo
         sp.f1 = new(1, 1, self.hid_pad, zero=True)          # padded channels stay zero (they meet zero weights in fc2)
-        a = ops.conv_args(dtc, V(sp.a[9]), V(sp.f1), wptr + O[("f", "fc1")], N, 4, 4, 512, self.hid_pad, cout_store=self.hid, ksize=4, stride=2,
-                          pad=0, bias=fptr + 4 * self._poff("classifier.0.bias"), act=A.ACT_LRELU, slope=SLOPE)
-        fw.append(("conv", a))
+        fw.append(cv(V(sp.a[9]), V(sp.f1), wptr + O[("f", "fc1")], N, 4, 4, 512, self.hid_pad, cout_store=self.hid, ksize=4, stride=2,
+                     pad=0, bias=fptr + 4 * self._poff("classifier.0.bias"), act=A.ACT_LRELU, slope=SLOPE))
         sp.fw = fw
         f1_v, hid, w2, b2 = V(sp.f1), self.hid_pad, wptr + O[("f", "fc2")], fptr + 4 * self._poff("classifier.2.bias")   # no `sp` / `self` in the closure
-        sp.logits_conv = lambda logits: ("conv", ops.conv_args(dtc, f1_v, A.View(logits.data_ptr(), 1, 0), w2, N, 1, 1, hid, 32,
+        sp.logits_conv = lambda logits: ops.Conv(ops.conv_args(dtc, f1_v, A.View(logits.data_ptr(), 1, 0), w2, N, 1, 1, hid, 32,
                                                                cout_store=1, ksize=1, pad=0, bias=b2, y_f32=True))
         sp.bn_ws = torch.empty(2048 * 256 + 3 * 256, dtype=torch.float32, device=device)
         self._plan_backward(sp, pk)
@@ -118,17 +117,17 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
 
         def wg(pname, bname, x, dy, h, w, cin, cout, k, s, pad, cin_real=None, cout_real=None):
             plan = wplans.conv(h, w, cin, cout, self._poff(pname), self._poff(bname) if bname else -1, cin_real, cout_real, ksize=k, stride=s, pad=pad)
-            return ("wgrad", plan, V(x), V(dy), None)
+            return ops.Wgrad(plan, V(x), V(dy))
 
         def s2_dgrad(key, dy, dx, hd, wd, cout, cin, mask, pad):
             """data gradient of a 4x4 stride-2 conv as 4 output-parity classes (2x2-tap convs over dy).  pad = 1: class
             (py,px) has hd x wd outputs; pad = 0 (the classifier's 4x4 'valid' conv): hd+1 x wd+1 outputs, the tap pairs of
             the opposite parity and one row/column of zero padding on the low side."""
-            return [("conv", a) for a in ops.parity_class_launches(
+            return ops.parity_class_launches(
                 dtc, V(dy), V(dx), wptr, [O[("b", key, c)] for c in range(4)], N, hd, wd, cout, cin, 2, 1, valid=pad == 0,
-                **ops.dgrad_epilogue(mask=None if mask is None else V(mask), mask_slope=SLOPE))]
+                **ops.dgrad_epilogue(mask=None if mask is None else V(mask), mask_slope=SLOPE))
 
-        cv = lambda *a, **k: ("conv", ops.conv_args(dtc, *a, **k))
+        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
         sp.dl = new(1, 1, 32)
         df1 = new(1, 1, self.hid_pad)
         bw = [
@@ -143,7 +142,7 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
             fi, ci, co, ks, st = self.convs[i]
             h, w, ho, wo = sp.hw[i]
             dY = new(ho, wo, co)
-            bw.append(("bn_bwd", i, V(dA), V(dY)))
+            bw.append(ops.Item("bn_bwd", (i, V(dA), V(dY))))
             xprev = sp.a[i - 1]
             bw.append(wg(f"features.{fi}.weight", None, xprev, dY, h, w, ci, co, ks, st, 1))
             dAp = new(h, w, ci)
@@ -160,7 +159,7 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
         bw.append(wg("features.0.weight", "features.0.bias", sp.xin, dA, sp.H, sp.W, 32, 64, 3, 1, 1, cin_real=3))
         sp.bw = bw
         sp.dxp = torch.empty(N, sp.H, sp.W, 4, dtype=torch.float32, device=device)
-        sp.dx_conv = ("conv", ops.conv_args(dtc, V(dA), V(sp.dxp), wptr + O[("b", 0)], N, sp.H, sp.W, 64, 32, cout_store=3, y_f32=True))
+        sp.dx_conv = cv(V(dA), V(sp.dxp), wptr + O[("b", 0)], N, sp.H, sp.W, 64, 32, cout_store=3, y_f32=True)
         self._backward_workspaces(sp, wplans)
 
     # ---- execution: the core's loops, plus BatchNorm2d + LeakyReLU as one fused pass per stage ----
@@ -179,8 +178,9 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
         _, _, ho, wo = sp.hw[i]
         return self.owner.features[fi + 1], sp.N * ho * wo, co, 4 * self._poff(f"features.{fi + 1}.weight"), 4 * self._poff(f"features.{fi + 1}.bias")
 
-    def _forward_item(self, kind, i, sp, training, L, st) -> None:
-        """("bn", i): BatchNorm2d + LeakyReLU of stage i"""
+    def _forward_item(self, item, sp, training, L, st) -> None:
+        """Item("bn", i): BatchNorm2d + LeakyReLU of stage i"""
+        i = item.payload
         bn, npix, co, gamma, beta = self._bn_args(sp, i)
         if bn.running_mean.device != sp.device:
             raise A.SrganfdError("BatchNorm buffers must live on the module's GPU")
@@ -192,8 +192,8 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
             bn.num_batches_tracked += 1
 
     def _backward_item(self, item, sp, flat_grad, L, st) -> None:
-        """("bn_bwd", i, dA, dY): dA (w.r.t. the post-activation) -> dY (w.r.t. the conv output); dgamma / dbeta into the flat gradient"""
-        _, i, dAv, dYv = item
+        """Item("bn_bwd", (i, dA, dY)): dA (w.r.t. the post-activation) -> dY (w.r.t. the conv output); dgamma / dbeta into the flat gradient"""
+        i, dAv, dYv = item.payload
         _, npix, co, gamma, beta = self._bn_args(sp, i)
         A.check(L.srganfd_batchnorm_act_bwd(A.view(sp.y[i]), dAv, dYv, sp.dtc, npix, co, self.fp.flat.data_ptr() + gamma, sp.save[i].data_ptr(),
                                             flat_grad.data_ptr() + gamma, flat_grad.data_ptr() + beta, 0.0, sp.bn_ws.data_ptr(),

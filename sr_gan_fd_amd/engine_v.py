@@ -62,22 +62,15 @@ class VggEngineBase(EngineBase):
             dst = A.View(sp.xin.data_ptr() + half * N * H * W * cpad * sp.xin.element_size(), cpad, 0)
             A.check(L.srganfd_nchw_to_nhwc(img.data_ptr(), N, cin, H, W, dst, dtc, cpad, mean.data_ptr(), std.data_ptr(), st), "nchw_to_nhwc")
 
-    def _feature_conv(self, sp: _Shape, pk: dict, dtc: int, idx: int, x: Tensor, y: Tensor, cin: int, act: int) -> tuple:
-        """launch item of features.idx + activation over the 2N batch: x (its padded channel count is cin) -> y"""
+    def _feature_conv(self, sp: _Shape, pk: dict, dtc: int, idx: int, x: Tensor, y: Tensor, cin: int, act: int):
+        """launch item (ops.Conv or ops.ThinLaunch) of features.idx + activation over the 2N batch: x (its padded channel count is cin) -> y"""
         n, h, w, co = y.shape
         fptr = self.fp.flat.data_ptr()
         bias = fptr + 4 * self._poff(f"features.{idx}.bias")
         if idx == 0 and sp.thin:
-            return ("thin", ops.ThinLaunch("thin_in", ops.thin_args(dtc, n, h, w, self.convs[0][1].weight.shape[1], fptr + 4 * self._poff("features.0.weight"),
-                                                                    A.view(y), w_big_is_cout=True, bias=bias, act=act, thin=sp.xin)))
-        return ("conv", ops.conv_args(dtc, A.view(x), A.view(y), pk["buf"].data_ptr() + pk["offs"][self._fkey(idx)], n, h, w, cin, co, bias=bias, act=act))
-
-
-def _launch(kind: str, item, rec, what: str, L, st) -> None:
-    if kind == "thin":
-        item.launch(rec)
-    else:
-        ops.conv2d(item, rec, what, L, st)
+            return ops.ThinLaunch("thin_in", ops.thin_args(dtc, n, h, w, self.convs[0][1].weight.shape[1], fptr + 4 * self._poff("features.0.weight"),
+                                                           A.view(y), w_big_is_cout=True, bias=bias, act=act, thin=sp.xin))
+        return ops.Conv(ops.conv_args(dtc, A.view(x), A.view(y), pk["buf"].data_ptr() + pk["offs"][self._fkey(idx)], n, h, w, cin, co, bias=bias, act=act))
 
 
 class ContentLossEngine(VggEngineBase):
@@ -127,7 +120,11 @@ class ContentLossEngine(VggEngineBase):
                 tap = idx in self.want
                 # taps are observed after the in-place ReLU unless they are the last requested node
                 relu_in_conv = not (tap and (idx == last or not post))
-                _launch(*self._feature_conv(sp, pk, dtc, idx, cur, out, ch, A.ACT_RELU if relu_in_conv else A.ACT_NONE), rec, "conv2d(vgg)", L, st)
+                item = self._feature_conv(sp, pk, dtc, idx, cur, out, ch, A.ACT_RELU if relu_in_conv else A.ACT_NONE)
+                if item.kind == "conv":
+                    ops.conv2d(item.args, rec, "conv2d(vgg)", L, st)
+                else:
+                    item.launch(rec, L, st)
                 if tap:
                     half_b = N * h * w * co * out.element_size()
                     A.check(L.srganfd_l1_loss_views(A.View(out.data_ptr(), co, 0), A.View(out.data_ptr() + half_b, co, 0), dtc, N * h * w, co, 0, 1.0,
@@ -182,7 +179,7 @@ class ContentLossGradEngine(VggEngineBase):
                 cur, ch = out, co
             elif isinstance(m, nn.MaxPool2d):
                 out = torch.empty(2 * N, h // 2, w // 2, ch, dtype=dt, device=dev)
-                fw.append(("pool", (A.view(cur), A.view(out), h, w, ch)))
+                fw.append(ops.Item("pool", (A.view(cur), A.view(out), h, w, ch)))
                 chain.append(("pool", idx, cur, out, h, w, ch, ch))
                 cur, h, w = out, h // 2, w // 2
             sp.keep.append(cur)
@@ -201,22 +198,22 @@ class ContentLossGradEngine(VggEngineBase):
             if kind == "conv":
                 if idx == 0:
                     if sp.thin:
-                        bw.append(("thin", ops.ThinLaunch("thin_out", ops.thin_args(dtc, N, hh, ww, 3, fptr + 4 * self.fp.off("features.0.weight"), A.view(g),
-                                                                                    w_big_is_cout=True, flip=True, thin_out=sp.dxp, thin_out_pitch=4))))
+                        bw.append(ops.ThinLaunch("thin_out", ops.thin_args(dtc, N, hh, ww, 3, fptr + 4 * self.fp.off("features.0.weight"), A.view(g),
+                                                                           w_big_is_cout=True, flip=True, thin_out=sp.dxp, thin_out_pitch=4)))
                     else:
-                        bw.append(("conv", ops.conv_args(dtc, A.view(g), A.view(sp.dxp), wptr + O[("b", 0)], N, hh, ww, cout, 32, cout_store=3, y_f32=True)))
+                        bw.append(ops.Conv(ops.conv_args(dtc, A.view(g), A.view(sp.dxp), wptr + O[("b", 0)], N, hh, ww, cout, 32, cout_store=3, y_f32=True)))
                     break
                 prev_kind = chain[j - 1][0]
                 gin = torch.empty(N, hh, ww, cin, dtype=dt, device=dev)
                 sp.keep.append(gin)
                 # the conv's input is a ReLU output (mask it here) or a pooled map (the pool's backward applies the ReLU')
                 mask = half(tin) if prev_kind == "conv" else A.NULL_VIEW
-                bw.append(("conv", ops.conv_args(dtc, A.view(g), A.view(gin), wptr + O[("b", idx)], N, hh, ww, cout, cin, mask=mask, mask_slope=0.0)))
+                bw.append(ops.Conv(ops.conv_args(dtc, A.view(g), A.view(gin), wptr + O[("b", idx)], N, hh, ww, cout, cin, mask=mask, mask_slope=0.0)))
                 g = gin
             else:
                 gin = torch.empty(N, hh, ww, cin, dtype=dt, device=dev)
                 sp.keep.append(gin)
-                bw.append(("poolbwd", (half(tin), A.view(g), A.view(gin), hh, ww, cin)))
+                bw.append(ops.Item("poolbwd", (half(tin), A.view(g), A.view(gin), hh, ww, cin)))
                 g = gin
         sp.bw = bw
         self.shapes[key] = sp
@@ -234,11 +231,14 @@ class ContentLossGradEngine(VggEngineBase):
         L, st = A.lib(), A.stream_ptr()
         self._load_input(sp, sr, gt, dtc, L, st)
         rec = profiling.REC
-        for kind, item in sp.fw:
-            if kind != "pool":
-                _launch(kind, item, rec, "conv2d(vgg)", L, st)
-            else:
-                xv, yv, h, w, c = item
+        for item in sp.fw:
+            kind = item.kind
+            if kind == "conv":
+                ops.conv2d(item.args, rec, "conv2d(vgg)", L, st)
+            elif kind == "thin":
+                item.launch(rec, L, st)
+            else:                                   # "pool"
+                xv, yv, h, w, c = item.payload
                 A.check(L.srganfd_resample(3, xv, yv, dtc, 2 * N, h, w, c, st), "maxpool")
         loss = torch.zeros(1, dtype=torch.float32, device=dev)
         h, w, c = sp.feat_dims
@@ -262,11 +262,14 @@ class ContentLossGradEngine(VggEngineBase):
         A.check(L.srganfd_l1_grad_views(sp.loss_views[0], sp.loss_views[1], A.view(sp.g_tap), dtc, N * h * w, c, upstream_ptr,
                                         weight / float(N * h * w * c), st), "l1_grad_views")
         rec = profiling.REC
-        for kind, item in sp.bw:
-            if kind != "poolbwd":
-                _launch(kind, item, rec, "conv2d(vgg dgrad)", L, st)
-            else:
-                xv, dyv, dxv, hh, ww, cc = item
+        for item in sp.bw:
+            kind = item.kind
+            if kind == "conv":
+                ops.conv2d(item.args, rec, "conv2d(vgg dgrad)", L, st)
+            elif kind == "thin":
+                item.launch(rec, L, st)
+            else:                                   # "poolbwd"
+                xv, dyv, dxv, hh, ww, cc = item.payload
                 A.check(L.srganfd_maxpool2_relu_bwd(xv, dyv, dxv, dtc, N, hh, ww, cc, st), "maxpool2_relu_bwd")
         dsr = torch.empty(N, 3, sp.H, sp.W, dtype=torch.float32, device=sp.device)
         A.check(L.srganfd_nhwc_to_nchw_scaled(A.view(sp.dxp), N, 3, sp.H, sp.W, dsr.data_ptr(), self.owner.std.data_ptr(), st), "nhwc_to_nchw_scaled")

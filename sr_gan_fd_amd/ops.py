@@ -144,14 +144,15 @@ def class4_ok(dtype: int, n_out: int, offsets: Sequence[int], pack_bytes: int, k
 
 
 def parity_class_launches(dtc: int, x: A.View, y: A.View, wptr: int, offs4: Sequence[int], n: int, h: int, w: int, kdim: int, ndim: int,
-                          ksize: int, class_pad: int, valid: bool = False, **epilogue) -> List[A.ConvArgs]:
+                          ksize: int, class_pad: int, valid: bool = False, tag: str = "", **epilogue) -> List["Conv"]:
     """A strided conv's data gradient, or a nearest-x2 conv's forward, as its four output-parity classes: stride-1 ``ksize``-tap
     convs over the (h, w) input ``x``, class (py, px) writing the pixels (2i + py, 2j + px) of ``y``.  ``offs4``: byte offsets of the
     four packed operands behind ``wptr``.  ``class_pad`` 1: class (py, px) reads the window one row / column earlier where py / px is
     0 (3x3 and 4x4 pad-1 kernels); 0: every class reads the same window (2x2 stride-2 kernels).  ``valid``: the strided conv had no
     padding (4x4 stride 2 over an even size) -- each class then has one more row and column of outputs, takes the tap pairs of the
     opposite parity and one row / column of zero padding on the low side.  ONE launch when the library takes the four classes
-    together (class4_ok), else one per class.  ``epilogue``: conv_args' bias / act / slope / r1 / r2 / mask keywords."""
+    together (class4_ok), else one per class.  ``tag``: the layer form profiling.conv_label adds to the kernel's name; ``epilogue``:
+    conv_args' bias / act / slope / r1 / r2 / mask keywords.  Returns the launches' items."""
     one = not valid and class4_ok(dtc, ndim, offs4, packed_bytes(dtc, ksize, kdim, ndim), ksize)
     ext = 1 if valid else 0
     out = []
@@ -163,7 +164,8 @@ def parity_class_launches(dtc: int, x: A.View, y: A.View, wptr: int, offs4: Sequ
         a.out_h_full, a.out_w_full = 2 * (h + ext), 2 * (w + ext)
         a.pad_y, a.pad_x = (1, 1) if valid else (class_pad * (1 - py), class_pad * (1 - px))
         a.out_classes, a.class_pad_step = (4, class_pad) if one else (0, 0)     # one launch: the classes' workgroups share each input patch through L2
-        out.append(a)
+        a._label_tag = tag
+        out.append(Conv(a))
     return out
 
 
@@ -190,6 +192,49 @@ def conv2d(args: A.ConvArgs, rec=None, what: str = "conv2d", L=None, st=None) ->
             A.check(rc, what)
     else:
         rec.bracket(profiling.conv_label(args), profiling.conv_work(args), lambda: A.check(L.srganfd_conv2d(C.byref(args), st), what))
+
+
+# ---- launch items: what the engines' per-shape launch lists (sp.fw / sp.bw) hold.  The loops dispatch on ``item.kind``: "conv" (Conv),
+# "thin" (ThinLaunch), "chain" (DenseChain), "call" (Call), "wgrad" (Wgrad) and, as Item(kind, payload), the markers of the generator's
+# backward list ("ready", "fence") and the kinds only one engine launches ("bn", "bn_bwd", "pool", "poolbwd").  An item holds structs and
+# addresses, never a closure: what the addresses point to is kept alive by the plan's buffers.
+class Item:
+    __slots__ = ("kind", "payload")
+
+    def __init__(self, kind: str, payload=None):
+        self.kind, self.payload = kind, payload
+
+
+class Conv:
+    """one fused-conv launch: ``conv2d(item.args, rec, what, L, st)``"""
+    __slots__ = ("args",)
+    kind = "conv"
+
+    def __init__(self, args: A.ConvArgs):
+        self.args = args
+
+
+class Call:
+    """an auxiliary kernel: the C entry point's name, its arguments without the trailing stream, and what A.check reports"""
+    __slots__ = ("name", "args", "what")
+    kind = "call"
+
+    def __init__(self, name: str, args: tuple, what: str):
+        self.name, self.args, self.what = name, args, what
+
+    def launch(self, rec, L, st) -> None:          # (never bracketed: ``rec`` is there for the signature ThinLaunch and DenseChain have)
+        A.check(getattr(L, self.name)(*self.args, st), self.what)
+
+
+class Wgrad:
+    """one weight-gradient launch of ``plan`` over the views x / dy.  ``dw_off``: elements added to the flat gradient's base (the
+    generator's dense-block plans hold offsets relative to their block); ``sn``: the spectral-norm slot of a discriminator layer, whose
+    gradient goes to the scratch buffer first, or None; ``block``: the generator's dense-block index (batched slab reduction), or None"""
+    __slots__ = ("plan", "x", "dy", "dw_off", "sn", "block")
+    kind = "wgrad"
+
+    def __init__(self, plan: "WgradPlan", x: A.View, dy: A.View, dw_off: int = 0, sn: Optional[int] = None, block: Optional[int] = None):
+        self.plan, self.x, self.dy, self.dw_off, self.sn, self.block = plan, x, dy, dw_off, sn, block
 
 
 # ---- LDS-resident dense-block launch (csrc/dense_chain.hip): the five convs of a dense block, or of its data-gradient pass, as one launch ----
@@ -230,6 +275,7 @@ def dense_chain_wanted(n: int, h: int, w: int, cus: int = 256) -> bool:
 class DenseChain:
     """n conv launches (A.ConvArgs, the arguments srganfd_conv2d would get) run by srganfd_dense_chain; ``ok`` False when the library
     refuses them (then the caller keeps the separate launches)."""
+    kind = "chain"
 
     def __init__(self, layers: Sequence[A.ConvArgs], device):
         self.n = len(layers)
@@ -246,14 +292,16 @@ class DenseChain:
         self.label = "dense_chain_kernel<%s,%d layers%s>" % (A.DT_NAME[layers[0].dtype], self.n, ",mask" if layers[0].mask.ptr else "")
         self.work = (self.flops, self.bytes)
 
-    def run(self) -> None:
-        A.check(A.lib().srganfd_dense_chain(self.arr, self.n, self.ws.data_ptr(), self.ws.numel(), A.stream_ptr()), "dense_chain")
+    def run(self, L=None, st=None) -> None:
+        if L is None:
+            L, st = A.lib(), A.stream_ptr()
+        A.check(L.srganfd_dense_chain(self.arr, self.n, self.ws.data_ptr(), self.ws.numel(), st), "dense_chain")
 
-    def launch(self, rec=None) -> None:
+    def launch(self, rec, L, st) -> None:
         if rec is None:
-            self.run()
+            self.run(L, st)
         else:
-            rec.bracket(self.label, self.work, self.run)
+            rec.bracket(self.label, self.work, lambda: self.run(L, st))
 
     def errors(self) -> int:
         """hand-off waits that gave up since the workspace was allocated (synchronises; tests)"""
@@ -261,13 +309,13 @@ class DenseChain:
 
 
 def dense_chain_or_launches(layers: Sequence[A.ConvArgs], device) -> list:
-    """[DenseChain] when the batch is in the chain's regime and the library accepts the launches, else the launches themselves"""
+    """a dense block's items: [DenseChain] when the batch is in the chain's regime and the library accepts the launches, else a Conv each"""
     a = layers[0]
     if a.dtype in (A.F16, A.BF16) and dense_chain_wanted(a.n, a.h_in, a.w_in):
         ch = DenseChain(layers, device)
         if ch.ok:
             return [ch]
-    return list(layers)
+    return [Conv(a) for a in layers]
 
 
 # ---- thin-side convolutions (csrc/conv_thin.hip): 1..4 channels against 64, 3x3 stride 1 pad 1, 16-bit dtypes ----
@@ -321,67 +369,63 @@ def thin_wgrad(a: A.ThinArgs, dw, db, workspace: torch.Tensor) -> None:
 
 
 class ThinLaunch:
-    """One thin-side launch in an engine's launch list.  kind: "thin_in" / "thin_out" / "thin_wgrad" (the latter writes the weight and
+    """One thin-side launch in an engine's launch list.  op: "thin_in" / "thin_out" / "thin_wgrad" (the latter writes the weight and
     bias gradient at element offsets ``dw_off`` / ``db_off`` of the flat gradient whose address ``launch`` is given)."""
+    kind = "thin"
 
-    def __init__(self, kind: str, args: A.ThinArgs, dw_off: int = -1, db_off: int = -1, ws: Optional[torch.Tensor] = None, keep=()):
-        self.kind, self.args, self.dw_off, self.db_off, self.ws = kind, args, dw_off, db_off, ws
-        self.keep = keep                  # tensors whose addresses the struct holds
-        self.is_wgrad = kind == "thin_wgrad"
-        self.label = "%s_kernel<%s%s>" % (kind, A.DT_NAME[args.dtype], ",mask" if args.mask.ptr else "")
-        self.work = thin_work(args, kind)
+    def __init__(self, op: str, args: A.ThinArgs, dw_off: int = -1, db_off: int = -1, ws: Optional[torch.Tensor] = None):
+        self.op, self.args, self.dw_off, self.db_off, self.ws = op, args, dw_off, db_off, ws
+        self.is_wgrad = op == "thin_wgrad"
+        self.label = "%s_kernel<%s%s>" % (op, A.DT_NAME[args.dtype], ",mask" if args.mask.ptr else "")
+        self.work = thin_work(args, op)
 
-    def run(self, grad_ptr: int = 0) -> None:
-        L, st, a = A.lib(), A.stream_ptr(), self.args
-        if self.kind == "thin_in":
+    def launch(self, rec, L, st, grad_ptr: int = 0) -> None:
+        if rec is not None:
+            return rec.bracket(self.label, self.work, lambda: self.launch(None, L, st, grad_ptr))
+        a = self.args
+        if self.op == "thin_in":
             rc = L.srganfd_conv2d_thin_in(C.byref(a), st)
-        elif self.kind == "thin_out":
+        elif self.op == "thin_out":
             rc = L.srganfd_conv2d_thin_out(C.byref(a), st)
         else:
             rc = L.srganfd_conv2d_thin_wgrad(C.byref(a), grad_ptr + 4 * self.dw_off, (grad_ptr + 4 * self.db_off) if self.db_off >= 0 else None,
                                              self.ws.data_ptr(), self.ws.numel() * self.ws.element_size(), st)
         if rc:
-            A.check(rc, self.kind)
-
-    def launch(self, rec=None, grad_ptr: int = 0) -> None:
-        if rec is None:
-            self.run(grad_ptr)
-        else:
-            rec.bracket(self.label, self.work, lambda: self.run(grad_ptr))
+            A.check(rc, self.op)
 
 
 # ---- image-side layers: a 3x3 conv between an image-like tensor (``cs`` = 1..4 real channels) and ``big_ch`` feature channels.  In the
 # 16-bit modes with 64 feature channels (thin_ok) the image side is NHWC with a 4-channel pitch and the thin kernels read the layer's
 # raw fp32 ``weight`` (an address in the flat parameters); otherwise it is padded to 32 channels for conv2d and the packed operand.
 # ``w_big_is_cout``: the weight's output channels are the feature side (a network's first layer; False: its last).  Each returns one
-# launch item: ("thin", ThinLaunch) or ("conv", ConvArgs) / ("wgrad", plan, x view, dy view) + extra.
+# launch item: a ThinLaunch, or a Conv / Wgrad.
 def image_to_features(dtc: int, thin: bool, image: torch.Tensor, big: A.View, weight: int, w_packed: int, n: int, h: int, w: int, cs: int,
-                      big_ch: int, w_big_is_cout: bool, flip: bool = False, **epilogue) -> tuple:
+                      big_ch: int, w_big_is_cout: bool, flip: bool = False, **epilogue):
     """a first layer's forward, or (flip) a last layer's data gradient; epilogue: bias / act / slope / mask / mask_slope"""
     if thin:
-        return ("thin", ThinLaunch("thin_in", thin_args(dtc, n, h, w, cs, weight, big, w_big_is_cout=w_big_is_cout, flip=flip, thin=image, **epilogue)))
-    return ("conv", conv_args(dtc, A.view(image), big, w_packed, n, h, w, image.shape[-1], big_ch, **epilogue))
+        return ThinLaunch("thin_in", thin_args(dtc, n, h, w, cs, weight, big, w_big_is_cout=w_big_is_cout, flip=flip, thin=image, **epilogue))
+    return Conv(conv_args(dtc, A.view(image), big, w_packed, n, h, w, image.shape[-1], big_ch, **epilogue))
 
 
 def features_to_image(dtc: int, thin: bool, big: A.View, out, out_pitch: int, weight: int, w_packed: int, n: int, h: int, w: int, cs: int,
-                      big_ch: int, w_big_is_cout: bool, flip: bool = False, bias=None) -> tuple:
+                      big_ch: int, w_big_is_cout: bool, flip: bool = False, bias=None):
     """a last layer's forward, or (flip) a first layer's data gradient, written as fp32 at ``out`` (tensor or address) with a pitch of
     ``out_pitch`` channels"""
     if thin:
-        return ("thin", ThinLaunch("thin_out", thin_args(dtc, n, h, w, cs, weight, big, w_big_is_cout=w_big_is_cout, flip=flip, bias=bias,
-                                                         thin_out=out, thin_out_pitch=out_pitch)))
-    return ("conv", conv_args(dtc, big, A.View(_ptr(out), out_pitch, 0), w_packed, n, h, w, big_ch, 32, cout_store=cs, bias=bias, y_f32=True))
+        return ThinLaunch("thin_out", thin_args(dtc, n, h, w, cs, weight, big, w_big_is_cout=w_big_is_cout, flip=flip, bias=bias,
+                                                thin_out=out, thin_out_pitch=out_pitch))
+    return Conv(conv_args(dtc, big, A.View(_ptr(out), out_pitch, 0), w_packed, n, h, w, big_ch, 32, cout_store=cs, bias=bias, y_f32=True))
 
 
 def image_wgrad(dtc: int, thin: bool, wplans: "WgradPlans", image: torch.Tensor, big: torch.Tensor, weight: int, dw_off: int, db_off: int,
-                thin_ws: Optional[torch.Tensor], n: int, h: int, w: int, cs: int, big_ch: int, w_big_is_cout: bool, extra: tuple = ()) -> tuple:
-    """weight and bias gradient of either layer, at elements dw_off / db_off of the flat gradient"""
+                thin_ws: Optional[torch.Tensor], n: int, h: int, w: int, cs: int, big_ch: int, w_big_is_cout: bool):
+    """weight and bias gradient of either layer, at elements dw_off / db_off of the flat gradient (held by the plan: the item adds nothing)"""
     if thin:
-        return ("thin", ThinLaunch("thin_wgrad", thin_args(dtc, n, h, w, cs, weight, A.view(big), w_big_is_cout=w_big_is_cout, thin=image),
-                                   dw_off=dw_off, db_off=db_off, ws=thin_ws))
+        return ThinLaunch("thin_wgrad", thin_args(dtc, n, h, w, cs, weight, A.view(big), w_big_is_cout=w_big_is_cout, thin=image),
+                          dw_off=dw_off, db_off=db_off, ws=thin_ws)
     if w_big_is_cout:
-        return ("wgrad", wplans.conv(h, w, image.shape[-1], big_ch, dw_off, db_off, cin_real=cs), A.view(image), A.view(big)) + extra
-    return ("wgrad", wplans.conv(h, w, big_ch, 32, dw_off, db_off, cout_real=cs), A.view(big), A.view(image)) + extra
+        return Wgrad(wplans.conv(h, w, image.shape[-1], big_ch, dw_off, db_off, cin_real=cs), A.view(image), A.view(big), dw_off=0, sn=None)
+    return Wgrad(wplans.conv(h, w, big_ch, 32, dw_off, db_off, cout_real=cs), A.view(big), A.view(image), dw_off=0, sn=None)
 
 
 class WgradPlan:

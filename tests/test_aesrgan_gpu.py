@@ -339,7 +339,7 @@ def test_aesrgan_iteration_at_the_config_crop_f16_vs_oracle():
     tr = GanTrainer(gen, d, None, g_lr=5e-5, d_lr=1e-5, pixel_weight=10.0, adversarial_weight=0.1)
     s = tr.step(lr_img.cuda(), gt.cuda()).cpu().numpy()
     sp = tr.ge._last
-    n_chain = len([a for a in sp.fw if type(a) is ops.DenseChain]) + len([it for it in sp.bw if it[0] == "chain"])
+    n_chain = len([it for it in sp.fw + sp.bw if it.kind == "chain"])
     assert n_chain == 6 * 23 or ops.DENSE_CHAIN == "0", n_chain
     got = [s[0] + s[1], s[2], s[3], s[4], s[5]]
     want = [out[k] for k in ("d_loss", "pixel_loss", "adversarial_loss", "d_gt_probability", "d_sr_probability")]

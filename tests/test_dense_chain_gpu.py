@@ -170,7 +170,7 @@ def test_generator_iteration_at_the_reference_crops_through_the_launch_meets_the
             loss = tr.step(lr_img.cuda(), gt.cuda())
             torch.cuda.synchronize()
             sp = tr.eng._last
-            chains = [a for a in sp.fw if type(a) is ops.DenseChain] + [it[1] for it in sp.bw if it[0] == "chain"]
+            chains = [it for it in sp.fw + sp.bw if it.kind == "chain"]
             assert len(chains) == (6 * num_rrdb if mode == "auto" else 0), (mode, len(chains))
             if mode == "auto":
                 assert ops.dense_chain_giveups(torch.device("cuda", torch.cuda.current_device())) == 0

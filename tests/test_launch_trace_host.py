@@ -20,6 +20,13 @@ The fixture is regenerated (``python tests/golden/make_golden_launch_trace.py``)
 launched -- a new kernel, another packing, a reordered schedule.  The difference in the fixture is then part of that change and
 is to be reviewed like the code (decompress both versions and diff them: one call per line); a refactoring of the host code
 leaves the fixture alone and this test passing.
+
+The profiled path: with ``profiling.REC`` set, every conv, thin, dense-chain and weight-gradient launch goes through
+``rec.bracket(label, work, fn)`` instead, and bench.py builds its ``kernel_classes`` and ``roofline`` fields from those labels and
+work figures.  Each scenario runs a second time under a recorder stub that notes ``(label, flop, bytes)`` and calls ``fn``: the
+trace must be the same one (but for the ``srganfd_conv2d_describe`` calls that ask the library for the labels) and the brackets,
+in order, must equal tests/golden/launch_labels.json.gz (``python tests/golden/make_golden_launch_labels.py``, regenerated under
+the same rule as the trace).
 """
 import ctypes as C
 import gzip
@@ -32,6 +39,7 @@ import pytest
 import torch
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_trace.json.gz")
+LABELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_labels.json.gz")
 NODES = ["features.2", "features.7", "features.16", "features.25", "features.34"]
 MEAN, STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
 DTYPES = {"f32": torch.float32, "f16": torch.float16}
@@ -209,20 +217,40 @@ SCENARIOS = {
 CASES = ["%s-%s" % (s, d) for s in SCENARIOS for d in DTYPES]
 
 
-def record(case):
-    """run one scenario under the recorder: {"launches": [...], "queries": [...], "tables": [...]}"""
-    from sr_gan_fd_amd import _abi as A, ops
+class Brackets:
+    """stands in for profiling.Recorder: notes the label and the algorithmic work of every bracketed launch, then makes it"""
+
+    def __init__(self):
+        self.items = []
+
+    def bracket(self, label, work, fn):
+        flops, nbytes = work if isinstance(work, tuple) else (work, 0.0)
+        self.items.append([label, round(float(flops), 9), round(float(nbytes), 9)])
+        fn()
+
+
+def record(case, profiled=False):
+    """run one scenario under the recorder: {"launches": [...], "queries": [...], "tables": [...]}; ``profiled``: with
+    profiling.REC set -- the label queries are left out of the launches, and "brackets" holds [label, flop, bytes] per bracket"""
+    from sr_gan_fd_amd import _abi as A, ops, profiling
     name, dt = case.rsplit("-", 1)
     A.set_dry_run(True)
     rec = Recorder(A.lib())
     ops._DC_WS.clear()                 # the process-wide dense-chain workspace: its size query belongs to the scenario that plans the first chain
     A._lib = rec
+    assert profiling.REC is None
+    if profiled:
+        profiling.REC = Brackets()
     try:
         torch.manual_seed(0)
         keep = SCENARIOS[name](DTYPES[dt])
         out = {"launches": rec.launches, "queries": rec.queries, "tables": rec.tables()}
+        if profiled:
+            out["launches"] = [c for c in rec.launches if c[0] != "srganfd_conv2d_describe"]
+            out["brackets"] = profiling.REC.items
         del keep
     finally:
+        profiling.REC = None
         A._lib = rec._lib
         ops._DC_WS.clear()
         A.set_dry_run(False)
@@ -274,3 +302,26 @@ def test_fixture_covers_every_case(recorded):
 def test_launch_trace_matches_the_recorded_one(case, recorded):
     msg = compare(case, recorded[case], record(case))
     assert msg is None, msg
+
+
+@pytest.fixture(scope="module")
+def recorded_labels():
+    with gzip.open(LABELS, "rt") as f:
+        return json.load(f)
+
+
+def test_label_fixture_covers_every_case(recorded_labels):
+    assert sorted(recorded_labels) == sorted(CASES)
+    assert sum(len(b) for b in recorded_labels.values()) > 3000
+    assert os.path.getsize(LABELS) < 1 << 18
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_profiled_path_launches_the_same_under_the_recorded_labels(case, recorded, recorded_labels):
+    got = record(case, profiled=True)
+    msg = compare(case, recorded[case], got)
+    assert msg is None, "with profiling.REC set, " + msg
+    want, have = recorded_labels[case], got["brackets"]
+    for i, (a, b) in enumerate(zip(want, have)):
+        assert a == b, "%s: bracket %d was %s, is now %s" % (case, i, a, b)
+    assert len(want) == len(have), "%s: %d brackets recorded, %d now" % (case, len(want), len(have))

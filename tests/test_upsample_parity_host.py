@@ -8,11 +8,6 @@ import pytest
 import torch
 
 
-def _fn_names(fn):
-    """global / attribute names a launch-list callable refers to (the ("call", fn) items are lambdas over the C ABI)"""
-    return set(fn.__code__.co_names)
-
-
 def _plan(fac, kw, dt, parity, x_shape):
     from sr_gan_fd_amd import engine as E, model as M
     old = os.environ.get("SRGANFD_UPSAMPLE_PARITY")
@@ -37,13 +32,11 @@ def _plan(fac, kw, dt, parity, x_shape):
 def _summary(eng, sp):
     """shape signature of the plan: (ksize, stride, pad, up, h_in, w_in, h_out, w_out, cin, cout, classes) per conv launch, and the C
     entry points of the backward's "call" items"""
-    from sr_gan_fd_amd import ops
-
     def sig(a):
         return (a.ksize, a.stride, a.pad, a.up, a.h_in, a.w_in, a.h_out, a.w_out, a.cin, a.cout, a.out_classes, bool(a.mask.ptr), bool(a.bias))
-    fw = [sig(a) for a in sp.fw if not isinstance(a, (ops.ThinLaunch, ops.DenseChain))]
-    bw = [sig(it[1]) for it in sp.bw if it[0] == "conv"]
-    calls = [n for it in sp.bw if it[0] == "call" for n in _fn_names(it[1]) if n.startswith("srganfd_")]
+    fw = [sig(it.args) for it in sp.fw if it.kind == "conv"]
+    bw = [sig(it.args) for it in sp.bw if it.kind == "conv"]
+    calls = [it.name for it in sp.bw if it.kind == "call"]
     return fw, bw, calls
 
 
@@ -70,7 +63,7 @@ def test_parity_plan_16bit(fac, kw, shape):
             h, w = sp.H, sp.W
             for u, s in enumerate(cls):
                 assert s[:2] == (2, 1) and (s[4], s[5], s[6], s[7]) == (h << u, w << u, h << u, w << u) and s[12]
-            ups = [a for a in sp.fw if getattr(a, "out_classes", 0) == 4]
+            ups = [it.args for it in sp.fw if it.kind == "conv" and it.args.out_classes == 4]
             for u, a in enumerate(ups):
                 assert (a.out_h_full, a.out_w_full, a.pad_y, a.pad_x, a.class_pad_step, a.act) == (sp.H << (u + 1), sp.W << (u + 1), 1, 1, 1, A.ACT_LRELU)
             # backward: one 4x4 stride-2 pad-1 launch per layer, high-res gradient in, low-res out; the mask only where the layer's input
