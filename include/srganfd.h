@@ -369,7 +369,12 @@ int srganfd_sigmoid_bwd(const float* ds, const float* s, float* out, int64_t num
 int srganfd_gate_mul(int32_t bwd, srganfd_view x, const float* gate, srganfd_view y, srganfd_view dx, float* dgate,
                      int32_t dtype, int64_t npix, int32_t c, void* stream);
 /* nn.BatchNorm2d (model.py:233).  save: 4*c floats [mean | invstd | scale | shift]; workspace: 2048*c + 3*c floats.
- * training=1: batch statistics, running stats updated with `momentum` (unbiased variance); 0: running stats. */
+ * training=1: batch statistics, running stats updated with `momentum` (unbiased variance); 0: running stats.
+ * Refused with SRGANFD_EINVAL before anything is launched or written (all forward and backward forms below alike):
+ *   - c that is no multiple of one 16-byte chunk (4 fp32 / 8 16-bit channels), or a view whose ptr, c0 or cstride is not 16-byte aligned;
+ *   - a channel block (256 channels, the last one c % 256) that is not a power-of-two number of chunks: c = 268 in fp32 (12 channels,
+ *     3 chunks), c = 280 in a 16-bit type (24 channels, 3 chunks);
+ *   - training=1 with npix < 2 (phase 2 of the two-phase form: total_npix < 2): the unbiased variance needs two values per channel. */
 int srganfd_batchnorm_fwd(srganfd_view x, srganfd_view y, int32_t dtype, int64_t npix, int32_t c, const float* gamma,
                           const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                           int32_t training, float* save, float* workspace, void* stream);

@@ -347,6 +347,14 @@ extern "C" int srganfd_spectral_norm_grad(const float* G, const float* W, const 
 static constexpr int kBnBlocks = 1024;  // workspace: kBnBlocks * 2 * c floats (+ 3c for the backward coefficients)
 extern "C" int64_t srganfd_batchnorm_partial_floats(int32_t c) { return (long long)kBnBlocks * 2 * c; }
 static inline bool bn_chunks_ok(int dtype, int c) { const int cv = c / (dtype == SRGANFD_F32 ? 4 : 8); return cv > 0 && 256 % cv == 0; }
+// every channel block of <= 256, checked before the first launch: a refused call has written nothing.  Returns the bad block's size or 0.
+static inline int bn_bad_block(int dtype, int c) {
+  for (int cb = 0; cb < c; cb += 256) {
+    const int cc = c - cb < 256 ? c - cb : 256;
+    if (!bn_chunks_ok(dtype, cc)) return cc;
+  }
+  return 0;
+}
 static inline unsigned bn_grid(size_t npix, int dtype, int c) { const int lanes = 256 / (c / (dtype == SRGANFD_F32 ? 4 : 8)); return grid_for((npix + lanes - 1) / lanes, 1, 16384); }
 // Channels are processed in blocks of <= 256 (the statistics kernels map one thread to one channel); `save` is
 // [block][mean | invstd | scale | shift] and is only read back by batchnorm_bwd_impl with the same blocking.
@@ -359,10 +367,13 @@ static int batchnorm_fwd_impl(srganfd_view x, srganfd_view y, int dtype, size_t 
   if (!x.ptr || !y.ptr || !gamma || !beta || !rm || !rv || !save || !ws || c <= 0 || !vec_ok(dtype, c, {x, y}))
     return set_err(SRGANFD_EINVAL, "batchnorm_fwd: bad args (16-byte aligned views)");
   if (phase && (c > 256 || !training)) return set_err(SRGANFD_EINVAL, "batchnorm_fwd: the two-phase form takes training mode and at most 256 channels");
+  if (const int bad = bn_bad_block(dtype, c)) return set_err(SRGANFD_EINVAL, "batchnorm_fwd: channel block of %d is not a power-of-two number of 16-byte chunks", bad);
+  // the unbiased running variance is var * n / (n - 1): one value per channel has none (torch refuses it as well)
+  if (training && phase != 1 && (phase == 2 ? total_npix : npix) < 2)
+    return set_err(SRGANFD_EINVAL, "batchnorm_fwd: training mode needs more than one value per channel (npix = %lld)", (long long)(phase == 2 ? total_npix : npix));
   const float count = (float)(phase == 2 ? total_npix : npix);
   for (int cb = 0; cb < c; cb += 256) {
     const int cc = c - cb < 256 ? c - cb : 256;
-    if (!bn_chunks_ok(dtype, cc)) return set_err(SRGANFD_EINVAL, "batchnorm_fwd: channel block of %d is not a power-of-two number of 16-byte chunks", cc);
     const srganfd_view xs = sub_view(x, cb), ys = sub_view(y, cb);
     float* sv = save + 4 * cb;
     if (training && phase != 2) {
@@ -386,10 +397,10 @@ static int batchnorm_bwd_impl(srganfd_view x, srganfd_view dy, srganfd_view dx, 
     return set_err(SRGANFD_EINVAL, "batchnorm_bwd: bad args");
   if (phase && c > 256) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: the two-phase form takes at most 256 channels");
   if (phase == 2 && !ws_global) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: phase 2 needs the all-reduced table");
+  if (const int bad = bn_bad_block(dtype, c)) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: channel block of %d is not a power-of-two number of 16-byte chunks", bad);
   const float count = (float)(phase == 2 ? total_npix : npix);
   for (int cb = 0; cb < c; cb += 256) {
     const int cc = c - cb < 256 ? c - cb : 256;
-    if (!bn_chunks_ok(dtype, cc)) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: channel block of %d is not a power-of-two number of 16-byte chunks", cc);
     const srganfd_view xs = sub_view(x, cb), dys = sub_view(dy, cb), dxs = sub_view(dx, cb), as = sub_view(act, cb);
     const float* sv = save + 4 * cb;
     float* coef = ws + (size_t)kBnBlocks * 2 * cc;
