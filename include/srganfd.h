@@ -49,7 +49,8 @@ typedef struct {
   int32_t planar;  /* 0: NHWC, a pixel's cstride channels are contiguous.  1: per image, every group of 32 channels is its own
                       (H, W, 32) plane -- element (p, c) of an image at (c / 32) * H*W*32 + p * 32 + c % 32 (same bytes per image).
                       Only srganfd_conv2d and srganfd_conv2d_wgrad take planar views (the dense-block buffers: each 32-channel
-                      chunk pass then reads whole contiguous 128-byte lines); c0 must be a multiple of 32. */
+                      chunk pass then reads whole contiguous 128-byte lines); c0 must be a multiple of 32.  Every other entry
+                      point that takes a view refuses a planar one (SRGANFD_EINVAL). */
   int32_t pad_;
 } srganfd_view;
 
@@ -223,7 +224,7 @@ int srganfd_wgrad_reduce_batch(const srganfd_wgrad_reduce_job* jobs, int32_t njo
 int srganfd_nchw_to_nhwc(const float* src, int32_t n, int32_t c, int32_t h, int32_t w, srganfd_view dst,
                          int32_t dtype, int32_t cpad, const float* ch_mean, const float* ch_std, void* stream);
 /* (ch_mean, ch_std: optional per-channel (x - mean) / std of ContentLoss.normalize, model.py:542-543) */
-/* NHWC view (dtype) -> NCHW fp32; clamp01 = torch.clamp_(out, 0, 1) of model.py:379 */
+/* NHWC view (dtype) -> NCHW fp32; clamp01 = torch.clamp_(out, 0, 1) of model.py:379 (a NaN stays a NaN, as there) */
 int srganfd_nhwc_to_nchw(srganfd_view src, int32_t dtype, int32_t n, int32_t c, int32_t h, int32_t w,
                          float* dst, int32_t clamp01, void* stream);
 /* backward of that clamp + relayout: dst[p][c] = (0 <= pre[p][c] <= 1) ? dsr[n][c][p] : 0 ; pre is fp32 NHWC */
@@ -233,7 +234,7 @@ int srganfd_clamp_grad_to_nhwc(const float* dsr_nchw, srganfd_view pre_f32, int3
 /* resampling: op 0 = backward of nearest x2 (model.py:372,374), 1 = bilinear x2 forward
  * (align_corners=False, model.py:150,154,158), 2 = its backward, 3 = 2x2 max-pool (VGG-19).
  * 4 = ReLU copy.  (h, w) are the LOW-resolution dims for ops 0-2 and the input dims for ops 3-4;
- * a = source view, b = destination view. */
+ * a = source view, b = destination view; op 4 alone may run in place (b the same view as a). */
 int srganfd_resample(int32_t op, srganfd_view a, srganfd_view b, int32_t dtype, int32_t n, int32_t h,
                      int32_t w, int32_t c, void* stream);
 /* Backward of `lrelu(conv(bilinear_x2(u))) + skip` chains (the U-Net decoder, model.py:150-161) in one pass: dx_raw = adjoint of the

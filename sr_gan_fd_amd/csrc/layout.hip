@@ -57,7 +57,7 @@ __global__ void nhwc_to_nchw_kernel(const void* __restrict__ src, int sC, int s0
     const int ch = (int)(t % c);
     const size_t img = t / c;
     float v = ld<T>(src, (img * hw + pix) * sC + s0 + ch);
-    if (clamp01) v = fminf(fmaxf(v, 0.f), 1.0f);
+    if (clamp01) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);       // torch's clamp_: a NaN stays a NaN (fminf(fmaxf(v, 0), 1) made it 0), -0 stays -0
     dst[i] = v;
   }
 }
@@ -190,6 +190,7 @@ extern "C" int srganfd_nchw_to_nhwc(const float* src, int32_t n, int32_t c, int3
                                     const float* mean, const float* stdv, void* stream) {
   const hipStream_t s = (hipStream_t)stream;
   if (!src || !dst.ptr || n <= 0 || c <= 0 || cpad < c || dst.c0 + cpad > dst.cstride) return set_err(SRGANFD_EINVAL, "nchw_to_nhwc: bad args");
+  if (dst.planar) return set_err(SRGANFD_EINVAL, "nchw_to_nhwc: NHWC views only, not planar ones");
   const size_t total = (size_t)n * h * w * cpad;
   if (dtype != SRGANFD_F32 && c <= 4 && cpad == 4 && dst.cstride == 4 && dst.c0 == 0 && ((uintptr_t)dst.ptr & 7) == 0) {
     const size_t npix = (size_t)n * h * w;
@@ -215,6 +216,7 @@ extern "C" int srganfd_nchw_to_nhwc(const float* src, int32_t n, int32_t c, int3
 extern "C" int srganfd_nhwc_to_nchw(srganfd_view src, int32_t dtype, int32_t n, int32_t c, int32_t h, int32_t w, float* dst, int32_t clamp01, void* stream) {
   const hipStream_t s = (hipStream_t)stream;
   if (!src.ptr || !dst || src.c0 + c > src.cstride) return set_err(SRGANFD_EINVAL, "nhwc_to_nchw: bad args");
+  if (src.planar) return set_err(SRGANFD_EINVAL, "nhwc_to_nchw: NHWC views only, not planar ones");
   const size_t total = (size_t)n * h * w * c;
   DISPATCH_T(dtype,
              SRGANFD_LAUNCH(nhwc_to_nchw_kernel<TT>, dim3(grid_for(total)), dim3(256), 0, s, src.ptr, src.cstride, src.c0, dst, n, c, h * w, clamp01));
@@ -225,6 +227,7 @@ extern "C" int srganfd_clamp_grad_to_nhwc(const float* dsr, srganfd_view pre, in
                                           int32_t cpad, void* stream) {
   const hipStream_t s = (hipStream_t)stream;
   if (!dsr || !pre.ptr || !dst.ptr || dst.c0 + cpad > dst.cstride) return set_err(SRGANFD_EINVAL, "clamp_grad: bad args");
+  if (pre.planar || dst.planar) return set_err(SRGANFD_EINVAL, "clamp_grad: NHWC views only, not planar ones");
   const size_t total = (size_t)n * h * w * cpad;
   if (dtype != SRGANFD_F32 && c <= 4 && cpad == 4 && pre.cstride == 4 && pre.c0 == 0 && dst.cstride == 4 && dst.c0 == 0 &&
       ((uintptr_t)pre.ptr & 15) == 0 && ((uintptr_t)dst.ptr & 7) == 0) {
@@ -250,6 +253,7 @@ extern "C" int srganfd_clamp_grad_to_nhwc(const float* dsr, srganfd_view pre, in
 extern "C" int srganfd_nhwc_to_nchw_scaled(srganfd_view src, int32_t n, int32_t c, int32_t h, int32_t w, float* dst, const float* ch_div, void* stream) {
   const hipStream_t s = (hipStream_t)stream;
   if (!src.ptr || !dst || !ch_div || n <= 0 || c <= 0) return set_err(SRGANFD_EINVAL, "nhwc_to_nchw_scaled: bad args");
+  if (src.planar) return set_err(SRGANFD_EINVAL, "nhwc_to_nchw_scaled: NHWC views only, not planar ones");
   SRGANFD_LAUNCH(nhwc_to_nchw_scaled_kernel, dim3(grid_for((size_t)n * c * h * w)), dim3(256), 0, s, (const float*)src.ptr, src.cstride, src.c0, dst, n, c, h * w, ch_div);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;

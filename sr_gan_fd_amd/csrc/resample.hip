@@ -4,7 +4,8 @@
 
 namespace srganfd {
 
-// generic 2-D resampling on vectors: op 0 nearest-x2 backward, 1 bilinear-x2 forward, 2 bilinear-x2 backward, 3 maxpool2, 4 relu
+// generic 2-D resampling on vectors: op 0 nearest-x2 backward, 1 bilinear-x2 forward, 2 bilinear-x2 backward, 3 maxpool2 (op 4, the ReLU
+// copy, has relu_copy_vec_kernel below: it runs in place, which this kernel's __restrict__ input rules out)
 __device__ __forceinline__ void bil_taps(int d, int n, int& i0, int& i1, float& w0, float& w1);
 __device__ __forceinline__ int bil_bwd_taps(int k, int n, int* d, float* wt);
 
@@ -16,7 +17,8 @@ __global__ __launch_bounds__(256) void resample_vec_kernel(const void* __restric
                                                            int b20 = 0, float slope = 0.f) {
   constexpr int N = VecN<T>::N;
   const int cv = c / N;
-  // output extents: op0/2 -> (h, w) low-res ; op1 -> (2h, 2w) ; op3 -> (h/2, w/2) ; op4 -> (h, w)
+  static_assert(OP >= 0 && OP <= 3, "op 4 is relu_copy_vec_kernel");
+  // output extents: op0/2 -> (h, w) low-res ; op1 -> (2h, 2w) ; op3 -> (h/2, w/2)
   const int oh = OP == 1 ? 2 * h : (OP == 3 ? h / 2 : h), ow = OP == 1 ? 2 * w : (OP == 3 ? w / 2 : w);
   const size_t total = (size_t)n * oh * ow * cv;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -48,13 +50,13 @@ __global__ __launch_bounds__(256) void resample_vec_kernel(const void* __restric
       for (int q = 0; q < N; ++q) acc[q] = wya * wxa * t[q];
       ldv<T>(a, (r0 + xb) * aC + a0 + ch, t);
 #pragma unroll
-      for (int q = 0; q < N; ++q) acc[q] += wya * wxb * t[q];
+      for (int q = 0; q < N; ++q) acc[q] = fmaf(wya * wxb, t[q], acc[q]);
       ldv<T>(a, (r1 + xa) * aC + a0 + ch, t);
 #pragma unroll
-      for (int q = 0; q < N; ++q) acc[q] += wyb * wxa * t[q];
+      for (int q = 0; q < N; ++q) acc[q] = fmaf(wyb * wxa, t[q], acc[q]);
       ldv<T>(a, (r1 + xb) * aC + a0 + ch, t);
 #pragma unroll
-      for (int q = 0; q < N; ++q) acc[q] += wyb * wxb * t[q];
+      for (int q = 0; q < N; ++q) acc[q] = fmaf(wyb * wxb, t[q], acc[q]);
     } else if constexpr (OP == 2) {   // bilinear backward (gather form)
       int dys[6], dxs[6]; float wys[6], wxs[6];
       const int ny = bil_bwd_taps(oy, h, dys, wys), nx = bil_bwd_taps(ox, w, dxs, wxs);
@@ -65,9 +67,9 @@ __global__ __launch_bounds__(256) void resample_vec_kernel(const void* __restric
           ldv<T>(a, ((img * 2 * h + dys[ia]) * 2 * w + dxs[ib]) * aC + a0 + ch, t);
           const float ww = wys[ia] * wxs[ib];
 #pragma unroll
-          for (int q = 0; q < N; ++q) acc[q] += ww * t[q];
+          for (int q = 0; q < N; ++q) acc[q] = fmaf(ww, t[q], acc[q]);
         }
-    } else if constexpr (OP == 3) {   // 2x2 max pool
+    } else {                           // 2x2 max pool
       const size_t bq = (img * h + 2 * oy) * w + 2 * ox;
       ldv<T>(a, bq * aC + a0 + ch, acc);
       ldv<T>(a, (bq + 1) * aC + a0 + ch, t);
@@ -79,10 +81,6 @@ __global__ __launch_bounds__(256) void resample_vec_kernel(const void* __restric
       ldv<T>(a, (bq + w + 1) * aC + a0 + ch, t);
 #pragma unroll
       for (int q = 0; q < N; ++q) acc[q] = fmaxf(acc[q], t[q]);
-    } else {                           // relu copy
-      ldv<T>(a, ((img * h + oy) * w + ox) * aC + a0 + ch, acc);
-#pragma unroll
-      for (int q = 0; q < N; ++q) acc[q] = fmaxf(acc[q], 0.f);
     }
     if constexpr (OP == 2) {
       const size_t op_ = (img * oh + oy) * ow + ox;
@@ -102,7 +100,9 @@ __global__ __launch_bounds__(256) void resample_vec_kernel(const void* __restric
 // ---- bilinear x2 (align_corners=False, model.py:150-158), row-grid forms: blockIdx.y = group of kBilRows low-res rows, blockIdx.z = image, one thread per
 // (low-res column, 16-byte channel vector).  The generic kernel above spends its time on 64-bit div/mod chains and per-thread tap tables;
 // here the row taps are wave-uniform, the column taps closed-form, and every address is 32-bit arithmetic on top of one 64-bit row base.
-// Same products and the same accumulation order per output as resample_vec_kernel<T, 1 / 2>: results are bit-identical.
+// Same products and the same accumulation order per output as resample_vec_kernel<T, 1 / 2>, every step after the first an explicit fmaf
+// in both: results are bit-identical.  (Written as `acc += w * t` the compiler fused the steps of one form and, where it could share a
+// product between two outputs, not all of the other's: the fp32 forward results then differed in the last bit.)
 // Each thread walks kBilRows consecutive low-res rows with a sliding window of source rows in registers: the forward pass reads
 // (R + 2) x 3 vectors for 4R stores (2x2 high-res block per low-res pixel), the adjoint (2R + 2) x 4 for R.
 static constexpr int kBilRows = 4;
@@ -143,11 +143,11 @@ __global__ __launch_bounds__(256) void bilinear_up2_block_kernel(const void* __r
 #pragma unroll
         for (int q = 0; q < N; ++q) acc[q] = wya * wxa * t[ra][qa][q];
 #pragma unroll
-        for (int q = 0; q < N; ++q) acc[q] += wya * wxb * t[ra][qb][q];
+        for (int q = 0; q < N; ++q) acc[q] = fmaf(wya * wxb, t[ra][qb][q], acc[q]);
 #pragma unroll
-        for (int q = 0; q < N; ++q) acc[q] += wyb * wxa * t[rb][qa][q];
+        for (int q = 0; q < N; ++q) acc[q] = fmaf(wyb * wxa, t[rb][qa][q], acc[q]);
 #pragma unroll
-        for (int q = 0; q < N; ++q) acc[q] += wyb * wxb * t[rb][qb][q];
+        for (int q = 0; q < N; ++q) acc[q] = fmaf(wyb * wxb, t[rb][qb][q], acc[q]);
         // non-temporal: 142 -> 107 us (512 channels, 64^2 -> 128^2), 268 -> 199 us (256 channels), 525 -> 505 us (128 channels), bit-equal outputs
         stv_nt<T>(b, (orow + dx) * (size_t)bC + b0 + ch, acc);
       }
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void bilinear_up2_bwd_rows_kernel(const void* 
           widen<T>(win[(2 * r + ia) % 4][ib], t);
           const float ww = wys[ia] * wxs[ib];
 #pragma unroll
-          for (int q = 0; q < N; ++q) acc[q] += ww * t[q];
+          for (int q = 0; q < N; ++q) acc[q] = fmaf(ww, t[q], acc[q]);
         }
       }
     }
@@ -320,13 +320,32 @@ __global__ void maxpool2_kernel(const void* __restrict__ x, int xC, int x0, void
 }
 
 // ---- ReLU copy (VGG taps observed pre-ReLU) ----
+// The content loss runs it in place, x and y the same view (engine_v.py): neither pointer is __restrict__.  Every element is read and
+// then written by one thread and by no other, so the copy in place gives what the copy out of place gives.
+// x < 0 ? 0 : x is torch's relu on every input: a NaN stays a NaN (fmaxf would make it 0) and -0 stays -0.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
 template <typename T>
-__global__ void relu_copy_kernel(const void* __restrict__ x, int xC, int x0, void* y, int yC, int y0, int n, int h, int w, int c) {
+__global__ void relu_copy_kernel(const void* x, int xC, int x0, void* y, int yC, int y0, int n, int h, int w, int c) {
   const size_t total = (size_t)n * h * w * c;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int ch = (int)(i % c);
     const size_t p = i / c;
-    st<T>(y, p * yC + y0 + ch, fmaxf(ld<T>(x, p * xC + x0 + ch), 0.f));
+    st<T>(y, p * yC + y0 + ch, relu_keep_nan(ld<T>(x, p * xC + x0 + ch)));
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void relu_copy_vec_kernel(const void* x, int xC, int x0, void* y, int yC, int y0, int n, int h, int w, int c) {
+  constexpr int N = VecN<T>::N;
+  const int cv = c / N;
+  const size_t total = (size_t)n * h * w * cv;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int ch = (int)(i % cv) * N;
+    const size_t p = i / cv;
+    float v[N];
+    ldv<T>(x, p * xC + x0 + ch, v);
+#pragma unroll
+    for (int q = 0; q < N; ++q) v[q] = relu_keep_nan(v[q]);
+    stv<T>(y, p * (size_t)yC + y0 + ch, v);
   }
 }
 
@@ -456,6 +475,7 @@ __global__ __launch_bounds__(256) void maxpool2_relu_bwd_kernel(const void* __re
 extern "C" int srganfd_resample(int32_t op, srganfd_view a, srganfd_view b, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, void* stream) {
   const hipStream_t s = (hipStream_t)stream;
   if (!a.ptr || !b.ptr || a.c0 + c > a.cstride || b.c0 + c > b.cstride) return set_err(SRGANFD_EINVAL, "resample: bad args");
+  if (a.planar || b.planar) return set_err(SRGANFD_EINVAL, "resample: NHWC views only, not planar ones");
   const size_t lo = (size_t)n * h * w * c;
 #define RS(K, TOTAL) DISPATCH_T(dtype, \
     SRGANFD_LAUNCH(K<TT>, dim3(grid_for(TOTAL)), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, n, h, w, c))
@@ -479,7 +499,9 @@ extern "C" int srganfd_resample(int32_t op, srganfd_view a, srganfd_view b, int3
     else if (op == 1) { RSV(1, lo * 4); }
     else if (op == 2) { RSV(2, lo); }
     else if (op == 3) { RSV(3, lo / 4); }
-    else if (op == 4) { RSV(4, lo); }
+    else if (op == 4) {
+      DISPATCH_T(dtype, SRGANFD_LAUNCH(relu_copy_vec_kernel<TT>, dim3(grid_for(lo / vn, 256, 65536)), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, n, h, w, c));
+    }
     else return set_err(SRGANFD_EINVAL, "resample: bad op %d", op);
   }
   else if (op == 0) { RS(up2_nearest_bwd_kernel, lo); }
@@ -501,7 +523,8 @@ extern "C" int srganfd_resample_bwd_lrelu(srganfd_view dy, srganfd_view dx_raw, 
   if (!dy.ptr || !act.ptr || !dx_masked.ptr) return set_err(SRGANFD_EINVAL, "resample_bwd_lrelu: null view");
   const int vn = dtype == SRGANFD_F32 ? 4 : 8;
   auto ok = [&](const srganfd_view& v) { return !v.ptr || (v.c0 % vn == 0 && v.cstride % vn == 0 && ((uintptr_t)v.ptr & 15) == 0 && v.c0 + c <= v.cstride && !v.planar); };
-  if (c % vn || !ok(dy) || !ok(dx_raw) || !ok(act) || !ok(dx_masked)) return set_err(SRGANFD_EINVAL, "resample_bwd_lrelu: views must be 16-byte aligned NHWC slices");
+  if (c % vn || !ok(dy) || !ok(dx_raw) || !ok(act) || !ok(dx_masked))
+    return set_err(SRGANFD_EINVAL, "resample_bwd_lrelu: views must be 16-byte aligned NHWC slices, not planar ones");
   const size_t lo = (size_t)n * h * w * c;
   const int cv = c / vn, cv_shift = (cv & (cv - 1)) == 0 ? __builtin_ctz(cv) : -1;
   if (h <= 65535 && n <= 65535 && (size_t)w * cv < (1u << 31)) {
@@ -523,6 +546,7 @@ extern "C" int srganfd_resize_bilinear(int32_t bwd, srganfd_view a, srganfd_view
                                        int32_t c, void* stream) {
   const hipStream_t s = (hipStream_t)stream;
   if (!a.ptr || !b.ptr || !vec_ok(dtype, c, {a, b})) return set_err(SRGANFD_EINVAL, "resize_bilinear: views must be 16-byte aligned channel multiples");
+  if (a.planar || b.planar) return set_err(SRGANFD_EINVAL, "resize_bilinear: NHWC views only, not planar ones");
   const int vn = dtype == SRGANFD_F32 ? 4 : 8;
   if (!bwd) {
     const size_t total = (size_t)n * ho * wo * c / vn;
@@ -540,6 +564,7 @@ extern "C" int srganfd_maxpool2_relu_bwd(srganfd_view x, srganfd_view dy, srganf
                                          void* stream) {
   const hipStream_t s = (hipStream_t)stream;
   if (!x.ptr || !dy.ptr || !dx.ptr || n <= 0 || h <= 0 || w <= 0 || (h & 1) || (w & 1) || c <= 0) return set_err(SRGANFD_EINVAL, "maxpool2_relu_bwd: bad args");
+  if (x.planar || dy.planar || dx.planar) return set_err(SRGANFD_EINVAL, "maxpool2_relu_bwd: NHWC views only, not planar ones");
   const size_t total = (size_t)n * (h / 2) * (w / 2) * c;
   DISPATCH_T(dtype,
              SRGANFD_LAUNCH(maxpool2_relu_bwd_kernel<TT>, dim3(grid_for(total)), dim3(256), 0, s, x.ptr, x.cstride, x.c0, dy.ptr, dy.cstride, dy.c0, dx.ptr, dx.cstride, dx.c0, n, h, w, c));

@@ -264,6 +264,45 @@ def test_planar_views_are_validated():
         A.set_dry_run(False)
 
 
+def test_resampling_and_layout_entry_points_refuse_planar_views_and_bad_arguments():
+    """include/srganfd.h: only the convolutions take planar views.  Every other entry point read one as NHWC without a word."""
+    from sr_gan_fd_amd import _abi as A
+    L = A.lib()
+    A.set_dry_run(True)
+    try:
+        p = 4096                                              # a non-null, 16-byte aligned address; nothing is dereferenced in dry-run mode
+        V = lambda planar=0, cs=64, c0=0: A.View(p, cs, c0, planar, 0)
+        calls = {
+            "resample a": lambda a, b: L.srganfd_resample(1, a, b, A.F16, 2, 4, 4, 32, 0),
+            "resample_bwd_lrelu": lambda a, b: L.srganfd_resample_bwd_lrelu(a, b, V(), V(), A.F16, 2, 4, 4, 32, 0.2, 0),
+            "resample_bwd_lrelu act": lambda a, b: L.srganfd_resample_bwd_lrelu(V(), V(), a, b, A.F16, 2, 4, 4, 32, 0.2, 0),
+            "resize_bilinear": lambda a, b: L.srganfd_resize_bilinear(0, a, b, A.F16, 2, 4, 4, 8, 8, 32, 0),
+            "maxpool2_relu_bwd": lambda a, b: L.srganfd_maxpool2_relu_bwd(a, b, V(), A.F16, 2, 4, 4, 32, 0),
+            "maxpool2_relu_bwd dx": lambda a, b: L.srganfd_maxpool2_relu_bwd(V(), a, b, A.F16, 2, 4, 4, 32, 0),
+            "clamp_grad": lambda a, b: L.srganfd_clamp_grad_to_nhwc(p, a, 2, 3, 4, 4, b, A.F16, 32, 0),
+        }
+        one_view = {
+            "nchw_to_nhwc": lambda v: L.srganfd_nchw_to_nhwc(p, 2, 3, 4, 4, v, A.F16, 32, None, None, 0),
+            "nhwc_to_nchw": lambda v: L.srganfd_nhwc_to_nchw(v, A.F16, 2, 3, 4, 4, p, 1, 0),
+            "nhwc_to_nchw_scaled": lambda v: L.srganfd_nhwc_to_nchw_scaled(v, 2, 3, 4, 4, p, p, 0),
+        }
+        for name, f in calls.items():
+            assert f(V(), V()) == 0, name + ": " + L.srganfd_last_error().decode()
+            for a, b in ((V(1), V()), (V(), V(1))):
+                assert f(a, b) == -1 and b"planar" in L.srganfd_last_error(), name
+        for name, f in one_view.items():
+            assert f(V()) == 0, name + ": " + L.srganfd_last_error().decode()
+            assert f(V(1)) == -1 and b"planar" in L.srganfd_last_error(), name
+        # channels past the buffer's, an operation there is not
+        assert L.srganfd_resample(1, V(c0=40), V(), A.F16, 2, 4, 4, 32, 0) == -1 and L.srganfd_resample(1, V(), V(c0=40), A.F16, 2, 4, 4, 32, 0) == -1
+        for vec in (V(), V(c0=4)):                            # the vector and the scalar forms' dispatch
+            assert L.srganfd_resample(5, vec, V(), A.F16, 2, 4, 4, 32, 0) == -1 and b"bad op" in L.srganfd_last_error()
+            assert L.srganfd_resample(-1, vec, V(), A.F16, 2, 4, 4, 32, 0) == -1
+            assert all(L.srganfd_resample(op, vec, V(), A.F16, 2, 4, 4, 32, 0) == 0 for op in range(5))
+    finally:
+        A.set_dry_run(False)
+
+
 def test_validation_side_argument_checks():
     from sr_gan_fd_amd import _abi as A
     A.set_dry_run(True)
