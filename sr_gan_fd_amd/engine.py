@@ -19,7 +19,7 @@ Data layout in HBM (per engine, per input shape):
 """
 from __future__ import annotations
 
-import ctypes as C
+import functools
 import os
 import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -29,7 +29,6 @@ from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
-from . import profiling
 
 _ENGINES: "weakref.WeakKeyDictionary[nn.Module, object]" = weakref.WeakKeyDictionary()
 
@@ -404,9 +403,8 @@ class TrunkEngine(EngineBase):
         Cc, G, Ccat, R = self.Cc, self.G, self.Ccat, self.R
         wptr = pk["buf"].data_ptr()
         V = A.view
-        VC = lambda t, c0=0: A.view(t, c0=c0, planar=sp.planar)      # forward dense-block buffers
-        VD = VC                                                       # stacked-gradient buffers (same layout: planar only one of
-        #                                                               the two measured half the gain each)
+        VC = VD = lambda t, c0=0: A.view(t, c0=c0, planar=sp.planar)      # forward dense-block buffers and stacked-gradient buffers (same
+        #                                                                   layout: planar only one of the two measured half the gain each)
 
         def new(*shape, dtype=dt):
             return torch.empty(*shape, dtype=dtype, device=device)
@@ -414,7 +412,7 @@ class TrunkEngine(EngineBase):
         sp.dy = [new(N, H, W, Ccat) for _ in range(4)]
         sp.dx0 = new(N, H, W, Cc)           # gradient w.r.t. the trunk input
         dyb = lambda i: sp.dy[i % 4]
-        bw = []                              # ops.Conv | Wgrad | ThinLaunch | DenseChain | Call and the markers Item("ready", (lo, hi)) | Item("fence", block)
+        bw = []                              # ops.Conv | Wgrad | ThinLaunch | DenseChain | Call and the bucket markers ops.Ready
         cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
         wplans = ops.WgradPlans(device, dtc, N)
 
@@ -463,12 +461,7 @@ class TrunkEngine(EngineBase):
                     bw.append(ops.Call("srganfd_resample", (0, oth_v, V(glo), dtc, N, hin, win, Cc), "nearest_bwd"))
                     if u >= 2:   # input of this stage is the LeakyReLU output of the previous upsampling conv
                         bw.append(ops.Call("srganfd_lrelu_bwd", (V(glo), V(xin_t), A.NULL_VIEW, V(glo), dtc, N * hin * win, Cc, 0.2), "lrelu_bwd"))
-                if u >= 2:
-                    # next stage works at (hin, win): reuse gA/gB as scratch, the gradient lives in glo
-                    cur, other = glo, sp.gA
-                    # make cur the full buffer view expected above
-                else:
-                    cur = glo
+                cur, other = glo, sp.gA      # the next stage works at (hin, win): gA is its scratch, the gradient lives in glo
             d_f0 = cur if self.n_up else sp.gB
             sp.d_f0 = d_f0
             # conv2: f0 = out1 + conv2(trunk_out)
@@ -476,7 +469,7 @@ class TrunkEngine(EngineBase):
             bw.append(cv(V(d_f0), VD(dyb(R - 1)), wptr + pk["offs"][("b", "conv2")], N, H, W, Cc, Cc))
             # gradient buckets for the data-parallel exchange (parallel.BucketReducer): parameters sit in named_parameters() order --
             # conv1, the dense blocks, conv2 and the tail -- so "everything from conv2 on" is one contiguous range, final here
-            bw.append(ops.Item("ready", (self._poff("conv2.weight"), self.fp.total)))
+            bw.append(ops.Ready(self._poff("conv2.weight"), self.fp.total))
         # dense blocks, last to first
         rdb_names = ["conv%d" % k for k in range(1, 6)]
         plans = {}
@@ -508,26 +501,21 @@ class TrunkEngine(EngineBase):
             blk.append(ops.conv_args(dtc, VD(di), dst, wptr + pk["offs"][("b", i, 4)], N, H, W, Ccat, Cc, **kw))
             chain = ops.dense_chain_or_launches(blk, sp.device) if (Cc, G) == (64, 32) else [ops.Conv(a) for a in blk]
             wg = ops.Wgrad(plans[s5], VC(ci), VD(di), dw_off=self._poff(pre + "conv1.weight"), block=i)     # the plan's offsets are relative to the block
-            fence = [ops.Item("fence", i + 3)] if i > 0 else []     # dst is the buffer block i + 3's weight gradient read (side-stream mode, see backward())
-            ready = [ops.Item("ready", (self._poff(pre + "conv1.weight"), self._poff("conv2.weight")))] if self.full and R >= 4 and i == R // 2 else []     # upper half of the trunk is final: second bucket
-            if len(chain) == 1:
-                # one launch for the five data-gradient convs (it writes dst, so the fence comes first); the weight gradient reads what
-                # the chain's four growth layers wrote and follows it
-                bw.extend(fence + chain + [wg] + ready)
-            else:
-                bw.extend(chain[:4] + [wg] + ready + fence + chain[4:])
+            ready = [ops.Ready(self._poff(pre + "conv1.weight"), self._poff("conv2.weight"))] if self.full and R >= 4 and i == R // 2 else []     # upper half of the trunk is final: second bucket
+            # the weight gradient reads what the four growth layers of the data gradient wrote and follows them (or the one launch for all five convs)
+            bw.extend(chain[:4] + [wg] + ready + chain[4:])
         if self.full:
             bw.append(ops.Call("srganfd_axpby", (V(sp.d_f0), V(sp.dx0), dtc, N * H * W, Cc, 1.0, 1.0), "axpby"))
             bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, sp.xin, sp.dx0, fptr + 4 * self._poff("conv1.weight"), self._poff("conv1.weight"),
                                       self._poff("conv1.bias"), sp.thin_ws, N, H, W, self.in_ch, Cc, True))
         # last bucket: whatever the earlier markers did not cover
-        covered = min([it.payload[0] for it in bw if it.kind == "ready"], default=self.fp.total)
-        bw.append(ops.Item("ready", (0, covered)))
-        sp.bw = bw
+        covered = min([it.lo for it in bw if isinstance(it, ops.Ready)], default=self.fp.total)
+        bw.append(ops.Ready(0, covered))
         sp.wg_ws = wplans.workspace()
         # four more workspaces of the dense-block plan's size for the batched slab reduction (34 MB each at B=32, 128x128)
         dense_ws = max((p_.workspace_bytes for p_ in plans.values()), default=0)
         sp.wg_ws4 = [torch.empty(dense_ws, dtype=torch.uint8, device=device) for _ in range(_BATCH_REDUCE)] if (dense_ws and _BATCH_REDUCE > 1) else None
+        sp.bw = batch_reductions(bw, sp.wg_ws4) if sp.wg_ws4 is not None else bw
 
     # -- execution ----------------------------------------------------------------------------
     def trunk_size(self, shape) -> Tuple[int, int, int]:
@@ -573,12 +561,7 @@ class TrunkEngine(EngineBase):
             A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.in_ch, H, W, A.view(sp.xin), dtc, sp.xin.shape[-1], None, None, st), "nchw_to_nhwc")
         else:
             A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.Cc, H, W, A.view(sp.catb(0)), dtc, self.Cc, None, None, st), "nchw_to_nhwc")
-        rec = profiling.REC
-        for item in sp.fw:
-            if item.kind == "conv":
-                ops.conv2d(item.args, rec, "conv2d", L, st)
-            else:                                   # "thin" | "chain"
-                item.launch(rec, L, st)
+        ops.run_items(sp.fw, ops.Run("conv2d"))
         if self.full:
             out = torch.empty(N, self.out_ch, sp.hs, sp.ws, dtype=torch.float32, device=dev)
             A.check(L.srganfd_nhwc_to_nchw(A.view(sp.srp), A.F32, N, self.out_ch, sp.hs, sp.ws, out.data_ptr(), 1, st), "nhwc_to_nchw")
@@ -605,81 +588,8 @@ class TrunkEngine(EngineBase):
             A.check(L.srganfd_clamp_grad_to_nhwc(dout.data_ptr(), A.view(sp.srp), N, self.out_ch, sp.hs, sp.ws, A.view(sp.dsrp), dtc, sp.dsrp.shape[-1], st), "clamp_grad")
         else:
             A.check(L.srganfd_nchw_to_nhwc(dout.data_ptr(), N, self.Cc, H, W, A.view(sp.dy[(self.R - 1) % 4]), dtc, self.Cc, None, None, st), "nchw_to_nhwc")
-        gptr = flat_grad.data_ptr()
-        rec = profiling.REC
-        pend_red = []          # dense-block weight-gradient launches whose slabs wait for the batched reduction
-        # SRGANFD_WGRAD_STREAM=1: the dense blocks' weight-gradient launches (and their slab reductions) run on a second stream beside
-        # the data-gradient chain of the following blocks -- they only read what the chain has finished (block i's stacked gradient and
-        # activations); the chain waits ("fence") before it overwrites a gradient buffer a pending weight gradient still reads.
-        side = None
-        if _WGRAD_STREAM and sp.wg_ws4 is not None:
-            side = getattr(sp, "wg_stream", None)
-            if side is None:
-                side = sp.wg_stream = torch.cuda.Stream(device=sp.device)
-            main = torch.cuda.current_stream()
-            wg_done = {}       # dense block -> event behind its weight-gradient launch on the side stream
-
-        def on_side(fn):
-            if side is None:
-                return fn()
-            with torch.cuda.stream(side):
-                return fn()
-
-        def flush_reduce():
-            if not pend_red:
-                return
-            jobs = (A.WgradReduceJob * len(pend_red))()
-            for j, (plan, goff, ws) in zip(jobs, pend_red):
-                j.plan_host, j.plan_dev = C.addressof(plan.host), plan.dev.data_ptr()
-                j.grads, j.scalars, j.workspace = gptr + 4 * goff, None, ws.data_ptr()
-            n_jobs = len(pend_red)
-            run = lambda: A.check(L.srganfd_wgrad_reduce_batch(jobs, n_jobs, A.stream_ptr()), "wgrad_reduce_batch")
-            on_side(run if rec is None else lambda: rec.bracket("wgrad_reduce_batch", (0.0, float(sum(w.numel() for _, _, w in pend_red))), run))
-            pend_red.clear()
-        for item in sp.bw:
-            kind = item.kind
-            if kind == "conv":
-                ops.conv2d(item.args, rec, "conv2d(dgrad)", L, st)
-            elif kind == "chain":
-                item.launch(rec, L, st)
-            elif kind == "wgrad":
-                plan = item.plan
-                if item.block is not None and sp.wg_ws4 is not None:
-                    # dense block: MFMA kernel now, slabs into one of four workspaces; the slab reduction of up to four blocks is ONE
-                    # launch (srganfd_wgrad_reduce_batch: the reduction is latency-bound at ~20 us whatever it reduces)
-                    ws = sp.wg_ws4[len(pend_red)]
-                    run = lambda: A.check(L.srganfd_conv2d_wgrad_partial(plan.host, plan.dev.data_ptr(), item.x, item.dy, ws.data_ptr(), ws.numel(),
-                                                                         A.stream_ptr()), "conv2d_wgrad_partial")      # (the side stream's, inside on_side)
-                    if side is not None:
-                        side.wait_stream(main)          # the block's four data-gradient launches have written its stacked gradient
-                    on_side(run if rec is None else lambda: rec.bracket(plan.label, (plan.flops, plan.nbytes), run))
-                    if side is not None:
-                        ev = torch.cuda.Event()
-                        ev.record(side)
-                        wg_done[item.block] = ev
-                    pend_red.append((plan, item.dw_off, ws))
-                    if len(pend_red) == len(sp.wg_ws4):
-                        flush_reduce()
-                else:
-                    flush_reduce()                      # the launches share workspace slot 0
-                    ops.conv2d_wgrad(plan, item.x, item.dy, gptr + 4 * item.dw_off, sp.wg_ws, rec, L, st)
-            elif kind == "thin":
-                flush_reduce()                          # (keeps the launch order of the padded path: slot-0 workspace users come after pending slabs)
-                item.launch(rec, L, st, gptr)
-            elif kind == "ready":
-                flush_reduce()
-                if side is not None:
-                    main.wait_stream(side)
-                if on_ready is not None:
-                    on_ready(flat_grad, *item.payload)
-            elif kind == "fence":
-                if side is not None and item.payload in wg_done:
-                    main.wait_event(wg_done.pop(item.payload))
-            else:                                       # "call"
-                item.launch(rec, L, st)
-        flush_reduce()
-        if side is not None:
-            main.wait_stream(side)
+        ops.run_items(sp.bw, ops.Run("conv2d(dgrad)", grad=flat_grad.data_ptr(), ws=sp.wg_ws,
+                                     on_ready=None if on_ready is None else functools.partial(on_ready, flat_grad)))
         dx = None
         if need_dx and not self.full:
             dx = torch.empty(N, self.Cc, H, W, dtype=torch.float32, device=sp.device)
@@ -689,7 +599,31 @@ class TrunkEngine(EngineBase):
 
 # dense blocks whose weight-gradient slabs one srganfd_wgrad_reduce_batch launch reduces (<= 8 = SRGANFD's kRedBatch; 0 / 1: every block's own)
 _BATCH_REDUCE = max(0, min(8, int(os.environ.get("SRGANFD_BATCH_REDUCE", "4"))))
-_WGRAD_STREAM = int(os.environ.get("SRGANFD_WGRAD_STREAM", "0"))
+
+
+def batch_reductions(items: Sequence, slots: Sequence[Tensor]) -> list:
+    """The generator's backward list with the dense blocks' weight gradients (ops.Wgrad with a ``block``) as the MFMA launch alone
+    (ops.WgradPartial, slabs into the next free workspace of ``slots``) and one ops.WgradReduce per batch: after len(slots) of them,
+    before a launch that shares workspace slot 0 (any other weight gradient; a thin launch, which keeps the padded path's order),
+    before every gradient bucket is announced, and at the end."""
+    out, pending = [], []
+
+    def reduce_pending():
+        if pending:
+            out.append(ops.WgradReduce(pending))
+            pending.clear()
+    for it in items:
+        if isinstance(it, ops.Wgrad) and it.block is not None:
+            pending.append(ops.WgradPartial(it, len(pending), slots[len(pending)]))
+            out.append(pending[-1])
+            if len(pending) == len(slots):
+                reduce_pending()
+            continue
+        if isinstance(it, (ops.Wgrad, ops.ThinLaunch, ops.Ready)):
+            reduce_pending()
+        out.append(it)
+    reduce_pending()
+    return out
 
 
 class _TrunkFn(torch.autograd.Function):

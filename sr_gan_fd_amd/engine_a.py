@@ -21,7 +21,7 @@ from torch import Tensor, nn
 from . import _abi as A
 from . import ops
 from .engine import _engine, _Shape
-from .engine_core import DiscriminatorEngineCore, discriminator_forward
+from .engine_core import DiscriminatorEngineCore, discriminator_forward, first_layer_dgrad
 
 # (name, ksize, stride, pad) of the spectral-normalised convs, in forward order
 SN_LAYERS = [("conv1", 3, 2, 1), ("conv2", 3, 2, 1), ("conv3", 3, 2, 1), ("gating", 1, 1, 1), ("cat_1.convU", 3, 1, 1),
@@ -35,6 +35,64 @@ def _mod(owner: nn.Module, name: str) -> nn.Module:
     for part in name.split("."):
         m = getattr(m, part)
     return m
+
+
+class GateBatchNorm:
+    """BatchNorm2d of an attention gate's W branch, x -> y (its half of the concatenation buffer) over ``npix`` pixels of ``channels``.
+    ``gamma_off`` / ``beta_off``: elements of the flat parameters and gradient; ``bn``: the module (running buffers, momentum, eps, batch
+    counter); ``save``: the statistics the backward pass needs; ``ws``: what the plan's BatchNorm items share -- [statistics workspace,
+    the buffer the sync-BN backward reduces the ranks' sums in (allocated by its first use)]"""
+    kind = "bn"
+
+    def __init__(self, eng, x: A.View, y: A.View, dtc: int, npix: int, channels: int, gamma_off: int, beta_off: int, bn: nn.Module, save: Tensor, ws: list):
+        self.eng, self.x, self.y, self.dtc, self.npix, self.channels = weakref.proxy(eng), x, y, dtc, npix, channels     # (a plan must not hold its engine)
+        self.gamma_off, self.beta_off, self.bn, self.save, self.ws = gamma_off, beta_off, bn, save, ws
+
+    def launch(self, run: ops.Run) -> None:
+        bn, L, st, npix, Ck, ws, sb = self.bn, run.L, run.st, self.npix, self.channels, self.ws[0], self.eng.sync_bn
+        if bn.running_mean.device != ws.device:
+            raise A.SrganfdError("BatchNorm buffers must live on the module's GPU")
+        flat = self.eng.fp.flat.data_ptr()
+        args = (self.x, self.y, self.dtc, npix, Ck, flat + 4 * self.gamma_off, flat + 4 * self.beta_off, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                bn.momentum, bn.eps)
+        if run.training and sb is not None:
+            # (sum x, sum x^2) of this rank's pixels -> summed over the ranks -> statistics of the whole batch (pixel count = ranks * npix)
+            args += (self.save.data_ptr(), ws.data_ptr(), 1.0)
+            A.check(L.srganfd_batchnorm_fwd_sync(*args, 1, 0, st), "batchnorm_fwd_sync")
+            sb.all_reduce(ws[:L.srganfd_batchnorm_partial_floats(Ck)])
+            A.check(L.srganfd_batchnorm_fwd_sync(*args, 2, npix * sb.world, st), "batchnorm_fwd_sync")
+        else:
+            A.check(L.srganfd_batchnorm_fwd(*args, 1 if run.training else 0, self.save.data_ptr(), ws.data_ptr(), st), "batchnorm_fwd")
+        if run.training:
+            bn.num_batches_tracked += 1
+
+
+class GateBatchNormBwd:
+    """backward of the GateBatchNorm ``fwd``: dy -> dx; dgamma / dbeta go into the pass's flat gradient"""
+    kind = "bn_bwd"
+
+    def __init__(self, fwd: GateBatchNorm, dy: A.View, dx: A.View):
+        self.fwd, self.dy, self.dx = fwd, dy, dx
+
+    def launch(self, run: ops.Run) -> None:
+        f, L, st = self.fwd, run.L, run.st
+        npix, Ck, ws, sb = f.npix, f.channels, f.ws[0], f.eng.sync_bn
+        args = (f.x, self.dy, self.dx, f.dtc, npix, Ck, f.eng.fp.flat.data_ptr() + 4 * f.gamma_off, f.save.data_ptr(), run.grad + 4 * f.gamma_off,
+                run.grad + 4 * f.beta_off, 0.0, ws.data_ptr())
+        if sb is not None:
+            # dgamma/dbeta stay this rank's sums (the flat-gradient all-reduce averages them with everything else); the
+            # dx coefficients need (sum dy, sum dy*xhat) over the whole batch
+            nfl = L.srganfd_batchnorm_partial_floats(Ck)
+            if f.ws[1] is None:
+                f.ws[1] = torch.empty(L.srganfd_batchnorm_partial_floats(256), dtype=torch.float32, device=ws.device)
+            glob = f.ws[1]
+            args += (glob.data_ptr(), A.NULL_VIEW, 1.0)
+            A.check(L.srganfd_batchnorm_bwd_sync(*args, 1, 0, st), "batchnorm_bwd_sync")
+            glob[:nfl].copy_(ws[:nfl])
+            sb.all_reduce(glob[:nfl])
+            A.check(L.srganfd_batchnorm_bwd_sync(*args, 2, npix * sb.world, st), "batchnorm_bwd_sync")
+        else:
+            A.check(L.srganfd_batchnorm_bwd(*args, st), "batchnorm_bwd")
 
 
 class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
@@ -95,8 +153,7 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
         sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
         V = A.view
         fptr, wptr, O = self.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
-        me = weakref.proxy(self)                    # closures stored on the plan must not hold the engine (reference cycle)
-        P = lambda name: fptr + 4 * me._poff(name)
+        P = lambda name: fptr + 4 * self._poff(name)      # (used while the plan is built only, not stored on it)
         Wp = lambda *key: wptr + O[key]
         nf = self.nf
 
@@ -113,8 +170,8 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
         B["cat1"], B["cat2"], B["cat3"] = new(*R[2], 8 * nf), new(*R[1], 4 * nf), new(*R[0], 2 * nf)
         B["b3"], B["x4"], B["b4"], B["x5"], B["b5"] = new(*R[2], 8 * nf), new(*R[2], 4 * nf), new(*R[1], 4 * nf), new(*R[1], 2 * nf), new(*R[0], 2 * nf)
         B["x6"], B["c7"], B["c8"] = new(*R[0], nf), new(*R[0], nf), new(*R[0], nf)
-        sp.bn_ws = torch.empty(2048 * 256 + 3 * 256, dtype=torch.float32, device=device)
-        sp.bn_ws_global = None
+        bn_ws = [torch.empty(2048 * 256 + 3 * 256, dtype=torch.float32, device=device), None]
+        sp.bn = {}
         lre = dict(act=A.ACT_LRELU, slope=0.2)
         cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
         rs = lambda op, a, b, h, w, c, dtype=dtc: ops.Call("srganfd_resample", (op, a, b, dtype, N, h, w, c), "resample")
@@ -140,7 +197,6 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
             T["save"] = torch.empty(4 * Ck, dtype=torch.float32, device=device)
             T["dims"] = (h, w, hh, wh, Ck)
             sp.attn[k] = T
-            bn = _mod(self.owner, pre + ".W.1")
             fw += [
                 cv(V(B[xname]), V(T["theta"]), Wp("f", pre + ".theta"), N, h, w, Ck, Ck, ksize=2, stride=2, pad=0),
                 cv(V(B["gated"]), V(T["phi"]), Wp("f", pre + ".phi"), N, Hg, Wg, 4 * nf, Ck, ksize=1, pad=0, bias=P(pre + ".phi.bias")),
@@ -151,8 +207,10 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
                 rs(1, V(T["sig"]), V(T["sigup"]), hh, wh, 1, A.F32),
                 ops.Call("srganfd_gate_mul", (0, V(B[xname]), T["sigup"].data_ptr(), V(T["y"]), A.NULL_VIEW, None, dtc, N * h * w, Ck), "gate_mul"),
                 cv(V(T["y"]), V(T["wy"]), Wp("f", pre + ".W.0"), N, h, w, Ck, Ck, ksize=1, pad=0, bias=P(pre + ".W.0.bias")),
-                ops.Item("bn", (k, V(T["wy"]), V(B[cat]), N * h * w, Ck, P(pre + ".W.1.weight"), P(pre + ".W.1.bias"), bn, T["save"])),
             ]
+            sp.bn[k] = GateBatchNorm(self, V(T["wy"]), V(B[cat]), dtc, N * h * w, Ck, self._poff(pre + ".W.1.weight"), self._poff(pre + ".W.1.bias"),
+                                     _mod(self.owner, pre + ".W.1"), T["save"], bn_ws)
+            fw.append(sp.bn[k])
         fw += [
             rs(1, V(B["x3"]), V(B["b3"]), *R[3], 8 * nf),
             cv(V(B["b3"]), V(B["cat1"], c0=4 * nf), Wp("f", "cat_1.convU"), N, *R[2], 8 * nf, 4 * nf, **lre),
@@ -166,10 +224,10 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
             cv(V(B["x6"]), V(B["c7"]), Wp("f", "conv7"), N, *R[0], nf, nf, **lre),
             cv(V(B["c7"]), V(B["c8"]), Wp("f", "conv8"), N, *R[0], nf, nf, **lre),
         ]
+        # conv9 writes the logits, allocated per forward
+        fw.append(ops.PerCall(ops.features_to_image(dtc, sp.thin_o, V(B["c8"]), 0, 1, P("conv9.weight"), Wp("f", "conv9"), N, H, W, 1, nf, False,
+                                                    bias=P("conv9.bias"))))
         sp.fw = fw
-        thin_o = sp.thin_o
-        sp.logits_conv = lambda logits: ops.features_to_image(dtc, thin_o, V(B["c8"]), logits.data_ptr(), 1, P("conv9.weight"), Wp("f", "conv9"),
-                                                              N, H, W, 1, nf, False, bias=P("conv9.bias"))
         sp.R, sp.Rg = R, (Hg, Wg)
         self._plan_backward(sp, pk)
         self.shapes[key] = sp
@@ -226,7 +284,7 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
             D["dsig"] = torch.empty(N, hh, wh, 1, dtype=torch.float32, device=device)
             D["dpsip"], D["df"], D["dxt"], D["dphi"] = new(hh, wh, 32), new(hh, wh, Ck), new(h, w, Ck), new(Hg, Wg, Ck)
             items = [
-                ops.Item("bn_bwd", (V(T["wy"]), V(dcat), V(D["dwy"]), N * h * w, Ck, pre, T["save"])),
+                GateBatchNormBwd(sp.bn[k], V(dcat), V(D["dwy"])),
                 wg(pre + ".W.0", T["y"], D["dwy"], h, w, Ck, Ck, k=1, pad=0, bias=True),
                 cv(V(D["dwy"]), V(D["dy"]), Wp("b", pre + ".W.0"), N, h, w, Ck, Ck, ksize=1, pad=0),
                 ops.Call("srganfd_gate_mul", (1, V(B[xname]), T["sigup"].data_ptr(), V(D["dy"]), V(D["dxg"]), D["dsigup"].data_ptr(), dtc, N * h * w, Ck),
@@ -302,58 +360,17 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
                             r1=sp.attn[3]["grad"]["dxg"], r2=sp.attn[3]["grad"]["dxt"], mask=B["x0"])
         bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, B["xin"], G["dx0"], P("conv0.weight"), self._poff("conv0.weight"), self._poff("conv0.bias"),
                                   sp.thin_ws, N, H, W, self.in_ch, nf, True))
-        sp.dx_conv = ops.features_to_image(dtc, sp.thin_i, V(G["dx0"]), sp.dxp, 4, P("conv0.weight"), Wp("b", "conv0"), N, H, W, self.in_ch, nf, True, flip=True)
+        sp.dx_conv = first_layer_dgrad(ops.features_to_image(dtc, sp.thin_i, V(G["dx0"]), sp.dxp, 4, P("conv0.weight"), Wp("b", "conv0"), N, H, W,
+                                                             self.in_ch, nf, True, flip=True))
         sp.bw = bw
-        self._backward_workspaces(sp, wplans)
+        self._backward_workspaces(sp, wplans, pk)
 
-    # ---- execution: the core's loops, plus the attention gates' BatchNorm ----
-    def _forward_item(self, item, sp, training, L, st) -> None:
-        """Item("bn", ...): BatchNorm2d of an attention gate's W branch, written into its half of the concatenation buffer"""
-        k, xv, yv, npix, Ck, gamma, beta, bn, save = item.payload
-        dtc = sp.dtc
-        if bn.running_mean.device != sp.device:
-            raise A.SrganfdError("BatchNorm buffers must live on the module's GPU")
-        if training and self.sync_bn is not None:
-            # (sum x, sum x^2) of this rank's pixels -> summed over the ranks -> statistics of the whole batch (pixel count = ranks * npix)
-            sb, ws = self.sync_bn, sp.bn_ws
-            args = (xv, yv, dtc, npix, Ck, gamma, beta, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.momentum, bn.eps,
-                    save.data_ptr(), ws.data_ptr(), 1.0)
-            A.check(L.srganfd_batchnorm_fwd_sync(*args, 1, 0, st), "batchnorm_fwd_sync")
-            sb.all_reduce(ws[:L.srganfd_batchnorm_partial_floats(Ck)])
-            A.check(L.srganfd_batchnorm_fwd_sync(*args, 2, npix * sb.world, st), "batchnorm_fwd_sync")
-        else:
-            A.check(L.srganfd_batchnorm_fwd(xv, yv, dtc, npix, Ck, gamma, beta, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                            bn.momentum, bn.eps, 1 if training else 0, save.data_ptr(), sp.bn_ws.data_ptr(), st), "batchnorm_fwd")
-        if training:
-            bn.num_batches_tracked += 1
-
+    # ---- execution: the core's passes; the attention maps of the last forward are kept on the module ----
     def forward(self, x: Tensor, training: bool) -> Tensor:
         logits = super().forward(x, training)
         sp, o = self._last, self.owner
         o.ly1, o.ly2, o.ly3 = (sp.attn[k]["sigup"].view(sp.N, 1, *sp.attn[k]["dims"][:2]).clone() for k in (1, 2, 3))
         return logits
-
-    def _backward_item(self, item, sp, flat_grad, L, st) -> None:
-        """Item("bn_bwd", ...): the flat gradient receives dgamma / dbeta"""
-        xv, dyv, dxv, npix, Ck, pre, save = item.payload
-        dtc, flat = sp.dtc, self.fp.flat
-        gamma, beta = 4 * self._poff(pre + ".W.1.weight"), 4 * self._poff(pre + ".W.1.bias")
-        if self.sync_bn is not None:
-            # dgamma/dbeta stay this rank's sums (the flat-gradient all-reduce averages them with everything else); the
-            # dx coefficients need (sum dy, sum dy*xhat) over the whole batch
-            sb, ws = self.sync_bn, sp.bn_ws
-            nfl = L.srganfd_batchnorm_partial_floats(Ck)
-            if sp.bn_ws_global is None:
-                sp.bn_ws_global = torch.empty(L.srganfd_batchnorm_partial_floats(256), dtype=torch.float32, device=ws.device)
-            args = (xv, dyv, dxv, dtc, npix, Ck, flat.data_ptr() + gamma, save.data_ptr(), flat_grad.data_ptr() + gamma, flat_grad.data_ptr() + beta,
-                    0.0, ws.data_ptr(), sp.bn_ws_global.data_ptr(), A.NULL_VIEW, 1.0)
-            A.check(L.srganfd_batchnorm_bwd_sync(*args, 1, 0, st), "batchnorm_bwd_sync")
-            sp.bn_ws_global[:nfl].copy_(ws[:nfl])
-            sb.all_reduce(sp.bn_ws_global[:nfl])
-            A.check(L.srganfd_batchnorm_bwd_sync(*args, 2, npix * sb.world, st), "batchnorm_bwd_sync")
-        else:
-            A.check(L.srganfd_batchnorm_bwd(xv, dyv, dxv, dtc, npix, Ck, flat.data_ptr() + gamma, save.data_ptr(), flat_grad.data_ptr() + gamma,
-                                            flat_grad.data_ptr() + beta, 0.0, sp.bn_ws.data_ptr(), st), "batchnorm_bwd")
 
 
 def aesrgan_engine(owner: nn.Module) -> AesrganDiscriminatorEngine:

@@ -1,18 +1,21 @@
 """What the three discriminator engines (engine_d.py, engine_a.py, engine_e.py) share: spectral-norm state and packing, the
-forward and backward launch loops, and the autograd glue.
+forward and backward passes over the launch lists, and the autograd glue.
 
-A subclass describes its network: the layer tables, ``_build_pack``, ``_plan`` / ``_plan_backward`` (the launch lists) and, for
-launch kinds only it has (BatchNorm), ``_forward_item`` / ``_backward_item``.  A plan ``sp`` carries (items: ops.py's, by ``kind``)
+A subclass describes its network: the layer tables, ``_build_pack``, ``_plan`` / ``_plan_backward`` (the launch lists) and, beside
+itself, the launch items only it has (BatchNorm).  A plan ``sp`` carries (items: ops.py's, each with ``launch(run)``)
   sp.xin                 NHWC input buffer (4-channel pitch for the thin kernels, else padded to 32)
-  sp.fw                  forward items: ops.Conv | ops.ThinLaunch | ops.Call | ops.Item(own kind, payload)
-  sp.logits_conv(t)      the item of the last layer, which writes the fp32 logits tensor ``t`` (allocated per forward)
+  sp.fw                  forward items: ops.Conv | ops.ThinLaunch | ops.Call | the engine's own; the last one, an ops.PerCall, writes
+                         the fp32 logits (allocated per forward: ``run.out``)
   sp.dl                  NHWC buffer of the logits' gradient
-  sp.bw                  backward items: the forward kinds and ops.Wgrad (``sn``: the layer's spectral-norm slot, or None)
-  sp.dx_conv, sp.dxp     the item (Conv or ThinLaunch) of the first layer's data gradient and its fp32 NHWC4 output
-  sp.wg_ws, sp.gtmp, sp.sn_ws   workspaces (``_backward_workspaces``)
+  sp.bw                  backward items: the forward kinds and ops.Wgrad (``sn``: the layer's spectral-norm slot, or None); the last
+                         one is the SnGradBatch ``_backward_workspaces`` appends
+  sp.dx_conv, sp.dxp     the item (``first_layer_dgrad``) of the first layer's data gradient and its fp32 NHWC4 output
+  sp.wg_ws, sp.gtmp      workspaces (``_backward_workspaces``)
 """
 from __future__ import annotations
 
+import ctypes as C
+import weakref
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -20,8 +23,37 @@ from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
-from . import profiling
 from .engine import EngineBase, _dt, _require_gpu, _Shape, check_channels
+
+
+class SnGradBatch:
+    """Last item of a backward list: dL/d(W/sigma) of every spectral-normalised layer sits in its own range of the scratch gradient,
+    and one batched pass turns them into dL/dW_orig in the flat gradient.  ``layers``: the spectral-norm slots of the list's Wgrad
+    items; ``inv_sigma``: the packed record's scalars; nothing to do for a pass with frozen parameters (no Wgrad ran)."""
+    kind = "sn_grad"
+
+    def __init__(self, eng: "DiscriminatorEngineCore", layers: Sequence[int], inv_sigma: Optional[Tensor], ws: Tensor):
+        self.eng, self.layers, self.inv_sigma, self.ws = weakref.proxy(eng), list(layers), inv_sigma, ws     # (a plan must not hold its engine)
+
+    def launch(self, run: ops.Run) -> None:
+        if not (run.need_wgrad and self.layers):
+            return
+        eng, jobs = self.eng, []
+        flat, isig = eng.fp.flat.data_ptr(), self.inv_sigma.data_ptr()
+        for l in self.layers:
+            name, rows, cols = eng.sn[l]
+            off = 4 * eng._poff(name)
+            u, v = eng._sn_uv(l)
+            jobs.append((run.scratch + off, flat + off, u.data_ptr(), v.data_ptr(), isig + 4 * (2 * l + 1), run.grad + off, rows, cols))
+        ops.spectral_norm_grad_batch(jobs, self.ws)
+
+
+def first_layer_dgrad(item):
+    """sp.dx_conv from the item of the first layer's data gradient (launched only by a pass that wants the input's gradient): the
+    conv is never bracketed (its thin twin is) and reported under a name of its own"""
+    if isinstance(item, ops.Conv):
+        return ops.Call("srganfd_conv2d", (C.byref(item.args),), "conv2d(dgrad of the first layer)")      # (the byref object keeps the struct alive)
+    return item
 
 
 class DiscriminatorEngineCore(EngineBase):
@@ -61,12 +93,13 @@ class DiscriminatorEngineCore(EngineBase):
         pk["table"].run(flat, pk["buf"], pk.get("scalars"))
         return pk
 
-    def _backward_workspaces(self, sp: _Shape, wplans: ops.WgradPlans) -> None:
+    def _backward_workspaces(self, sp: _Shape, wplans: ops.WgradPlans, pk: dict) -> None:
         sp.wg_ws = wplans.workspace()
         # spectral-normalised layers write dL/d(W/sigma) here, each into its own range; passes with frozen parameters also send
         # BatchNorm's dgamma / dbeta here
         sp.gtmp = torch.zeros(self.fp.total, dtype=torch.float32, device=sp.device)
-        sp.sn_ws = torch.empty(len(self.sn) * A.SN_GRAD_WS_FLOATS, dtype=torch.float32, device=sp.device)
+        sn_ws = torch.empty(len(self.sn) * A.SN_GRAD_WS_FLOATS, dtype=torch.float32, device=sp.device)
+        sp.bw.append(SnGradBatch(self, [it.sn for it in sp.bw if isinstance(it, ops.Wgrad) and it.sn is not None], pk.get("scalars"), sn_ws))
 
     # ---- execution ----
     def _check_input(self, x: Tensor) -> None:
@@ -74,12 +107,6 @@ class DiscriminatorEngineCore(EngineBase):
 
     def _logits(self, N: int, H: int, W: int, device) -> Tensor:
         return torch.empty(N, 1, H, W, dtype=torch.float32, device=device)
-
-    def _forward_item(self, item, sp, training, L, st) -> None:
-        raise A.SrganfdError(f"{self.what}: unknown launch kind {item.kind!r}")
-
-    def _backward_item(self, item, sp, flat_grad, L, st) -> None:
-        raise A.SrganfdError(f"{self.what}: unknown launch kind {item.kind!r}")
 
     def forward(self, x: Tensor, training: bool) -> Tensor:
         self._check_input(x)                       # the shape contract, before anything is packed, planned or launched
@@ -93,17 +120,9 @@ class DiscriminatorEngineCore(EngineBase):
         x = x.contiguous().float()
         A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.in_ch, H, W, A.view(sp.xin), dtc, sp.xin.shape[-1], None, None, st), "nchw_to_nhwc")
         logits = self._logits(N, H, W, dev)
-        rec = profiling.REC
-        for item in sp.fw + [sp.logits_conv(logits)]:
-            kind = item.kind
-            if kind == "conv":
-                ops.conv2d(item.args, rec, "conv2d", L, st)
-            elif kind == "thin" or kind == "call":
-                item.launch(rec, L, st)
-            else:
-                self._forward_item(item, sp, training, L, st)
+        ops.run_items(sp.fw, ops.Run("conv2d", training=training, out=logits.data_ptr()))
         self.token += 1
-        sp.token, sp.training, sp.inv_sigma = self.token, training, pk.get("scalars")
+        sp.token, sp.training = self.token, training
         self._last = sp
         return logits
 
@@ -117,42 +136,13 @@ class DiscriminatorEngineCore(EngineBase):
         dlogits = dlogits.contiguous().float()
         A.check(L.srganfd_nchw_to_nhwc(dlogits.data_ptr(), N, 1, sp.dl.shape[1], sp.dl.shape[2], A.view(sp.dl), dtc, sp.dl.shape[-1], None, None, st),
                 "nchw_to_nhwc")
-        flat = self.fp.flat
         # frozen parameters: the weight-gradient launches are skipped; what else lands in the flat gradient goes to scratch
         flat_grad = self.fp.new_grad(sp.device) if need_wgrad else sp.gtmp
-        rec = profiling.REC
-        sn_grads = []
-        for item in sp.bw:
-            kind = item.kind
-            if kind == "conv":
-                ops.conv2d(item.args, rec, "conv2d(dgrad)", L, st)
-            elif kind == "thin":
-                if need_wgrad or not item.is_wgrad:
-                    item.launch(rec, L, st, flat_grad.data_ptr())
-            elif kind == "wgrad":
-                if not need_wgrad:
-                    continue
-                l = item.sn
-                ops.conv2d_wgrad(item.plan, item.x, item.dy, (flat_grad if l is None else sp.gtmp).data_ptr(), sp.wg_ws, rec, L, st)
-                if l is not None:
-                    name, rows, cols = self.sn[l]
-                    off = 4 * self._poff(name)
-                    u, v = self._sn_uv(l)
-                    sn_grads.append((sp.gtmp.data_ptr() + off, flat.data_ptr() + off, u.data_ptr(), v.data_ptr(),
-                                     sp.inv_sigma.data_ptr() + 4 * (2 * l + 1), flat_grad.data_ptr() + off, rows, cols))
-            elif kind == "call":
-                item.launch(rec, L, st)
-            else:
-                self._backward_item(item, sp, flat_grad, L, st)
-        # dL/d(W/sigma) of every spectral-normalised layer sits in its own range of gtmp: one batched pass turns them into dL/dW_orig
-        ops.spectral_norm_grad_batch(sn_grads, sp.sn_ws)
+        run = ops.Run("conv2d(dgrad)", need_wgrad=need_wgrad, grad=flat_grad.data_ptr(), scratch=sp.gtmp.data_ptr(), ws=sp.wg_ws)
+        ops.run_items(sp.bw, run)
         dx = None
         if need_dx:
-            item = sp.dx_conv
-            if item.kind == "thin":
-                item.launch(rec, L, st)
-            else:
-                ops.conv2d(item.args, None, "conv2d(dgrad of the first layer)", L, st)
+            sp.dx_conv.launch(run)
             dx = torch.empty(N, self.in_ch, H, W, dtype=torch.float32, device=sp.device)
             A.check(L.srganfd_nhwc_to_nchw(A.view(sp.dxp), A.F32, N, self.in_ch, H, W, dx.data_ptr(), 0, st), "nhwc_to_nchw")
         return (flat_grad if need_wgrad else None), dx

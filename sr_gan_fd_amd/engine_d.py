@@ -11,7 +11,7 @@ place and produces 1/sigma on the device; the weight packer multiplies it in, so
 W/sigma without an extra pass.  Backward: dL/d(W/sigma) from the wgrad kernel goes through
 srganfd_spectral_norm_grad (both the 1/sigma path and the -<G,W>/sigma^2 u v^T path).
 The stride-2 data gradient runs as 4 output-parity classes, each a 2x2-tap stride-1 conv.
-The launch loops, the spectral-norm plumbing and the autograd glue are engine_core.py's.
+The passes over the launch lists, the spectral-norm plumbing and the autograd glue are engine_core.py's.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ from torch import Tensor, nn
 from . import _abi as A
 from . import ops
 from .engine import _engine, _Shape
-from .engine_core import DiscriminatorEngineCore, discriminator_forward
+from .engine_core import DiscriminatorEngineCore, discriminator_forward, first_layer_dgrad
 
 SN_LAYERS = [("down_block1", 4, 2), ("down_block2", 4, 2), ("down_block3", 4, 2), ("up_block1", 3, 1),
              ("up_block2", 3, 1), ("up_block3", 3, 1), ("conv2", 3, 1), ("conv3", 3, 1)]
@@ -100,11 +100,10 @@ class DiscriminatorEngine(DiscriminatorEngineCore):
             cv(V(sp.u3), V(sp.c2), wptr + O[("f", "conv2")], N, H, W, 64, 64, **lre),
             cv(V(sp.c2), V(sp.c3), wptr + O[("f", "conv3")], N, H, W, 64, 64, **lre),
         ]
+        # conv4 writes the logits, allocated per forward
+        fw.append(ops.PerCall(ops.features_to_image(dtc, sp.thin_o, V(sp.c3), 0, 1, fptr + 4 * self._poff("conv4.weight"), wptr + O[("f", "conv4")],
+                                                    N, H, W, 1, 64, False, bias=fptr + 4 * self._poff("conv4.bias"))))
         sp.fw = fw
-        # locals only: a closure stored on sp that captured `sp` or `self` would be a reference cycle, and the plan's activation
-        # buffers would then outlive the module until a cyclic collection (found as an OOM between full-size tests)
-        thin_o, c3_v, w4raw, w4, b4 = sp.thin_o, V(sp.c3), fptr + 4 * self._poff("conv4.weight"), wptr + O[("f", "conv4")], fptr + 4 * self._poff("conv4.bias")
-        sp.logits_conv = lambda logits: ops.features_to_image(dtc, thin_o, c3_v, logits.data_ptr(), 1, w4raw, w4, N, H, W, 1, 64, False, bias=b4)
         self._plan_backward(sp, pk)
         self.shapes[key] = sp
         return sp
@@ -175,9 +174,10 @@ class DiscriminatorEngine(DiscriminatorEngineCore):
         bw += s2_dgrad("down_block1", h4, gD, H // 2, W // 2, 128, 64, gA, None)         # gD = d out1 (+ skip d u3)
         bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, sp.xin, gD, w1raw, self._poff("conv1.weight"), self._poff("conv1.bias"), sp.thin_ws,
                                   N, H, W, self.in_ch, 64, True))
-        sp.dx_conv = ops.features_to_image(dtc, sp.thin_i, V(gD), sp.dxp, 4, w1raw, wptr + O[("b", "conv1")], N, H, W, self.in_ch, 64, True, flip=True)
+        sp.dx_conv = first_layer_dgrad(ops.features_to_image(dtc, sp.thin_i, V(gD), sp.dxp, 4, w1raw, wptr + O[("b", "conv1")], N, H, W, self.in_ch, 64,
+                                                             True, flip=True))
         sp.bw = bw
-        self._backward_workspaces(sp, wplans)
+        self._backward_workspaces(sp, wplans, pk)
 
 
 def discriminator_engine(owner: nn.Module) -> DiscriminatorEngine:

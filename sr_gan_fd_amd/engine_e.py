@@ -16,17 +16,56 @@ without padding, one output pixel per image), and Linear(100,1) is a 1x1 conv.  
 """
 from __future__ import annotations
 
+import weakref
+
 import torch
 from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
 from .engine import _engine, _Shape
-from .engine_core import DiscriminatorEngineCore, discriminator_forward
+from .engine_core import DiscriminatorEngineCore, discriminator_forward, first_layer_dgrad
 
 CONV_IDX = (0, 2, 5, 8, 11, 14, 17, 20, 23, 26)          # positions of the convs inside `features`
 SLOPE = 0.2
 RING = 4                                                   # activation sets per input shape (live forwards of one iteration)
+
+
+class StageBatchNorm:
+    """BatchNorm2d + LeakyReLU of one stage as one fused pass: the conv's output y -> the activation a, ``npix`` pixels of ``channels``.
+    ``gamma_off`` / ``beta_off``: elements of the flat parameters and gradient; ``bn``: the module (running buffers, momentum, eps, batch
+    counter); ``save``: the statistics the backward pass needs; ``ws``: the plan's statistics workspace"""
+    kind = "bn"
+
+    def __init__(self, eng, y: A.View, a: A.View, dtc: int, npix: int, channels: int, gamma_off: int, beta_off: int, bn: nn.Module, save: Tensor, ws: Tensor):
+        self.eng, self.y, self.a, self.dtc, self.npix, self.channels = weakref.proxy(eng), y, a, dtc, npix, channels     # (a plan must not hold its engine)
+        self.gamma_off, self.beta_off, self.bn, self.save, self.ws = gamma_off, beta_off, bn, save, ws
+
+    def launch(self, run: ops.Run) -> None:
+        bn = self.bn
+        if bn.running_mean.device != self.ws.device:
+            raise A.SrganfdError("BatchNorm buffers must live on the module's GPU")
+        flat = self.eng.fp.flat.data_ptr()
+        A.check(run.L.srganfd_batchnorm_act_fwd(self.y, self.a, self.dtc, self.npix, self.channels, flat + 4 * self.gamma_off, flat + 4 * self.beta_off,
+                                                bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.momentum, bn.eps,
+                                                1 if run.training else 0, self.save.data_ptr(), self.ws.data_ptr(), SLOPE, run.st), "batchnorm_act_fwd")
+        if run.training:
+            bn.num_batches_tracked += 1
+
+
+class StageBatchNormBwd:
+    """backward of the StageBatchNorm ``fwd``: dA (w.r.t. the post-activation) -> dY (w.r.t. the conv output); dgamma / dbeta into the
+    pass's flat gradient"""
+    kind = "bn_bwd"
+
+    def __init__(self, fwd: StageBatchNorm, dA: A.View, dY: A.View):
+        self.fwd, self.dA, self.dY = fwd, dA, dY
+
+    def launch(self, run: ops.Run) -> None:
+        f = self.fwd
+        gamma, beta = 4 * f.gamma_off, 4 * f.beta_off
+        A.check(run.L.srganfd_batchnorm_act_bwd(f.y, self.dA, self.dY, f.dtc, f.npix, f.channels, f.eng.fp.flat.data_ptr() + gamma, f.save.data_ptr(),
+                                                run.grad + gamma, run.grad + beta, 0.0, f.ws.data_ptr(), f.a, SLOPE, run.st), "batchnorm_act_bwd")
 
 
 class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
@@ -76,7 +115,8 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
             f = torch.zeros if zero else torch.empty
             return f(N, h, w, c, dtype=dtype, device=device)
         sp.xin = new(H, W, 32)
-        sp.y, sp.a, sp.save, sp.hw = {}, {}, {}, {}
+        sp.y, sp.a, sp.save, sp.hw, sp.bn = {}, {}, {}, {}, {}
+        sp.bn_ws = torch.empty(2048 * 256 + 3 * 256, dtype=torch.float32, device=device)
         h, w = H, W
         fw = []
         cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
@@ -92,16 +132,17 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
                 sp.y[i] = new(ho, wo, co)
                 sp.save[i] = torch.empty(4 * co, dtype=torch.float32, device=device)
                 fw.append(cv(V(prev), V(sp.y[i]), wptr + O[("f", fi)], N, h, w, ci, co, ksize=ks, stride=st))
-                fw.append(ops.Item("bn", i))
+                sp.bn[i] = StageBatchNorm(self, V(sp.y[i]), V(sp.a[i]), dtc, N * ho * wo, co, self._poff(f"features.{fi + 1}.weight"),
+                                          self._poff(f"features.{fi + 1}.bias"), self.owner.features[fi + 1], sp.save[i], sp.bn_ws)
+                fw.append(sp.bn[i])
             prev, h, w = sp.a[i], ho, wo
         sp.f1 = new(1, 1, self.hid_pad, zero=True)          # padded channels stay zero (they meet zero weights in fc2)
         fw.append(cv(V(sp.a[9]), V(sp.f1), wptr + O[("f", "fc1")], N, 4, 4, 512, self.hid_pad, cout_store=self.hid, ksize=4, stride=2,
                      pad=0, bias=fptr + 4 * self._poff("classifier.0.bias"), act=A.ACT_LRELU, slope=SLOPE))
+        # Linear(100,1) writes the logits, allocated per forward
+        fw.append(ops.PerCall(cv(V(sp.f1), A.View(0, 1, 0), wptr + O[("f", "fc2")], N, 1, 1, self.hid_pad, 32, cout_store=1, ksize=1, pad=0,
+                                 bias=fptr + 4 * self._poff("classifier.2.bias"), y_f32=True)))
         sp.fw = fw
-        f1_v, hid, w2, b2 = V(sp.f1), self.hid_pad, wptr + O[("f", "fc2")], fptr + 4 * self._poff("classifier.2.bias")   # no `sp` / `self` in the closure
-        sp.logits_conv = lambda logits: ops.Conv(ops.conv_args(dtc, f1_v, A.View(logits.data_ptr(), 1, 0), w2, N, 1, 1, hid, 32,
-                                                               cout_store=1, ksize=1, pad=0, bias=b2, y_f32=True))
-        sp.bn_ws = torch.empty(2048 * 256 + 3 * 256, dtype=torch.float32, device=device)
         self._plan_backward(sp, pk)
         self.shapes[key] = sp
         return sp
@@ -142,7 +183,7 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
             fi, ci, co, ks, st = self.convs[i]
             h, w, ho, wo = sp.hw[i]
             dY = new(ho, wo, co)
-            bw.append(ops.Item("bn_bwd", (i, V(dA), V(dY))))
+            bw.append(StageBatchNormBwd(sp.bn[i], V(dA), V(dY)))
             xprev = sp.a[i - 1]
             bw.append(wg(f"features.{fi}.weight", None, xprev, dY, h, w, ci, co, ks, st, 1))
             dAp = new(h, w, ci)
@@ -159,10 +200,10 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
         bw.append(wg("features.0.weight", "features.0.bias", sp.xin, dA, sp.H, sp.W, 32, 64, 3, 1, 1, cin_real=3))
         sp.bw = bw
         sp.dxp = torch.empty(N, sp.H, sp.W, 4, dtype=torch.float32, device=device)
-        sp.dx_conv = cv(V(dA), V(sp.dxp), wptr + O[("b", 0)], N, sp.H, sp.W, 64, 32, cout_store=3, y_f32=True)
-        self._backward_workspaces(sp, wplans)
+        sp.dx_conv = first_layer_dgrad(cv(V(dA), V(sp.dxp), wptr + O[("b", 0)], N, sp.H, sp.W, 64, 32, cout_store=3, y_f32=True))
+        self._backward_workspaces(sp, wplans, pk)
 
-    # ---- execution: the core's loops, plus BatchNorm2d + LeakyReLU as one fused pass per stage ----
+    # ---- execution: the core's passes ----
     def _check_input(self, x: Tensor) -> None:
         super()._check_input(x)
         if tuple(x.shape[2:]) != (128, 128):
@@ -171,33 +212,6 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
 
     def _logits(self, N, H, W, device) -> Tensor:
         return torch.empty(N, 1, dtype=torch.float32, device=device)
-
-    def _bn_args(self, sp, i):
-        """stage i's BatchNorm2d: (module, pixels, channels, element offsets of gamma and beta in the flat buffers)"""
-        fi, _, co, _, _ = self.convs[i]
-        _, _, ho, wo = sp.hw[i]
-        return self.owner.features[fi + 1], sp.N * ho * wo, co, 4 * self._poff(f"features.{fi + 1}.weight"), 4 * self._poff(f"features.{fi + 1}.bias")
-
-    def _forward_item(self, item, sp, training, L, st) -> None:
-        """Item("bn", i): BatchNorm2d + LeakyReLU of stage i"""
-        i = item.payload
-        bn, npix, co, gamma, beta = self._bn_args(sp, i)
-        if bn.running_mean.device != sp.device:
-            raise A.SrganfdError("BatchNorm buffers must live on the module's GPU")
-        flat = self.fp.flat.data_ptr()
-        A.check(L.srganfd_batchnorm_act_fwd(A.view(sp.y[i]), A.view(sp.a[i]), sp.dtc, npix, co, flat + gamma, flat + beta,
-                                            bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.momentum, bn.eps,
-                                            1 if training else 0, sp.save[i].data_ptr(), sp.bn_ws.data_ptr(), SLOPE, st), "batchnorm_act_fwd")
-        if training:
-            bn.num_batches_tracked += 1
-
-    def _backward_item(self, item, sp, flat_grad, L, st) -> None:
-        """Item("bn_bwd", (i, dA, dY)): dA (w.r.t. the post-activation) -> dY (w.r.t. the conv output); dgamma / dbeta into the flat gradient"""
-        i, dAv, dYv = item.payload
-        _, npix, co, gamma, beta = self._bn_args(sp, i)
-        A.check(L.srganfd_batchnorm_act_bwd(A.view(sp.y[i]), dAv, dYv, sp.dtc, npix, co, self.fp.flat.data_ptr() + gamma, sp.save[i].data_ptr(),
-                                            flat_grad.data_ptr() + gamma, flat_grad.data_ptr() + beta, 0.0, sp.bn_ws.data_ptr(),
-                                            A.view(sp.a[i]), SLOPE, st), "batchnorm_act_bwd")
 
 
 def esrgan_discriminator_engine(owner: nn.Module) -> EsrganDiscriminatorEngine:

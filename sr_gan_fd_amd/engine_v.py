@@ -20,7 +20,6 @@ from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
-from . import profiling
 from .engine import EngineBase, _dt, _engine, _require_gpu, _Shape
 
 
@@ -73,10 +72,70 @@ class VggEngineBase(EngineBase):
         return ops.Conv(ops.conv_args(dtc, A.view(x), A.view(y), pk["buf"].data_ptr() + pk["offs"][self._fkey(idx)], n, h, w, cin, co, bias=bias, act=act))
 
 
+class LossTap:
+    """L1 distance between the SR half ``a`` and the GT half ``b`` of a feature map (``npix`` pixels of ``channels``), written to float
+    ``slot`` of the pass's loss vector (``run.out``, zeroed per call)"""
+    kind = "loss_tap"
+
+    def __init__(self, feat: Tensor, dtc: int, slot: int, ws: Tensor):
+        n2, h, w, c = feat.shape
+        gt_half = feat.data_ptr() + feat[:n2 // 2].numel() * feat.element_size()
+        self.a, self.b = A.View(feat.data_ptr(), c, 0), A.View(gt_half, c, 0)
+        self.dtc, self.npix, self.channels, self.slot, self.ws = dtc, n2 // 2 * h * w, c, slot, ws
+
+    def launch(self, run: ops.Run) -> None:
+        A.check(run.L.srganfd_l1_loss_views(self.a, self.b, self.dtc, self.npix, self.channels, 0, 1.0, run.out + 4 * self.slot, 0, self.ws.data_ptr(),
+                                            run.st), "l1_views")
+
+
 class ContentLossEngine(VggEngineBase):
     def __init__(self, owner: nn.Module):
         super().__init__(owner, len(owner.features))
         self.want = [int(n.split(".")[1]) for n in owner.feature_model_extractor_nodes]
+
+    def _plan(self, N, Cin, H, W, dt, dtc, dev, pk):
+        key = (N, H, W, dtc, str(dev), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
+        sp = self.shapes.get(key)
+        if sp is not None:
+            return sp
+        sp = _Shape()
+        self._new_input(sp, N, H, W, Cin, dt, dtc, dev)
+        sp.bufs = {}
+        sp.ws = torch.empty(A.LOSS_WS_FLOATS, dtype=torch.float32, device=dev)
+        sp.dt, sp.dtc = dt, dtc
+        last = max(self.want)
+        post = self.owner.taps_post_relu
+        cur, ch, h, w = sp.xin, 32, H, W
+
+        def buf(tag, hh, ww, cc):
+            b = sp.bufs.get((tag, hh, ww, cc))
+            if b is None:
+                b = torch.empty(2 * N, hh, ww, cc, dtype=dt, device=dev)
+                sp.bufs[(tag, hh, ww, cc)] = b
+            return b
+        fw, flip = [], 0
+        for idx in range(last + 1):
+            m = self.owner.features[idx]
+            if isinstance(m, nn.Conv2d):
+                co = m.weight.shape[0]
+                out = buf(flip, h, w, co)
+                flip ^= 1
+                tap = idx in self.want
+                # taps are observed after the in-place ReLU unless they are the last requested node
+                relu_in_conv = not (tap and (idx == last or not post))
+                fw.append(self._feature_conv(sp, pk, dtc, idx, cur, out, ch, A.ACT_RELU if relu_in_conv else A.ACT_NONE))
+                if tap:
+                    fw.append(LossTap(out, dtc, self.want.index(idx), sp.ws))
+                    if not relu_in_conv and idx != last:
+                        fw.append(ops.Call("srganfd_resample", (4, A.view(out), A.view(out), dtc, 2 * N, h, w, co), "relu"))
+                cur, ch = out, co
+            elif isinstance(m, nn.MaxPool2d):
+                out = buf("p", h // 2, w // 2, ch)
+                fw.append(ops.Call("srganfd_resample", (3, A.view(cur), A.view(out), dtc, 2 * N, h, w, ch), "maxpool"))
+                cur, h, w = out, h // 2, w // 2
+        sp.fw = fw
+        self.shapes[key] = sp
+        return sp
 
     def forward(self, sr: Tensor, gt: Tensor) -> Tensor:
         _require_gpu(sr)
@@ -87,55 +146,10 @@ class ContentLossEngine(VggEngineBase):
         if H < 16 or W < 16:
             raise A.SrganfdError("ContentLoss input height/width must be at least 16 (four 2x2 max-pools; odd sizes floor like torch)")
         L, st = A.lib(), A.stream_ptr()
-        key = (N, H, W, dtc, str(dev), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
-        sp = self.shapes.get(key)
-        if sp is None:
-            sp = _Shape()
-            self._new_input(sp, N, H, W, Cin, dt, dtc, dev)
-            sp.bufs = {}
-            sp.ws = torch.empty(A.LOSS_WS_FLOATS, dtype=torch.float32, device=dev)
-            sp.dt, sp.dtc = dt, dtc
-            self.shapes[key] = sp
-        self._last = sp
+        sp = self._last = self._plan(N, Cin, H, W, dt, dtc, dev, pk)
         self._load_input(sp, sr, gt, dtc, L, st)
         losses = torch.zeros(len(self.want), dtype=torch.float32, device=dev)
-        last = max(self.want)
-        post = self.owner.taps_post_relu
-        cur, ch, h, w = sp.xin, 32, H, W
-        rec = profiling.REC
-
-        def buf(tag, hh, ww, cc):
-            b = sp.bufs.get((tag, hh, ww, cc))
-            if b is None:
-                b = torch.empty(2 * N, hh, ww, cc, dtype=dt, device=dev)
-                sp.bufs[(tag, hh, ww, cc)] = b
-            return b
-        flip = 0
-        for idx in range(last + 1):
-            m = self.owner.features[idx]
-            if isinstance(m, nn.Conv2d):
-                co = m.weight.shape[0]
-                out = buf(flip, h, w, co)
-                flip ^= 1
-                tap = idx in self.want
-                # taps are observed after the in-place ReLU unless they are the last requested node
-                relu_in_conv = not (tap and (idx == last or not post))
-                item = self._feature_conv(sp, pk, dtc, idx, cur, out, ch, A.ACT_RELU if relu_in_conv else A.ACT_NONE)
-                if item.kind == "conv":
-                    ops.conv2d(item.args, rec, "conv2d(vgg)", L, st)
-                else:
-                    item.launch(rec, L, st)
-                if tap:
-                    half_b = N * h * w * co * out.element_size()
-                    A.check(L.srganfd_l1_loss_views(A.View(out.data_ptr(), co, 0), A.View(out.data_ptr() + half_b, co, 0), dtc, N * h * w, co, 0, 1.0,
-                                                    losses.data_ptr() + 4 * self.want.index(idx), 0, sp.ws.data_ptr(), st), "l1_views")
-                    if not relu_in_conv and idx != last:
-                        A.check(L.srganfd_resample(4, A.view(out), A.view(out), dtc, 2 * N, h, w, co, st), "relu")
-                cur, ch = out, co
-            elif isinstance(m, nn.MaxPool2d):
-                out = buf("p", h // 2, w // 2, ch)
-                A.check(L.srganfd_resample(3, A.view(cur), A.view(out), dtc, 2 * N, h, w, ch, st), "maxpool")
-                cur, h, w = out, h // 2, w // 2
+        ops.run_items(sp.fw, ops.Run("conv2d(vgg)", out=losses.data_ptr()))
         return losses.view(1, -1)
 
 
@@ -166,7 +180,7 @@ class ContentLossGradEngine(VggEngineBase):
         self._new_input(sp, N, H, W, 3, dt, dtc, dev)      # (thin: features.0's data gradient runs on the thin-side kernel too)
         half = lambda t: A.View(t.data_ptr(), t.shape[3], 0)                     # SR half (first N images)
         other = lambda t: A.View(t.data_ptr() + t[:N].numel() * es, t.shape[3], 0)   # GT half
-        fw, chain = [], []          # chain: (kind, index, tensor, h, w, c) in forward order
+        fw, chain = [], []          # chain: (layer, index, input, output, h, w, cin, cout) in forward order
         cur, ch, h, w = sp.xin, 32, H, W
         sp.keep = [sp.xin]
         for idx in range(self.last + 1):
@@ -179,14 +193,15 @@ class ContentLossGradEngine(VggEngineBase):
                 cur, ch = out, co
             elif isinstance(m, nn.MaxPool2d):
                 out = torch.empty(2 * N, h // 2, w // 2, ch, dtype=dt, device=dev)
-                fw.append(ops.Item("pool", (A.view(cur), A.view(out), h, w, ch)))
+                fw.append(ops.Call("srganfd_resample", (3, A.view(cur), A.view(out), dtc, 2 * N, h, w, ch), "maxpool"))
                 chain.append(("pool", idx, cur, out, h, w, ch, ch))
                 cur, h, w = out, h // 2, w // 2
             sp.keep.append(cur)
-        sp.fw = fw
         sp.feat, sp.feat_dims = cur, (h, w, ch)
         sp.loss_views = (half(cur), other(cur))
         sp.ws = torch.empty(A.LOSS_WS_FLOATS, dtype=torch.float32, device=dev)
+        fw.append(LossTap(cur, dtc, 0, sp.ws))           # the loss, a one-element vector allocated per forward
+        sp.fw = fw
         # ---- backward launch list (SR half only) ----
         bw = []
         g = torch.empty(N, h, w, ch, dtype=dt, device=dev)
@@ -194,27 +209,20 @@ class ContentLossGradEngine(VggEngineBase):
         sp.keep.append(g)
         sp.dxp = torch.empty(N, H, W, 4, dtype=torch.float32, device=dev)
         for j in range(len(chain) - 1, -1, -1):
-            kind, idx, tin, tout, hh, ww, cin, cout = chain[j]
-            if kind == "conv":
-                if idx == 0:
-                    if sp.thin:
-                        bw.append(ops.ThinLaunch("thin_out", ops.thin_args(dtc, N, hh, ww, 3, fptr + 4 * self.fp.off("features.0.weight"), A.view(g),
-                                                                           w_big_is_cout=True, flip=True, thin_out=sp.dxp, thin_out_pitch=4)))
-                    else:
-                        bw.append(ops.Conv(ops.conv_args(dtc, A.view(g), A.view(sp.dxp), wptr + O[("b", 0)], N, hh, ww, cout, 32, cout_store=3, y_f32=True)))
-                    break
-                prev_kind = chain[j - 1][0]
-                gin = torch.empty(N, hh, ww, cin, dtype=dt, device=dev)
-                sp.keep.append(gin)
+            layer, idx, tin, tout, hh, ww, cin, cout = chain[j]
+            if idx == 0:
+                bw.append(ops.features_to_image(dtc, sp.thin, A.view(g), sp.dxp, 4, fptr + 4 * self.fp.off("features.0.weight"), wptr + O[("b", 0)],
+                                                N, hh, ww, 3, cout, True, flip=True))
+                break
+            gin = torch.empty(N, hh, ww, cin, dtype=dt, device=dev)
+            sp.keep.append(gin)
+            if layer == "conv":
                 # the conv's input is a ReLU output (mask it here) or a pooled map (the pool's backward applies the ReLU')
-                mask = half(tin) if prev_kind == "conv" else A.NULL_VIEW
+                mask = half(tin) if chain[j - 1][0] == "conv" else A.NULL_VIEW
                 bw.append(ops.Conv(ops.conv_args(dtc, A.view(g), A.view(gin), wptr + O[("b", idx)], N, hh, ww, cout, cin, mask=mask, mask_slope=0.0)))
-                g = gin
             else:
-                gin = torch.empty(N, hh, ww, cin, dtype=dt, device=dev)
-                sp.keep.append(gin)
-                bw.append(ops.Item("poolbwd", (half(tin), A.view(g), A.view(gin), hh, ww, cin)))
-                g = gin
+                bw.append(ops.Call("srganfd_maxpool2_relu_bwd", (half(tin), A.view(g), A.view(gin), dtc, N, hh, ww, cin), "maxpool2_relu_bwd"))
+            g = gin
         sp.bw = bw
         self.shapes[key] = sp
         return sp
@@ -230,19 +238,8 @@ class ContentLossGradEngine(VggEngineBase):
         sp = self._plan(N, H, W, dt, dtc, dev, pk)
         L, st = A.lib(), A.stream_ptr()
         self._load_input(sp, sr, gt, dtc, L, st)
-        rec = profiling.REC
-        for item in sp.fw:
-            kind = item.kind
-            if kind == "conv":
-                ops.conv2d(item.args, rec, "conv2d(vgg)", L, st)
-            elif kind == "thin":
-                item.launch(rec, L, st)
-            else:                                   # "pool"
-                xv, yv, h, w, c = item.payload
-                A.check(L.srganfd_resample(3, xv, yv, dtc, 2 * N, h, w, c, st), "maxpool")
         loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        h, w, c = sp.feat_dims
-        A.check(L.srganfd_l1_loss_views(sp.loss_views[0], sp.loss_views[1], dtc, N * h * w, c, 0, 1.0, loss.data_ptr(), 0, sp.ws.data_ptr(), st), "l1_views")
+        ops.run_items(sp.fw, ops.Run("conv2d(vgg)", out=loss.data_ptr()))
         self.token += 1
         sp.token = self.token
         self._last = sp
@@ -261,16 +258,7 @@ class ContentLossGradEngine(VggEngineBase):
             upstream_ptr = dloss.data_ptr()
         A.check(L.srganfd_l1_grad_views(sp.loss_views[0], sp.loss_views[1], A.view(sp.g_tap), dtc, N * h * w, c, upstream_ptr,
                                         weight / float(N * h * w * c), st), "l1_grad_views")
-        rec = profiling.REC
-        for item in sp.bw:
-            kind = item.kind
-            if kind == "conv":
-                ops.conv2d(item.args, rec, "conv2d(vgg dgrad)", L, st)
-            elif kind == "thin":
-                item.launch(rec, L, st)
-            else:                                   # "poolbwd"
-                xv, dyv, dxv, hh, ww, cc = item.payload
-                A.check(L.srganfd_maxpool2_relu_bwd(xv, dyv, dxv, dtc, N, hh, ww, cc, st), "maxpool2_relu_bwd")
+        ops.run_items(sp.bw, ops.Run("conv2d(vgg dgrad)"))
         dsr = torch.empty(N, 3, sp.H, sp.W, dtype=torch.float32, device=sp.device)
         A.check(L.srganfd_nhwc_to_nchw_scaled(A.view(sp.dxp), N, 3, sp.H, sp.W, dsr.data_ptr(), self.owner.std.data_ptr(), st), "nhwc_to_nchw_scaled")
         return dsr

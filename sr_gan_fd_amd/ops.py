@@ -194,47 +194,140 @@ def conv2d(args: A.ConvArgs, rec=None, what: str = "conv2d", L=None, st=None) ->
         rec.bracket(profiling.conv_label(args), profiling.conv_work(args), lambda: A.check(L.srganfd_conv2d(C.byref(args), st), what))
 
 
-# ---- launch items: what the engines' per-shape launch lists (sp.fw / sp.bw) hold.  The loops dispatch on ``item.kind``: "conv" (Conv),
-# "thin" (ThinLaunch), "chain" (DenseChain), "call" (Call), "wgrad" (Wgrad) and, as Item(kind, payload), the markers of the generator's
-# backward list ("ready", "fence") and the kinds only one engine launches ("bn", "bn_bwd", "pool", "poolbwd").  An item holds structs and
-# addresses, never a closure: what the addresses point to is kept alive by the plan's buffers.
-class Item:
-    __slots__ = ("kind", "payload")
+# ---- launch items: what the engines' per-shape launch lists (sp.fw / sp.bw) hold.  Every item has ``launch(run)`` and ``run_items`` is
+# the one loop over a list; ``kind`` names the class for tests and debugging, nothing dispatches on it.  Here: Conv, Call, Wgrad,
+# WgradPartial / WgradReduce (the generator's dense blocks: batched slab reduction), Ready (the generator's gradient buckets), PerCall (a
+# layer that writes the pass's own output) and, further down, DenseChain and ThinLaunch; the engines define the items only they launch
+# beside themselves (BatchNorm, the spectral-norm gradient, the loss taps).  An item holds structs and addresses, never a closure:
+# what the addresses point to is kept alive by the plan's buffers.
+class Run:
+    """What one pass over a launch list needs besides the items: the library handle, the stream and profiling.REC; ``what``: the name
+    A.check reports for the list's convs; the ``training`` / ``need_wgrad`` flags of the pass; the addresses that exist per call only
+    -- ``grad`` (the flat gradient), ``scratch`` (where a spectral-normalised layer's weight gradient goes first) and ``out`` (the
+    logits, the loss vector); ``ws``: the workspace the list's weight-gradient launches share; ``on_ready(lo, hi)``: told when
+    elements [lo, hi) of the flat gradient are final."""
+    __slots__ = ("L", "st", "rec", "what", "training", "need_wgrad", "grad", "scratch", "out", "ws", "on_ready")
 
-    def __init__(self, kind: str, payload=None):
-        self.kind, self.payload = kind, payload
+    def __init__(self, what: str, training: bool = False, need_wgrad: bool = True, grad: int = 0, scratch: int = 0, out: int = 0,
+                 ws: Optional[torch.Tensor] = None, on_ready=None):
+        self.L, self.st, self.rec = A.lib(), A.stream_ptr(), profiling.REC
+        self.what, self.training, self.need_wgrad = what, training, need_wgrad
+        self.grad, self.scratch, self.out, self.ws, self.on_ready = grad, scratch, out, ws, on_ready
+
+
+def run_items(items: Sequence, run: Run) -> None:
+    for item in items:
+        item.launch(run)
 
 
 class Conv:
-    """one fused-conv launch: ``conv2d(item.args, rec, what, L, st)``"""
+    """one fused-conv launch"""
     __slots__ = ("args",)
     kind = "conv"
 
     def __init__(self, args: A.ConvArgs):
         self.args = args
 
+    def launch(self, run: Run) -> None:
+        conv2d(self.args, run.rec, run.what, run.L, run.st)
+
+    def set_output(self, ptr: int) -> None:
+        self.args.y.ptr = ptr
+
+
+class PerCall:
+    """a Conv or thin_out ThinLaunch whose output is the pass's own (``run.out``: allocated per call), put into the struct at launch"""
+    __slots__ = ("item",)
+    kind = "per_call"
+
+    def __init__(self, item):
+        self.item = item
+
+    def launch(self, run: Run) -> None:
+        self.item.set_output(run.out)
+        self.item.launch(run)
+
 
 class Call:
-    """an auxiliary kernel: the C entry point's name, its arguments without the trailing stream, and what A.check reports"""
+    """an auxiliary kernel: the C entry point's name, its arguments without the trailing stream, and what A.check reports (never bracketed)"""
     __slots__ = ("name", "args", "what")
     kind = "call"
 
     def __init__(self, name: str, args: tuple, what: str):
         self.name, self.args, self.what = name, args, what
 
-    def launch(self, rec, L, st) -> None:          # (never bracketed: ``rec`` is there for the signature ThinLaunch and DenseChain have)
-        A.check(getattr(L, self.name)(*self.args, st), self.what)
+    def launch(self, run: Run) -> None:
+        A.check(getattr(run.L, self.name)(*self.args, run.st), self.what)
+
+
+class Ready:
+    """marker of the generator's backward list: every launch that writes elements [lo, hi) of the flat gradient has been enqueued"""
+    __slots__ = ("lo", "hi")
+    kind = "ready"
+
+    def __init__(self, lo: int, hi: int):
+        self.lo, self.hi = lo, hi
+
+    def launch(self, run: Run) -> None:
+        if run.on_ready is not None:
+            run.on_ready(self.lo, self.hi)
 
 
 class Wgrad:
-    """one weight-gradient launch of ``plan`` over the views x / dy.  ``dw_off``: elements added to the flat gradient's base (the
-    generator's dense-block plans hold offsets relative to their block); ``sn``: the spectral-norm slot of a discriminator layer, whose
-    gradient goes to the scratch buffer first, or None; ``block``: the generator's dense-block index (batched slab reduction), or None"""
+    """one weight-gradient launch of ``plan`` over the views x / dy, skipped by a pass with frozen parameters.  ``dw_off``: elements
+    added to the flat gradient's base (the generator's dense-block plans hold offsets relative to their block); ``sn``: the
+    spectral-norm slot of a discriminator layer, whose gradient goes to the scratch buffer first, or None; ``block``: the generator's
+    dense-block index (engine.batch_reductions turns these into WgradPartial + WgradReduce), or None"""
     __slots__ = ("plan", "x", "dy", "dw_off", "sn", "block")
     kind = "wgrad"
 
     def __init__(self, plan: "WgradPlan", x: A.View, dy: A.View, dw_off: int = 0, sn: Optional[int] = None, block: Optional[int] = None):
         self.plan, self.x, self.dy, self.dw_off, self.sn, self.block = plan, x, dy, dw_off, sn, block
+
+    def launch(self, run: Run) -> None:
+        if run.need_wgrad:
+            conv2d_wgrad(self.plan, self.x, self.dy, (run.grad if self.sn is None else run.scratch) + 4 * self.dw_off, run.ws, run.rec, run.L, run.st)
+
+
+class _Bracketed:
+    """base of the items profiling.REC brackets under their ``label`` and algorithmic ``work``; ``_issue(run)`` makes the call"""
+
+    def launch(self, run: Run) -> None:
+        if run.rec is None:
+            self._issue(run)
+        else:
+            run.rec.bracket(self.label, self.work, lambda: self._issue(run))
+
+
+class WgradPartial(_Bracketed):
+    """a dense block's weight-gradient MFMA launch alone: the slabs stay in ``ws``, workspace ``slot`` of the batch a WgradReduce reduces"""
+    kind = "wgrad_partial"
+
+    def __init__(self, wg: Wgrad, slot: int, ws: torch.Tensor):
+        self.plan, self.x, self.dy, self.dw_off, self.slot, self.ws = wg.plan, wg.x, wg.dy, wg.dw_off, slot, ws
+        self.label, self.work = wg.plan.label, (wg.plan.flops, wg.plan.nbytes)
+
+    def _issue(self, run: Run) -> None:
+        plan, ws = self.plan, self.ws
+        A.check(run.L.srganfd_conv2d_wgrad_partial(plan.host, plan.dev.data_ptr(), self.x, self.dy, ws.data_ptr(), ws.numel(), run.st), "conv2d_wgrad_partial")
+
+
+class WgradReduce(_Bracketed):
+    """the slab reduction of up to SRGANFD's kRedBatch WgradPartial launches as ONE launch (the reduction is latency-bound at ~20 us
+    whatever it reduces).  The job array is built with the plan; a launch fills in where the pass's flat gradient is."""
+    kind, label = "wgrad_reduce", "wgrad_reduce_batch"
+
+    def __init__(self, partials: Sequence[WgradPartial]):
+        self.partials, self.n = list(partials), len(partials)
+        self.jobs = (A.WgradReduceJob * self.n)()
+        for j, p in zip(self.jobs, self.partials):
+            j.plan_host, j.plan_dev, j.scalars, j.workspace = C.addressof(p.plan.host), p.plan.dev.data_ptr(), None, p.ws.data_ptr()
+        self.work = (0.0, float(sum(p.ws.numel() for p in self.partials)))
+
+    def _issue(self, run: Run) -> None:
+        for j, p in zip(self.jobs, self.partials):
+            j.grads = run.grad + 4 * p.dw_off
+        A.check(run.L.srganfd_wgrad_reduce_batch(self.jobs, self.n, run.st), "wgrad_reduce_batch")
 
 
 # ---- LDS-resident dense-block launch (csrc/dense_chain.hip): the five convs of a dense block, or of its data-gradient pass, as one launch ----
@@ -272,7 +365,7 @@ def dense_chain_wanted(n: int, h: int, w: int, cus: int = 256) -> bool:
     return DENSE_CHAIN == "1" or n * per <= cus
 
 
-class DenseChain:
+class DenseChain(_Bracketed):
     """n conv launches (A.ConvArgs, the arguments srganfd_conv2d would get) run by srganfd_dense_chain; ``ok`` False when the library
     refuses them (then the caller keeps the separate launches)."""
     kind = "chain"
@@ -297,11 +390,8 @@ class DenseChain:
             L, st = A.lib(), A.stream_ptr()
         A.check(L.srganfd_dense_chain(self.arr, self.n, self.ws.data_ptr(), self.ws.numel(), st), "dense_chain")
 
-    def launch(self, rec, L, st) -> None:
-        if rec is None:
-            self.run(L, st)
-        else:
-            rec.bracket(self.label, self.work, lambda: self.run(L, st))
+    def _issue(self, run: Run) -> None:
+        self.run(run.L, run.st)
 
     def errors(self) -> int:
         """hand-off waits that gave up since the workspace was allocated (synchronises; tests)"""
@@ -368,9 +458,9 @@ def thin_wgrad(a: A.ThinArgs, dw, db, workspace: torch.Tensor) -> None:
                                               A.stream_ptr()), "conv2d_thin_wgrad")
 
 
-class ThinLaunch:
+class ThinLaunch(_Bracketed):
     """One thin-side launch in an engine's launch list.  op: "thin_in" / "thin_out" / "thin_wgrad" (the latter writes the weight and
-    bias gradient at element offsets ``dw_off`` / ``db_off`` of the flat gradient whose address ``launch`` is given)."""
+    bias gradient at element offsets ``dw_off`` / ``db_off`` of the pass's flat gradient, and is skipped by a pass with frozen parameters)."""
     kind = "thin"
 
     def __init__(self, op: str, args: A.ThinArgs, dw_off: int = -1, db_off: int = -1, ws: Optional[torch.Tensor] = None):
@@ -379,10 +469,15 @@ class ThinLaunch:
         self.label = "%s_kernel<%s%s>" % (op, A.DT_NAME[args.dtype], ",mask" if args.mask.ptr else "")
         self.work = thin_work(args, op)
 
-    def launch(self, rec, L, st, grad_ptr: int = 0) -> None:
-        if rec is not None:
-            return rec.bracket(self.label, self.work, lambda: self.launch(None, L, st, grad_ptr))
-        a = self.args
+    def set_output(self, ptr: int) -> None:
+        self.args.thin_out = ptr
+
+    def launch(self, run: Run) -> None:
+        if run.need_wgrad or not self.is_wgrad:
+            _Bracketed.launch(self, run)
+
+    def _issue(self, run: Run) -> None:
+        a, L, st, grad_ptr = self.args, run.L, run.st, run.grad
         if self.op == "thin_in":
             rc = L.srganfd_conv2d_thin_in(C.byref(a), st)
         elif self.op == "thin_out":

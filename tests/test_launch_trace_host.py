@@ -135,7 +135,7 @@ class Recorder:
         return sorted(out)
 
 
-# ---- scenarios: tiny shapes, one num_rrdb=1 generator; each returns what must stay alive until the tables are read ----
+# ---- scenarios: tiny shapes, num_rrdb=1 generators but for generator_only_rrdb2; each returns what must stay alive until the tables are read ----
 def _pin(dt, *modules):
     for m in modules:
         m.compute_dtype = dt
@@ -167,10 +167,10 @@ def _esrgan(dt):
     return g, d, cl, tr
 
 
-def _g_only(dt):
+def _g_only(dt, num_rrdb=1):
     from sr_gan_fd_amd import model as M
     from sr_gan_fd_amd.trainer import GeneratorTrainer
-    g, = _pin(dt, M.bsrgan_x4(num_rrdb=1))
+    g, = _pin(dt, M.bsrgan_x4(num_rrdb=num_rrdb))
     tr = GeneratorTrainer(g, lr=1e-4)
     tr.step(torch.rand(2, 3, 16, 16), torch.rand(2, 3, 64, 64))
     return g, tr
@@ -213,6 +213,8 @@ SCENARIOS = {
     "esrgan_gan": _esrgan,
     "generator_only": _g_only,
     "modules": _modules,
+    # six dense blocks: one full batch of four slab reductions and a remainder of two, and the mid-trunk bucket marker (R >= 4)
+    "generator_only_rrdb2": lambda dt: _g_only(dt, 2),
 }
 CASES = ["%s-%s" % (s, d) for s in SCENARIOS for d in DTYPES]
 
