@@ -646,6 +646,22 @@ int srganfd_attention_fwd(const srganfd_attn_args* a, void* stream);
 int srganfd_attention_weights(const srganfd_attn_args* a, void* stream);
 int srganfd_attention_bwd(const srganfd_attn_args* a, void* stream);
 
+/* ---- A-ESRGAN's pixel attention (A-ESRGAN/model.py:105-106 in US, :136-137 in RPA; csrc/pixel_gate.hip) ----
+ * A feature map times 1 + sigmoid of a pre-activation map, per pixel and channel, with s = sigmoid(a):
+ *   bwd = 0   z = x * (1 + s)                                      z_or_dz is z; dx and da are not used (null views)
+ *   bwd = 1   dx = dz * (1 + s),  da = dz * x * s * (1 - s)        z_or_dz is dz; s is recomputed from a, no sigmoid map is stored
+ * One grid-stride pass over npix pixels x c channels; every view is an NHWC channel slice of type `dtype` (F32 / F16 / BF16), the
+ * arithmetic is fp32 with one rounding at the store; one owner per element, no atomics: bit-reproducible.  |a| of any size gives
+ * finite results (the exponential is taken of -|a|).
+ * Aliasing: z may alias neither x nor a; dx may alias nothing that the pass reads (x, a, dz); da may be dz itself, the same view,
+ * written in place (a lane reads its 16 bytes of dz before it writes them), and may alias nothing else.  Slices of one buffer at
+ * disjoint channel ranges do not alias.
+ * SRGANFD_EINVAL: a bad dtype; npix <= 0; c not a positive multiple of 32; among the views the pass uses a null pointer, a planar
+ * view, a pointer that is not 16-byte aligned, c0 or cstride that is no multiple of 8 elements (every lane moves 16 bytes), a slice
+ * that exceeds its buffer's channels (c0 + c > cstride), or aliasing other than the above. */
+int srganfd_pixel_gate(int32_t bwd, srganfd_view x, srganfd_view a, srganfd_view z_or_dz, srganfd_view dx, srganfd_view da,
+                       int32_t dtype, int64_t npix, int32_t c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

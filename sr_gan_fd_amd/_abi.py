@@ -249,6 +249,7 @@ SYMBOLS = {
     "srganfd_attention_fwd": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
     "srganfd_attention_weights": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
     "srganfd_attention_bwd": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
+    "srganfd_pixel_gate": (C.c_int, [C.c_int32, View, View, View, View, View, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
 }
 
 LOSS_WS_FLOATS = 2049

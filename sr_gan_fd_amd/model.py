@@ -33,6 +33,7 @@ __all__ = [
     "UNetDiscriminatorAesrgan", "uNetDiscriminatorAesrgan",
     "Discriminator", "discriminator",
     "SelfAttention", "BSRGANsa", "bsrgansa_x2",
+    "RPA", "US", "Generator_RPA", "gen_rpa2x",
 ]
 
 
@@ -322,6 +323,86 @@ class Discriminator(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         from .engine_e import esrgan_discriminator_apply
         return esrgan_discriminator_apply(self, x)
+
+
+class US(nn.Module):
+    """A-ESRGAN/model.py:87-109: up-sampling block with pixel attention (nearest x2, 1x1 conv, LeakyReLU, the gate
+    ``x * sigmoid(pa_conv(x)) + x``, 3x3 conv, LeakyReLU).  Parameter container; forward and backward run on the HIP engine
+    (engine_rpa.py), which applies the per-pixel layers before the up-sampling (same values, a quarter of the work).  Only ``scale`` 2
+    has a kernel (the only value the reference's generator passes)."""
+
+    def __init__(self, num_feat, scale):
+        super().__init__()
+        from .engine_rpa import check_features
+        check_features("us", num_feat)
+        self.scale = scale
+        self.conv1 = nn.Conv2d(num_feat, num_feat, 1)
+        self.pa_conv = nn.Conv2d(num_feat, num_feat, 1)
+        self.pa_sigmoid = nn.Sigmoid()
+        self.conv2 = nn.Conv2d(num_feat, num_feat, 3, 1, 1)
+        self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+        self.compute_dtype = None
+
+    def forward(self, x: Tensor) -> Tensor:
+        from .engine_rpa import rpa_apply
+        return rpa_apply(self, "us", x)
+
+
+class RPA(nn.Module):
+    """A-ESRGAN/model.py:112-140: residual pixel-attention block (1x1 convs F -> 2F -> 4F, 3x3 conv 4F -> F, the gate
+    ``x * sigmoid(.) + x``, 3x3 conv F -> F, LeakyReLU).  Parameter container; forward and backward run on the HIP engine
+    (engine_rpa.py)."""
+
+    def __init__(self, num_feat):
+        super().__init__()
+        from .engine_rpa import check_features
+        check_features("rpa", num_feat)
+        self.conv1 = nn.Conv2d(num_feat, num_feat * 2, 1)
+        self.conv2 = nn.Conv2d(num_feat * 2, num_feat * 4, 1)
+        self.conv3 = nn.Conv2d(num_feat * 4, num_feat, 3, 1, 1)
+        self.conv4 = nn.Conv2d(num_feat, num_feat, 3, 1, 1)
+        self.sigmoid = nn.Sigmoid()
+        self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+        # model.py:125-128, literally: conv3 is drawn twice and conv4 keeps nn.Conv2d's own initialisation -- the same random stream,
+        # so a seeded construction gives the reference's initial values
+        for layer in [self.conv1, self.conv2, self.conv3, self.conv3]:
+            nn.init.kaiming_normal_(layer.weight)
+            layer.weight.data *= 0.1
+        self.compute_dtype = None
+
+    def forward(self, x: Tensor) -> Tensor:
+        from .engine_rpa import rpa_apply
+        return rpa_apply(self, "rpa", x)
+
+
+class Generator_RPA(nn.Module):
+    """A-ESRGAN/model.py:144-175: conv1, ``num_block`` RPA blocks, the long skip, ceil(log2(scale)) US blocks, conv2, conv3.  Same
+    constructor arguments, state_dict keys (``conv1..3``, ``rpa.rpa{i}.conv1..4``, ``us.us{i}.conv1 / pa_conv / conv2``) and
+    construction order.  ``num_feat`` must be a multiple of 64 (conv2 writes num_feat // 2 channels)."""
+
+    def __init__(self, num_in_ch=3, num_out_ch=3, scale=2, num_feat=64, num_block=20):
+        super().__init__()
+        from collections import OrderedDict
+        from .engine_rpa import check_features, num_usblock
+        check_features("gen", num_feat)
+        self.scale = scale
+        self.conv1 = nn.Conv2d(num_in_ch, num_feat, 3, 1, 1)
+        self.rpa = nn.Sequential(OrderedDict([("rpa{}".format(i), RPA(num_feat=num_feat)) for i in range(num_block)]))
+        self.us = nn.Sequential(OrderedDict([("us{}".format(i), US(num_feat=num_feat, scale=2)) for i in range(num_usblock(scale))]))
+        self.conv2 = nn.Conv2d(num_feat, num_feat // 2, 3, 1, 1)
+        self.conv3 = nn.Conv2d(num_feat // 2, num_out_ch, 3, 1, 1)
+        self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+        self.compute_dtype = None
+
+    def forward(self, x: Tensor) -> Tensor:
+        from .engine_rpa import rpa_apply
+        return rpa_apply(self, "gen", x)
+
+
+def gen_rpa2x() -> Generator_RPA:
+    """A-ESRGAN/model.py:217-221"""
+    print("* Generator_RPA 2x")
+    return Generator_RPA(scale=2)
 
 
 def discriminator() -> Discriminator:

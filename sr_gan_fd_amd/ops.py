@@ -659,6 +659,37 @@ def attention_bwd(a: A.AttnArgs, rec=None, L=None, st=None) -> None:
     _attention("bwd", a, rec, L, st)
 
 
+# ---- A-ESRGAN's pixel attention (csrc/pixel_gate.hip): z = x * (1 + sigmoid(a)) and its backward ----
+def pixel_gate_args(dtype: int, npix: int, c: int, x: A.View, a: A.View, *, z: A.View = A.NULL_VIEW, dz: A.View = A.NULL_VIEW,
+                    dx: A.View = A.NULL_VIEW, da: A.View = A.NULL_VIEW) -> tuple:
+    """srganfd_pixel_gate's arguments without the stream: the forward with ``z``, the backward with ``dz``, ``dx`` and ``da`` (``da``
+    may be ``dz`` itself: written in place)"""
+    bwd = 1 if dz.ptr else 0
+    return (bwd, x, a, dz if bwd else z, dx, da, dtype, npix, c)
+
+
+class PixelGate(_Bracketed):
+    """one srganfd_pixel_gate launch (``args``: pixel_gate_args').  Algorithmic work: bytes only -- x and a read and z written, or
+    x, a and dz read and dx and da written, once each."""
+    kind = "pixel_gate"
+
+    def __init__(self, args: tuple):
+        self.args = args
+        bwd, dtype, npix, c = args[0], args[6], args[7], args[8]
+        self.label = "pixel_gate_%s_kernel<%s>" % ("bwd" if bwd else "fwd", A.DT_NAME[dtype])
+        self.work = (0.0, float(npix) * c * esize(dtype) * (5 if bwd else 3))
+
+    def _issue(self, run: Run) -> None:
+        A.check(run.L.srganfd_pixel_gate(*self.args, run.st), "pixel_gate(bwd)" if self.args[0] else "pixel_gate")
+
+
+def pixel_gate(args: tuple, rec=None) -> None:
+    """one launch on the current stream, outside a launch list (tests, tools)"""
+    run = Run("pixel_gate")
+    run.rec = rec
+    PixelGate(args).launch(run)
+
+
 # same-box A/B switch (0: one group of launches per layer, the round-1 form); both forms run in the HIP library and agree to the bit
 _SN_BATCH = os.environ.get("SRGANFD_SN_BATCH", "1") != "0"
 
