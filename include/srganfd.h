@@ -588,6 +588,26 @@ int srganfd_jpeg_roundtrip(const float* image, int32_t b, int32_t c, int32_t h, 
  * more than 65535 planes. */
 int srganfd_filter2d_mirror_f64(const float* image, const double* kernels, int32_t kmax, const int32_t* ksize,
                                 const int32_t* ksize_host, int32_t b, int32_t c, int32_t h, int32_t w, float* out, void* stream);
+/* The per-image filter kernels Real-ESRGAN's dataset makes per sample (Real_ESRGAN/dataset.py:64-133: imgproc.random_mixed_kernels,
+ * imgproc.py:495-576, and generate_sinc_kernel, :579-606), synthesised on the device from their drawn parameters (csrc/blur_kernels.hip):
+ * one launch writes n kernels, kernel i being ksize[i] x ksize[i], CENTRED in its kmax x kmax array with exact 0.0f around it -- what
+ * srganfd_filter2d takes.  Every element, the sum and the division are fp64; the store is the one rounding to fp32 (the reference's
+ * torch.FloatTensor(float64 array)).
+ *   kind, ksize: n int32 each in DEVICE memory; params: (n, 5) fp64 in device memory, {sigma_x, sigma_y, theta, beta, omega} per kernel.
+ *   On ax = arange(-ksize // 2 + 1, ksize // 2 + 1), element [row r][col c] has x = ax[c], y = ax[r]; with Sigma = U diag(sigma_x^2,
+ *   sigma_y^2) U^T, U the rotation by theta, and q = (x, y) Sigma^-1 (x, y)^T:
+ *     kind 0  delta: 1 at the centre of the kmax array, 0 elsewhere; ksize ignored, not normalised;
+ *     kind 1  Gaussian: exp(-q / 2);            kind 2  generalized Gaussian: exp(-pow(q, beta) / 2);
+ *     kind 3  plateau: 1 / (pow(q, beta) + 1);   kind 4  sinc: omega * J1(omega r) / (2 pi r), r the distance from the centre element,
+ *             which itself is omega^2 / (4 pi);
+ *   kinds 1..4 divided by the fp64 sum of their ksize^2 elements.  An isotropic kernel is its kind with sigma_y = sigma_x, theta = 0.
+ *   kind_host, ksize_host: the same values in host memory, or both NULL (no validation; the kernel then clamps a kind into 0..4 and a
+ *   size to an odd one in 3..kmax).  The parameters are not validated: a non-positive sigma gives non-finite values, as in the reference.
+ *   out: (n, kmax, kmax) fp32.  One workgroup per kernel, a fixed-order reduction: two runs give identical bits.
+ * SRGANFD_EINVAL: null pointer, n <= 0, kmax not odd in 3..25, only one of the host arrays given, kind_host[i] outside 0..4,
+ * ksize_host[i] not odd in 3..kmax for a kind 1..4 (the message names i). */
+int srganfd_blur_kernel_bank(const int32_t* kind, const int32_t* ksize, const double* params, const int32_t* kind_host,
+                             const int32_t* ksize_host, int32_t n, int32_t kmax, float* out, void* stream);
 /* F.interpolate as degradation_process calls it (imgproc.py:2374, :2415-2418, :2440-2442, :2454-2456): mode 0 "area"
  * (adaptive average pooling), 1 "bilinear", 2 "bicubic" (A = -0.75), align_corners unset.  `planes` = b*c NCHW fp32 planes.
  * rscale_h/w: 1 / scale_factor when the caller passed scale_factor= (torch maps coordinates with it), 0 = in / out. */

@@ -215,6 +215,7 @@ SYMBOLS = {
     "srganfd_jpeg_workspace_bytes": (C.c_int64, [C.c_int32] * 3),
     "srganfd_jpeg_roundtrip": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 5),
     "srganfd_filter2d_mirror_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
+    "srganfd_blur_kernel_bank": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 2 + [C.c_void_p, C.c_void_p]),
     "srganfd_resize": (C.c_int, [C.c_void_p] + [C.c_int32] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "srganfd_gaussian_noise": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
     "srganfd_poisson_prepare": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 6),

@@ -26,10 +26,17 @@ class CUDAPrefetcher:
     ``imgproc.degradation_process(gt, upscale_factor, jpeg_prob, scale2_prob)`` in cv2, scipy and numpy): a dict with ``upscale_factor`` and
     optionally ``jpeg_prob`` / ``scale2_prob``; a batch that has ``"gt"`` and no ``"lr"`` gets ``batch["lr"] =
     imgproc.degradation_process_bsrgan(batch["gt"], **dict)`` on the copy stream, the random draws taken from the global ``random`` /
-    ``np.random`` streams when the batch is staged.  It excludes ``synthesize_lr`` (``ValueError``): a batch gets one LR."""
+    ``np.random`` streams when the batch is staged.  It excludes ``synthesize_lr`` (``ValueError``): a batch gets one LR.
+
+    ``synthesize_kernels_realesrgan`` (an addition; Real_ESRGAN/dataset.py:64-133 makes three filter kernels per sample on the host with
+    ``imgproc.random_mixed_kernels`` / ``generate_sinc_kernel`` in numpy and scipy): the degradation-model parameter dict
+    (realesrgan_config.py:46-65); a batch that has ``"gt"`` and no ``"gaussian_kernel1"`` gets ``"gaussian_kernel1"``,
+    ``"gaussian_kernel2"`` and ``"sinc_kernel"`` from ``imgproc.realesrgan_kernel_draws`` (the global ``random`` / ``np.random`` streams,
+    when the batch is staged) and ``imgproc.realesrgan_blur_kernels`` (one launch on the copy stream), so the dataset returns ``"gt"``
+    only.  A batch that brings its own kernels keeps them; a dict that lacks a key raises ``ValueError`` here, naming it."""
 
     def __init__(self, dataloader, device: torch.device, ingest_u8: bool = False, bgr: bool = True, synthesize_lr: int | None = None,
-                 synthesize_lr_bsrgan: dict | None = None):
+                 synthesize_lr_bsrgan: dict | None = None, synthesize_kernels_realesrgan: dict | None = None):
         self.original_dataloader = dataloader
         self.ingest_u8, self.bgr = ingest_u8, bgr
         if synthesize_lr is not None and not synthesize_lr >= 1:
@@ -44,6 +51,11 @@ class CUDAPrefetcher:
                                  f"{sorted(synthesize_lr_bsrgan)}")
             synthesize_lr_bsrgan = dict(synthesize_lr_bsrgan)
         self.synthesize_lr_bsrgan = synthesize_lr_bsrgan
+        if synthesize_kernels_realesrgan is not None:
+            from .imgproc import check_realesrgan_kernel_parameters
+            check_realesrgan_kernel_parameters(synthesize_kernels_realesrgan)
+            synthesize_kernels_realesrgan = dict(synthesize_kernels_realesrgan)
+        self.synthesize_kernels_realesrgan = synthesize_kernels_realesrgan
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.batch_data = None
@@ -69,6 +81,13 @@ class CUDAPrefetcher:
             if self.synthesize_lr_bsrgan is not None and "lr" not in self.batch_data and torch.is_tensor(self.batch_data.get("gt")):
                 from .imgproc import degradation_process_bsrgan
                 self.batch_data["lr"] = degradation_process_bsrgan(self.batch_data["gt"], **self.synthesize_lr_bsrgan)
+            if (self.synthesize_kernels_realesrgan is not None and "gaussian_kernel1" not in self.batch_data
+                    and torch.is_tensor(self.batch_data.get("gt"))):
+                from .imgproc import realesrgan_blur_kernels, realesrgan_kernel_draws
+                P = self.synthesize_kernels_realesrgan
+                draws = realesrgan_kernel_draws(self.batch_data["gt"].shape[0], P)
+                kernels = realesrgan_blur_kernels(draws, P, self.device)
+                self.batch_data.update(zip(("gaussian_kernel1", "gaussian_kernel2", "sinc_kernel"), kernels))
 
     def next(self):
         """the staged batch (or None at the end of the epoch); starts staging the following one"""

@@ -1,8 +1,9 @@
 """Device-side mirror of the data-side helpers the train loops call on GPU tensors (reference: BSRGAN/imgproc.py for
 ``random_crop``; Real_ESRGAN/imgproc.py for the on-device degradation stages -- SURVEY 8f N4: ``filter2d_torch``,
 ``USMSharp``, ``DiffJPEG``, the noise stages, ``degradation_process``; BSRGAN/imgproc.py:492-562 for the blind degradation,
-``degradation_process_bsrgan``, with its real JPEG round trip and fp64 blur).  The CPU-side pieces of that file (kernel synthesis with numpy / scipy, cv2 image I/O)
-stay the reference's own."""
+``degradation_process_bsrgan``, with its real JPEG round trip and fp64 blur; Real_ESRGAN/dataset.py:64-133 with imgproc.py:228-606 for
+the per-image filter kernels, ``realesrgan_kernel_draws`` / ``blur_kernel_bank`` / ``realesrgan_blur_kernels``).  The cv2 image I/O of that
+file stays the reference's own."""
 from __future__ import annotations
 
 import math
@@ -466,6 +467,175 @@ def degradation_process(gt: Tensor, gaussian_kernel1: Tensor, gaussian_kernel2: 
         out = filter2d_torch(out, sinc_kernel)
     lr = quantize_u8(out)
     return gt_usm, gt, lr
+
+
+# ---- Real-ESRGAN's per-image filter kernels (Real_ESRGAN/dataset.py:64-133, imgproc.py:228-606) -----------------------------------
+KERNEL_DELTA, KERNEL_GAUSSIAN, KERNEL_GENERALIZED, KERNEL_PLATEAU, KERNEL_SINC = 0, 1, 2, 3, 4
+KERNEL_BANK_KMAX = 25
+# gaussian_kernel_type name -> (kind, anisotropic); any other name takes the isotropic Gaussian, as random_mixed_kernels' else does
+_MIXED_KERNEL_TYPES = {
+    "isotropic": (KERNEL_GAUSSIAN, False), "anisotropic": (KERNEL_GAUSSIAN, True),
+    "generalized_isotropic": (KERNEL_GENERALIZED, False), "generalized_anisotropic": (KERNEL_GENERALIZED, True),
+    "plateau_isotropic": (KERNEL_PLATEAU, False), "plateau_anisotropic": (KERNEL_PLATEAU, True),
+}
+_KERNEL_PARAMETER_KEYS = ("sinc_kernel_size", "gaussian_kernel_range", "gaussian_kernel_type", "sinc_kernel_probability3") + tuple(
+    f"{name}{n}" for n in (1, 2) for name in ("gaussian_kernel_probability", "sinc_kernel_probability", "gaussian_sigma_range",
+                                              "generalized_kernel_beta_range", "plateau_kernel_beta_range"))
+
+
+def _odd_kernel_size(k) -> bool:
+    return isinstance(k, (int, np.integer)) and 3 <= k <= KERNEL_BANK_KMAX and k % 2 == 1
+
+
+def check_realesrgan_kernel_parameters(degradation_model_parameters_dict: dict) -> None:
+    """``ValueError`` unless the dict holds what ``realesrgan_kernel_draws`` and ``realesrgan_blur_kernels`` read, in a form both can use:
+    every key of the reference's ``degradation_model_parameters_dict`` (realesrgan_config.py:46-65; the message names the first missing
+    one), odd kernel sizes from 3 to 25 with the largest of ``gaussian_kernel_range`` last (the dataset pads to ``range[-1]``), one
+    probability per kernel type, and ``lo < hi`` sigma ranges (the reference asserts that at every draw)."""
+    P = degradation_model_parameters_dict
+    if not isinstance(P, dict):
+        raise ValueError(f"the degradation-model parameters are a dict, got {type(P).__name__}")
+    for key in _KERNEL_PARAMETER_KEYS:
+        if key not in P:
+            raise ValueError(f"degradation-model parameters: key {key!r} is missing")
+    sizes = list(P["gaussian_kernel_range"])
+    if not sizes or not all(_odd_kernel_size(k) for k in sizes) or sizes[-1] != max(sizes):
+        raise ValueError(f"degradation-model parameters: 'gaussian_kernel_range' holds odd sizes from 3 to {KERNEL_BANK_KMAX}, the largest last; got {sizes}")
+    if not _odd_kernel_size(P["sinc_kernel_size"]):
+        raise ValueError(f"degradation-model parameters: 'sinc_kernel_size' is an odd size from 3 to {KERNEL_BANK_KMAX}, got {P['sinc_kernel_size']!r}")
+    types = list(P["gaussian_kernel_type"])
+    for n in (1, 2):
+        if not types or len(P[f"gaussian_kernel_probability{n}"]) != len(types):
+            raise ValueError(f"degradation-model parameters: 'gaussian_kernel_probability{n}' holds one weight per entry of 'gaussian_kernel_type' "
+                             f"({len(types)})")
+        for key in (f"gaussian_sigma_range{n}", f"generalized_kernel_beta_range{n}", f"plateau_kernel_beta_range{n}"):
+            if len(P[key]) != 2:
+                raise ValueError(f"degradation-model parameters: {key!r} is a [lo, hi] pair, got {P[key]!r}")
+        lo, hi = P[f"gaussian_sigma_range{n}"]
+        if not lo < hi:
+            raise ValueError(f"degradation-model parameters: 'gaussian_sigma_range{n}' needs lo < hi, got {[lo, hi]}")
+
+
+def _kernel_record(kind: int, ksize: int, sigma_x=0.0, sigma_y=0.0, theta=0.0, beta=0.0, omega=0.0) -> dict:
+    return {"kind": int(kind), "ksize": int(ksize), "sigma_x": float(sigma_x), "sigma_y": float(sigma_y), "theta": float(theta),
+            "beta": float(beta), "omega": float(omega)}
+
+
+def _draw_blur_kernel(P: dict, n: int) -> dict:
+    """blur kernel ``n`` (1 or 2) of one image: dataset.py:65-86 / :92-113 with random_mixed_kernels and its _random_bivariate_* helpers"""
+    sizes = P["gaussian_kernel_range"]
+    ksize = random.choice(sizes)
+    if np.random.uniform() < P[f"sinc_kernel_probability{n}"]:
+        if ksize < int(np.median(sizes)):
+            omega = np.random.uniform(np.pi / 3, np.pi)
+        else:
+            omega = np.random.uniform(np.pi / 5, np.pi)
+        return _kernel_record(KERNEL_SINC, ksize, omega=omega)
+    name = random.choices(P["gaussian_kernel_type"], P[f"gaussian_kernel_probability{n}"])[0]
+    kind, anisotropic = _MIXED_KERNEL_TYPES.get(name, (KERNEL_GAUSSIAN, False))
+    sigma_range = P[f"gaussian_sigma_range{n}"]
+    sigma_x = np.random.uniform(sigma_range[0], sigma_range[1])
+    if anisotropic:
+        sigma_y = np.random.uniform(sigma_range[0], sigma_range[1])
+        theta = np.random.uniform(-math.pi, math.pi)
+    else:
+        sigma_y, theta = sigma_x, 0.0
+    beta = 0.0
+    if kind != KERNEL_GAUSSIAN:
+        beta_range = P[f"generalized_kernel_beta_range{n}" if kind == KERNEL_GENERALIZED else f"plateau_kernel_beta_range{n}"]
+        if np.random.uniform() < 0.5:
+            beta = np.random.uniform(beta_range[0], 1)
+        else:
+            beta = np.random.uniform(1, beta_range[1])
+    return _kernel_record(kind, ksize, sigma_x, sigma_y, theta, beta)
+
+
+def realesrgan_kernel_draws(batch: int, degradation_model_parameters_dict: dict) -> list:
+    """Every random decision of ``DegeneratedImageDataset.__getitem__`` (Real_ESRGAN/dataset.py:64-129) and of ``random_mixed_kernels``
+    with its ``_random_bivariate_*`` helpers (imgproc.py:333-576) for ``batch`` images, drawn image by image from the global ``random`` /
+    ``np.random`` streams in exactly the reference's order, so that a seeded run gets the kernels the reference's loader would make.
+    Per blur kernel (the first, then the second): ``random.choice(gaussian_kernel_range)``; ``np.random.uniform() <
+    sinc_kernel_probabilityN``; on a hit ``np.random.uniform(pi / 3, pi)`` for a size below ``int(np.median(range))``, else
+    ``uniform(pi / 5, pi)``; on a miss ``random.choices(types, probabilities)[0]``, ``uniform(sigma range)``, for the anisotropic types
+    ``uniform(sigma range)`` and ``uniform(-pi, pi)``, for the generalized / plateau types ``np.random.uniform() < 0.5`` and
+    ``uniform(beta0, 1)`` or ``uniform(1, beta1)``.  Then the final sinc filter: ``np.random.uniform() < sinc_kernel_probability3``; on a
+    hit ``random.choice(range)`` and ``uniform(pi / 3, pi)``, on a miss the delta.  (``noise_range``: the dataset passes None and nothing
+    is drawn for it.)
+    One plain dict per image, ``{"kernel1", "kernel2", "sinc_kernel"}``, each a record ``{"kind", "ksize", "sigma_x", "sigma_y", "theta",
+    "beta", "omega"}`` with ``kind`` 0 delta, 1 Gaussian, 2 generalized Gaussian, 3 plateau, 4 sinc -- the arguments of
+    ``blur_kernel_bank``; fields a kind does not use are 0, and an isotropic kernel has ``sigma_y = sigma_x``, ``theta = 0``."""
+    P = degradation_model_parameters_dict
+    check_realesrgan_kernel_parameters(P)
+    out = []
+    for _ in range(batch):
+        rec = {"kernel1": _draw_blur_kernel(P, 1), "kernel2": _draw_blur_kernel(P, 2)}
+        if np.random.uniform() < P["sinc_kernel_probability3"]:
+            ksize = random.choice(P["gaussian_kernel_range"])
+            rec["sinc_kernel"] = _kernel_record(KERNEL_SINC, ksize, omega=np.random.uniform(np.pi / 3, np.pi))
+        else:
+            rec["sinc_kernel"] = _kernel_record(KERNEL_DELTA, P["sinc_kernel_size"])
+        out.append(rec)
+    return out
+
+
+def blur_kernel_bank(kind, ksize, params, kmax: int, device=None) -> Tensor:
+    """srganfd_blur_kernel_bank: ``n`` filter kernels from their parameters in one launch, ``(n, kmax, kmax)`` fp32 on the GPU.  ``kind``
+    (n integers: 0 delta, 1 Gaussian, 2 generalized Gaussian, 3 plateau, 4 sinc), ``ksize`` (n odd sizes from 3 to ``kmax`` <= 25; kernel
+    i sits centred in its array with exact zeros around it; ignored by a delta) and ``params`` ((n, 5) floats: sigma_x, sigma_y, theta,
+    beta, omega) are host arrays or lists, uploaded with one small copy each.  fp64 arithmetic, one rounding to fp32 (include/srganfd.h
+    has the formulas); the launch goes to the current stream of ``device`` (default: the current GPU)."""
+    kd, ks = np.asarray(kind), np.asarray(ksize)
+    if kd.ndim != 1 or kd.size == 0 or kd.dtype.kind not in "iu" or ks.dtype.kind not in "iu" or ks.shape != kd.shape:
+        raise A.SrganfdError(f"blur_kernel_bank: kind and ksize hold one integer per kernel (at least one), got {kd.dtype} {kd.shape} and {ks.dtype} {ks.shape}")
+    try:
+        pr = np.ascontiguousarray(np.asarray(params), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise A.SrganfdError("blur_kernel_bank: params holds 5 numbers per kernel (sigma_x, sigma_y, theta, beta, omega)") from None
+    if pr.shape != (kd.size, 5):
+        raise A.SrganfdError(f"blur_kernel_bank: params is (n, 5) = ({kd.size}, 5): sigma_x, sigma_y, theta, beta, omega; got {pr.shape}")
+    if not isinstance(kmax, (int, np.integer)):
+        raise A.SrganfdError(f"blur_kernel_bank: kmax is an odd integer from 3 to {KERNEL_BANK_KMAX}, got {kmax!r}")
+    kd, ks = np.ascontiguousarray(kd, dtype=np.int32), np.ascontiguousarray(ks, dtype=np.int32)
+    host = [torch.from_numpy(a) for a in (kd, ks, pr)]
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        _need_gpu(host[0], "blur_kernel_bank")
+    with torch.cuda.device(dev):
+        kd_dev, ks_dev, pr_dev = (t.to(dev) for t in host)
+        out = torch.empty(kd.size, int(kmax), int(kmax), dtype=torch.float32, device=dev)
+        A.check(A.lib().srganfd_blur_kernel_bank(kd_dev.data_ptr(), ks_dev.data_ptr(), pr_dev.data_ptr(), kd.ctypes.data, ks.ctypes.data, kd.size,
+                                                 int(kmax), out.data_ptr(), A.stream_ptr()), "blur_kernel_bank")
+    return out
+
+
+_KERNEL_PARAM_FIELDS = ("sigma_x", "sigma_y", "theta", "beta", "omega")
+
+
+def realesrgan_blur_kernels(draws: list, degradation_model_parameters_dict: dict, device=None):
+    """The three filter kernels of every image of ``draws`` (``realesrgan_kernel_draws``) as the reference's collated batch holds them
+    (Real_ESRGAN/dataset.py:72-133): ``(gaussian_kernel1, gaussian_kernel2, sinc_kernel)``, each (B, K, K) fp32 on the GPU with
+    K = ``gaussian_kernel_range[-1]`` for the first two and ``sinc_kernel_size`` for the third, every kernel centred in its array -- what
+    ``degradation_process`` / ``filter2d_torch`` take.  One ``blur_kernel_bank`` launch for all 3 B kernels when the two sizes agree (the
+    reference's configs: 21), else two.  ``ValueError`` for a drawn sinc filter larger than ``sinc_kernel_size`` (the reference would hand
+    its collate function tensors of different shapes)."""
+    P = degradation_model_parameters_dict
+    check_realesrgan_kernel_parameters(P)
+    b = len(draws)
+    if b == 0:
+        raise ValueError("realesrgan_blur_kernels: no draws")
+    k_blur, k_sinc = int(P["gaussian_kernel_range"][-1]), int(P["sinc_kernel_size"])
+    recs = [rec[name] for name in ("kernel1", "kernel2", "sinc_kernel") for rec in draws]          # (3, B) order: each output is one slice
+    for n, r in enumerate(recs[2 * b:]):
+        if r["kind"] != KERNEL_DELTA and r["ksize"] > k_sinc:
+            raise ValueError(f"realesrgan_blur_kernels: image {n} drew a {r['ksize']} x {r['ksize']} sinc filter, larger than sinc_kernel_size = {k_sinc}")
+    kind = np.array([r["kind"] for r in recs], dtype=np.int32)
+    ksize = np.array([r["ksize"] for r in recs], dtype=np.int32)
+    params = np.array([[r[f] for f in _KERNEL_PARAM_FIELDS] for r in recs], dtype=np.float64)
+    if k_blur == k_sinc:
+        bank = blur_kernel_bank(kind, ksize, params, k_blur, device)
+        return bank[:b], bank[b:2 * b], bank[2 * b:]
+    blur = blur_kernel_bank(kind[:2 * b], ksize[:2 * b], params[:2 * b], k_blur, device)
+    return blur[:b], blur[b:], blur_kernel_bank(kind[2 * b:], ksize[2 * b:], params[2 * b:], k_sinc, device)
 
 
 # ---- BSRGAN / A-ESRGAN blind degradation (BSRGAN/imgproc.py:161-225, 284-293, 492-562; the same text in A-ESRGAN/imgproc.py) ------
