@@ -242,17 +242,31 @@ int srganfd_resample(int32_t op, srganfd_view a, srganfd_view b, int32_t dtype, 
  * LeakyReLU output of the upsampled layer.  dx_raw.ptr may be NULL; dx_masked may alias nothing it reads. */
 int srganfd_resample_bwd_lrelu(srganfd_view dy, srganfd_view dx_raw, srganfd_view act, srganfd_view dx_masked,
                                int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, float slope, void* stream);
-/* out = dy * (act - skip > 0 ? 1 : slope): LeakyReLU backward where only act = lrelu(z) + skip was
- * stored (U-Net skip adds, model.py:153,157,161); skip.ptr may be NULL (plain LeakyReLU backward). */
+/* Entry points on channel-slice views outside the convolutions (this group, the L1 losses on views, the attention gate's pieces and
+ * BatchNorm below) refuse with SRGANFD_EINVAL, before anything is launched: a planar view; a slice that ends past its buffer
+ * (c0 < 0 or c0 + c > cstride); c <= 0; npix <= 0 (BatchNorm states its own rule for npix).  A view that may be NULL passes these.
+ *
+ * out = dy * (act - skip > 0 ? 1 : slope): LeakyReLU backward where only act = lrelu(z) + skip was
+ * stored (U-Net skip adds, model.py:153,157,161); skip.ptr may be NULL (plain LeakyReLU backward).  act - skip is taken in fp32; 0, -0
+ * and NaN count as the slope side (ATen's leaky_relu_backward).  In place is allowed: out may be the same view as dy (and only as dy).
+ * 16-byte vectors are used when c, every c0 and cstride are multiples of a vector and every ptr is 16-byte aligned, a scalar
+ * kernel otherwise; both give the same bits.  SRGANFD_EINVAL: dy, act or out NULL; the view rules above; a bad dtype. */
 int srganfd_lrelu_bwd(srganfd_view dy, srganfd_view act, srganfd_view skip, srganfd_view out, int32_t dtype,
                       int64_t npix, int32_t c, float slope, void* stream);
-/* y = alpha * x + beta * y over npix pixels x c channels */
+/* y = fmaf(alpha, x, beta * y) over npix pixels x c channels; beta == 0 does not read y (a NaN there does not reach the result).
+ * Vector and scalar forms as above, the same bits from both.  x may not overlap y.  SRGANFD_EINVAL: x or y NULL; the view rules
+ * above; a bad dtype. */
 int srganfd_axpby(srganfd_view x, srganfd_view y, int32_t dtype, int64_t npix, int32_t c, float alpha,
                   float beta, void* stream);
 
 /* ---- losses (train_bsrgan.py:297,301,417,427,450-452).  workspace: >= 2048 floats.
  * *out = (accumulate ? *out : 0) + weight * mean(...).  Deterministic two-stage reductions. */
 #define SRGANFD_LOSS_WS_FLOATS 2049
+/* A NaN input gives a NaN loss, as torch's does; relu_first clamps as torch.relu does, so a NaN stays one.  The L1 gradients are
+ * torch.sign's: 0 at a difference of 0 and, as torch has it, at a NaN difference too.
+ * SRGANFD_EINVAL, before anything is launched: a NULL pointer where none is allowed (inputs, out, workspace); numel <= 0 (either count
+ * of the relativistic form); srganfd_l1_loss_views: the view rules of srganfd_lrelu_bwd (npix <= 0, c <= 0, planar, slice past its
+ * buffer) and a bad dtype. */
 /* grad = grad_scale * (grad_scale_dev ? *grad_scale_dev : 1) * d(mean)/d(input): grad_scale_dev is the device-resident loss scale of
  * f16 training (srganfd_loss_scale_update), NULL otherwise. */
 int srganfd_l1_loss(const float* a, const float* b, int64_t numel, float weight, float* out,
@@ -302,6 +316,10 @@ typedef struct srganfd_sn_grad_job {
 } srganfd_sn_grad_job;
 int srganfd_spectral_norm_grad_batch(const srganfd_sn_grad_job* jobs, int32_t njobs, float beta, void* stream);
 
+/* SRGANFD_EINVAL for both Adam entry points: param, grad, exp_avg or exp_avg_sq NULL; numel <= 0; ema_mode outside 0..2; ema NULL with
+ * ema_mode != 0; srganfd_adam_ema: step < 1; srganfd_adam_ema_dev: step_dev or bc_dev NULL.
+ * srganfd_loss_scale_update: state or found_inf NULL, growth_interval < 1, growth_factor < 1 (or NaN), backoff_factor outside (0, 1].
+ * srganfd_nonfinite_flag: x or flag NULL, x not 16-byte aligned, numel <= 0. */
 /* ---- fused Adam + EMA over flat buffers (torch.optim.Adam maths, train_bsrgan.py:311-323,436,466;
  * AveragedModel with the reference's avg_fn, :290-291,470).  ema_mode: 0 none, 1 copy (first
  * update), 2 ema = (1-decay)*ema + decay*param.  grad_scale multiplies the gradient first
@@ -361,18 +379,23 @@ int srganfd_conv2d_thin_wgrad(const srganfd_thin_args* a, float* dw, float* db, 
  * bwd=1: a = dy (ho x wo) -> b = dx (hi x wi), deterministic gather. */
 int srganfd_resize_bilinear(int32_t bwd, srganfd_view a, srganfd_view b, int32_t dtype, int32_t n, int32_t hi,
                             int32_t wi, int32_t ho, int32_t wo, int32_t c, void* stream);
-/* out = relu(a + b)  (model.py:246) */
+/* out = relu(a + b)  (model.py:246).  SRGANFD_EINVAL: a NULL view, views that cannot be read as 16-byte vectors over c channels, the
+ * view rules of srganfd_lrelu_bwd. */
 int srganfd_add_relu(srganfd_view a, srganfd_view b, srganfd_view out, int32_t dtype, int64_t npix, int32_t c, void* stream);
-/* in-place sigmoid of an fp32 map (model.py:248) and its backward out = ds * s * (1 - s) */
+/* in-place sigmoid of an fp32 map (model.py:248) and its backward out = ds * s * (1 - s).  In place is allowed in the backward as
+ * well: out may be ds (not s).  SRGANFD_EINVAL: a NULL pointer; numel <= 0. */
 int srganfd_sigmoid(float* x, int64_t numel, void* stream);
 int srganfd_sigmoid_bwd(const float* ds, const float* s, float* out, int64_t numel, void* stream);
-/* attention gate y = gate[p] * x[p][c] (model.py:252).  bwd=1: y is dy; dx = gate * dy, dgate[p] = sum_c dy * x */
+/* attention gate y = gate[p] * x[p][c] (model.py:252).  bwd=1: y is dy; dx = gate * dy, dgate[p] = sum_c dy * x.
+ * SRGANFD_EINVAL: x, gate or y NULL (bwd: dx or dgate too); views that cannot be read as 16-byte vectors; c / vector no power of two
+ * <= 64; the view rules of srganfd_lrelu_bwd. */
 int srganfd_gate_mul(int32_t bwd, srganfd_view x, const float* gate, srganfd_view y, srganfd_view dx, float* dgate,
                      int32_t dtype, int64_t npix, int32_t c, void* stream);
 /* nn.BatchNorm2d (model.py:233).  save: 4*c floats [mean | invstd | scale | shift]; workspace: 2048*c + 3*c floats.
  * training=1: batch statistics, running stats updated with `momentum` (unbiased variance); 0: running stats.
  * Refused with SRGANFD_EINVAL before anything is launched or written (all forward and backward forms below alike):
  *   - c that is no multiple of one 16-byte chunk (4 fp32 / 8 16-bit channels), or a view whose ptr, c0 or cstride is not 16-byte aligned;
+ *   - a planar view, or a slice that ends past its buffer (c0 + c > cstride), `act` included where it is given;
  *   - a channel block (256 channels, the last one c % 256) that is not a power-of-two number of chunks: c = 268 in fp32 (12 channels,
  *     3 chunks), c = 280 in a 16-bit type (24 channels, 3 chunks);
  *   - training=1 with npix < 2 (phase 2 of the two-phase form: total_npix < 2): the unbiased variance needs two values per channel. */
@@ -412,7 +435,8 @@ int srganfd_batchnorm_act_bwd(srganfd_view x, srganfd_view dy, srganfd_view dx, 
                               float* workspace, srganfd_view act, float act_slope, void* stream);
 
 /* ---- differentiable VGG tap (ESRGAN/model.py:281-292: F.l1_loss between one feature node of SR and GT) ----
- * out = scale * (*upstream or 1) * sign(a - b): the gradient of weight * mean|a - b| when scale = weight / numel. */
+ * out = scale * (*upstream or 1) * sign(a - b): the gradient of weight * mean|a - b| when scale = weight / numel.  torch.sign: sign(0) = 0
+ * and sign(NaN) = 0.  SRGANFD_EINVAL: a NULL view; the view rules of srganfd_lrelu_bwd; a bad dtype. */
 int srganfd_l1_grad_views(srganfd_view a, srganfd_view b, srganfd_view out, int32_t dtype, int64_t npix, int32_t c,
                           const float* upstream /* device scalar or NULL */, float scale, void* stream);
 /* MaxPool2d(2,2) backward fused with the derivative of the ReLU in front of it: x = the ReLU output (pre-pool,

@@ -6,8 +6,10 @@
 namespace srganfd {
 
 // ---- LeakyReLU backward with the sign recovered from act - skip ----
+// out may be dy itself (the engines overwrite the gradient in place), so dy is not __restrict__: every element is read before it is
+// written, by the same lane.  The vector and the scalar form do the same fp32 operations per element: the same bits from both.
 template <typename T>
-__global__ __launch_bounds__(256) void lrelu_bwd_vec_kernel(const void* __restrict__ dy, int dC, int d0, const void* __restrict__ act, int aC, int a0,
+__global__ __launch_bounds__(256) void lrelu_bwd_vec_kernel(const void* dy, int dC, int d0, const void* __restrict__ act, int aC, int a0,
                                                             const void* __restrict__ skip, int sC, int s0, void* out, int oC, int o0, size_t npix, int c, float slope) {
   constexpr int N = VecN<T>::N;
   const int cv = c / N;
@@ -29,7 +31,7 @@ __global__ __launch_bounds__(256) void lrelu_bwd_vec_kernel(const void* __restri
   }
 }
 template <typename T>
-__global__ void lrelu_bwd_kernel(const void* __restrict__ dy, int dC, int d0, const void* __restrict__ act, int aC, int a0,
+__global__ void lrelu_bwd_kernel(const void* dy, int dC, int d0, const void* __restrict__ act, int aC, int a0,
                                  const void* __restrict__ skip, int sC, int s0, void* out, int oC, int o0, size_t npix, int c, float slope) {
   const size_t total = npix * c;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -42,13 +44,15 @@ __global__ void lrelu_bwd_kernel(const void* __restrict__ dy, int dC, int d0, co
 }
 
 // ---- y = a*x + b*y on channel-slice views ----
+// Both forms spell the same fmaf(a, x, b * y), so that the compiler cannot contract them differently: bit-identical in f32.
+// b == 0 never reads y (a NaN there does not reach the result).
 template <typename T>
 __global__ void axpby_kernel(const void* __restrict__ x, int xC, int x0, void* y, int yC, int y0, size_t npix, int c, float a, float b) {
   const size_t total = npix * c;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int ch = (int)(i % c);
     const size_t p = i / c;
-    const float v = a * ld<T>(x, p * xC + x0 + ch) + (b != 0.f ? b * ld<T>(y, p * yC + y0 + ch) : 0.f);
+    const float v = fmaf(a, ld<T>(x, p * xC + x0 + ch), b != 0.f ? b * ld<T>(y, p * yC + y0 + ch) : 0.f);
     st<T>(y, p * yC + y0 + ch, v);
   }
 }
@@ -64,7 +68,7 @@ __global__ __launch_bounds__(256) void axpby_vec_kernel(const void* __restrict__
     ldv<T>(x, p * xC + x0 + ch, vx);
     if (b != 0.f) ldv<T>(y, p * yC + y0 + ch, vy);
 #pragma unroll
-    for (int q = 0; q < N; ++q) vx[q] = a * vx[q] + (b != 0.f ? b * vy[q] : 0.f);
+    for (int q = 0; q < N; ++q) vx[q] = fmaf(a, vx[q], b != 0.f ? b * vy[q] : 0.f);
     stv<T>(y, p * yC + y0 + ch, vx);
   }
 }
@@ -90,7 +94,8 @@ __global__ __launch_bounds__(256) void add_relu_kernel(const void* __restrict__ 
 __global__ __launch_bounds__(256) void sigmoid_kernel(float* x, size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) x[i] = 1.f / (1.f + expf(-x[i]));
 }
-__global__ __launch_bounds__(256) void sigmoid_bwd_kernel(const float* __restrict__ ds, const float* __restrict__ s, float* out, size_t n) {
+// out may be ds itself (engine_a overwrites the gradient in place): ds is not __restrict__
+__global__ __launch_bounds__(256) void sigmoid_bwd_kernel(const float* ds, const float* __restrict__ s, float* out, size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { const float v = s[i]; out[i] = ds[i] * v * (1.f - v); }
 }
 // y[p][c] = gate[p] * x[p][c]
@@ -147,6 +152,7 @@ extern "C" int srganfd_lrelu_bwd(srganfd_view dy, srganfd_view act, srganfd_view
   const size_t npix = (size_t)npix64;
   const hipStream_t s = (hipStream_t)stream;
   if (!dy.ptr || !act.ptr || !out.ptr) return set_err(SRGANFD_EINVAL, "lrelu_bwd: null");
+  if (const char* why = views_bad(npix64, c, {dy, act, skip, out})) return set_err(SRGANFD_EINVAL, "lrelu_bwd: %s", why);
   {
     const int vn = dtype == SRGANFD_F32 ? 4 : 8;
     auto ok = [&](const srganfd_view& v) { return !v.ptr || (v.c0 % vn == 0 && v.cstride % vn == 0 && ((uintptr_t)v.ptr & 15) == 0); };
@@ -168,6 +174,7 @@ extern "C" int srganfd_axpby(srganfd_view x, srganfd_view y, int32_t dtype, int6
   const size_t npix = (size_t)npix64;
   const hipStream_t s = (hipStream_t)stream;
   if (!x.ptr || !y.ptr) return set_err(SRGANFD_EINVAL, "axpby: null");
+  if (const char* why = views_bad(npix64, c, {x, y})) return set_err(SRGANFD_EINVAL, "axpby: %s", why);
   {
     const int vn = dtype == SRGANFD_F32 ? 4 : 8;
     auto ok = [&](const srganfd_view& v) { return v.c0 % vn == 0 && v.cstride % vn == 0 && ((uintptr_t)v.ptr & 15) == 0; };
@@ -187,6 +194,7 @@ extern "C" int srganfd_add_relu(srganfd_view a, srganfd_view b, srganfd_view out
   const size_t npix = (size_t)npix64;
   const hipStream_t s = (hipStream_t)stream;
   if (!a.ptr || !b.ptr || !out.ptr || !vec_ok(dtype, c, {a, b, out})) return set_err(SRGANFD_EINVAL, "add_relu: bad views");
+  if (const char* why = views_bad(npix64, c, {a, b, out})) return set_err(SRGANFD_EINVAL, "add_relu: %s", why);
   const int vn = dtype == SRGANFD_F32 ? 4 : 8;
   DISPATCH_T(dtype,
              SRGANFD_LAUNCH(add_relu_kernel<TT>, dim3(grid_for(npix * c / vn, 256, 65536)), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, out.ptr, out.cstride, out.c0, npix, c));
@@ -197,6 +205,7 @@ extern "C" int srganfd_sigmoid(float* x, int64_t numel, void* stream) {
   const size_t n = (size_t)numel;
   const hipStream_t s = (hipStream_t)stream;
   if (!x) return set_err(SRGANFD_EINVAL, "sigmoid: null");
+  if (numel <= 0) return set_err(SRGANFD_EINVAL, "sigmoid: numel <= 0");
   SRGANFD_LAUNCH(sigmoid_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, n);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
@@ -205,6 +214,7 @@ extern "C" int srganfd_sigmoid_bwd(const float* ds, const float* sg, float* out,
   const size_t n = (size_t)numel;
   const hipStream_t s = (hipStream_t)stream;
   if (!ds || !sg || !out) return set_err(SRGANFD_EINVAL, "sigmoid_bwd: null");
+  if (numel <= 0) return set_err(SRGANFD_EINVAL, "sigmoid_bwd: numel <= 0");
   SRGANFD_LAUNCH(sigmoid_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, ds, sg, out, n);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
@@ -216,6 +226,7 @@ extern "C" int srganfd_gate_mul(int32_t bwd, srganfd_view x, const float* gate, 
   const int vn = dtype == SRGANFD_F32 ? 4 : 8;
   const int cv = c / vn;
   if (!x.ptr || !gate || !y.ptr || !vec_ok(dtype, c, {x, y, dx}) || cv > 64 || (cv & (cv - 1))) return set_err(SRGANFD_EINVAL, "gate_mul: bad args");
+  if (const char* why = views_bad(npix64, c, {x, y, dx})) return set_err(SRGANFD_EINVAL, "gate_mul: %s", why);
   if (!bwd) {
     DISPATCH_T(dtype,
                SRGANFD_LAUNCH(gate_fwd_kernel<TT>, dim3(grid_for(npix * cv, 256, 65536)), dim3(256), 0, s, x.ptr, x.cstride, x.c0, gate, y.ptr, y.cstride, y.c0, npix, c));

@@ -84,6 +84,22 @@ inline bool vec_ok(int dtype, int c, std::initializer_list<srganfd_view> vs) {
     if (v.ptr && (v.c0 % vn || v.cstride % vn || ((uintptr_t)v.ptr & 15))) return false;
   return true;
 }
+// What every entry point on channel-slice views refuses before it sizes a grid: a planar view (only the convolutions read those), a
+// slice of c channels that ends past its buffer's cstride.  Returns the cause, or nullptr when all is well.  (a null view passes)
+inline const char* views_bad(int c, std::initializer_list<srganfd_view> vs) {
+  if (c <= 0) return "c <= 0";
+  for (const auto& v : vs) {
+    if (!v.ptr) continue;
+    if (v.planar) return "NHWC views only, not planar ones";
+    if (v.c0 < 0 || (long long)v.c0 + c > (long long)v.cstride) return "a channel slice ends past its buffer (c0 + c > cstride)";
+  }
+  return nullptr;
+}
+// the same with the pixel count in front: it arrives as int64 and becomes a size_t, so a negative one would size a grid over 2^64 elements
+inline const char* views_bad(long long npix, int c, std::initializer_list<srganfd_view> vs) {
+  if (npix <= 0) return "npix <= 0";
+  return views_bad(c, vs);
+}
 // the same view, cb channels further on
 inline srganfd_view sub_view(srganfd_view v, int cb) { if (v.ptr) v.c0 += cb; return v; }
 

@@ -14,7 +14,7 @@ __global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const float d = a[i] - b[i];
     s += fabsf(d);
-    if (grad) grad[i] = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f);
+    if (grad) grad[i] = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f);      // torch.sign: 0 at 0 and at a NaN
   }
   const float r = block_reduce_sum(s, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = r;
@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void l1_views_partial_kernel(const void* __res
     const int ch = (int)(i % c);
     const size_t p = i / c;
     float va = ld<T>(a, p * aC + a0 + ch), vb = ld<T>(b, p * bC + b0 + ch);
-    if (relu) { va = fmaxf(va, 0.f); vb = fmaxf(vb, 0.f); }
+    if (relu) { va = va < 0.f ? 0.f : va; vb = vb < 0.f ? 0.f : vb; }      // torch's relu: a NaN stays one (fmaxf would turn it into 0)
     s += fabsf(va - vb);
   }
   const float r = block_reduce_sum(s, sh);
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void l1_views_vec_partial_kernel(const void* _
 #pragma unroll
     for (int q = 0; q < N; ++q) {
       float x = va[q], y = vb[q];
-      if (relu) { x = fmaxf(x, 0.f); y = fmaxf(y, 0.f); }
+      if (relu) { x = x < 0.f ? 0.f : x; y = y < 0.f ? 0.f : y; }
       s += fabsf(x - y);
     }
   }
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void l1_grad_views_kernel(const void* __restri
     const int ch = (int)(i % c);
     const size_t p = i / c;
     const float d = ld<T>(a, p * aC + a0 + ch) - ld<T>(b, p * bC + b0 + ch);
-    st<T>(out, p * oC + o0 + ch, d > 0.f ? sc : (d < 0.f ? -sc : 0.f));     // torch: sign(0) = 0
+    st<T>(out, p * oC + o0 + ch, d > 0.f ? sc : (d < 0.f ? -sc : 0.f));     // torch.sign: 0 at 0 and at a NaN
   }
 }
 
@@ -200,7 +200,8 @@ extern "C" int srganfd_l1_loss(const float* a, const float* b, int64_t numel, fl
                                const float* grad_scale_dev, float* ws, void* stream) {
   const size_t n = (size_t)numel;
   const hipStream_t s = (hipStream_t)stream;
-  if (!a || !b || !out || !ws || n == 0) return set_err(SRGANFD_EINVAL, "l1_loss: bad args");
+  if (!a || !b || !out || !ws) return set_err(SRGANFD_EINVAL, "l1_loss: bad args");
+  if (numel <= 0) return set_err(SRGANFD_EINVAL, "l1_loss: numel <= 0");
   const unsigned g = grid_for(n, 256, kRedBlocks);
   SRGANFD_LAUNCH(l1_partial_kernel, dim3(g), dim3(256), 0, s, a, b, n, grad_scale / (float)n, grad_scale_dev, grad, ws);
   SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, out, accumulate);
@@ -212,6 +213,7 @@ extern "C" int srganfd_l1_loss_views(srganfd_view a, srganfd_view b, int32_t dty
   const size_t npix = (size_t)npix64;
   const hipStream_t s = (hipStream_t)stream;
   if (!a.ptr || !b.ptr || !out || !ws) return set_err(SRGANFD_EINVAL, "l1_views: bad args");
+  if (const char* why = views_bad(npix64, c, {a, b})) return set_err(SRGANFD_EINVAL, "l1_views: %s", why);      // npix * c == 0 would store weight / 0 * 0 = NaN
   const size_t n = npix * c;
   const unsigned g = grid_for(n, 256, kRedBlocks);
   const int vn = dtype == SRGANFD_F32 ? 4 : 8;
@@ -229,7 +231,8 @@ extern "C" int srganfd_l1_grad_views(srganfd_view a, srganfd_view b, srganfd_vie
                                      float scale, void* stream) {
   const size_t npix = (size_t)npix64;
   const hipStream_t s = (hipStream_t)stream;
-  if (!a.ptr || !b.ptr || !out.ptr || npix == 0 || c <= 0) return set_err(SRGANFD_EINVAL, "l1_grad_views: bad args");
+  if (!a.ptr || !b.ptr || !out.ptr) return set_err(SRGANFD_EINVAL, "l1_grad_views: bad args");
+  if (const char* why = views_bad(npix64, c, {a, b, out})) return set_err(SRGANFD_EINVAL, "l1_grad_views: %s", why);
   DISPATCH_T(dtype,
              SRGANFD_LAUNCH(l1_grad_views_kernel<TT>, dim3(grid_for(npix * c)), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, out.ptr, out.cstride, out.c0, npix, c, upstream, scale));
   SRGANFD_HIP_CHECK(hipGetLastError());
@@ -239,7 +242,8 @@ extern "C" int srganfd_bce_logits(const float* x, int64_t numel, float target, f
                                   float* grad, float grad_scale, const float* grad_scale_dev, float* ws, void* stream) {
   const size_t n = (size_t)numel;
   const hipStream_t s = (hipStream_t)stream;
-  if (!x || !loss_out || !ws || n == 0) return set_err(SRGANFD_EINVAL, "bce: bad args");
+  if (!x || !loss_out || !ws) return set_err(SRGANFD_EINVAL, "bce: bad args");
+  if (numel <= 0) return set_err(SRGANFD_EINVAL, "bce: numel <= 0");
   const unsigned g = grid_for(n, 256, kRedBlocks);
   SRGANFD_LAUNCH(bce_partial_kernel, dim3(g), dim3(256), 0, s, x, n, target, grad_scale / (float)n, grad_scale_dev, grad, ws, ws + kRedBlocks);
   SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, loss_out, accumulate);
@@ -280,7 +284,8 @@ extern "C" int srganfd_bce_logits_relativistic(const float* x, int64_t numel, co
 extern "C" int srganfd_nonfinite_flag(const float* x, int64_t numel, float* flag, int32_t accumulate, void* stream) {
   const size_t n = (size_t)numel;
   const hipStream_t s = (hipStream_t)stream;
-  if (!x || !flag || n == 0 || ((uintptr_t)x & 15)) return set_err(SRGANFD_EINVAL, "nonfinite_flag: bad args");
+  if (!x || !flag || ((uintptr_t)x & 15)) return set_err(SRGANFD_EINVAL, "nonfinite_flag: bad args");
+  if (numel <= 0) return set_err(SRGANFD_EINVAL, "nonfinite_flag: numel <= 0");
   if (!accumulate) SRGANFD_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(float), s));
   SRGANFD_LAUNCH(nonfinite_flag_kernel, dim3(grid_for(n / 4 + 1, 256, 2048)), dim3(256), 0, s, x, n, flag);
   SRGANFD_HIP_CHECK(hipGetLastError());

@@ -366,6 +366,7 @@ static int batchnorm_fwd_impl(srganfd_view x, srganfd_view y, int dtype, size_t 
                               size_t total_npix) {
   if (!x.ptr || !y.ptr || !gamma || !beta || !rm || !rv || !save || !ws || c <= 0 || !vec_ok(dtype, c, {x, y}))
     return set_err(SRGANFD_EINVAL, "batchnorm_fwd: bad args (16-byte aligned views)");
+  if (const char* why = views_bad(c, {x, y})) return set_err(SRGANFD_EINVAL, "batchnorm_fwd: %s", why);
   if (phase && (c > 256 || !training)) return set_err(SRGANFD_EINVAL, "batchnorm_fwd: the two-phase form takes training mode and at most 256 channels");
   if (const int bad = bn_bad_block(dtype, c)) return set_err(SRGANFD_EINVAL, "batchnorm_fwd: channel block of %d is not a power-of-two number of 16-byte chunks", bad);
   // the unbiased running variance is var * n / (n - 1): one value per channel has none (torch refuses it as well)
@@ -395,6 +396,7 @@ static int batchnorm_bwd_impl(srganfd_view x, srganfd_view dy, srganfd_view dx, 
                               const float* ws_global, size_t total_npix) {
   if (!x.ptr || !dy.ptr || !dx.ptr || !gamma || !save || !dgamma || !dbeta || !ws || c <= 0 || !vec_ok(dtype, c, {x, dy, dx, act}))
     return set_err(SRGANFD_EINVAL, "batchnorm_bwd: bad args");
+  if (const char* why = views_bad(c, {x, dy, dx, act})) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: %s", why);
   if (phase && c > 256) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: the two-phase form takes at most 256 channels");
   if (phase == 2 && !ws_global) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: phase 2 needs the all-reduced table");
   if (const int bad = bn_bad_block(dtype, c)) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: channel block of %d is not a power-of-two number of 16-byte chunks", bad);

@@ -75,7 +75,9 @@ extern "C" int srganfd_adam_ema(float* p, const float* g, float* m, float* v, fl
                                 void* stream) {
   const size_t n = (size_t)numel;
   const hipStream_t s = (hipStream_t)stream;
-  if (!p || !g || !m || !v || n == 0 || step < 1 || (ema_mode && !ema)) return set_err(SRGANFD_EINVAL, "adam: bad args");
+  if (!p || !g || !m || !v || step < 1 || (ema_mode && !ema)) return set_err(SRGANFD_EINVAL, "adam: bad args");
+  if (numel <= 0) return set_err(SRGANFD_EINVAL, "adam: numel <= 0");
+  if (ema_mode < 0 || ema_mode > 2) return set_err(SRGANFD_EINVAL, "adam: ema_mode %d is none of 0, 1, 2", (int)ema_mode);
   const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
   SRGANFD_LAUNCH(adam_ema_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, g, m, v, ema, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2),
                      grad_scale, ema_decay, ema_mode, skip_flag, grad_scale_dev);
@@ -87,7 +89,9 @@ extern "C" int srganfd_adam_ema_dev(float* p, const float* g, float* m, float* v
                                     const float* grad_scale_dev, void* stream) {
   const size_t n = (size_t)numel;
   const hipStream_t s = (hipStream_t)stream;
-  if (!p || !g || !m || !v || n == 0 || !step_dev || !bc_dev || (ema_mode && !ema)) return set_err(SRGANFD_EINVAL, "adam(dev): bad args");
+  if (!p || !g || !m || !v || !step_dev || !bc_dev || (ema_mode && !ema)) return set_err(SRGANFD_EINVAL, "adam(dev): bad args");
+  if (numel <= 0) return set_err(SRGANFD_EINVAL, "adam(dev): numel <= 0");
+  if (ema_mode < 0 || ema_mode > 2) return set_err(SRGANFD_EINVAL, "adam(dev): ema_mode %d is none of 0, 1, 2", (int)ema_mode);
   SRGANFD_LAUNCH(adam_step_kernel, dim3(1), dim3(64), 0, s, step_dev, b1, b2, bc_dev, skip_flag);
   SRGANFD_LAUNCH(adam_ema_dev_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, g, m, v, ema, n, lr, b1, b2, eps, wd, (const float*)bc_dev, grad_scale,
                  ema_decay, ema_mode, skip_flag, grad_scale_dev);

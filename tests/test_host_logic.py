@@ -303,6 +303,98 @@ def test_resampling_and_layout_entry_points_refuse_planar_views_and_bad_argument
         A.set_dry_run(False)
 
 
+def test_elementwise_loss_and_adam_entry_points_refuse_planar_views_bad_slices_and_bad_counts():
+    """include/srganfd.h: only the convolutions take planar views.  The per-element maps, the L1 losses on views, the attention gate's
+    pieces and BatchNorm read one as NHWC without a word, took a slice that ends past its buffer, and turned a negative count into a
+    grid over 2^64 elements.  Dry run with made-up addresses: nothing of this may ever reach a GPU."""
+    from sr_gan_fd_amd import _abi as A
+    L = A.lib()
+    A.set_dry_run(True)
+    try:
+        p = 4096                                              # a non-null, 16-byte aligned address; nothing is dereferenced in dry-run mode
+        V = lambda planar=0, cs=64, c0=0: A.View(p, cs, c0, planar, 0)
+        err = lambda: L.srganfd_last_error()
+        wrong = []                                            # every case is tried, so that a failure lists all of them
+
+        def expect(ok, what):
+            if not ok:
+                wrong.append(str(what))
+
+        bn_fwd = lambda x, y: (x, y, A.F16, 64, 32, p, p, p, p, 0.1, 1e-5)
+        bn_bwd = lambda x, dy, dx: (x, dy, dx, A.F16, 64, 32, p, p, p, p, 0.0, p)
+        # every view argument of every entry point in turn: (name, number of views, call(views, npix, c))
+        on_views = [
+            ("lrelu_bwd", 4, lambda v, n, c: L.srganfd_lrelu_bwd(v[0], v[1], v[2], v[3], A.F16, n, c, 0.2, 0)),
+            ("lrelu_bwd scalar form", 4, lambda v, n, c: L.srganfd_lrelu_bwd(v[0], v[1], v[2], v[3], A.F32, n, c - 1 if c > 1 else c, 0.2, 0)),
+            ("axpby", 2, lambda v, n, c: L.srganfd_axpby(v[0], v[1], A.F16, n, c, 1.0, 1.0, 0)),
+            ("axpby scalar form", 2, lambda v, n, c: L.srganfd_axpby(v[0], v[1], A.F32, n, c - 1 if c > 1 else c, 1.0, 0.0, 0)),
+            ("add_relu", 3, lambda v, n, c: L.srganfd_add_relu(v[0], v[1], v[2], A.F16, n, c, 0)),
+            ("gate_mul", 2, lambda v, n, c: L.srganfd_gate_mul(0, v[0], p, v[1], A.NULL_VIEW, None, A.F16, n, c, 0)),
+            ("gate_mul bwd", 3, lambda v, n, c: L.srganfd_gate_mul(1, v[0], p, v[1], v[2], p, A.F16, n, c, 0)),
+            ("l1_loss_views", 2, lambda v, n, c: L.srganfd_l1_loss_views(v[0], v[1], A.F16, n, c, 1, 1.0, p, 0, p, 0)),
+            ("l1_loss_views scalar form", 2, lambda v, n, c: L.srganfd_l1_loss_views(v[0], v[1], A.F32, n, c - 1 if c > 1 else c, 0, 1.0, p, 0, p, 0)),
+            ("l1_grad_views", 3, lambda v, n, c: L.srganfd_l1_grad_views(v[0], v[1], v[2], A.F16, n, c, None, 1.0, 0)),
+        ]
+        for name, nv, f in on_views:
+            good = [V() for _ in range(nv)]
+            expect(f(good, 6, 32) == 0, name + ": " + err().decode())
+            for k in range(nv):
+                expect(f(good[:k] + [V(1)] + good[k + 1:], 6, 32) == -1 and b"planar" in err(), f"{name}: planar view {k}")
+                expect(f(good[:k] + [V(c0=40)] + good[k + 1:], 6, 32) == -1 and b"past its buffer" in err(), f"{name}: view {k} ends past its buffer")
+                expect(f(good[:k] + [V(c0=32)] + good[k + 1:], 6, 32) == 0, f"{name}: view {k} ends with its buffer: " + err().decode())
+            for n in (-1, -2 ** 40, 0):
+                expect(f(good, n, 32) == -1 and b"npix <= 0" in err(), f"{name}: npix = {n}")
+            for c in (0, -8):
+                expect(f(good, 6, c) == -1, f"{name}: c = {c}")
+        expect(L.srganfd_lrelu_bwd(V(), V(), V(), V(), A.F16, 6, 0, 0.2, 0) == -1 and b"c <= 0" in err(), "lrelu_bwd: c = 0 names its cause")
+        expect(L.srganfd_axpby(V(), V(), A.F16, 6, 0, 1.0, 1.0, 0) == -1 and b"c <= 0" in err(), "axpby: c = 0 names its cause")
+        expect(L.srganfd_l1_loss_views(V(), V(), A.F16, 6, 0, 0, 1.0, p, 0, p, 0) == -1 and b"c <= 0" in err(), "l1_loss_views: c = 0 names its cause")
+        # the flat single-channel form the trainers add gradients with
+        expect(L.srganfd_axpby(A.View(p, 1, 0), A.View(p + 64, 1, 0), A.F32, 1000, 1, 1.0, 1.0, 0) == 0, "axpby: the flat form")
+        # BatchNorm, all six forms: planar, and a slice past its buffer, on every view (act included)
+        bn = [
+            ("batchnorm_fwd", 2, lambda v: L.srganfd_batchnorm_fwd(*bn_fwd(v[0], v[1]), 1, p, p, 0)),
+            ("batchnorm_act_fwd", 2, lambda v: L.srganfd_batchnorm_act_fwd(*bn_fwd(v[0], v[1]), 1, p, p, 0.2, 0)),
+            ("batchnorm_fwd_sync", 2, lambda v: L.srganfd_batchnorm_fwd_sync(*bn_fwd(v[0], v[1]), p, p, 0.2, 1, 0, 0)),
+            ("batchnorm_bwd", 3, lambda v: L.srganfd_batchnorm_bwd(*bn_bwd(v[0], v[1], v[2]), 0)),
+            ("batchnorm_act_bwd", 4, lambda v: L.srganfd_batchnorm_act_bwd(*bn_bwd(v[0], v[1], v[2]), v[3], 0.2, 0)),
+            ("batchnorm_bwd_sync", 4, lambda v: L.srganfd_batchnorm_bwd_sync(*bn_bwd(v[0], v[1], v[2]), None, v[3], 0.2, 1, 0, 0)),
+        ]
+        for name, nv, f in bn:
+            good = [V() for _ in range(nv)]
+            expect(f(good) == 0, name + ": " + err().decode())
+            for k in range(nv):
+                expect(f(good[:k] + [V(1)] + good[k + 1:]) == -1 and b"planar" in err(), f"{name}: planar view {k}")
+                expect(f(good[:k] + [V(c0=40)] + good[k + 1:]) == -1 and b"past its buffer" in err(), f"{name}: view {k} ends past its buffer")
+        # flat arrays: a count that is negative or zero
+        ws = p
+        flat = {
+            "l1_loss": lambda n: L.srganfd_l1_loss(p, p, n, 1.0, p, 0, p, 1.0, None, ws, 0),
+            "bce_logits": lambda n: L.srganfd_bce_logits(p, n, 1.0, 1.0, p, 0, p, p, 1.0, None, ws, 0),
+            "nonfinite_flag": lambda n: L.srganfd_nonfinite_flag(p, n, p, 0, 0),
+            "adam_ema": lambda n: L.srganfd_adam_ema(p, p, p, p, p, n, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, 1.0, 0.999, 2, None, None, 0),
+            "adam_ema_dev": lambda n: L.srganfd_adam_ema_dev(p, p, p, p, p, n, 1e-3, 0.9, 0.999, 1e-8, 0.0, p, p, 1.0, 0.999, 2, None, None, 0),
+            "sigmoid": lambda n: L.srganfd_sigmoid(p, n, 0),
+            "sigmoid_bwd": lambda n: L.srganfd_sigmoid_bwd(p, p, p, n, 0),
+            "sigmoid_of_mean": lambda n: L.srganfd_sigmoid_of_mean(p, n, p, ws, 0),
+            "bce_logits_relativistic": lambda n: L.srganfd_bce_logits_relativistic(p, n, p, 5, 1.0, 1.0, p, 0, p, 0, p, 0, 1.0, None, ws, 0),
+            "bce_logits_relativistic other": lambda n: L.srganfd_bce_logits_relativistic(p, 5, p, n, 1.0, 1.0, p, 0, p, 0, p, 0, 1.0, None, ws, 0),
+        }
+        for name, f in flat.items():
+            expect(f(1000) == 0 and f(1) == 0, name + ": " + err().decode())
+            for n in (-1, -2 ** 40, 0):
+                expect(f(n) == -1, f"{name}: numel = {n}")
+                if "relativistic" not in name and name != "sigmoid_of_mean":
+                    expect(b"numel <= 0" in err(), f"{name}: numel = {n}: {err().decode()}")
+        # Adam's EMA mode
+        for mode, rc in ((0, 0), (1, 0), (2, 0), (3, -1), (-1, -1)):
+            expect(L.srganfd_adam_ema(p, p, p, p, p, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1, 1.0, 0.999, mode, None, None, 0) == rc and (rc == 0 or b"ema_mode" in err()), f"adam: ema_mode = {mode}")
+            expect(L.srganfd_adam_ema_dev(p, p, p, p, p, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, p, p, 1.0, 0.999, mode, None, None, 0) == rc and (rc == 0 or b"ema_mode" in err()), f"adam: ema_mode = {mode}")
+        assert not wrong, "%d cases:\n  " % len(wrong) + "\n  ".join(wrong)
+    finally:
+        A.set_dry_run(False)
+
+
 def test_validation_side_argument_checks():
     from sr_gan_fd_amd import _abi as A
     A.set_dry_run(True)
