@@ -144,8 +144,9 @@ class FlatParams:
 # generator (RRDBNet / BSRGAN) engine
 # ------------------------------------------------------------------------------------------------
 class _Shape:
-    """Per-(N,H,W,training) buffers and pre-built launch lists."""
-    pass
+    """Per-(N,H,W,training) buffers and pre-built launch lists.  EngineBase names what the passes read of a plan; the class
+    attributes are what a plan that has no such thing need not set."""
+    result = per_call = dx_out = dx_conv = gtmp = token = None
 
 
 class PlanCache:
@@ -188,7 +189,30 @@ class PlanCache:
 
 class EngineBase:
     """What every engine owns: the module's parameters as one flat buffer, the per-shape plans, one packed-weight record per compute
-    dtype (built by the subclass's ``_build_pack``) and the token that ties a backward pass to its forward."""
+    dtype (built by the subclass's ``_build_pack``), the token that ties a backward pass to its forward, and the one forward and
+    backward pass over a plan's launch lists.
+
+    A subclass describes its network -- ``_build_pack`` and ``_plan(N, H, W, dt, dtc, device, pk, train)`` -- and names its
+    ``what`` (the reference class, for messages), ``in_ch`` and ``out_ch``.  What differs between the engines at the boundary of a
+    pass is data on the plan ``sp`` (items: ops.py's, each with ``launch(run)``):
+      sp.fw                  forward items
+      sp.x_in                (view, pitch): where the NCHW input goes as NHWC, in_ch real channels of ``pitch`` written
+      sp.hs, sp.ws           height and width of the result
+      sp.result              (view, dtype code, clamp): the NHWC buffer the (N, out_ch, hs, ws) result is read from (``clamp``: to
+                             [0, 1], the generator's image), or None: the result is the per-call tensor
+      sp.per_call            shape of an fp32 tensor allocated per forward, which the list's ops.PerCall item writes (``run.out``): the
+                             discriminators' logits, SelfAttention's weights; or None
+    and, on a plan built with ``train`` (sp.token: the forward it holds the activations of),
+      sp.bw                  backward items
+      sp.dy_in               (view, pitch): where the result's NCHW gradient goes as NHWC (through the clamp's derivative where the
+                             result was clamped)
+      sp.dx_out              (view, dtype code) of the input's gradient, or None (an image: nobody asks)
+      sp.dx_conv             None, or the item of the first layer's data gradient: launched only by a pass that wants dx
+      sp.wg_ws, sp.gtmp      the weight-gradient workspace; None, or the scratch gradient of an engine whose backward list writes
+                             gradients that are no Wgrad's (BatchNorm, spectral norm): where they go when the parameters are frozen"""
+    what = "engine"
+    unshuffle = 1                      # PixelUnshuffle factor in front of the first layer (Real-ESRGAN's generator below x4)
+    batch_stats = False                # BatchNorm layers: backward needs the batch statistics of a training-mode forward
 
     def __init__(self, owner: nn.Module, named_params: Sequence[Tuple[str, nn.Parameter]]):
         self.owner = owner
@@ -210,12 +234,86 @@ class EngineBase:
             self.packed[dtc] = pk
         return pk
 
-    def _ensure_packed(self, dtc: int, device) -> dict:
+    def _ensure_packed(self, dtc: int, device, training: bool = False) -> dict:
         """... and packed again when the parameter values changed since this record was last packed"""
         pk = self._packed(dtc, device)
         if self.fp.stale(pk):
             pk["table"].run(self.fp.flat, pk["buf"])
         return pk
+
+    # -- execution ----------------------------------------------------------------------------
+    def _check_input(self, x: Tensor) -> Tuple[int, int, int]:
+        """the input contract, checked before anything is packed, planned or launched; returns the (N, H, W) the plan is built for"""
+        check_channels(self.what, x, self.in_ch)
+        return x.shape[0], x.shape[2], x.shape[3]
+
+    def _pass(self, x: Tensor, train: bool, training: bool = False, per_call: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+        """One forward pass.  x: NCHW; ``train``: on a plan with a backward list, which then holds this pass's activations;
+        ``training``: the module's mode (BatchNorm statistics, spectral-norm iteration); ``per_call``: False skips the plan's per-call
+        tensor and the launch that writes it.  Returns (the NCHW fp32 result read from sp.result, the per-call tensor)."""
+        N, H, W = self._check_input(x)
+        _require_gpu(x)
+        dt, dtc = _dt(self.owner)
+        dev = x.device
+        pk = self._ensure_packed(dtc, dev, training)
+        sp = self._plan(N, H, W, dt, dtc, dev, pk, train)
+        if self.unshuffle > 1:
+            # a pure re-indexing of the image (no parameters, no arithmetic; the image needs no gradient): conv1 then reads 12 / 48
+            # channels (padded to 32 / 64 for the MFMA path) at the trunk's size
+            x = torch.nn.functional.pixel_unshuffle(x, self.unshuffle)
+        x = x.contiguous().float()
+        L, st = A.lib(), A.stream_ptr()
+        view, pitch = sp.x_in
+        A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.in_ch, H, W, view, dtc, pitch, None, None, st), "nchw_to_nhwc")
+        own = torch.empty(sp.per_call, dtype=torch.float32, device=dev) if per_call and sp.per_call else None
+        ops.run_items(sp.fw, ops.Run("conv2d", training=training, out=0 if own is None else own.data_ptr()))
+        out = None
+        if sp.result is not None:
+            view, code, clamp = sp.result
+            out = torch.empty(N, self.out_ch, sp.hs, sp.ws, dtype=torch.float32, device=dev)
+            A.check(L.srganfd_nhwc_to_nchw(view, code, N, self.out_ch, sp.hs, sp.ws, out.data_ptr(), clamp, st), "nhwc_to_nchw")
+        if train:
+            self.token += 1
+            sp.token, sp.training = self.token, training
+        self._last = sp
+        return out, own
+
+    def forward(self, x: Tensor, train: bool) -> Tensor:
+        """x: NCHW (an image, or a lone block's feature map).  Returns NCHW fp32."""
+        return self._pass(x, train)[0]
+
+    def backward(self, sp: "_Shape", token: int, dout: Tensor, need_wgrad: bool, need_dx: bool, on_ready=None) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+        """dout: NCHW gradient of forward()'s result.  Returns (flat parameter gradient or None, dx or None); a pass with frozen
+        parameters (``need_wgrad`` False) skips the weight-gradient launches.  ``on_ready(flat_grad, lo, hi)`` (data parallelism,
+        parallel.BucketReducer.bucket) is called when every launch that writes elements [lo, hi) of the flat gradient has been
+        enqueued; the ranges are disjoint and cover the whole buffer."""
+        if sp.token != token:
+            raise A.SrganfdError(f"{self.what}: activations or normalisation state were overwritten by a later forward of the same module "
+                                 "before backward ran")
+        if self.batch_stats and not sp.training:
+            raise A.SrganfdError(f"{self.what} backward is implemented for training-mode forwards (BatchNorm batch statistics)")
+        L, st = A.lib(), A.stream_ptr()
+        N, dtc = sp.N, sp.dtc
+        dout = dout.contiguous().float()
+        view, pitch = sp.dy_in
+        if sp.result is not None and sp.result[2]:
+            A.check(L.srganfd_clamp_grad_to_nhwc(dout.data_ptr(), sp.result[0], N, self.out_ch, sp.hs, sp.ws, view, dtc, pitch, st), "clamp_grad")
+        else:
+            A.check(L.srganfd_nchw_to_nhwc(dout.data_ptr(), N, self.out_ch, sp.hs, sp.ws, view, dtc, pitch, None, None, st), "nchw_to_nhwc")
+        # frozen parameters: what else lands in the flat gradient goes to the scratch gradient
+        flat_grad = self.fp.new_grad(sp.device) if need_wgrad else sp.gtmp
+        run = ops.Run("conv2d(dgrad)", need_wgrad=need_wgrad, grad=0 if flat_grad is None else flat_grad.data_ptr(),
+                      scratch=0 if sp.gtmp is None else sp.gtmp.data_ptr(), ws=sp.wg_ws,
+                      on_ready=None if on_ready is None else functools.partial(on_ready, flat_grad))
+        ops.run_items(sp.bw, run)
+        dx = None
+        if need_dx and sp.dx_out is not None:
+            if sp.dx_conv is not None:
+                sp.dx_conv.launch(run)
+            view, code = sp.dx_out
+            dx = torch.empty(N, self.in_ch, sp.H, sp.W, dtype=torch.float32, device=sp.device)
+            A.check(L.srganfd_nhwc_to_nchw(view, code, N, self.in_ch, sp.H, sp.W, dx.data_ptr(), 0, st), "nhwc_to_nchw")
+        return (flat_grad if need_wgrad else None), dx
 
 
 class TrunkEngine(EngineBase):
@@ -237,7 +335,8 @@ class TrunkEngine(EngineBase):
         if self.Cc % 32 or self.G % 32:
             raise A.SrganfdError("channels and growth_channels must be multiples of 32 for the MFMA path")
         self.Ccat = self.Cc + 4 * self.G
-        self.unshuffle = 1
+        self.what = "generator" if full else "dense block"
+        self.in_ch = self.out_ch = self.Cc
         # nearest-x2 + 3x3 upsampling layers in parity form (16-bit modes): the forward as four 2x2-tap classes over the low-res input, the data
         # gradient as one 4x4 stride-2 conv over the high-res gradient.  0: the up=1 gather forward, the high-res data gradient and the
         # nearest adjoint (same-process A/B: the switch is read when the engine is built)
@@ -304,7 +403,7 @@ class TrunkEngine(EngineBase):
         return pb.finish(device)
 
     # -- per-shape plan -----------------------------------------------------------------------
-    def _plan(self, N: int, H: int, W: int, dt: torch.dtype, dtc: int, device, train: bool, pk: dict) -> _Shape:
+    def _plan(self, N: int, H: int, W: int, dt: torch.dtype, dtc: int, device, pk: dict, train: bool) -> _Shape:
         # the launch lists bake absolute pointers into the packed buffer AND the flat parameter buffer (biases): both are in the key
         key = (N, H, W, dtc, train, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
         sp = self.shapes.get(key)
@@ -383,6 +482,10 @@ class TrunkEngine(EngineBase):
             fw.append(ops.features_to_image(dtc, sp.thin_o, V(sp.c3), sp.srp, 4, bias("conv4.weight"), wptr + pk["offs"][("f", "conv4")], N, h, w,
                                             self.out_ch, Cc, False, bias=bias("conv4.bias")))
             sp.hs, sp.ws = h, w
+            sp.x_in, sp.result = (V(sp.xin), sp.xin.shape[-1]), (V(sp.srp), A.F32, 1)
+        else:
+            sp.hs, sp.ws = H, W
+            sp.x_in, sp.result = (V(catb(0)), Cc), (V(catb(R)), dtc, 0)
         sp.fw = fw
         sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
         if train:
@@ -412,6 +515,8 @@ class TrunkEngine(EngineBase):
         sp.dy = [new(N, H, W, Ccat) for _ in range(4)]
         sp.dx0 = new(N, H, W, Cc)           # gradient w.r.t. the trunk input
         dyb = lambda i: sp.dy[i % 4]
+        if not self.full:
+            sp.dy_in, sp.dx_out = (V(dyb(R - 1)), Cc), (V(sp.dx0), dtc)
         bw = []                              # ops.Conv | Wgrad | ThinLaunch | DenseChain | Call and the bucket markers ops.Ready
         cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
         wplans = ops.WgradPlans(device, dtc, N)
@@ -420,6 +525,7 @@ class TrunkEngine(EngineBase):
             s = 1 << self.n_up
             hs, ws_ = sp.hs, sp.ws
             sp.dsrp = new(N, hs, ws_, 4 if sp.thin_o else 32)
+            sp.dy_in = (V(sp.dsrp), sp.dsrp.shape[-1])
             sp.gA = new(N, hs, ws_, Cc)
             fptr = self.fp.flat.data_ptr()
             sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device) if (sp.thin_i or sp.thin_o) else None
@@ -525,7 +631,7 @@ class TrunkEngine(EngineBase):
         shape = tuple(shape)
         u = self.unshuffle
         want_c = self.in_ch // (u * u) if self.full else self.Cc
-        what = "generator" if self.full else "dense block"
+        what = self.what
         if len(shape) != 4:
             raise A.SrganfdError(f"{what} expects a 4-D (N, {want_c}, H, W) input, got shape {shape}")
         N, c, H, W = shape
@@ -543,58 +649,13 @@ class TrunkEngine(EngineBase):
             return (N, self.Cc, H, W)
         return (N, self.out_ch, H << self.n_up, W << self.n_up)
 
-    def forward(self, x: Tensor, train: bool) -> Tensor:
-        """x: NCHW fp32 (generator: image; trunk-only: feature map).  Returns NCHW fp32."""
-        N, H, W = self.trunk_size(x.shape)
-        _require_gpu(x)
-        dt, dtc = _dt(self.owner)
-        dev = x.device
-        pk = self._ensure_packed(dtc, dev)
-        sp = self._plan(N, H, W, dt, dtc, dev, train, pk)
-        if self.unshuffle > 1:
-            # a pure re-indexing of the image (no parameters, no arithmetic; the image needs no gradient): conv1 then reads 12 / 48
-            # channels (padded to 32 / 64 for the MFMA path) at the trunk's size
-            x = torch.nn.functional.pixel_unshuffle(x, self.unshuffle)
-        x = x.contiguous().float()
-        L, st = A.lib(), A.stream_ptr()
-        if self.full:
-            A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.in_ch, H, W, A.view(sp.xin), dtc, sp.xin.shape[-1], None, None, st), "nchw_to_nhwc")
-        else:
-            A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.Cc, H, W, A.view(sp.catb(0)), dtc, self.Cc, None, None, st), "nchw_to_nhwc")
-        ops.run_items(sp.fw, ops.Run("conv2d"))
-        if self.full:
-            out = torch.empty(N, self.out_ch, sp.hs, sp.ws, dtype=torch.float32, device=dev)
-            A.check(L.srganfd_nhwc_to_nchw(A.view(sp.srp), A.F32, N, self.out_ch, sp.hs, sp.ws, out.data_ptr(), 1, st), "nhwc_to_nchw")
-        else:
-            out = torch.empty(N, self.Cc, H, W, dtype=torch.float32, device=dev)
-            A.check(L.srganfd_nhwc_to_nchw(A.view(sp.catb(self.R)), dtc, N, self.Cc, H, W, out.data_ptr(), 0, st), "nhwc_to_nchw")
-        if train:
-            self.token += 1
-            sp.token = self.token
-        self._last = sp
-        return out
+    def _check_input(self, x: Tensor) -> Tuple[int, int, int]:
+        return self.trunk_size(x.shape)
 
-    def backward(self, sp: _Shape, token: int, dout: Tensor, need_dx: bool, on_ready=None) -> Tuple[Tensor, Optional[Tensor]]:
-        """dout: NCHW fp32 gradient of forward()'s result.  Returns (flat parameter gradient, dx or None).
-        ``on_ready(flat_grad, lo, hi)`` (data parallelism, parallel.BucketReducer.bucket) is called when every launch that writes
-        elements [lo, hi) of the flat gradient has been enqueued; the ranges are disjoint and cover the whole buffer."""
-        if getattr(sp, "token", None) != token:
-            raise A.SrganfdError("generator activations were overwritten by a later training-mode forward before backward ran")
-        L, st = A.lib(), A.stream_ptr()
-        N, H, W, dtc = sp.N, sp.H, sp.W, sp.dtc
-        dout = dout.contiguous().float()
-        flat_grad = self.fp.new_grad(sp.device)
-        if self.full:
-            A.check(L.srganfd_clamp_grad_to_nhwc(dout.data_ptr(), A.view(sp.srp), N, self.out_ch, sp.hs, sp.ws, A.view(sp.dsrp), dtc, sp.dsrp.shape[-1], st), "clamp_grad")
-        else:
-            A.check(L.srganfd_nchw_to_nhwc(dout.data_ptr(), N, self.Cc, H, W, A.view(sp.dy[(self.R - 1) % 4]), dtc, self.Cc, None, None, st), "nchw_to_nhwc")
-        ops.run_items(sp.bw, ops.Run("conv2d(dgrad)", grad=flat_grad.data_ptr(), ws=sp.wg_ws,
-                                     on_ready=None if on_ready is None else functools.partial(on_ready, flat_grad)))
-        dx = None
-        if need_dx and not self.full:
-            dx = torch.empty(N, self.Cc, H, W, dtype=torch.float32, device=sp.device)
-            A.check(L.srganfd_nhwc_to_nchw(A.view(sp.dx0), dtc, N, self.Cc, H, W, dx.data_ptr(), 0, st), "nhwc_to_nchw")
-        return flat_grad, dx
+    def backward(self, sp: _Shape, token: int, dout: Tensor, need_wgrad: bool, need_dx: bool, on_ready=None) -> Tuple[Tensor, Optional[Tensor]]:
+        # the weight gradients are always computed: the dense blocks' WgradPartial / WgradReduce do not look at the flag, so a pass with
+        # frozen parameters launches what it always has (skipping them would change what is launched: a change of its own)
+        return super().backward(sp, token, dout, True, need_dx, on_ready)
 
 
 # dense blocks whose weight-gradient slabs one srganfd_wgrad_reduce_batch launch reduces (<= 8 = SRGANFD's kRedBatch; 0 / 1: every block's own)
@@ -626,20 +687,26 @@ def batch_reductions(items: Sequence, slots: Sequence[Tensor]) -> list:
     return out
 
 
-class _TrunkFn(torch.autograd.Function):
+class _EngineFn(torch.autograd.Function):
+    """An engine's forward(x, *args) under autograd: differentiable in the input and the parameters.  Where forward returns a tuple
+    (SelfAttention: the weights), the first element is the result and the rest is handed over beside it, detached.  engine_apply is
+    the only caller and asks a generator for a training plan, so a backward through a forward that ran without gradients cannot
+    happen (a plan without a backward list has no token, and EngineBase.backward's token check would refuse it)."""
+
     @staticmethod
-    def forward(ctx, x, eng, train, *params):
-        out = eng.forward(x, train)
-        ctx.eng, ctx.sp, ctx.token, ctx.train = eng, eng._last, eng.token, train
-        ctx.need_dx = ctx.needs_input_grad[0]
+    def forward(ctx, x, eng, args, *params):
+        out = eng.forward(x, *args)
+        ctx.eng, ctx.sp, ctx.token = eng, eng._last, eng.token
+        ctx.need_dx, ctx.need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[3:])
+        if isinstance(out, tuple):
+            ctx.mark_non_differentiable(*(t for t in out[1:] if t is not None))
         return out
 
     @staticmethod
-    def backward(ctx, dout):
-        if not ctx.train:
-            raise A.SrganfdError("backward through a forward that ran without gradients")
-        flat_grad, dx = ctx.eng.backward(ctx.sp, ctx.token, dout, ctx.need_dx)
-        return (dx, None, None) + tuple(ctx.eng.fp.grad_views(flat_grad))
+    def backward(ctx, dout, *_):
+        g, dx = ctx.eng.backward(ctx.sp, ctx.token, dout, ctx.need_w, ctx.need_dx)
+        grads = tuple(ctx.eng.fp.grad_views(g)) if g is not None else (None,) * len(ctx.eng.fp.params)
+        return (dx, None, None) + grads
 
 
 def _engine(owner: nn.Module, factory):
@@ -656,15 +723,18 @@ def _engine(owner: nn.Module, factory):
     return eng
 
 
-def _run_trunk(eng: "TrunkEngine", x: Tensor) -> Tensor:
+def engine_apply(eng: EngineBase, x: Tensor, *args):
+    """A module's forward: through autograd when the input or a parameter wants a gradient.  ``args``: what the engine's forward takes
+    after x (a discriminator's ``training``, SelfAttention's ``need_weights``); none for a generator, whose ``train`` is the answer"""
     train = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in eng.fp.params))
+    args = args or (train,)
     if not train:
-        return eng.forward(x, False)
-    return _TrunkFn.apply(x, eng, True, *eng.fp.params)
+        return eng.forward(x, *args)
+    return _EngineFn.apply(x, eng, args, *eng.fp.params)
 
 
 def trunk_apply(owner: nn.Module, x: Tensor, rdbs: Sequence[nn.Module], rrdb: bool) -> Tensor:
-    return _run_trunk(_engine(owner, lambda: TrunkEngine(owner, rdbs, rrdb, full=False)), x)
+    return engine_apply(_engine(owner, lambda: TrunkEngine(owner, rdbs, rrdb, full=False)), x)
 
 
 def generator_engine(owner: nn.Module) -> TrunkEngine:
@@ -677,7 +747,7 @@ def generator_engine(owner: nn.Module) -> TrunkEngine:
 
 
 def generator_apply(owner: nn.Module, x: Tensor) -> Tensor:
-    return _run_trunk(generator_engine(owner), x)
+    return engine_apply(generator_engine(owner), x)
 
 
 def discriminator_apply(owner: nn.Module, x: Tensor) -> Tensor:

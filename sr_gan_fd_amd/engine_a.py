@@ -20,8 +20,8 @@ from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
-from .engine import _engine, _Shape
-from .engine_core import DiscriminatorEngineCore, discriminator_forward, first_layer_dgrad
+from .engine import _engine, _Shape, engine_apply
+from .engine_core import DiscriminatorEngineCore, first_layer_dgrad
 
 # (name, ksize, stride, pad) of the spectral-normalised convs, in forward order
 SN_LAYERS = [("conv1", 3, 2, 1), ("conv2", 3, 2, 1), ("conv3", 3, 2, 1), ("gating", 1, 1, 1), ("cat_1.convU", 3, 1, 1),
@@ -142,7 +142,7 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
         return pb.finish(device)
 
     # ---- plan ----
-    def _plan(self, N, H, W, dt, dtc, device, pk):
+    def _plan(self, N, H, W, dt, dtc, device, pk, train=True):
         key = (N, H, W, dtc, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
         sp = self.shapes.get(key)
         if sp is not None:
@@ -365,7 +365,7 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
         sp.bw = bw
         self._backward_workspaces(sp, wplans, pk)
 
-    # ---- execution: the core's passes; the attention maps of the last forward are kept on the module ----
+    # ---- execution: EngineBase's passes; the attention maps of the last forward are kept on the module ----
     def forward(self, x: Tensor, training: bool) -> Tensor:
         logits = super().forward(x, training)
         sp, o = self._last, self.owner
@@ -378,4 +378,4 @@ def aesrgan_engine(owner: nn.Module) -> AesrganDiscriminatorEngine:
 
 
 def aesrgan_discriminator_apply(owner: nn.Module, x: Tensor) -> Tensor:
-    return discriminator_forward(aesrgan_engine(owner), owner, x)
+    return engine_apply(aesrgan_engine(owner), x, owner.training)

@@ -1,16 +1,13 @@
-"""What the three discriminator engines (engine_d.py, engine_a.py, engine_e.py) share: spectral-norm state and packing, the
-forward and backward passes over the launch lists, and the autograd glue.
+"""What the three discriminator engines (engine_d.py, engine_a.py, engine_e.py) share: the spectral-norm state, the packing step
+that runs its power iteration, the last item of their backward lists (SnGradBatch) and the plan data that is the same for all three.
+The passes over the launch lists and the autograd glue are engine.py's (EngineBase).
 
 A subclass describes its network: the layer tables, ``_build_pack``, ``_plan`` / ``_plan_backward`` (the launch lists) and, beside
-itself, the launch items only it has (BatchNorm).  A plan ``sp`` carries (items: ops.py's, each with ``launch(run)``)
-  sp.xin                 NHWC input buffer (4-channel pitch for the thin kernels, else padded to 32)
-  sp.fw                  forward items: ops.Conv | ops.ThinLaunch | ops.Call | the engine's own; the last one, an ops.PerCall, writes
-                         the fp32 logits (allocated per forward: ``run.out``)
-  sp.dl                  NHWC buffer of the logits' gradient
-  sp.bw                  backward items: the forward kinds and ops.Wgrad (``sn``: the layer's spectral-norm slot, or None); the last
-                         one is the SnGradBatch ``_backward_workspaces`` appends
-  sp.dx_conv, sp.dxp     the item (``first_layer_dgrad``) of the first layer's data gradient and its fp32 NHWC4 output
-  sp.wg_ws, sp.gtmp      workspaces (``_backward_workspaces``)
+itself, the launch items only it has (BatchNorm).  Its plans always carry a backward list.  Of what EngineBase reads from a plan, a
+subclass sets sp.xin (the NHWC input buffer: 4-channel pitch for the thin kernels, else padded to 32), sp.dl (NHWC buffer of the
+logits' gradient), sp.dxp and sp.dx_conv (the fp32 NHWC4 gradient of the input and the item, ``first_layer_dgrad``, that writes it);
+``_backward_workspaces`` derives the rest, sp.per_call among it: the shape of the logits, which the last forward item, an
+ops.PerCall, writes.  In sp.bw, an ops.Wgrad carries ``sn``: the layer's spectral-norm slot, or None.
 """
 from __future__ import annotations
 
@@ -23,7 +20,7 @@ from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
-from .engine import EngineBase, _dt, _require_gpu, _Shape, check_channels
+from .engine import EngineBase, _Shape
 
 
 class SnGradBatch:
@@ -58,7 +55,7 @@ def first_layer_dgrad(item):
 
 class DiscriminatorEngineCore(EngineBase):
     what = "discriminator"             # the reference class's name, for messages
-    batch_stats = False                # BatchNorm layers: backward needs the batch statistics of a training-mode forward
+    out_ch = 1                         # the logits
 
     def __init__(self, owner: nn.Module, in_ch: int, sn_params: Sequence[str] = ()):
         """sn_params: names of the spectral-normalised weights (``....weight_orig``) in the order of their 1/sigma slots: layer l's
@@ -94,6 +91,10 @@ class DiscriminatorEngineCore(EngineBase):
         return pk
 
     def _backward_workspaces(self, sp: _Shape, wplans: ops.WgradPlans, pk: dict) -> None:
+        """what every discriminator's plan ends with: where the passes enter and leave it (EngineBase), and the workspaces"""
+        sp.x_in, sp.dy_in, sp.dx_out = (A.view(sp.xin), sp.xin.shape[-1]), (A.view(sp.dl), sp.dl.shape[-1]), (A.view(sp.dxp), A.F32)
+        sp.hs, sp.ws = sp.dl.shape[1:3]
+        sp.per_call = (sp.N, 1, sp.hs, sp.ws)
         sp.wg_ws = wplans.workspace()
         # spectral-normalised layers write dL/d(W/sigma) here, each into its own range; passes with frozen parameters also send
         # BatchNorm's dgamma / dbeta here
@@ -101,71 +102,6 @@ class DiscriminatorEngineCore(EngineBase):
         sn_ws = torch.empty(len(self.sn) * A.SN_GRAD_WS_FLOATS, dtype=torch.float32, device=sp.device)
         sp.bw.append(SnGradBatch(self, [it.sn for it in sp.bw if isinstance(it, ops.Wgrad) and it.sn is not None], pk.get("scalars"), sn_ws))
 
-    # ---- execution ----
-    def _check_input(self, x: Tensor) -> None:
-        check_channels(self.what, x, self.in_ch)
-
-    def _logits(self, N: int, H: int, W: int, device) -> Tensor:
-        return torch.empty(N, 1, H, W, dtype=torch.float32, device=device)
-
     def forward(self, x: Tensor, training: bool) -> Tensor:
-        self._check_input(x)                       # the shape contract, before anything is packed, planned or launched
-        _require_gpu(x)
-        dt, dtc = _dt(self.owner)
-        dev = x.device
-        pk = self._ensure_packed(dtc, dev, training)
-        N, _, H, W = x.shape
-        sp = self._plan(N, H, W, dt, dtc, dev, pk)
-        L, st = A.lib(), A.stream_ptr()
-        x = x.contiguous().float()
-        A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.in_ch, H, W, A.view(sp.xin), dtc, sp.xin.shape[-1], None, None, st), "nchw_to_nhwc")
-        logits = self._logits(N, H, W, dev)
-        ops.run_items(sp.fw, ops.Run("conv2d", training=training, out=logits.data_ptr()))
-        self.token += 1
-        sp.token, sp.training = self.token, training
-        self._last = sp
-        return logits
-
-    def backward(self, sp: _Shape, token: int, dlogits: Tensor, need_wgrad: bool, need_dx: bool) -> Tuple[Optional[Tensor], Optional[Tensor]]:
-        if getattr(sp, "token", None) != token:
-            raise A.SrganfdError("discriminator activations / normalisation state were overwritten by a later forward before backward ran")
-        if self.batch_stats and not sp.training:
-            raise A.SrganfdError(f"{self.what} backward is implemented for training-mode forwards (BatchNorm batch statistics)")
-        L, st = A.lib(), A.stream_ptr()
-        N, H, W, dtc = sp.N, sp.H, sp.W, sp.dtc
-        dlogits = dlogits.contiguous().float()
-        A.check(L.srganfd_nchw_to_nhwc(dlogits.data_ptr(), N, 1, sp.dl.shape[1], sp.dl.shape[2], A.view(sp.dl), dtc, sp.dl.shape[-1], None, None, st),
-                "nchw_to_nhwc")
-        # frozen parameters: the weight-gradient launches are skipped; what else lands in the flat gradient goes to scratch
-        flat_grad = self.fp.new_grad(sp.device) if need_wgrad else sp.gtmp
-        run = ops.Run("conv2d(dgrad)", need_wgrad=need_wgrad, grad=flat_grad.data_ptr(), scratch=sp.gtmp.data_ptr(), ws=sp.wg_ws)
-        ops.run_items(sp.bw, run)
-        dx = None
-        if need_dx:
-            sp.dx_conv.launch(run)
-            dx = torch.empty(N, self.in_ch, H, W, dtype=torch.float32, device=sp.device)
-            A.check(L.srganfd_nhwc_to_nchw(A.view(sp.dxp), A.F32, N, self.in_ch, H, W, dx.data_ptr(), 0, st), "nhwc_to_nchw")
-        return (flat_grad if need_wgrad else None), dx
-
-
-class _DiscriminatorFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, eng, training, *params):
-        out = eng.forward(x, training)
-        ctx.eng, ctx.sp, ctx.token = eng, eng._last, eng.token
-        ctx.need_dx = ctx.needs_input_grad[0]
-        ctx.need_w = any(ctx.needs_input_grad[3:])
-        return out
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        g, dx = ctx.eng.backward(ctx.sp, ctx.token, dlogits, ctx.need_w, ctx.need_dx)
-        grads = tuple(ctx.eng.fp.grad_views(g)) if g is not None else tuple(None for _ in ctx.eng.fp.params)
-        return (dx, None, None) + grads
-
-
-def discriminator_forward(eng: DiscriminatorEngineCore, owner: nn.Module, x: Tensor) -> Tensor:
-    """the module's forward: through autograd when the input or a parameter wants a gradient"""
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in eng.fp.params)):
-        return _DiscriminatorFn.apply(x, eng, owner.training, *eng.fp.params)
-    return eng.forward(x, owner.training)
+        """the logits of one forward: always on a plan with a backward list, in the module's mode ``training``"""
+        return self._pass(x, True, training)[1]

@@ -11,7 +11,7 @@ place and produces 1/sigma on the device; the weight packer multiplies it in, so
 W/sigma without an extra pass.  Backward: dL/d(W/sigma) from the wgrad kernel goes through
 srganfd_spectral_norm_grad (both the 1/sigma path and the -<G,W>/sigma^2 u v^T path).
 The stride-2 data gradient runs as 4 output-parity classes, each a 2x2-tap stride-1 conv.
-The passes over the launch lists, the spectral-norm plumbing and the autograd glue are engine_core.py's.
+The spectral-norm plumbing is engine_core.py's; the passes over the launch lists and the autograd glue are engine.py's (EngineBase).
 """
 from __future__ import annotations
 
@@ -20,8 +20,8 @@ from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
-from .engine import _engine, _Shape
-from .engine_core import DiscriminatorEngineCore, discriminator_forward, first_layer_dgrad
+from .engine import _engine, _Shape, engine_apply
+from .engine_core import DiscriminatorEngineCore, first_layer_dgrad
 
 SN_LAYERS = [("down_block1", 4, 2), ("down_block2", 4, 2), ("down_block3", 4, 2), ("up_block1", 3, 1),
              ("up_block2", 3, 1), ("up_block3", 3, 1), ("conv2", 3, 1), ("conv3", 3, 1)]
@@ -55,7 +55,7 @@ class DiscriminatorEngine(DiscriminatorEngineCore):
         return pb.finish(device)
 
     # ---- per-shape plan ----
-    def _plan(self, N, S1, S2, dt, dtc, device, pk) -> _Shape:
+    def _plan(self, N, S1, S2, dt, dtc, device, pk, train=True) -> _Shape:
         key = (N, S1, S2, dtc, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
         sp = self.shapes.get(key)
         if sp is not None:
@@ -185,4 +185,4 @@ def discriminator_engine(owner: nn.Module) -> DiscriminatorEngine:
 
 
 def discriminator_apply(owner: nn.Module, x: Tensor) -> Tensor:
-    return discriminator_forward(discriminator_engine(owner), owner, x)
+    return engine_apply(discriminator_engine(owner), x, owner.training)

@@ -23,8 +23,8 @@ from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
-from .engine import _engine, _Shape
-from .engine_core import DiscriminatorEngineCore, discriminator_forward, first_layer_dgrad
+from .engine import _engine, _Shape, engine_apply
+from .engine_core import DiscriminatorEngineCore, first_layer_dgrad
 
 CONV_IDX = (0, 2, 5, 8, 11, 14, 17, 20, 23, 26)          # positions of the convs inside `features`
 SLOPE = 0.2
@@ -100,7 +100,7 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
         return pb.finish(device)
 
     # ---- per-shape plan ----
-    def _plan(self, N, H, W, dt, dtc, device, pk):
+    def _plan(self, N, H, W, dt, dtc, device, pk, train=True):
         self._fw_count += 1
         key = (N, H, W, dtc, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr(), self._fw_count % RING)
         sp = self.shapes.get(key)
@@ -202,16 +202,15 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
         sp.dxp = torch.empty(N, sp.H, sp.W, 4, dtype=torch.float32, device=device)
         sp.dx_conv = first_layer_dgrad(cv(V(dA), V(sp.dxp), wptr + O[("b", 0)], N, sp.H, sp.W, 64, 32, cout_store=3, y_f32=True))
         self._backward_workspaces(sp, wplans, pk)
+        sp.per_call = (N, 1)                      # the classifier's logits: no height and width
 
-    # ---- execution: the core's passes ----
-    def _check_input(self, x: Tensor) -> None:
-        super()._check_input(x)
+    # ---- execution: EngineBase's passes ----
+    def _check_input(self, x: Tensor):
+        dims = super()._check_input(x)
         if tuple(x.shape[2:]) != (128, 128):
             raise A.SrganfdError(f"Discriminator expects 3x128x128 inputs: its classifier is Linear(512*4*4, 100) (ESRGAN/model.py:129); "
                                  f"got shape {tuple(x.shape)}")
-
-    def _logits(self, N, H, W, device) -> Tensor:
-        return torch.empty(N, 1, dtype=torch.float32, device=device)
+        return dims
 
 
 def esrgan_discriminator_engine(owner: nn.Module) -> EsrganDiscriminatorEngine:
@@ -219,4 +218,4 @@ def esrgan_discriminator_engine(owner: nn.Module) -> EsrganDiscriminatorEngine:
 
 
 def esrgan_discriminator_apply(owner: nn.Module, x: Tensor) -> Tensor:
-    return discriminator_forward(esrgan_discriminator_engine(owner), owner, x)
+    return engine_apply(esrgan_discriminator_engine(owner), x, owner.training)

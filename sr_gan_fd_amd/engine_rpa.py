@@ -1,5 +1,7 @@
 """HIP engine of A-ESRGAN's pixel-attention generator (A-ESRGAN/model.py:87-175): one engine class for a lone ``RPA``, a lone ``US``
-and the whole ``Generator_RPA``, which is a list of such blocks between a head (conv1) and a tail (conv2, conv3).
+and the whole ``Generator_RPA``, which is a list of such blocks between a head (conv1) and a tail (conv2, conv3).  The class checks
+the module, packs its weights and plans the launch lists; running them, the layout conversions at both ends of a pass and the
+autograd glue are engine.py's (EngineBase).
 
 Every convolution is a launch of the implicit-GEMM kernel (1x1 and 3x3, forward, data gradient, weight-gradient plans); the one thing
 no existing kernel does, ``z = x * (1 + sigmoid(a))`` and its backward, is srganfd_pixel_gate (csrc/pixel_gate.hip).
@@ -31,14 +33,14 @@ output is its stored y widened to fp32.
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+from typing import Tuple
 
 import torch
 from torch import Tensor, nn
 
 from . import _abi as A
 from . import ops
-from .engine import EngineBase, _dt, _engine, _require_gpu, _Shape, check_channels
+from .engine import EngineBase, _engine, _Shape, engine_apply
 from .engine_core import first_layer_dgrad
 
 WHAT = {"rpa": "RPA", "us": "US", "gen": "Generator_RPA"}
@@ -161,6 +163,8 @@ class RpaEngine(EngineBase):
             fw.append(ops.Conv(ops.conv_args(dtc, V(sp.c2), V(sp.srp), wptr + O[("f", "conv3")], N, h, w, F // 2, 32, cout_store=self.out_ch,
                                              bias=P("conv3.bias"), y_f32=True)))
         sp.fw, sp.last, sp.hs, sp.ws = fw, cur, h, w
+        sp.x_in = (V(sp.xin), sp.xin.shape[-1])
+        sp.result = (V(sp.srp), A.F32, 0) if self.gen else (V(cur), dtc, 0)      # (a lone block: its stored y, widened)
         if train:
             self._plan_backward(sp, pk)
         self.shapes.put(key, sp, pinned=train)
@@ -271,66 +275,13 @@ class RpaEngine(EngineBase):
             sp.dx_conv = first_layer_dgrad(ops.features_to_image(dtc, sp.thin_i, V(dpre), sp.dxp, 4, P("conv1.weight"), wptr + O[("b", "conv1")], N, H, W,
                                                                  self.in_ch, F, True, flip=True))
         sp.pool, sp.wg_ws, sp.bw = pool, wplans.workspace(), bw
+        sp.dy_in, sp.dx_out = (V(sp.dout), sp.dout.shape[-1]), (V(sp.dxp), A.F32)
 
     # ---- execution ----
     def output_shape(self, shape) -> Tuple[int, int, int, int]:
         N, _, H, W = shape
         up = sum(1 for k, _ in self.blocks if k == "us")
         return (N, self.out_ch, H << up, W << up)
-
-    def forward(self, x: Tensor, train: bool) -> Tensor:
-        check_channels(self.what, x, self.in_ch)
-        _require_gpu(x)
-        dt, dtc = _dt(self.owner)
-        dev = x.device
-        pk = self._ensure_packed(dtc, dev)
-        N, _, H, W = x.shape
-        sp = self._plan(N, H, W, dt, dtc, dev, pk, train)
-        L, st = A.lib(), A.stream_ptr()
-        x = x.contiguous().float()
-        A.check(L.srganfd_nchw_to_nhwc(x.data_ptr(), N, self.in_ch, H, W, A.view(sp.xin), dtc, sp.xin.shape[-1], None, None, st), "nchw_to_nhwc")
-        ops.run_items(sp.fw, ops.Run("conv2d"))
-        out = torch.empty(N, self.out_ch, sp.hs, sp.ws, dtype=torch.float32, device=dev)
-        src, src_dt = (sp.srp, A.F32) if self.gen else (sp.last, dtc)
-        A.check(L.srganfd_nhwc_to_nchw(A.view(src), src_dt, N, self.out_ch, sp.hs, sp.ws, out.data_ptr(), 0, st), "nhwc_to_nchw")
-        if train:
-            self.token += 1
-            sp.token = self.token
-        self._last = sp
-        return out
-
-    def backward(self, sp: _Shape, token: int, dout: Tensor, need_wgrad: bool, need_dx: bool) -> Tuple[Optional[Tensor], Optional[Tensor]]:
-        if getattr(sp, "token", None) != token:
-            raise A.SrganfdError(f"{self.what} activations were overwritten by a later forward of the same module before backward ran")
-        L, st = A.lib(), A.stream_ptr()
-        N, H, W, dtc = sp.N, sp.H, sp.W, sp.dtc
-        dout = dout.contiguous().float()
-        A.check(L.srganfd_nchw_to_nhwc(dout.data_ptr(), N, self.out_ch, sp.hs, sp.ws, A.view(sp.dout), dtc, sp.dout.shape[-1], None, None, st), "nchw_to_nhwc")
-        flat_grad = self.fp.new_grad(sp.device) if need_wgrad else None
-        run = ops.Run("conv2d(dgrad)", need_wgrad=need_wgrad, grad=flat_grad.data_ptr() if need_wgrad else 0, ws=sp.wg_ws)
-        ops.run_items(sp.bw, run)
-        dx = None
-        if need_dx:
-            sp.dx_conv.launch(run)
-            dx = torch.empty(N, self.in_ch, H, W, dtype=torch.float32, device=sp.device)
-            A.check(L.srganfd_nhwc_to_nchw(A.view(sp.dxp), A.F32, N, self.in_ch, H, W, dx.data_ptr(), 0, st), "nhwc_to_nchw")
-        return flat_grad, dx
-
-
-class _Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, eng, *params):
-        out = eng.forward(x, True)
-        ctx.eng, ctx.sp, ctx.token = eng, eng._last, eng.token
-        ctx.need_dx = ctx.needs_input_grad[0]
-        ctx.need_w = any(ctx.needs_input_grad[2:])
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        g, dx = ctx.eng.backward(ctx.sp, ctx.token, dout, ctx.need_w, ctx.need_dx)
-        grads = tuple(ctx.eng.fp.grad_views(g)) if g is not None else tuple(None for _ in ctx.eng.fp.params)
-        return (dx, None) + grads
 
 
 def rpa_engine(owner: nn.Module, kind: str) -> RpaEngine:
@@ -339,10 +290,7 @@ def rpa_engine(owner: nn.Module, kind: str) -> RpaEngine:
 
 def rpa_apply(owner: nn.Module, kind: str, x: Tensor) -> Tensor:
     """forward of RPA / US / Generator_RPA: through autograd when the input or a parameter wants a gradient"""
-    eng = rpa_engine(owner, kind)
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in eng.fp.params)):
-        return _Fn.apply(x, eng, *eng.fp.params)
-    return eng.forward(x, False)
+    return engine_apply(rpa_engine(owner, kind), x)
 
 
 def num_usblock(scale: int) -> int:

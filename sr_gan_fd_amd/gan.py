@@ -108,7 +108,7 @@ class GanTrainer(GanCheckpointMixin):
             _, dsr_adv = de.backward(de._last, de.token, dl, False, True)
             A.check(L.srganfd_axpby(A.View(dsr_adv.data_ptr(), 1, 0), A.View(dsr.data_ptr(), 1, 0), A.F32, dsr.numel(), 1, 1.0, 1.0, st), "axpby")
             self.g_reducer.begin()
-            gg, _ = ge.backward(g_sp, g_tok, dsr, False, on_ready=self.g_reducer.bucket)
+            gg, _ = ge.backward(g_sp, g_tok, dsr, True, False, on_ready=self.g_reducer.bucket)
             self.scaler.step(self.g_opt, gg, self.g_reducer.finish())
             ge.fp.touch()
         s = self.scalars.data_ptr()
@@ -165,7 +165,7 @@ class GanTrainer(GanCheckpointMixin):
             _, dsr_adv = de.backward(de._last, de.token, dl, False, True)
             A.check(L.srganfd_axpby(A.View(dsr_adv.data_ptr(), 1, 0), A.View(dsr.data_ptr(), 1, 0), A.F32, dsr.numel(), 1, 1.0, 1.0, st), "axpby")
             self.g_reducer.begin()
-            gg, _ = ge.backward(g_sp, g_tok, dsr, False, on_ready=self.g_reducer.bucket)
+            gg, _ = ge.backward(g_sp, g_tok, dsr, True, False, on_ready=self.g_reducer.bucket)
             self.scaler.step(self.g_opt, gg, self.g_reducer.finish())        # scaler.step(g_optimizer); scaler.update(); EMA  (:466-470)
             ge.fp.touch()
         self.sr = sr

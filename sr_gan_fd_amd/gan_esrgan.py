@@ -102,7 +102,7 @@ class EsrganGanTrainer(GanCheckpointMixin):
             dsr_c = self.ce.backward(c_sp, c_tok, None, self.cw, self.scaler.seed_ptr)
             A.check(L.srganfd_axpby(A.View(dsr_c.data_ptr(), 1, 0), A.View(dsr.data_ptr(), 1, 0), A.F32, dsr.numel(), 1, 1.0, 1.0, st), "axpby")
         self.g_reducer.begin()
-        gg, _ = ge.backward(g_sp, g_tok, dsr, False, on_ready=self.g_reducer.bucket)
+        gg, _ = ge.backward(g_sp, g_tok, dsr, True, False, on_ready=self.g_reducer.bucket)
         self.scaler.step(self.g_opt, gg, self.g_reducer.finish())           # scaler.step(g_optimizer); scaler.update(); EMA (:383-389)
         ge.fp.touch()
         # ---- discriminator (train_esrgan.py:394-425) ----

@@ -197,7 +197,7 @@ def conv2d(args: A.ConvArgs, rec=None, what: str = "conv2d", L=None, st=None) ->
 # ---- launch items: what the engines' per-shape launch lists (sp.fw / sp.bw) hold.  Every item has ``launch(run)`` and ``run_items`` is
 # the one loop over a list; ``kind`` names the class for tests and debugging, nothing dispatches on it.  Here: Conv, Call, Wgrad,
 # WgradPartial / WgradReduce (the generator's dense blocks: batched slab reduction), Ready (the generator's gradient buckets), PerCall (a
-# layer that writes the pass's own output) and, further down, DenseChain and ThinLaunch; the engines define the items only they launch
+# layer that writes the pass's own output) and, further down, DenseChain, ThinLaunch, Attention and PixelGate; the engines define the items only they launch
 # beside themselves (BatchNorm, the spectral-norm gradient, the loss taps).  An item holds structs and addresses, never a closure:
 # what the addresses point to is kept alive by the plan's buffers.
 class Run:
@@ -236,7 +236,8 @@ class Conv:
 
 
 class PerCall:
-    """a Conv or thin_out ThinLaunch whose output is the pass's own (``run.out``: allocated per call), put into the struct at launch"""
+    """a Conv, thin_out ThinLaunch or Attention whose output is the pass's own (``run.out``: allocated per call), put into the struct at
+    launch; skipped by a pass that did not ask for that output (``run.out`` 0)"""
     __slots__ = ("item",)
     kind = "per_call"
 
@@ -244,8 +245,9 @@ class PerCall:
         self.item = item
 
     def launch(self, run: Run) -> None:
-        self.item.set_output(run.out)
-        self.item.launch(run)
+        if run.out:
+            self.item.set_output(run.out)
+            self.item.launch(run)
 
 
 class Call:
@@ -633,30 +635,42 @@ def attn_work(a: A.AttnArgs, kind: str):
     return 5 * unit, tok * (8 * c * es + 12 * a.heads)
 
 
-def _attention(kind: str, a: A.AttnArgs, rec, L, st) -> None:
-    if L is None:
-        L, st = A.lib(), A.stream_ptr()
-    what = "attention_" + kind
-    run = lambda: A.check(getattr(L, "srganfd_" + what)(C.byref(a), st), what)
-    if rec is None:
-        run()
-    else:
-        rec.bracket("attn_%s_kernel<%s,D=%d>" % (kind, A.DT_NAME[a.dtype], a.head_dim), attn_work(a, kind), run)
+class Attention(_Bracketed):
+    """one call of the fused attention kernels: ``op`` "fwd" | "weights" | "bwd" over ``args`` (attn_args').  Under a PerCall, the
+    weights launch writes the pass's own tensor."""
+    kind = "attention"
+
+    def __init__(self, op: str, args: A.AttnArgs):
+        self.op, self.args = op, args
+        self.label, self.work = "attn_%s_kernel<%s,D=%d>" % (op, A.DT_NAME[args.dtype], args.head_dim), attn_work(args, op)
+
+    def set_output(self, ptr: int) -> None:
+        self.args.weights = ptr
+
+    def _issue(self, run: Run) -> None:
+        A.check(getattr(run.L, "srganfd_attention_" + self.op)(C.byref(self.args), run.st), "attention_" + self.op)
 
 
-def attention_fwd(a: A.AttnArgs, rec=None, L=None, st=None) -> None:
+def launch_alone(item, rec=None) -> None:
+    """one item on the current stream, outside a launch list (tests, tools)"""
+    run = Run(item.kind)
+    run.rec = rec
+    item.launch(run)
+
+
+def attention_fwd(a: A.AttnArgs, rec=None) -> None:
     """out = softmax(q k^T / sqrt(D)) v and lse, one launch on the current stream"""
-    _attention("fwd", a, rec, L, st)
+    launch_alone(Attention("fwd", a), rec)
 
 
-def attention_weights(a: A.AttnArgs, rec=None, L=None, st=None) -> None:
+def attention_weights(a: A.AttnArgs, rec=None) -> None:
     """the head-averaged probabilities (nn.MultiheadAttention's second result), a launch of its own"""
-    _attention("weights", a, rec, L, st)
+    launch_alone(Attention("weights", a), rec)
 
 
-def attention_bwd(a: A.AttnArgs, rec=None, L=None, st=None) -> None:
+def attention_bwd(a: A.AttnArgs, rec=None) -> None:
     """d_qkv from qkv, out, lse and d_out: two launches (dq per query block, dk / dv per key block), bit-reproducible"""
-    _attention("bwd", a, rec, L, st)
+    launch_alone(Attention("bwd", a), rec)
 
 
 # ---- A-ESRGAN's pixel attention (csrc/pixel_gate.hip): z = x * (1 + sigmoid(a)) and its backward ----
@@ -685,9 +699,7 @@ class PixelGate(_Bracketed):
 
 def pixel_gate(args: tuple, rec=None) -> None:
     """one launch on the current stream, outside a launch list (tests, tools)"""
-    run = Run("pixel_gate")
-    run.rec = rec
-    PixelGate(args).launch(run)
+    launch_alone(PixelGate(args), rec)
 
 
 # same-box A/B switch (0: one group of launches per layer, the round-1 form); both forms run in the HIP library and agree to the bit

@@ -124,7 +124,7 @@ class BucketReducer:
     xGMI is per-link bound and needs few CUs, so the exchange costs the backward pass next to nothing and only the last bucket's
     tail is exposed.  No process group (or CPU tensors: the dry-run host tests): ``bucket`` reduces inline / does nothing.
 
-        flat_grad, _ = engine.backward(sp, token, dout, False, on_ready=reducer.bucket)
+        flat_grad, _ = engine.backward(sp, token, dout, True, False, on_ready=reducer.bucket)
         scale = reducer.finish()          # 1 / world for the optimizer"""
 
     def __init__(self, device, pg):

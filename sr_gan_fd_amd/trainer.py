@@ -442,7 +442,7 @@ class GeneratorTrainer:
                                         self.dsr.data_ptr(), self.loss_weight, self.scaler.seed_ptr, self.ws.data_ptr(), A.stream_ptr()), "l1_loss")
         # RCCL over xGMI: the flat gradient goes out in three buckets as the backward pass finishes them (parallel.BucketReducer)
         self.g_reducer.begin()
-        grad, _ = eng.backward(sp, token, self.dsr, False, on_ready=self.g_reducer.bucket)
+        grad, _ = eng.backward(sp, token, self.dsr, True, False, on_ready=self.g_reducer.bucket)
         scale = self.g_reducer.finish()
         self.scaler.step(self.opt, grad, scale)        # scaler.step(optimizer); scaler.update(); ema update
         eng.fp.touch()                             # parameters changed behind autograd's back -> re-pack

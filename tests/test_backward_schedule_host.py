@@ -94,7 +94,7 @@ def _on_ready_notes(dt):
         notes.append((len(rec.launches), lo, hi))
     A._lib = rec
     try:
-        eng.backward(sp, token, torch.rand(2, 3, 64, 64), False, on_ready=on_ready)
+        eng.backward(sp, token, torch.rand(2, 3, 64, 64), True, False, on_ready=on_ready)
     finally:
         A._lib = rec._lib
     return notes, len(rec.launches)

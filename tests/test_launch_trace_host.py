@@ -206,6 +206,45 @@ def _aesrgan():
     return M.uNetDiscriminatorAesrgan()
 
 
+def _four_ways(m, x, result=lambda out: out):
+    """a module's ``__call__`` under autograd in the four gradient configurations (tests/test_rpa_host.py::test_module_call_sequence)"""
+    result(m(x)).sum().backward()                  # input and parameters
+    for p in m.parameters():
+        p.requires_grad_(False)
+    result(m(x)).sum().backward()                  # parameters frozen: no weight-gradient launches
+    with torch.no_grad():
+        m(x.detach())                              # nothing wants a gradient: the forward alone
+    for p in m.parameters():
+        p.requires_grad_(True)
+    result(m(x.detach())).sum().backward()         # parameters only: the input's gradient is not computed
+
+
+def _rpa_blocks(dt):
+    from sr_gan_fd_amd import model as M
+    keep = _pin(dt, M.RPA(64), M.US(64, 2))
+    for m in keep:
+        _four_ways(m, torch.rand(2, 64, 5, 7, requires_grad=True))
+    return keep
+
+
+def _gen_rpa(dt):
+    """odd, non-square sizes: swapped H and W in the engines' shell would show"""
+    from sr_gan_fd_amd import model as M
+    keep = _pin(dt, *(M.Generator_RPA(scale=s, num_block=2) for s in (1, 2, 4)))
+    for m in keep:
+        _four_ways(m, torch.rand(2, 3, 5, 7, requires_grad=True))
+    return keep
+
+
+def _self_attention(dt):
+    from sr_gan_fd_amd import model as M
+    m, = _pin(dt, M.SelfAttention(256, 8))
+    for need_weights in (True, False):
+        m.need_weights = need_weights
+        _four_ways(m, torch.randn(2, 256, 4, 6, requires_grad=True), lambda out: out[0])
+    return m,
+
+
 SCENARIOS = {
     "gan_unet": lambda dt: _gan(dt, _unet),
     "gan_unet_generator_first": lambda dt: _gan(dt, _unet, True),
@@ -215,6 +254,11 @@ SCENARIOS = {
     "modules": _modules,
     # six dense blocks: one full batch of four slab reductions and a remainder of two, and the mid-trunk bucket marker (R >= 4)
     "generator_only_rrdb2": lambda dt: _g_only(dt, 2),
+    # the pixel-attention generator's blocks alone and the generator at every scale (0, 1 and 2 US blocks), then SelfAttention with
+    # and without the weights launch: each in the four gradient configurations of _four_ways
+    "rpa_blocks": _rpa_blocks,
+    "gen_rpa": _gen_rpa,
+    "self_attention": _self_attention,
 }
 CASES = ["%s-%s" % (s, d) for s in SCENARIOS for d in DTYPES]
 
