@@ -218,6 +218,18 @@ typedef struct {
 int srganfd_conv2d_wgrad_partial(const void* plan_host, const void* plan_dev, srganfd_view x, srganfd_view dy,
                                  void* workspace, size_t workspace_bytes, void* stream);
 int srganfd_wgrad_reduce_batch(const srganfd_wgrad_reduce_job* jobs, int32_t njobs, void* stream);
+/* The MFMA kernel of up to 8 launches as ONE launch (the generator's dense blocks, four at a time): the grid is
+ * njobs * splits * channel groups workgroups, so plans built with 1/njobs of one launch's pixel splits keep the chip filled while each job
+ * leaves 1/njobs of the slabs to write and to reduce.  Every job brings its own plan, tensors and workspace; the plans must agree in
+ * everything the kernel reads (shape, dtype, splits, channel groups: the plan header and group table) and the views in cstride, c0
+ * and planar form.  The task tables (alpha, beta, gradient offsets: read by the reduction only) may differ.  One job is
+ * srganfd_conv2d_wgrad_partial bit for bit; each job's slabs are then reduced by srganfd_wgrad_reduce_batch as before. */
+typedef struct {
+  const void* plan_host; const void* plan_dev;
+  srganfd_view x, dy;
+  void* workspace; size_t workspace_bytes;
+} srganfd_wgrad_partial_job;
+int srganfd_conv2d_wgrad_partial_batch(const srganfd_wgrad_partial_job* jobs, int32_t njobs, void* stream);
 
 /* ---- boundary layout conversion (the reference's modules take/return NCHW fp32) ---- */
 /* BSRGAN.forward input (model.py:366): NCHW fp32 -> NHWC dtype view, zero padded to cpad channels */

@@ -73,6 +73,11 @@ class WgradReduceJob(C.Structure):
     _fields_ = [("plan_host", C.c_void_p), ("plan_dev", C.c_void_p), ("grads", C.c_void_p), ("scalars", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class WgradPartialJob(C.Structure):
+    C_NAME = "srganfd_wgrad_partial_job"
+    _fields_ = [("plan_host", C.c_void_p), ("plan_dev", C.c_void_p), ("x", View), ("dy", View), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 class SnJob(C.Structure):
     C_NAME = "srganfd_sn_job"
     _fields_ = [("w_orig", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("sigma_out", C.c_void_p), ("inv_sigma_out", C.c_void_p),
@@ -171,6 +176,7 @@ SYMBOLS = {
                                            C.POINTER(C.c_size_t)]),
     "srganfd_conv2d_wgrad_partial": (C.c_int, [C.c_void_p, C.c_void_p, View, View, C.c_void_p, C.c_size_t, C.c_void_p]),
     "srganfd_wgrad_reduce_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "srganfd_conv2d_wgrad_partial_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "srganfd_conv2d_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, View, View, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_void_p]),
     "srganfd_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, View, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

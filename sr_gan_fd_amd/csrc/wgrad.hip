@@ -14,6 +14,10 @@
 // wavefronts of a workgroup share the staged X / dY tiles.  Pixel tiles are split over workgroups;
 // each wave writes an fp32 partial slab and a second kernel reduces the slabs deterministically
 // (no float atomics: results are bitwise reproducible) straight into the NCHW fp32 gradient.
+// One launch can cover up to kRedBatch JOBS -- launches that share the plan's geometry, splits and channel groups and differ in their
+// tensors and workspaces (srganfd_conv2d_wgrad_partial_batch: four dense blocks of the generator at a time).  The workgroup id decodes as
+// (job, pixel split, channel group); with 1/n of the splits per job the grid is one launch's, every workgroup runs n times the tiles of
+// one job, and each job leaves 1/n of the slabs to write and to reduce (36 -> 9 per dense block at batch 32, 128 x 128).
 // f32 mode (parity) uses v_mfma_f32_32x32x2_f32 with plain ds_read_b32 (channels on the lanes).
 #include "conv_common.hpp"
 #include <stdlib.h>
@@ -42,9 +46,14 @@ struct WgHeader {
   long long groups_off, tasks_off, total_bytes;
 };
 
+// One launch covers up to kRedBatch jobs (dense blocks) that share the plan's geometry and group table: the grid is
+// njobs * S * ngroups workgroups and each job brings its own tensors and slab workspace.
+static constexpr int kRedBatch = 8;
+struct WgJob { const void* x; const void* dy; float* slabs; float* bslabs; };
 struct WgK {
-  const void* x; const void* dy; float* slabs; float* bslabs;
+  WgJob job[kRedBatch];
   const WgGroup* groups;
+  int njobs, pad_;
   int xC, x_c0v, dyC, dy_c0v;
   int x_ps, x_gs, dy_ps, dy_gs;   // pixel / 32-channel-group strides in elements: NHWC (C, 32) or planar groups (32, H*W*32), see srganfd_view
   int N, Hin, Win, up, pad, Hout, Wout, S, x_upad, dy_upad, ntiles, tiles_x, tiles_y, ngroups;
@@ -124,7 +133,10 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
     const int nwg = gridDim.x, xcd = wgid & 7, q = nwg >> 3, rr = nwg & 7;
     wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (wgid >> 3);
   }
-  const int grp = wgid % a.ngroups, split = wgid / a.ngroups;
+  // group (fastest), then split, then job: the channel groups of one (job, split) stay neighbours on one XCD
+  const int grp = wgid % a.ngroups, gs = wgid / a.ngroups;
+  const int split = gs % a.S;
+  const WgJob& J = a.job[gs / a.S];
   const WgGroup& G = a.groups[grp];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -138,8 +150,8 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
   char* ldsY = smem + PR * PC * xRowB;
   const int Hl = a.Hin << a.up, Wl = a.Win << a.up;
   const int xcb = a.x_c0v + G.x_c0, ycb = a.dy_c0v + G.dy_c0;     // first channel this group stages
-  const T* __restrict__ xg = (const T*)a.x + ((xcb >> 5) * (size_t)a.x_gs + (xcb & 31));
-  const T* __restrict__ dyg = (const T*)a.dy + ((ycb >> 5) * (size_t)a.dy_gs + (ycb & 31));
+  const T* __restrict__ xg = (const T*)J.x + ((xcb >> 5) * (size_t)a.x_gs + (xcb & 31));
+  const T* __restrict__ dyg = (const T*)J.dy + ((ycb >> 5) * (size_t)a.dy_gs + (ycb & 31));
   const int x_gs2 = a.x_gs * G.x_u1, dy_gs2 = a.dy_gs * G.dy_u1;   // distance of the group's two staged units
 
   f32x16 acc[NT];
@@ -461,7 +473,7 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
     }
   }
   if (W.active) {
-    float* slab = a.slabs + (size_t)(W.slab_base + split * W.ks_n + W.ks_idx) * (KS * KS * 1024) + W.tap0 * 1024;
+    float* slab = J.slabs + (size_t)(W.slab_base + split * W.ks_n + W.ks_idx) * (KS * KS * 1024) + W.tap0 * 1024;
     if constexpr (VAR == 3) {
       // D of 16x16x32: column = lane & 15 (output channel inside its half), row = 4 * (lane >> 4) + register (input channel)
 #pragma unroll
@@ -478,14 +490,14 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
         (void)bsum16;
         t0 += __shfl_xor(t0, 16, 64); t0 += __shfl_xor(t0, 32, 64);
         t1 += __shfl_xor(t1, 16, 64); t1 += __shfl_xor(t1, 32, 64);
-        a.bslabs[(size_t)(W.bias_slab + split * W.ks_n + W.ks_idx) * 64 + lane] = lane < 16 ? t0 : (lane < 32 ? t1 : 0.f);
+        J.bslabs[(size_t)(W.bias_slab + split * W.ks_n + W.ks_idx) * 64 + lane] = lane < 16 ? t0 : (lane < 32 ? t1 : 0.f);
       }
     } else {
 #pragma unroll
     for (int tl = 0; tl < NT; ++tl)
 #pragma unroll
       for (int i = 0; i < 16; ++i) slab[(tl * 32 + mfma32_row(i, lane)) * 32 + r] = acc[tl][i];
-    if (W.bias_slab >= 0) a.bslabs[(size_t)(W.bias_slab + split * W.ks_n + W.ks_idx) * 64 + lane] = bsum;
+    if (W.bias_slab >= 0) J.bslabs[(size_t)(W.bias_slab + split * W.ks_n + W.ks_idx) * 64 + lane] = bsum;
     }
   }
 }
@@ -495,7 +507,6 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
 // taps x tasks ~ 230 blocks, so the memory parallelism has to come from threads), eight slabs in flight per thread
 // (independent accumulators, fixed summation order -> bitwise reproducible).
 struct WgRedJob { const WgTask* tasks; const float* slabs; const float* bslabs; float* grads; const float* scalars; int ntasks; int pad_; };
-static constexpr int kRedBatch = 8;
 struct WgRedJobs { WgRedJob j[kRedBatch]; };
 // blockIdx.z selects the job: several weight-gradient launches (dense blocks) reduced by ONE launch -- the kernel is bound by load round
 // trips at ~17-23 us whatever it reduces, so four blocks' slabs cost little more than one's
@@ -752,7 +763,7 @@ static int launch_wgrad4(const WgHeader& H, const WgK& k, hipStream_t stream) {
       attr_lds[dev & 63] = lds;
     }
   }
-  SRGANFD_LAUNCH(kern, dim3(H.S * H.ngroups), dim3(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))), lds, stream, k);
+  SRGANFD_LAUNCH(kern, dim3(k.njobs * H.S * H.ngroups), dim3(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))), lds, stream, k);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
@@ -778,19 +789,24 @@ static int launch_wgrad(const WgHeader& H, const WgK& k, hipStream_t stream) {
   return H.dy_upad == 2 ? launch_wgrad2<T, KS, STRIDE, 1, 2>(H, k, stream) : launch_wgrad2<T, KS, STRIDE, 1, 1>(H, k, stream);
 }
 
-// shared by srganfd_conv2d_wgrad (grads != NULL) and srganfd_conv2d_wgrad_partial (grads == NULL)
-static int wgrad_impl(const void* plan_host, const void* plan_dev, srganfd_view x, srganfd_view dy, float* grads, const float* scalars,
-                      void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!plan_host || !plan_dev || !x.ptr || !dy.ptr || !workspace) return set_err(SRGANFD_EINVAL, "wgrad: null pointer");
-  const WgHeader& H = *(const WgHeader*)plan_host;
-  if (H.magic != kWgMagic) return set_err(SRGANFD_EINVAL, "wgrad: bad plan");
+// the MFMA launch of njobs jobs (1 for srganfd_conv2d_wgrad and srganfd_conv2d_wgrad_partial); jobs past the first were checked by the caller
+// to share job 0's header, group table and view form
+static int wgrad_launch_jobs(const srganfd_wgrad_partial_job* jobs, int njobs, hipStream_t stream) {
+  const srganfd_wgrad_partial_job& j0 = jobs[0];
+  const WgHeader& H = *(const WgHeader*)j0.plan_host;
+  const srganfd_view &x = j0.x, &dy = j0.dy;
   if ((size_t)H.Hin * H.Win * (size_t)x.cstride >= 0x7fffffffULL || (size_t)H.Hout * H.Wout * (size_t)dy.cstride >= 0x7fffffffULL)
     return set_err(SRGANFD_EINVAL, "wgrad: one image is too large for 32-bit element offsets");
   const size_t need = (size_t)(H.bias_slab_off + H.nbias_slabs * 64) * sizeof(float);
-  if (workspace_bytes < need) return set_err(SRGANFD_ENOSPC, "wgrad: workspace %zu < %zu", workspace_bytes, need);
   WgK k;
-  k.x = x.ptr; k.dy = dy.ptr; k.slabs = (float*)workspace; k.bslabs = (float*)workspace + H.bias_slab_off;
-  k.groups = (const WgGroup*)((const char*)plan_dev + H.groups_off);
+  memset(&k, 0, sizeof(k));
+  for (int i = 0; i < njobs; ++i) {
+    if (jobs[i].workspace_bytes < need) return set_err(SRGANFD_ENOSPC, "wgrad: workspace %zu < %zu (job %d)", jobs[i].workspace_bytes, need, i);
+    k.job[i].x = jobs[i].x.ptr; k.job[i].dy = jobs[i].dy.ptr;
+    k.job[i].slabs = (float*)jobs[i].workspace; k.job[i].bslabs = (float*)jobs[i].workspace + H.bias_slab_off;
+  }
+  k.njobs = njobs;
+  k.groups = (const WgGroup*)((const char*)j0.plan_dev + H.groups_off);
   k.xC = x.cstride; k.x_c0v = x.c0; k.dyC = dy.cstride; k.dy_c0v = dy.c0;
   if ((x.planar && (x.c0 % 32 || x.cstride % 32)) || (dy.planar && (dy.c0 % 32 || dy.cstride % 32)))
     return set_err(SRGANFD_EINVAL, "wgrad: a planar view needs c0 and cstride multiples of 32");
@@ -806,10 +822,40 @@ static int wgrad_impl(const void* plan_host, const void* plan_dev, srganfd_view 
   else if (H.ks == 2) rc = WG_BY_TYPE(2, 2);
   else rc = WG_BY_TYPE(1, 1);
 #undef WG_BY_TYPE
+  return rc;
+}
+
+// shared by srganfd_conv2d_wgrad (grads != NULL) and srganfd_conv2d_wgrad_partial (grads == NULL)
+static int wgrad_impl(const void* plan_host, const void* plan_dev, srganfd_view x, srganfd_view dy, float* grads, const float* scalars,
+                      void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (!plan_host || !plan_dev || !x.ptr || !dy.ptr || !workspace) return set_err(SRGANFD_EINVAL, "wgrad: null pointer");
+  if (((const WgHeader*)plan_host)->magic != kWgMagic) return set_err(SRGANFD_EINVAL, "wgrad: bad plan");
+  const srganfd_wgrad_partial_job one = {plan_host, plan_dev, x, dy, workspace, workspace_bytes};
+  const int rc = wgrad_launch_jobs(&one, 1, stream);
   if (rc != SRGANFD_OK) return rc;
   if (!grads) return SRGANFD_OK;          // srganfd_conv2d_wgrad_partial: the slabs stay in the workspace for srganfd_wgrad_reduce_batch
   srganfd_wgrad_reduce_job job = {plan_host, plan_dev, grads, scalars, workspace};
   return srganfd_wgrad_reduce_batch(&job, 1, stream);
+}
+extern "C" int srganfd_conv2d_wgrad_partial_batch(const srganfd_wgrad_partial_job* jobs, int32_t njobs, void* stream) {
+  if (!jobs || njobs < 1 || njobs > kRedBatch) return set_err(SRGANFD_EINVAL, "wgrad_partial_batch: 1..%d jobs", kRedBatch);
+  const WgHeader* H0 = nullptr;
+  for (int i = 0; i < njobs; ++i) {
+    const srganfd_wgrad_partial_job& q = jobs[i];
+    if (!q.plan_host || !q.plan_dev || !q.x.ptr || !q.dy.ptr || !q.workspace) return set_err(SRGANFD_EINVAL, "wgrad_partial_batch: null pointer in job %d", i);
+    const WgHeader* H = (const WgHeader*)q.plan_host;
+    if (H->magic != kWgMagic) return set_err(SRGANFD_EINVAL, "wgrad_partial_batch: bad plan in job %d", i);
+    if (!i) { H0 = H; continue; }
+    // one grid, one set of shared kernel fields: the same shape, splits and slab layout (the header) and the same waves (the group
+    // table).  The task tables may differ: only the reduction reads them (alpha / beta, gradient offsets)
+    if (memcmp(H, H0, sizeof(WgHeader)) != 0 ||
+        memcmp((const char*)q.plan_host + H->groups_off, (const char*)jobs[0].plan_host + H0->groups_off, sizeof(WgGroup) * H0->ngroups) != 0)
+      return set_err(SRGANFD_EINVAL, "wgrad_partial_batch: job %d's plan differs from job 0's in geometry or channel groups", i);
+    const srganfd_view &a = jobs[0].x, &b = q.x, &c = jobs[0].dy, &d = q.dy;
+    if (a.cstride != b.cstride || a.c0 != b.c0 || !a.planar != !b.planar || c.cstride != d.cstride || c.c0 != d.c0 || !c.planar != !d.planar)
+      return set_err(SRGANFD_EINVAL, "wgrad_partial_batch: job %d's views differ from job 0's in stride, first channel or planar form", i);
+  }
+  return wgrad_launch_jobs(jobs, njobs, (hipStream_t)stream);
 }
 extern "C" int srganfd_conv2d_wgrad_partial(const void* plan_host, const void* plan_dev, srganfd_view x, srganfd_view dy, void* workspace,
                                             size_t workspace_bytes, void* stream) {

@@ -512,14 +512,39 @@ class TrunkEngine(EngineBase):
         def new(*shape, dtype=dt):
             return torch.empty(*shape, dtype=dtype, device=device)
 
-        sp.dy = [new(N, H, W, Ccat) for _ in range(4)]
+        wplans = ops.WgradPlans(device, dtc, N)
+        # the dense blocks' weight-gradient plans, by (conv5's scale, pixel splits; 0: the library's choice for one block per launch)
+        plans, rel = {}, self._poff(self._rdb_prefix[0] + "conv1.weight")
+
+        def dense_plan(s5, splits=0):
+            if (s5, splits) not in plans:
+                convs, pre = [], self._rdb_prefix[0]        # the plan's offsets are relative to the block: every block's are block 0's
+                for k in range(1, 6):
+                    cin, cout = Cc + (k - 1) * G, (Cc if k == 5 else G)
+                    convs.append(dict(ci_lo=0, cin=cin, co_lo=(0 if k == 5 else Cc + (4 - k) * G), cout=cout,
+                                      dw_off=self._poff(pre + f"conv{k}.weight") - rel, db_off=self._poff(pre + f"conv{k}.bias") - rel,
+                                      co_dst=cout, ci_dst=cin, alpha=(s5 if k == 5 else 1.0)))
+                plans[(s5, splits)] = wplans.plan(H, W, Ccat, Ccat, convs, splits=splits)
+            return plans[(s5, splits)]
+        block_s5 = lambda i: 0.2 * (0.2 if (self.rrdb and i % 3 == 2) else 1.0)
+        # _BATCH_WGRAD: up to _BATCH_REDUCE blocks' weight gradients as one MFMA launch (batch_wgrads).  "auto": where one block's
+        # launch already fills the chip -- at least as many pixel tiles as the device gives it splits -- so that a batch's fewer
+        # splits per block lose nothing
+        p0 = dense_plan(block_s5(R - 1))
+        sp.batch_wgrad = _BATCH_REDUCE > 1 and (_BATCH_WGRAD == "1" or (_BATCH_WGRAD == "auto" and p0.ntiles >= max(1, ops.device_cus(device) // p0.ngroups)))
+        # a batch's launch stands at its LAST block and reads every block's stacked-gradient buffer there.  Per-layer data gradients:
+        # four rotating buffers hold that long (a block's 192->64 launch, which overwrites the buffer four blocks up, follows its weight
+        # gradient; a batch of more than four blocks needs one each).  The dense-block launch takes all five convs before it: one
+        # buffer more than a batch has blocks
+        chain_form = (Cc, G) == (64, 32) and dtc in (A.F16, A.BF16) and ops.dense_chain_wanted(N, H, W)
+        ndy = max(4, _BATCH_REDUCE + (1 if chain_form else 0)) if sp.batch_wgrad else 4
+        sp.dy = [new(N, H, W, Ccat) for _ in range(ndy)]
         sp.dx0 = new(N, H, W, Cc)           # gradient w.r.t. the trunk input
-        dyb = lambda i: sp.dy[i % 4]
+        dyb = lambda i: sp.dy[i % ndy]
         if not self.full:
             sp.dy_in, sp.dx_out = (V(dyb(R - 1)), Cc), (V(sp.dx0), dtc)
         bw = []                              # ops.Conv | Wgrad | ThinLaunch | DenseChain | Call and the bucket markers ops.Ready
         cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
-        wplans = ops.WgradPlans(device, dtc, N)
 
         if self.full:
             s = 1 << self.n_up
@@ -578,7 +603,6 @@ class TrunkEngine(EngineBase):
             bw.append(ops.Ready(self._poff("conv2.weight"), self.fp.total))
         # dense blocks, last to first
         rdb_names = ["conv%d" % k for k in range(1, 6)]
-        plans = {}
         for i in range(R - 1, -1, -1):
             pre = self._rdb_prefix[i]
             last = self.rrdb and i % 3 == 2
@@ -586,15 +610,6 @@ class TrunkEngine(EngineBase):
             s_out = 0.2 if last else 1.0
             s5 = 0.2 * s_out
             ci, di = sp.catb(i), dyb(i)
-            if s5 not in plans:
-                base = self._poff(pre + "conv1.weight")
-                convs = []
-                for k in range(1, 6):
-                    cin, cout = Cc + (k - 1) * G, (Cc if k == 5 else G)
-                    convs.append(dict(ci_lo=0, cin=cin, co_lo=(0 if k == 5 else Cc + (4 - k) * G), cout=cout,
-                                      dw_off=self._poff(pre + f"conv{k}.weight") - base, db_off=self._poff(pre + f"conv{k}.bias") - base,
-                                      co_dst=cout, ci_dst=cin, alpha=(s5 if k == 5 else 1.0)))
-                plans[s5] = wplans.plan(H, W, Ccat, Ccat, convs)
             blk = []
             for step in range(4):
                 kdim = Cc + step * G
@@ -606,7 +621,7 @@ class TrunkEngine(EngineBase):
                 kw.update(r2=VD(dyb(i + 2)), r2_scale=1.0)
             blk.append(ops.conv_args(dtc, VD(di), dst, wptr + pk["offs"][("b", i, 4)], N, H, W, Ccat, Cc, **kw))
             chain = ops.dense_chain_or_launches(blk, sp.device) if (Cc, G) == (64, 32) else [ops.Conv(a) for a in blk]
-            wg = ops.Wgrad(plans[s5], VC(ci), VD(di), dw_off=self._poff(pre + "conv1.weight"), block=i)     # the plan's offsets are relative to the block
+            wg = ops.Wgrad(dense_plan(s5), VC(ci), VD(di), dw_off=self._poff(pre + "conv1.weight"), block=i)     # the plan's offsets are relative to the block
             ready = [ops.Ready(self._poff(pre + "conv1.weight"), self._poff("conv2.weight"))] if self.full and R >= 4 and i == R // 2 else []     # upper half of the trunk is final: second bucket
             # the weight gradient reads what the four growth layers of the data gradient wrote and follows them (or the one launch for all five convs)
             bw.extend(chain[:4] + [wg] + ready + chain[4:])
@@ -621,7 +636,13 @@ class TrunkEngine(EngineBase):
         # four more workspaces of the dense-block plan's size for the batched slab reduction (34 MB each at B=32, 128x128)
         dense_ws = max((p_.workspace_bytes for p_ in plans.values()), default=0)
         sp.wg_ws4 = [torch.empty(dense_ws, dtype=torch.uint8, device=device) for _ in range(_BATCH_REDUCE)] if (dense_ws and _BATCH_REDUCE > 1) else None
-        sp.bw = batch_reductions(bw, sp.wg_ws4) if sp.wg_ws4 is not None else bw
+        if sp.wg_ws4 is None:
+            sp.bw = bw
+        elif sp.batch_wgrad:
+            # a batch of n blocks: plans with 1 / n of one block's pixel splits, so the launch has one block's workgroups
+            sp.bw = batch_wgrads(bw, sp.wg_ws4, lambda wg, n: wg.plan if n == 1 else dense_plan(block_s5(wg.block), max(1, p0.splits // n)))
+        else:
+            sp.bw = batch_reductions(bw, sp.wg_ws4)
 
     # -- execution ----------------------------------------------------------------------------
     def trunk_size(self, shape) -> Tuple[int, int, int]:
@@ -684,6 +705,66 @@ def batch_reductions(items: Sequence, slots: Sequence[Tensor]) -> list:
             reduce_pending()
         out.append(it)
     reduce_pending()
+    return out
+
+
+# the MFMA launches of those blocks as ONE launch too (batch_wgrads): "0" never, "1" always, "auto" where one block's launch fills the chip
+_BATCH_WGRAD = os.environ.get("SRGANFD_BATCH_WGRAD", "auto")
+
+
+def _written(it) -> set:
+    """addresses of the buffers a backward item writes (its output views' base pointers)"""
+    if isinstance(it, ops.Conv):
+        return {it.args.y.ptr, it.args.y2.ptr} - {None}
+    if isinstance(it, ops.DenseChain):
+        return ({a.y.ptr for a in it.layers} | {a.y2.ptr for a in it.layers}) - {None}
+    if isinstance(it, ops.ThinLaunch):
+        return {it.args.big.ptr} if it.op == "thin_in" else set()
+    if isinstance(it, ops.Call):                     # auxiliary kernels: every view they take counts as written
+        return {a.ptr for a in it.args if isinstance(a, A.View)} - {None}
+    return set()
+
+
+def batch_wgrads(items: Sequence, slots: Sequence[Tensor], plan_for) -> list:
+    """batch_reductions with the MFMA launches batched as well: the dense blocks' weight gradients between two of its flush points
+    (len(slots) of them; another weight gradient or thin launch; a gradient bucket; the end) become ONE ops.WgradPartialBatch where the
+    LAST of them stood, followed by their ops.WgradReduce.  ``plan_for(wg, n)``: the plan block ``wg`` runs with in a batch of n.
+    The launch reads every block's stacked gradients later than the block's own launch did: the list is checked -- nothing between
+    the place a block's weight gradient had and its batch's launch may write that block's gradient buffer."""
+    groups, cur = [], []
+
+    def close():
+        if cur:
+            groups.append(list(cur))
+            cur.clear()
+    for idx, it in enumerate(items):
+        if isinstance(it, ops.Wgrad) and it.block is not None:
+            cur.append(idx)
+            if len(cur) == len(slots):
+                close()
+        elif isinstance(it, (ops.Wgrad, ops.ThinLaunch, ops.Ready)):
+            close()
+    close()
+    last = {g[-1]: g for g in groups}
+    member = {idx for g in groups for idx in g}
+    out, stood = [], {}                              # stood: index in ``out`` where a block's own weight gradient would have been
+    for idx, it in enumerate(items):
+        if idx not in member:
+            out.append(it)
+            continue
+        stood[idx] = len(out)
+        g = last.get(idx)
+        if g is None:
+            continue
+        parts = [ops.WgradPartial(ops.Wgrad(plan_for(items[j], len(g)), items[j].x, items[j].dy, dw_off=items[j].dw_off, block=items[j].block),
+                                  slot, slots[slot]) for slot, j in enumerate(g)]
+        for j, p in zip(g, parts):
+            for k in range(stood[j], len(out)):
+                if p.dy.ptr in _written(out[k]) or p.x.ptr in _written(out[k]):
+                    raise A.SrganfdError(f"batched weight gradient: block {items[j].block}'s buffers are overwritten by backward item {k} "
+                                         f"({out[k].kind}) before the batch's launch reads them")
+        out.append(ops.WgradPartialBatch(parts))
+        out.append(ops.WgradReduce(parts))
     return out
 
 

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import struct
 from typing import List, Optional, Sequence
 
 import torch
@@ -196,7 +197,7 @@ def conv2d(args: A.ConvArgs, rec=None, what: str = "conv2d", L=None, st=None) ->
 
 # ---- launch items: what the engines' per-shape launch lists (sp.fw / sp.bw) hold.  Every item has ``launch(run)`` and ``run_items`` is
 # the one loop over a list; ``kind`` names the class for tests and debugging, nothing dispatches on it.  Here: Conv, Call, Wgrad,
-# WgradPartial / WgradReduce (the generator's dense blocks: batched slab reduction), Ready (the generator's gradient buckets), PerCall (a
+# WgradPartial / WgradPartialBatch / WgradReduce (the generator's dense blocks: batched MFMA launch, batched slab reduction), Ready (the generator's gradient buckets), PerCall (a
 # layer that writes the pass's own output) and, further down, DenseChain, ThinLaunch, Attention and PixelGate; the engines define the items only they launch
 # beside themselves (BatchNorm, the spectral-norm gradient, the loss taps).  An item holds structs and addresses, never a closure:
 # what the addresses point to is kept alive by the plan's buffers.
@@ -306,12 +307,32 @@ class WgradPartial(_Bracketed):
     kind = "wgrad_partial"
 
     def __init__(self, wg: Wgrad, slot: int, ws: torch.Tensor):
-        self.plan, self.x, self.dy, self.dw_off, self.slot, self.ws = wg.plan, wg.x, wg.dy, wg.dw_off, slot, ws
+        self.plan, self.x, self.dy, self.dw_off, self.block, self.slot, self.ws = wg.plan, wg.x, wg.dy, wg.dw_off, wg.block, slot, ws
         self.label, self.work = wg.plan.label, (wg.plan.flops, wg.plan.nbytes)
 
     def _issue(self, run: Run) -> None:
         plan, ws = self.plan, self.ws
         A.check(run.L.srganfd_conv2d_wgrad_partial(plan.host, plan.dev.data_ptr(), self.x, self.dy, ws.data_ptr(), ws.numel(), run.st), "conv2d_wgrad_partial")
+
+
+class WgradPartialBatch(_Bracketed):
+    """the weight-gradient MFMA launches of up to SRGANFD's kRedBatch dense blocks as ONE launch (srganfd_conv2d_wgrad_partial_batch):
+    ``partials`` are the blocks' WgradPartial items, which are not in the list themselves -- their plans share geometry, pixel splits
+    and channel groups (engine.batch_wgrads builds them with 1 / n of one launch's splits), each keeps its own workspace, and a
+    WgradReduce over the same partials follows.  Bracketed under the plan's label with the jobs' summed work."""
+    kind = "wgrad_partial_batch"
+
+    def __init__(self, partials: Sequence[WgradPartial]):
+        self.partials, self.n = list(partials), len(partials)
+        self.jobs = (A.WgradPartialJob * self.n)()
+        for j, p in zip(self.jobs, self.partials):
+            j.plan_host, j.plan_dev, j.x, j.dy = C.addressof(p.plan.host), p.plan.dev.data_ptr(), p.x, p.dy
+            j.workspace, j.workspace_bytes = p.ws.data_ptr(), p.ws.numel()
+        self.label = self.partials[0].label
+        self.work = (sum(p.work[0] for p in self.partials), sum(p.work[1] for p in self.partials))
+
+    def _issue(self, run: Run) -> None:
+        A.check(run.L.srganfd_conv2d_wgrad_partial_batch(self.jobs, self.n, run.st), "conv2d_wgrad_partial_batch")
 
 
 class WgradReduce(_Bracketed):
@@ -556,6 +577,10 @@ class WgradPlan:
         A.check(L.srganfd_wgrad_plan_build(C.byref(s), carr, self.host, nbytes, C.byref(ws)), "wgrad_plan_build")
         self.workspace_bytes = ws.value
         self.dev = torch.frombuffer(bytearray(self.host.raw), dtype=torch.uint8).to(device)
+        # what the library chose: the plan starts with csrc/wgrad.hip's WgHeader, 32-bit fields -- [11] channel groups (workgroups per
+        # pixel split), [13] pixel splits, [17] pixel tiles
+        hdr = struct.unpack_from("<18i", self.host.raw)
+        self.ngroups, self.splits, self.ntiles = hdr[11], hdr[13], hdr[17]
 
     def run(self, x: A.View, dy: A.View, grads: torch.Tensor, workspace: torch.Tensor,
             scalars: Optional[torch.Tensor] = None) -> None:
@@ -576,6 +601,13 @@ def conv2d_wgrad(plan: WgradPlan, x: A.View, dy: A.View, grad_ptr: int, workspac
         run()
     else:
         rec.bracket(plan.label, (plan.flops, plan.nbytes), run)
+
+
+def device_cus(device) -> int:
+    """compute units of ``device``, what the library sizes a weight-gradient launch's pixel splits by (256 in dry runs, as in the library)"""
+    if A.DRY_RUN or torch.device(device).type != "cuda":
+        return 256
+    return int(torch.cuda.get_device_properties(device).multi_processor_count)
 
 
 class WgradPlans:
