@@ -16,21 +16,18 @@ convolutions, srganfd_adam_ema); nothing runs as an ATen op.  Mixed precision: t
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Optional
 
-import torch
 from torch import Tensor
 
 from . import _abi as A
 from .engine import _engine, generator_engine
 from .engine_e import esrgan_discriminator_engine
 from .engine_v import ContentLossGradEngine
-from .parallel import BucketReducer, allreduce_sum_
-from .trainer import (FlatAdamEMA, GanCheckpointMixin, LossScaler, check_loss_scaling, check_targets, needs_loss_scaling,
-                      pin_training_dtype)
+from .trainer import FlatAdamEMA, FusedTrainer, check_loss_scaling, check_targets, pin_training_dtype
 
 
-class EsrganGanTrainer(GanCheckpointMixin):
+class EsrganGanTrainer(FusedTrainer):
     def __init__(self, g_model, d_model, content_criterion=None, *, g_lr: float = 1e-4, d_lr: float = 1e-4, betas=(0.9, 0.99),
                  eps: float = 1e-8, weight_decay: float = 0.0, ema_decay: Optional[float] = 0.99998, pixel_weight: float = 0.01,
                  content_weight: float = 1.0, adversarial_weight: float = 0.005, process_group=None):
@@ -46,23 +43,11 @@ class EsrganGanTrainer(GanCheckpointMixin):
         self.g_opt = FlatAdamEMA(self.ge.fp.sync(dev), g_lr, betas, eps, weight_decay, ema_decay, layout=self.ge.fp)
         self.d_opt = FlatAdamEMA(self.de.fp.sync(dev), d_lr, betas, eps, weight_decay, None, layout=self.de.fp)
         self.pw, self.cw, self.aw = float(pixel_weight), float(content_weight), float(adversarial_weight)
-        self.scaler = LossScaler(dev, enabled=needs_loss_scaling(g_model, d_model, content_criterion))
         # Under data parallelism the discriminator's BatchNorm layers (ESRGAN/model.py:98-126) use per-rank batch statistics, which is
         # what the unconverted reference does under DistributedDataParallel; there is no SyncBatchNorm hook for this discriminator.
-        self.pg = process_group
-        self.g_reducer = BucketReducer(dev, process_group)
-        # [d_loss, pixel, content, adversarial, D(gt) prob, D(sr) prob, 0, 0]  (train_esrgan.py:416,430-431)
-        self.scalars = torch.zeros(8, dtype=torch.float32, device=dev)
-        self.ws = torch.empty(A.LOSS_WS_FLOATS, dtype=torch.float32, device=dev)
-        self._bufs: Dict[tuple, Tensor] = {}
+        # scalars: [d_loss, pixel, content, adversarial, D(gt) prob, D(sr) prob, 0, 0]  (train_esrgan.py:416,430-431)
+        super().__init__(dev, process_group, 8, g_model, d_model, content_criterion)
         self.sr: Optional[Tensor] = None
-
-    def _buf(self, name, like: Tensor) -> Tensor:
-        b = self._bufs.get((name, tuple(like.shape)))
-        if b is None:
-            b = torch.empty_like(like)
-            self._bufs[(name, tuple(like.shape))] = b
-        return b
 
     def _rel(self, x: Tensor, other: Tensor, target: float, weight: float, slot: int, accumulate: int, grad_x, acc_x: int, grad_other, acc_o: int,
              seed_weight: Optional[float] = None) -> None:
@@ -75,11 +60,9 @@ class EsrganGanTrainer(GanCheckpointMixin):
     def step(self, lr_img: Tensor, gt: Tensor) -> Tensor:
         """One iteration; returns the device tensor [d_loss, pixel, content, adversarial, D(gt), D(sr), 0, 0] (no host synchronisation)."""
         check_targets("EsrganGanTrainer.step", self.ge, lr_img, gt=gt)
-        L, st = A.lib(), A.stream_ptr()
         ge, de = self.ge, self.de
         gt = gt.contiguous().float()
         check_loss_scaling(self.scaler, self.g, self.d, self.content)
-        s = self.scalars.data_ptr()
         # ---- generator (train_esrgan.py:361-392) ----
         sr = ge.forward(lr_img, True)
         g_sp, g_tok = ge._last, ge.token
@@ -87,24 +70,19 @@ class EsrganGanTrainer(GanCheckpointMixin):
         sr_out = de.forward(sr, True)
         d_sp, d_tok = de._last, de.token
         dsr = self._buf("dsr", sr)
-        A.check(L.srganfd_l1_loss(sr.data_ptr(), gt.data_ptr(), sr.numel(), self.pw, s + 4, 0, dsr.data_ptr(), self.pw, self.scaler.seed_ptr,
-                                  self.ws.data_ptr(), st), "l1_loss")
+        self._pixel_loss(sr, gt, self.pw, 1, dsr)
         dl = self._buf("dl", sr_out)
         half = 0.5 * self.aw
         self._rel(gt_out, sr_out, 0.0, half, 3, 0, None, 0, dl, 0)           # reaches sr_out through the mean
         self._rel(sr_out, gt_out, 1.0, half, 3, 1, dl, 1, None, 0)           # reaches sr_out directly; loss values add up in slot 3
         _, dsr_adv = de.backward(d_sp, d_tok, dl, False, True)               # frozen D: data gradient only
-        A.check(L.srganfd_axpby(A.View(dsr_adv.data_ptr(), 1, 0), A.View(dsr.data_ptr(), 1, 0), A.F32, dsr.numel(), 1, 1.0, 1.0, st), "axpby")
+        self._add(dsr_adv, dsr)
         if self.ce is not None:
             closs = self.ce.forward(sr, gt)                                  # 1-element device tensor: L1 at the node
             c_sp, c_tok = self.ce._last, self.ce.token
-            A.check(L.srganfd_axpby(A.View(closs.data_ptr(), 1, 0), A.View(s + 8, 1, 0), A.F32, 1, 1, self.cw, 0.0, st), "axpby")
-            dsr_c = self.ce.backward(c_sp, c_tok, None, self.cw, self.scaler.seed_ptr)
-            A.check(L.srganfd_axpby(A.View(dsr_c.data_ptr(), 1, 0), A.View(dsr.data_ptr(), 1, 0), A.F32, dsr.numel(), 1, 1.0, 1.0, st), "axpby")
-        self.g_reducer.begin()
-        gg, _ = ge.backward(g_sp, g_tok, dsr, True, False, on_ready=self.g_reducer.bucket)
-        self.scaler.step(self.g_opt, gg, self.g_reducer.finish())           # scaler.step(g_optimizer); scaler.update(); EMA (:383-389)
-        ge.fp.touch()
+            self._add(closs, self.scalars[2:3], self.cw, 0.0)                # the weighted value into its slot
+            self._add(self.ce.backward(c_sp, c_tok, None, self.cw, self.scaler.seed_ptr), dsr)
+        self._update_generator(g_sp, g_tok, dsr)                             # scaler.step(g_optimizer); scaler.update(); EMA (:383-389)
         # ---- discriminator (train_esrgan.py:394-425) ----
         gt_out = de.forward(gt, True)
         gt_sp, gt_tok = de._last, de.token
@@ -116,10 +94,9 @@ class EsrganGanTrainer(GanCheckpointMixin):
         self._rel(sr_out, gt_out, 0.0, 0.5, 0, 1, dsr_l, 1, dgt, 1)          # d_loss_sr; d_loss = their sum in slot 0
         gd1, _ = de.backward(gt_sp, gt_tok, dgt, True, False)
         gd2, _ = de.backward(sr_sp, sr_tok, dsr_l, True, False)
-        A.check(L.srganfd_axpby(A.View(gd1.data_ptr(), 1, 0), A.View(gd2.data_ptr(), 1, 0), A.F32, gd2.numel(), 1, 1.0, 1.0, st), "axpby")
-        self.scaler.step(self.d_opt, gd2, allreduce_sum_(gd2, self.pg))      # scaler.step(d_optimizer); scaler.update() (:419-420)
+        self._update_discriminator(gd1, gd2)                                 # scaler.step(d_optimizer); scaler.update() (:419-420)
         de.fp.touch()
-        A.check(L.srganfd_sigmoid_of_mean(gt_out.data_ptr(), gt_out.numel(), s + 16, self.ws.data_ptr(), st), "sigmoid_of_mean")
-        A.check(L.srganfd_sigmoid_of_mean(sr_out.data_ptr(), sr_out.numel(), s + 20, self.ws.data_ptr(), st), "sigmoid_of_mean")
+        self._prob(gt_out, 4)
+        self._prob(sr_out, 5)
         self.sr = sr
         return self.scalars

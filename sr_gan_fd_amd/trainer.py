@@ -15,6 +15,7 @@ identity, as GradScaler is on the reference's CPU path.
 """
 from __future__ import annotations
 
+from collections import Counter
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -118,16 +119,16 @@ class LossScaler:
             self.state.view(torch.int32)[2] = int(sd.get("_growth_tracker", 0))
 
 
-class MultiStepLR:
-    """``torch.optim.lr_scheduler.MultiStepLR`` for the fused optimizers (torch's class insists on a ``torch.optim.Optimizer``).
-    The reference builds one per network from ``lr_scheduler_milestones`` / ``lr_scheduler_gamma`` (bsrgan_config.py:153-155,
-    train_bsrgan.py:314-323) and steps it once per epoch (:193-195).  ``state_dict()`` carries torch's keys, so a checkpoint written
-    by the reference's script resumes here and the other way round (utils.load_state_dict passes ``ckpt["scheduler"]`` through)."""
+class _StepScheduler:
+    """What ``MultiStepLR`` and ``StepLR`` below share: torch's constructor bookkeeping (its initial step included), the chained
+    form of the decay -- the CURRENT rate is multiplied, so a rate set by hand is kept -- and torch's ``state_dict()`` keys, so a
+    checkpoint written by the reference's scripts resumes here and the other way round.  A subclass names the one key of its own
+    (``key``: attribute and state-dict entry), reads it back from a checkpoint (``_coerce``) and says how many factors of ``gamma``
+    the epoch just reached applies (``_decays``)."""
+    key = ""
 
-    def __init__(self, optimizer: "FlatAdamEMA", milestones, gamma: float = 0.1, last_epoch: int = -1):
-        from collections import Counter
+    def __init__(self, optimizer: "FlatAdamEMA", gamma: float, last_epoch: int):
         self.optimizer = optimizer
-        self.milestones = Counter(int(m) for m in milestones)
         self.gamma = gamma
         self.base_lrs = [optimizer.lr]
         self.last_epoch = last_epoch
@@ -141,60 +142,56 @@ class MultiStepLR:
     def step(self) -> None:
         self._step_count += 1
         self.last_epoch += 1
-        if self.last_epoch in self.milestones:        # torch's chained form: multiply the CURRENT rate (a rate set by hand is kept)
-            self.optimizer.lr = self.optimizer.lr * self.gamma ** self.milestones[self.last_epoch]
+        n = self._decays()
+        if n:
+            self.optimizer.lr = self.optimizer.lr * self.gamma ** n
         self._last_lr = [self.optimizer.lr]
 
     def state_dict(self) -> dict:
-        return {"milestones": self.milestones, "gamma": self.gamma, "base_lrs": list(self.base_lrs), "last_epoch": self.last_epoch,
+        return {self.key: getattr(self, self.key), "gamma": self.gamma, "base_lrs": list(self.base_lrs), "last_epoch": self.last_epoch,
                 "verbose": False, "_step_count": self._step_count, "_get_lr_called_within_step": False, "_last_lr": list(self._last_lr)}
 
     def load_state_dict(self, sd: dict) -> None:
-        from collections import Counter
-        self.milestones = Counter({int(k): int(v) for k, v in dict(sd["milestones"]).items()})
+        setattr(self, self.key, self._coerce(sd[self.key]))
         self.gamma, self.base_lrs = sd["gamma"], list(sd["base_lrs"])
         self.last_epoch, self._step_count = int(sd["last_epoch"]), int(sd["_step_count"])
         self._last_lr = list(sd["_last_lr"])
         self.optimizer.lr = self._last_lr[0]
 
 
-class StepLR:
-    """``torch.optim.lr_scheduler.StepLR`` for the fused optimizers, built like ``MultiStepLR`` above.  The reference's generator
-    pre-training builds one from ``lr_scheduler_step_size`` / ``lr_scheduler_gamma`` (ESRGAN/rrdbnet_config.py:77-78: epochs // 5, 0.5;
-    train_rrdbnet.py:205-210) and steps it once per epoch.  ``state_dict()`` carries torch's keys, so the two resume from each other's
-    checkpoints."""
+class MultiStepLR(_StepScheduler):
+    """``torch.optim.lr_scheduler.MultiStepLR`` for the fused optimizers (torch's class insists on a ``torch.optim.Optimizer``).
+    The reference builds one per network from ``lr_scheduler_milestones`` / ``lr_scheduler_gamma`` (bsrgan_config.py:153-155,
+    train_bsrgan.py:314-323) and steps it once per epoch (:193-195; utils.load_state_dict passes ``ckpt["scheduler"]`` through)."""
+    key = "milestones"
+
+    def __init__(self, optimizer: "FlatAdamEMA", milestones, gamma: float = 0.1, last_epoch: int = -1):
+        self.milestones = Counter(int(m) for m in milestones)
+        super().__init__(optimizer, gamma, last_epoch)
+
+    def _decays(self) -> int:
+        return self.milestones[self.last_epoch]       # a milestone listed twice decays twice, as in torch
+
+    @staticmethod
+    def _coerce(milestones) -> Counter:
+        return Counter({int(k): int(v) for k, v in dict(milestones).items()})
+
+
+class StepLR(_StepScheduler):
+    """``torch.optim.lr_scheduler.StepLR`` for the fused optimizers.  The reference's generator pre-training builds one from
+    ``lr_scheduler_step_size`` / ``lr_scheduler_gamma`` (ESRGAN/rrdbnet_config.py:77-78: epochs // 5, 0.5; train_rrdbnet.py:205-210)
+    and steps it once per epoch."""
+    key = "step_size"
+    _coerce = staticmethod(int)
 
     def __init__(self, optimizer: "FlatAdamEMA", step_size: int, gamma: float = 0.1, last_epoch: int = -1):
-        self.optimizer = optimizer
         self.step_size = int(step_size)
         if self.step_size < 1:
             raise ValueError(f"StepLR: step_size must be at least 1, got {step_size}")
-        self.gamma = gamma
-        self.base_lrs = [optimizer.lr]
-        self.last_epoch = last_epoch
-        self._step_count = 0
-        self._last_lr = [optimizer.lr]
-        self.step()                                   # torch's constructor performs the initial step (last_epoch -> 0)
+        super().__init__(optimizer, gamma, last_epoch)
 
-    def get_last_lr(self):
-        return list(self._last_lr)
-
-    def step(self) -> None:
-        self._step_count += 1
-        self.last_epoch += 1
-        if self.last_epoch > 0 and self.last_epoch % self.step_size == 0:      # torch's chained form: multiply the CURRENT rate
-            self.optimizer.lr = self.optimizer.lr * self.gamma
-        self._last_lr = [self.optimizer.lr]
-
-    def state_dict(self) -> dict:
-        return {"step_size": self.step_size, "gamma": self.gamma, "base_lrs": list(self.base_lrs), "last_epoch": self.last_epoch,
-                "verbose": False, "_step_count": self._step_count, "_get_lr_called_within_step": False, "_last_lr": list(self._last_lr)}
-
-    def load_state_dict(self, sd: dict) -> None:
-        self.step_size, self.gamma, self.base_lrs = int(sd["step_size"]), sd["gamma"], list(sd["base_lrs"])
-        self.last_epoch, self._step_count = int(sd["last_epoch"]), int(sd["_step_count"])
-        self._last_lr = list(sd["_last_lr"])
-        self.optimizer.lr = self._last_lr[0]
+    def _decays(self) -> int:
+        return int(self.last_epoch > 0 and self.last_epoch % self.step_size == 0)
 
 
 def pin_training_dtype(*modules) -> torch.dtype:
@@ -357,37 +354,102 @@ class FlatAdamEMA:
                                          self.ema_decay or 0.0, mode, None, grad_scale_dev, A.stream_ptr()), "adam_ema")
 
 
-class GanCheckpointMixin:
-    """state_dict() / load_state_dict() of the two-network trainers (gan.GanTrainer, gan_esrgan.EsrganGanTrainer): the trainer-side
-    entries of the reference's two checkpoint files (train_bsrgan.py:203-260, ESRGAN/train_esrgan.py:216-262: d_*.pth.tar holds the
-    discriminator + its optimizer, g_*.pth.tar the generator + optimizer + EMA), keyed "g" / "d"; "scaler" is an addition (the
-    reference does not checkpoint its GradScaler and restarts it at 65536).  Needs self.g / .d / .ge / .de / .g_opt / .d_opt / .scaler."""
+class FusedTrainer:
+    """What the fused trainers share (GeneratorTrainer below, gan.GanTrainer, gan_esrgan.EsrganGanTrainer): the loss scaler, the
+    scalar tensor the loss kernels write their values to (``scalars``, addressed by slot), scratch buffers kept per name and shape,
+    the generator's and the discriminator's update, and the checkpoint entries of one network.  The two-network trainers name
+    their networks g / d, engines ge / de and optimizers g_opt / d_opt; GeneratorTrainer says where its own are (``_generator``)."""
+
+    def __init__(self, dev, process_group, n_scalars: int, *modules):
+        self.scaler = LossScaler(dev, enabled=needs_loss_scaling(*modules))     # ONE scaler for all networks (train_bsrgan.py:109)
+        self.pg = process_group
+        self.g_reducer = BucketReducer(dev, process_group)          # G's gradient exchange in buckets behind its own backward pass
+        self.scalars = torch.zeros(n_scalars, dtype=torch.float32, device=dev)
+        self.ws = torch.empty(A.LOSS_WS_FLOATS, dtype=torch.float32, device=dev)
+        self._bufs: Dict[tuple, Tensor] = {}
+
+    def _generator(self):
+        return self.ge, self.g_opt
+
+    def _buf(self, name, like: Tensor) -> Tensor:
+        b = self._bufs.get((name, tuple(like.shape)))
+        if b is None:
+            b = torch.empty_like(like)
+            self._bufs[(name, tuple(like.shape))] = b
+        return b
+
+    def _allreduce(self, grad: Tensor) -> float:
+        return allreduce_sum_(grad, self.pg)
+
+    # -- the kernels every step body launches ---------------------------------------------------------------------------
+    @staticmethod
+    def _add(src: Tensor, dst: Tensor, alpha: float = 1.0, beta: float = 1.0) -> None:
+        """dst = alpha * src + beta * dst over dst.numel() contiguous fp32 elements"""
+        A.check(A.lib().srganfd_axpby(A.View(src.data_ptr(), 1, 0), A.View(dst.data_ptr(), 1, 0), A.F32, dst.numel(), 1, alpha, beta,
+                                      A.stream_ptr()), "axpby")
+
+    def _pixel_loss(self, sr: Tensor, target: Tensor, weight: float, loss_slot: int, dsr: Tensor) -> None:
+        """scalars[loss_slot] = weight * L1(sr, target); dsr = its gradient times the loss scale the device holds when the kernel
+        runs (scaler.scale(loss): the factor rides on the gradient seed)"""
+        A.check(A.lib().srganfd_l1_loss(sr.data_ptr(), target.data_ptr(), sr.numel(), weight, self.scalars.data_ptr() + 4 * loss_slot, 0,
+                                        dsr.data_ptr(), weight, self.scaler.seed_ptr, self.ws.data_ptr(), A.stream_ptr()), "l1_loss")
+
+    def _prob(self, logits: Tensor, slot: int) -> None:
+        """scalars[slot] = sigmoid(mean(logits))"""
+        A.check(A.lib().srganfd_sigmoid_of_mean(logits.data_ptr(), logits.numel(), self.scalars.data_ptr() + 4 * slot, self.ws.data_ptr(),
+                                                A.stream_ptr()), "sigmoid_of_mean")
+
+    def _update_generator(self, sp, token, dsr: Tensor) -> None:
+        """G backward from dsr, scaler.step(g_optimizer); scaler.update(); EMA update.  RCCL over xGMI: the flat gradient goes out
+        in three buckets as the backward pass finishes them (parallel.BucketReducer)."""
+        eng, opt = self._generator()
+        self.g_reducer.begin()
+        grad, _ = eng.backward(sp, token, dsr, True, False, on_ready=self.g_reducer.bucket)
+        self.scaler.step(opt, grad, self.g_reducer.finish())
+        eng.fp.touch()                             # parameters changed behind autograd's back -> re-pack
+
+    def _update_discriminator(self, gd1: Tensor, gd2: Tensor) -> None:
+        """the two backward passes accumulate (gd2 += gd1), one all-reduce, scaler.step(d_optimizer); scaler.update()"""
+        self._add(gd1, gd2)
+        self.scaler.step(self.d_opt, gd2, self._allreduce(gd2))
+
+    # -- checkpoints: per network, the entries of the reference's checkpoint files that belong to the trainer ------------
+    @staticmethod
+    def _net_state(net, opt: FlatAdamEMA) -> dict:
+        out = {"state_dict": net.state_dict(), "optimizer": opt.state_dict()}
+        if opt.ema is not None:
+            out["ema_state_dict"] = opt.ema_state_dict()
+        return out
+
+    @staticmethod
+    def _load_net(net, eng, opt: FlatAdamEMA, c: dict) -> None:
+        """weights (in place, into the flat buffer), Adam moments + step, EMA copy + n_averaged"""
+        with torch.no_grad():
+            own = net.state_dict()
+            for k, v in c["state_dict"].items():            # spectral-norm u / v and BatchNorm running statistics included
+                if k in own and tuple(own[k].shape) == tuple(v.shape):
+                    own[k].copy_(v)
+        eng.fp.touch()
+        if "optimizer" in c:
+            opt.load_state_dict(c["optimizer"])
+        if "ema_state_dict" in c and opt.ema is not None:
+            opt.load_ema_state_dict(c["ema_state_dict"])
 
     def state_dict(self) -> dict:
-        g = {"state_dict": self.g.state_dict(), "optimizer": self.g_opt.state_dict()}
-        if self.g_opt.ema is not None:
-            g["ema_state_dict"] = self.g_opt.ema_state_dict()
-        return {"g": g, "d": {"state_dict": self.d.state_dict(), "optimizer": self.d_opt.state_dict()}, "scaler": self.scaler.state_dict()}
+        """The two-network trainers: the trainer-side entries of the reference's two checkpoint files (train_bsrgan.py:203-260,
+        ESRGAN/train_esrgan.py:216-262: d_*.pth.tar holds the discriminator + its optimizer, g_*.pth.tar the generator + optimizer +
+        EMA), keyed "g" / "d"; "scaler" is an addition (the reference does not checkpoint its GradScaler and restarts it at 65536)."""
+        return {"g": self._net_state(self.g, self.g_opt), "d": self._net_state(self.d, self.d_opt), "scaler": self.scaler.state_dict()}
 
     def load_state_dict(self, ckpt: dict) -> None:
-        with torch.no_grad():
-            for net, eng, opt, c in ((self.g, self.ge, self.g_opt, ckpt.get("g")), (self.d, self.de, self.d_opt, ckpt.get("d"))):
-                if c is None:
-                    continue
-                own = net.state_dict()
-                for k, v in c["state_dict"].items():        # spectral-norm u / v and BatchNorm running statistics included
-                    if k in own and tuple(own[k].shape) == tuple(v.shape):
-                        own[k].copy_(v)
-                eng.fp.touch()
-                if "optimizer" in c:
-                    opt.load_state_dict(c["optimizer"])
-                if "ema_state_dict" in c and opt.ema is not None:
-                    opt.load_ema_state_dict(c["ema_state_dict"])
+        for net, eng, opt, c in ((self.g, self.ge, self.g_opt, ckpt.get("g")), (self.d, self.de, self.d_opt, ckpt.get("d"))):
+            if c is not None:
+                self._load_net(net, eng, opt, c)
         if "scaler" in ckpt:
             self.scaler.load_state_dict(ckpt["scaler"])
 
 
-class GeneratorTrainer:
+class GeneratorTrainer(FusedTrainer):
     """Generator-only iteration (BASELINE.json configs[0] and [1])."""
 
     def __init__(self, g_model, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 0.0,
@@ -399,33 +461,19 @@ class GeneratorTrainer:
         self.flat = self.eng.fp.sync(dev)
         self.opt = FlatAdamEMA(self.flat, lr, betas, eps, weight_decay, ema_decay, layout=self.eng.fp)
         self.loss_weight = loss_weight
-        self.scaler = LossScaler(dev, enabled=needs_loss_scaling(g_model))      # train_rrdbnet.py:94 / train_bsrnet.py:94
-        self.pg = process_group
-        self.g_reducer = BucketReducer(dev, process_group)
-        self.loss_buf = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.ws = torch.empty(A.LOSS_WS_FLOATS, dtype=torch.float32, device=dev)
-        self.dsr: Optional[Tensor] = None
+        super().__init__(dev, process_group, 1, g_model)       # train_rrdbnet.py:94 / train_bsrnet.py:94
+        self.loss_buf = self.scalars
+
+    def _generator(self):
+        return self.eng, self.opt
 
     def state_dict(self) -> dict:
         """The entries of the reference's checkpoint that belong to the trainer (train_bsrnet.py:124-130)."""
-        out = {"state_dict": self.g.state_dict(), "optimizer": self.opt.state_dict()}
-        if self.opt.ema is not None:
-            out["ema_state_dict"] = self.opt.ema_state_dict()
-        return out
+        return self._net_state(self.g, self.opt)
 
     def load_state_dict(self, ckpt: dict) -> None:
-        """Resume from a checkpoint written by the reference's train script or by state_dict(): weights (in place, into the
-        flat buffer), Adam moments + step, EMA copy + n_averaged."""
-        with torch.no_grad():
-            own = self.g.state_dict()
-            for k, v in ckpt["state_dict"].items():
-                if k in own and tuple(own[k].shape) == tuple(v.shape):
-                    own[k].copy_(v)
-        self.eng.fp.touch()
-        if "optimizer" in ckpt:
-            self.opt.load_state_dict(ckpt["optimizer"])
-        if "ema_state_dict" in ckpt and self.opt.ema is not None:
-            self.opt.load_ema_state_dict(ckpt["ema_state_dict"])
+        """Resume from a checkpoint written by the reference's train script or by state_dict()."""
+        self._load_net(self.g, self.eng, self.opt, ckpt)
 
     def step(self, lr_img: Tensor, gt: Tensor) -> Tensor:
         """Returns the (device, 1-element) loss tensor; no host sync inside."""
@@ -433,18 +481,10 @@ class GeneratorTrainer:
         check_targets("GeneratorTrainer.step", eng, lr_img, gt=gt)
         sr = eng.forward(lr_img, True)
         sp, token = eng._last, eng.token
-        if self.dsr is None or self.dsr.shape != sr.shape:
-            self.dsr = torch.empty_like(sr)
+        dsr = self._buf("dsr", sr)
         gt = gt.contiguous().float()
         check_loss_scaling(self.scaler, self.g)
-        # scaler.scale(loss): the (device-resident) factor rides on the gradient seed
-        A.check(A.lib().srganfd_l1_loss(sr.data_ptr(), gt.data_ptr(), sr.numel(), self.loss_weight, self.loss_buf.data_ptr(), 0,
-                                        self.dsr.data_ptr(), self.loss_weight, self.scaler.seed_ptr, self.ws.data_ptr(), A.stream_ptr()), "l1_loss")
-        # RCCL over xGMI: the flat gradient goes out in three buckets as the backward pass finishes them (parallel.BucketReducer)
-        self.g_reducer.begin()
-        grad, _ = eng.backward(sp, token, self.dsr, True, False, on_ready=self.g_reducer.bucket)
-        scale = self.g_reducer.finish()
-        self.scaler.step(self.opt, grad, scale)        # scaler.step(optimizer); scaler.update(); ema update
-        eng.fp.touch()                             # parameters changed behind autograd's back -> re-pack
+        self._pixel_loss(sr, gt, self.loss_weight, 0, dsr)
+        self._update_generator(sp, token, dsr)
         self.sr = sr
         return self.loss_buf

@@ -147,31 +147,33 @@ def _unet():
     return M.discriminator_unet(in_channels=3, out_channels=1, channels=64)
 
 
-def _gan(dt, dfac, generator_first=False):
+def _gan(dt, dfac, generator_first=False, content=True, usm=True, **kw):
     from sr_gan_fd_amd import model as M
     from sr_gan_fd_amd.gan import GanTrainer
-    g, d, cl = _pin(dt, M.bsrgan_x4(num_rrdb=1), dfac(), M.ContentLoss(NODES, MEAN, STD))
-    tr = GanTrainer(g, d, cl, generator_first=generator_first)
+    g, d = _pin(dt, M.bsrgan_x4(num_rrdb=1), dfac())
+    cl = _pin(dt, M.ContentLoss(NODES, MEAN, STD))[0] if content else None
+    tr = GanTrainer(g, d, cl, generator_first=generator_first, **kw)
     for _ in range(2):                 # the second step sees cached plans and stale packs
-        tr.step(torch.rand(2, 3, 16, 16), torch.rand(2, 3, 64, 64), torch.rand(2, 3, 64, 64) if generator_first else None)
+        tr.step(torch.rand(2, 3, 16, 16), torch.rand(2, 3, 64, 64), torch.rand(2, 3, 64, 64) if generator_first and usm else None)
     return g, d, cl, tr
 
 
-def _esrgan(dt):
+def _esrgan(dt, content=True, **kw):
     from sr_gan_fd_amd import model as M
     from sr_gan_fd_amd.gan_esrgan import EsrganGanTrainer
-    g, d, cl = _pin(dt, M.RRDBNet(num_rrdb=1, upscale_factor=2), M.discriminator(), M.ContentLoss("features.34", MEAN, STD))
-    tr = EsrganGanTrainer(g, d, cl)
+    g, d = _pin(dt, M.RRDBNet(num_rrdb=1, upscale_factor=2), M.discriminator())
+    cl = _pin(dt, M.ContentLoss("features.34", MEAN, STD))[0] if content else None
+    tr = EsrganGanTrainer(g, d, cl, **kw)
     for _ in range(2):                 # the discriminator's ring of plans
         tr.step(torch.rand(2, 3, 64, 64), torch.rand(2, 3, 128, 128))
     return g, d, cl, tr
 
 
-def _g_only(dt, num_rrdb=1):
+def _g_only(dt, num_rrdb=1, **kw):
     from sr_gan_fd_amd import model as M
     from sr_gan_fd_amd.trainer import GeneratorTrainer
     g, = _pin(dt, M.bsrgan_x4(num_rrdb=num_rrdb))
-    tr = GeneratorTrainer(g, lr=1e-4)
+    tr = GeneratorTrainer(g, lr=1e-4, **kw)
     tr.step(torch.rand(2, 3, 16, 16), torch.rand(2, 3, 64, 64))
     return g, tr
 
@@ -259,6 +261,13 @@ SCENARIOS = {
     "rpa_blocks": _rpa_blocks,
     "gen_rpa": _gen_rpa,
     "self_attention": _self_attention,
+    # the trainers' remaining branches: a frozen generator, no content criterion, the generator-first order without a sharpened GT,
+    # and no EMA copy
+    "gan_unet_frozen_generator": lambda dt: _gan(dt, _unet, train_generator=False),
+    "gan_unet_no_content": lambda dt: _gan(dt, _unet, content=False),
+    "gan_unet_generator_first_no_usm": lambda dt: _gan(dt, _unet, True, usm=False),
+    "esrgan_gan_no_content_no_ema": lambda dt: _esrgan(dt, content=False, ema_decay=None),
+    "generator_only_no_ema": lambda dt: _g_only(dt, ema_decay=None),
 }
 CASES = ["%s-%s" % (s, d) for s in SCENARIOS for d in DTYPES]
 
