@@ -162,15 +162,17 @@ typedef struct {
   int32_t dtype, ksize;
   int32_t k, n;           /* packed K and N, multiples of 32 */
   int32_t nseg;
-  int32_t layout;         /* 0: B fragments of v_mfma_f32_32x32x16; 1: of v_mfma_f32_16x16x32 -- srganfd_pack_layout(dtype, ksize, n) says
-                             which one the consuming kernel reads under the current srganfd_set_mfma16 level */
+  int32_t layout;         /* B-fragment order; srganfd_pack_layout(dtype, ksize, n) says which one the consuming kernel reads.
+                             1: v_mfma_f32_16x16x32, what the 16-bit kernels of this library run on; 0: v_mfma_f32_32x32x2 for f32
+                             (for a 16-bit dtype 0 is the v_mfma_f32_32x32x16 order: still packed, read by no kernel of this library) */
   srganfd_pack_seg seg[5];
 } srganfd_pack_job;
 
 size_t srganfd_packed_bytes(int32_t dtype, int32_t ksize, int32_t k, int32_t n);
-/* MFMA form of the 16-bit convolutions: 3 = v_mfma_f32_16x16x32 for every kernel shape (the product library's only level). */
+/* MFMA form of the 16-bit convolutions: always 3 = v_mfma_f32_16x16x32 for every kernel shape.  The form follows the element type
+ * (f32 runs on v_mfma_f32_32x32x2); the levels below 3 and their setter exist in the experiment build only. */
 int srganfd_get_mfma16(void);
-/* the `layout` a pack job must carry for an operand of this dtype / kernel size / packed output width n under the current setting */
+/* the `layout` a pack job must carry for an operand of this dtype / kernel size / packed output width n: 1 for bf16 / f16, 0 for f32 */
 int srganfd_pack_layout(int32_t dtype, int32_t ksize, int32_t n);
 /* max_elems = max over jobs of ksize*ksize*k*n (grid sizing; host knows it) */
 int srganfd_pack_weights(const srganfd_pack_job* jobs_dev, int32_t njobs, int64_t max_elems,

@@ -33,13 +33,13 @@ __device__ __forceinline__ float bf2f(bf16_t v) {
 template <typename T> struct Elem;
 template <> struct Elem<bf16_t> {
   static constexpr int kDtype = SRGANFD_BF16;
-  static constexpr int kStep = 16;  // K per MFMA (v_mfma_f32_32x32x16_bf16)
+  static constexpr int kStep = 16;  // packing step: 16 channels per 1 KiB of B fragments (64 lanes x 8); one v_mfma_f32_16x16x32_bf16 eats two (K = 32)
   __device__ static __forceinline__ float to_f(bf16_t v) { return bf2f(v); }
   __device__ static __forceinline__ bf16_t from_f(float f) { return f2bf(f); }
 };
 template <> struct Elem<f16_t> {
   static constexpr int kDtype = SRGANFD_F16;
-  static constexpr int kStep = 16;  // K per MFMA (v_mfma_f32_32x32x16_f16)
+  static constexpr int kStep = 16;  // packing step, as for bf16 (v_mfma_f32_16x16x32_f16, K = 32)
   __device__ static __forceinline__ float to_f(f16_t v) { return (float)v; }
   __device__ static __forceinline__ f16_t from_f(float f) { return (f16_t)f; }   // round-to-nearest-even; overflow -> inf (caught by the loss scaler)
 };

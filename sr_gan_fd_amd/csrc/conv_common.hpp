@@ -63,14 +63,11 @@ inline unsigned div_magic(unsigned d, unsigned long long n_max) {
   if (d <= 1 || n_max * d >= (1ull << 32)) return 0u;
   return (unsigned)(((1ull << 32) + d - 1) / d);
 }
-bool conv_uses_m16(int dtype, int ksize, int cout);
-extern int g_mfma16;   // 1: the 3x3 16-bit convolutions run on the 16x16x32 form (weights packed in its B-fragment order: srganfd_pack_job.layout)
 
 // compile-time loop (indices as types), for the software-pipelined MFMA phase
 template <int I> struct IC { static constexpr int v = I; };
 template <class Fn, int... Is> __device__ __forceinline__ void static_for_impl(Fn&& f, std::integer_sequence<int, Is...>) { (f(IC<Is>{}), ...); }
 template <int N, class Fn> __device__ __forceinline__ void static_for(Fn&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-// last fragment load issued before MFMA i: the fragment it needs (7 loads / 6 MFMAs per column body) plus kD of read-ahead
 // 16x16x32 form, 3x3 stride 1, two rows per wave: fixed issue order of one kernel column's 14 fragment reads and 24 MFMAs.
 // reads:  B00 A00 A01 A10 A11 | B01 | B10 A20 A21 | B11 | B20 A30 A31 | B21      (B[ky][channel half], A[patch row][pixel half])
 // MFMAs:  group (ky, nh) = 4 MFMAs (row m, pixel half ph): acc[m][ph][nh] += A[m + ky][ph] x B[ky][nh]  -- eight independent
@@ -81,8 +78,8 @@ __host__ __device__ constexpr int m16_need(int j) {
   const int gq = j / 4, t = j % 4, a = m16_aidx((t >> 1) + (gq >> 1), t & 1), b = m16_bidx(gq >> 1, gq & 1);
   return a > b ? a : b;
 }
+// last fragment load issued before MFMA i: the fragment it needs plus d of read-ahead
 __host__ __device__ constexpr int m16_pipe_hi(int i, int d, int nl) { const int need = 14 * (i / 24) + m16_need(i % 24); return need + d < nl - 1 ? need + d : nl - 1; }
-__host__ __device__ constexpr int pipe_hi(int i, int d, int nl) { const int need = 7 * (i / 6) + (i % 6) + 1; return need + d < nl - 1 ? need + d : nl - 1; }
 
 // XCD-aware bijective remap of a 1-D grid: blocks b and b+8 share an XCD (private L2); give each XCD a contiguous range
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

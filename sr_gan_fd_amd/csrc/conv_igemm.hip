@@ -25,8 +25,8 @@
 //     (issue-early / write-late); all staging addresses are base + immediate (no per-chunk VALU).
 //   * epilogue: accumulators -> fp32 LDS tile -> 16-byte vector loads of residual / mask tensors and
 //     16-byte stores (one pixel's channels are contiguous in NHWC).
-//   * bf16: v_mfma_f32_32x32x16_bf16 (fp32 accumulate).  f32: v_mfma_f32_32x32x2_f32, an exact
-//     fp32 fma chain, used as the parity mode against the CPU oracle.
+//   * the MFMA form follows the element type: bf16 / f16 run on v_mfma_f32_16x16x32 (fp32 accumulate; a 32x32 tile is 2 pixel halves
+//     x 2 channel halves), f32 on v_mfma_f32_32x32x2_f32, an exact fp32 fma chain, used as the parity mode against the CPU oracle.
 #include "conv_common.hpp"
 #include <stdlib.h>
 #include <string.h>
@@ -48,12 +48,29 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 // weights per chunk next to a 42 KiB patch would leave room for ONE workgroup per CU; in halves two fit)
 template <typename T, int KS, int STRIDE, int MR, int WR, int WN, int TS = 1>
 struct ConvCfg {
+  // the shape itself, for the stages of the kernel body that take the configuration whole
+  typedef T Elt;
+  static constexpr int kKS = KS, kStride = STRIDE, kMR = MR, kWN = WN;
+  static constexpr bool k16 = sizeof(T) == 2;                  // 16-bit elements: the 16x16x32 MFMA form (f32: 32x32x2)
   static constexpr int NWAVES = WR * WN, NTHR = 64 * NWAVES;
   static constexpr int KT = KS * KS;
   static constexpr int TW = 32, TH = WR * MR;
   static constexpr int PR = (TH - 1) * STRIDE + KS;
   static constexpr int PC = (TW - 1) * STRIDE + KS;
   static constexpr int KC = 32;
+  // 16x16x32 form, stride 1: the slot swizzle is keyed on the patch COLUMN, 2*((px>>2)&1).  What keeps a 16-lane read group
+  // conflict free is that the four lanes whose pixels are 4 apart (same 64-byte position of the 256-byte bank row) alternate
+  // their slot bit, and 4 columns apart they do whatever the row start is.  The fragment address is then lane term (3 kernel
+  // columns) + wave-uniform row offset + immediate, instead of one precomputed VGPR per (row, column, pixel half) -- those 24
+  // registers pushed the 64-channel kernel over its 128 and spilled a prefetch pointer (scratch reload + vmcnt(0) inside the loop).
+  static constexpr bool kColSwz = k16 && STRIDE == 1;
+  // stride 2 (16x16x32 form): a patch row is stored even columns first, then the odd ones -- the 16 lanes of a fragment read want
+  // columns 2*l + kx, which interleaved sit 128 bytes apart (four 16-byte slots of the 256-byte bank row for 16 lanes: 4-way conflicts
+  // on every A read); de-interleaved they are 16 consecutive storage pixels, the stride-1 pattern the slot swizzle spreads
+  static constexpr bool kDeint = k16 && STRIDE == 2;
+  static constexpr int kHalf = (PC + 1) / 2;                  // even columns of a patch row
+  // storage pixel (within a patch row) of column 2*l + kx + 32*ph, before the lane term l: the A-fragment reads of the stride-2 forms
+  static __host__ __device__ constexpr int deint_col(int kx, int ph) { return (kx & 1) * kHalf + (kx >> 1) + 16 * ph; }
   static constexpr int E16 = 16 / (int)sizeof(T);            // elements per 16 bytes
   static constexpr int CPP = KC / E16;                        // 16-byte chunks per pixel
   static constexpr int PIXB = KC * (int)sizeof(T);            // bytes per pixel in LDS
@@ -81,16 +98,16 @@ struct ConvCfg {
   static constexpr int MIN_WAVES_PER_SIMD = WG_PER_CU * NTHR / 256 < 1 ? 1 : WG_PER_CU * NTHR / 256;
 };
 
-// LDS patch layout.  bf16: 4 chunks of 16 B per pixel, chunk index XOR (pix>>2)&3.  f32: 32 dwords per
-// pixel, dword index XOR (pix & 31) so 32 lanes reading one channel of 32 consecutive pixels hit 32 banks.
-__device__ __forceinline__ int lds_x_bf16_off(int pix, int c16) { return pix * 64 + ((c16 ^ ((pix >> 2) & 3)) << 4); }
+// LDS patch layout.  f32: 32 dwords per pixel, dword index XOR (pix & 31) so 32 lanes reading one channel of 32 consecutive pixels
+// hit 32 banks.
 __device__ __forceinline__ int lds_x_f32_off(int pix, int k) { return pix * 128 + ((k ^ (pix & 31)) << 2); }
-// 16x16x32 form: lane l reads pixel (l & 15), 16-byte slot (l >> 4); slot XOR 2*((pix>>2)&1) gives every 16-lane group of
-// ds_read_b128 sixteen distinct slots of the 256-byte bank row for any patch alignment
+// 16-bit (16x16x32 form): 4 slots of 16 B per pixel; lane l reads pixel (l & 15), 16-byte slot (l >> 4); slot XOR 2*((pix>>2)&1) gives
+// every 16-lane group of ds_read_b128 sixteen distinct slots of the 256-byte bank row for any patch alignment
 __device__ __forceinline__ int lds_x16_m16_off(int pix, int c16) { return pix * 64 + ((c16 ^ (((pix >> 2) & 1) << 1)) << 4); }
 
 // accumulators of one wave: MR rows x 32 pixels x 32 channels = 16 floats per lane and row in both MFMA forms
-template <bool M16, int MR> struct AccSet;
+// (K16 = 16-bit element type: the 16x16x32 form; else f32: 32x32x2)
+template <bool K16, int MR> struct AccSet;
 template <int MR> struct AccSet<false, MR> {
   f32x16 a[MR];
   __device__ __forceinline__ void zero() {
@@ -118,15 +135,186 @@ template <int MR> struct AccSet<true, MR> {
   static __device__ __forceinline__ int chan(int e, int lane) { return 16 * ((e >> 2) & 1) + (lane & 15); }
 };
 
+// fragment read-ahead (what fits 128 VGPRs) of the 3x3 stride-1 16x16x32 loop (0 = the compiler's own schedule)
+template <int WN> constexpr int kM16Pipe = WN == 2 ? SRGANFD_M16_PIPE : SRGANFD_M16_PIPE - 1;
+// kinds whose workgroups run persistent and request a tile's first chunk during the previous tile's last MFMA phase (the kinds whose
+// epilogue leaves room for the 32 staging registers); every other kernel gets one block per workgroup from the host
+template <typename T, int EK> constexpr bool kConvCross = sizeof(T) == 2 && EK >= 0 && (EK & SRGANFD_CROSS_MASK) == 0;
+
+// ---- MFMA phases of one staged 32-channel chunk.  The chunk loop itself (barrier, commit, barrier, request of the next chunk or
+// tile) stays in the body, so the loads keep their place in program order: after the second barrier, before the MFMA phase. ----
+
+// f32 (parity mode): v_mfma_f32_32x32x2, one kernel column x one K step (2 channels) at a time
+template <class C>
+__device__ __forceinline__ void mfma_chunk_f32(const char* ldsX, const char* ldsWn, int pix00, int h, AccSet<false, C::kMR>& A_) {
+  constexpr int KS = C::kKS, STRIDE = C::kStride, MR = C::kMR;
+  auto& acc = A_.a;
+  {
+#pragma unroll 1
+    for (int kx = 0; kx < KS; ++kx) {
+#pragma unroll 2
+      for (int s = 0; s < C::KSTEPS; ++s) {
+        float av[C::NROWS];
+#pragma unroll
+        for (int rr = 0; rr < C::NROWS; ++rr) av[rr] = *(const float*)(ldsX + lds_x_f32_off(pix00 + rr * C::PC + kx, 2 * s + h));
+#pragma unroll
+        for (int ky = 0; ky < KS; ++ky) {
+          const float bq = *(const float*)(ldsWn + ((ky * KS + kx) * C::KSTEPS + s) * 64 * C::FRAGB);
+#pragma unroll
+          for (int m = 0; m < MR; ++m) acc[m] = mfma32<float>(av[m * STRIDE + ky], bq, acc[m]);
+        }
+      }
+    }
+  }
+}
+
+// 16-bit: v_mfma_f32_16x16x32, one K step = the whole 32-channel chunk; per kernel column: (NROWS x 2 pixel halves) A fragments,
+// (KS x 2 channel halves) B.  colt = lane term of the fragment address per kernel column (stride 1, chunk-invariant).
+template <class C>
+__device__ __forceinline__ void mfma_chunk_16(const char* ldsX, const char* ldsWn, int wr, int lane, const int (&colt)[C::kKS],
+                                             AccSet<true, C::kMR>& A_) {
+  using T = typename C::Elt;
+  using Frag = typename FragAB<T>::type;
+  constexpr int KS = C::kKS, STRIDE = C::kStride, MR = C::kMR, kPipe = kM16Pipe<C::kWN>;
+  auto& acc = A_.a;
+  {
+    const int l15 = lane & 15, sl = lane >> 4;
+    const int pixb = (wr * MR * STRIDE) * C::PC + l15 * STRIDE;
+    const char* ldsXw = ldsX + (wr * MR * STRIDE) * C::PC * 64;        // this wave's first patch row (wave-uniform)
+    __builtin_amdgcn_s_setprio(1);   // waves in their MFMA phase win issue arbitration over waves that are staging (+1-3 %)
+    if constexpr (C::kColSwz && KS == 3 && MR == 2 && kPipe > 0) {
+      // software-pipelined fragment reads (see m16_need): every ds_read_b128 is issued kPipe fragments ahead of the MFMA that
+      // needs it, across the three kernel columns of the chunk; same accumulation order per accumulator as the plain loop below
+      constexpr int NL = 14 * KS, NM = 24 * KS;
+      Frag F[NL];
+      static_for<NM>([&](auto ic) {
+        constexpr int i = decltype(ic)::v;
+        constexpr int c = i / 24, j = i % 24, gq = j / 4, t = j % 4;
+        constexpr int hi = m16_pipe_hi(i, kPipe, NL), lo = i == 0 ? 0 : m16_pipe_hi(i - 1, kPipe, NL) + 1;
+        static_for<hi - lo + 1>([&](auto jc) {
+          constexpr int n = lo + decltype(jc)::v;
+          constexpr int kx = n / 14, l = n % 14;
+          constexpr bool isB = l == 0 || l == 5 || l == 6 || l == 9 || l == 10 || l == 13;
+          if constexpr (isB) {
+            constexpr int ky = l < 6 ? 0 : (l < 10 ? 1 : 2), nh = (l == 5 || l == 9 || l == 13) ? 1 : 0;
+            F[n] = *(const Frag*)(ldsWn + ((ky * KS + kx) * 2 + nh) * 64 * C::FRAGB);
+          } else {
+            constexpr int q = l < 5 ? l - 1 : (l < 9 ? l - 3 : l - 5), rr = q >> 1, ph = q & 1;
+            F[n] = *(const Frag*)(ldsXw + colt[kx] + (rr * C::PC + 16 * ph) * 64);
+          }
+        });
+        constexpr int ky = gq >> 1, nh = gq & 1, m = t >> 1, ph = t & 1;
+        acc[m][ph][nh] = mfma16<T>(F[14 * c + m16_aidx(m + ky, ph)], F[14 * c + m16_bidx(ky, nh)], acc[m][ph][nh]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+    } else
+#pragma unroll
+    for (int kx = 0; kx < KS; ++kx) {
+      Frag av[C::NROWS][2];
+      const int colterm = (l15 + kx) * 64 + ((sl ^ ((((l15 + kx) >> 2) & 1) << 1)) << 4);     // stride 1: lane term of column kx
+#pragma unroll
+      for (int rr = 0; rr < C::NROWS; ++rr)
+#pragma unroll
+        for (int ph = 0; ph < 2; ++ph) {
+          if constexpr (C::kColSwz) av[rr][ph] = *(const Frag*)(ldsXw + colterm + (rr * C::PC + 16 * ph) * 64);
+          else if constexpr (C::kDeint) av[rr][ph] = *(const Frag*)(ldsX + lds_x16_m16_off((wr * MR * STRIDE + rr) * C::PC + l15 + C::deint_col(kx, ph), sl));
+          else av[rr][ph] = *(const Frag*)(ldsX + lds_x16_m16_off(pixb + rr * C::PC + kx + 16 * ph * STRIDE, sl));
+        }
+#pragma unroll
+      for (int ky = 0; ky < KS; ++ky) {
+#pragma unroll
+        for (int nh = 0; nh < 2; ++nh) {
+          const Frag bq = *(const Frag*)(ldsWn + ((ky * KS + kx) * 2 + nh) * 64 * C::FRAGB);
+#pragma unroll
+          for (int m = 0; m < MR; ++m)
+#pragma unroll
+            for (int ph = 0; ph < 2; ++ph) acc[m][ph][nh] = mfma16<T>(av[m * STRIDE + ky][ph], bq, acc[m][ph][nh]);
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  }
+}
+
+// ---- epilogues (see srganfd.h for the formula; the vector and the scalar one are in the body) ----
+
+// Kind 0, 32-channel tiles (the growth convs of a dense block): bias + activation in registers, rounded to T there (the value
+// the fp32 tile path would round after its LDS round trip: same bits), and a 16-bit CHANNEL-major LDS tile per image row --
+// a lane's four accumulator registers of one (row, pixel half, channel half) are four consecutive pixels of one channel, so
+// they go out as one ds_write_b64; ds_read_b64_tr_b16 hands them back pixel-major (lane i of a 16-lane group: pixel i, four
+// channels), two reads = the 16 bytes of (pixel, 8 channels) one lane stores.  Every wave reads only the rows it wrote: one
+// barrier (staging buffers free) instead of two, 8 LDS writes + 8 reads per lane instead of 16 + 8 wider ones, no fp32 tile
+// unpacking / conversion after the reads.  Row tile = 32 channels x 64 bytes, dword index XOR (channel & 14): conflict-free
+// for the ds_write_b64 (16 channels of one 8-byte column) and for the transposed reads (4 channels x 16 pixels per group).
+template <class C>
+__device__ __forceinline__ void epilogue_rows16(const ConvK& a, char* smem, int lane, int wr, const AccSet<true, C::kMR>& A_, float alpha, float bvh0, float bvh1,
+                                                int n, int oy0, int ox0, int nb) {
+  using T = typename C::Elt;
+  constexpr int MR = C::kMR;
+  static_assert(C::k16 && C::kWN == 1 && C::kKS == 3, "row tiles of 32 channels x 32 pixels of a 16-bit type; 3x3: never a class launch");
+  auto& acc = A_.a;
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;
+  int lane_o = lane;
+  asm volatile("" : "+v"(lane_o));      // keeps this block's lane-only address terms out of the registers carried around the tile loop
+  const int cl = lane_o & 15, g4 = lane_o >> 4;
+  const float neg = a.act == SRGANFD_ACT_LRELU ? a.slope : (a.act == SRGANFD_ACT_RELU ? 0.f : 1.f);
+  const float ps_pos = a.post_scale, ps_neg = neg * a.post_scale;
+  char* rowt = smem + (wr * MR) * 2048;                                   // this wave's first row tile
+  const int w0 = cl * 64 + (((2 * g4) ^ (cl & 14)) << 2);                 // write: channel cl (+16 nh), pixels 4 g4 .. 4 g4 + 3 (+16 ph)
+  const int rq = 8 * g4 + ((lane_o >> 2) & 3), rp = lane_o & 3;               // read: this lane addresses channel rq (+4), pixels 4 rp .. (+16 pb)
+  const int r0 = rq * 64 + (((2 * rp) ^ (rq & 14)) << 2), r1 = (rq + 4) * 64 + (((2 * rp) ^ ((rq + 4) & 14)) << 2);
+  __syncthreads();   // all waves are done with the staging buffers
+#pragma unroll
+  for (int m = 0; m < MR; ++m)
+#pragma unroll
+    for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+      for (int nh = 0; nh < 2; ++nh) {
+        float v4[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float v = alpha * acc[m][ph][nh][i] + (nh ? bvh1 : bvh0);
+          v4[i] = v * (v > 0.f ? ps_pos : ps_neg);
+        }
+        u32x2_t pk;
+        if constexpr (Elem<T>::kDtype == SRGANFD_F16) {
+          typedef __attribute__((ext_vector_type(4))) _Float16 h4;
+          const h4 hv = {(_Float16)v4[0], (_Float16)v4[1], (_Float16)v4[2], (_Float16)v4[3]};
+          pk = __builtin_bit_cast(u32x2_t, hv);
+        } else {
+          pk = u32x2_t{(unsigned)f2bf(v4[0]) | ((unsigned)f2bf(v4[1]) << 16), (unsigned)f2bf(v4[2]) | ((unsigned)f2bf(v4[3]) << 16)};
+        }
+        *(u32x2_t*)(rowt + m * 2048 + nh * 1024 + (w0 ^ (ph << 5))) = pk;
+      }
+  const size_t img = (size_t)n * a.HoutF * a.WoutF;
+  const int cch = nb * C::NB + 8 * g4;                                  // this lane's 8 output channels
+  const int cc = a.y_c0 + cch;
+  T* ybase = (T*)a.y + img * a.yC + ((cc >> 5) * a.y_gs + (cc & 31));
+#pragma unroll
+  for (int m = 0; m < MR; ++m)
+#pragma unroll
+    for (int pb = 0; pb < 2; ++pb) {
+      const u32x2_t lo = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(rowt + m * 2048 + (r0 ^ (pb << 5)))));
+      const u32x2_t hi = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(rowt + m * 2048 + (r1 ^ (pb << 5)))));
+      const int oy = oy0 + wr * MR + m, ox = ox0 + 16 * pb + cl;
+      if (oy < a.Hout && ox < a.Wout) {
+        const int pp = (oy * a.osy + a.ooy) * a.WoutF + ox * a.osx + a.oox;
+        *(u32x4*)(ybase + pp * a.y_ps) = u32x4{lo.x, lo.y, hi.x, hi.y};
+      }
+    }
+}
+
 // EK = epilogue kind, fixed at compile time for the hot 3x3 stride-1 16-bit launches: -1 = every operand decided at run time (any
 // launch); >= 0 = vectorised epilogue with exactly the operands of the bit set (1: residual r1, 2: residual r2, 4: LeakyReLU' mask), no
 // y2, no fp32 / partial-channel output.  A fixed kind carries no loads, address arithmetic, prefetch registers or branches for tensors
 // the launch does not have: the four growth convs of a dense block (kind 0) and their data-gradient twins (kind 4) are 80 % of a
 // generator step's launches.
-template <typename T, int KS, int STRIDE, int MR, int WR, int WN, bool M16 = false, int TS = 1, int EK = -1, bool NT = false>
+template <typename T, int KS, int STRIDE, int MR, int WR, int WN, int TS = 1, int EK = -1, bool NT = false>
 __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
-  static_assert(!M16 || sizeof(T) == 2, "16x16x32 is a 16-bit form");
-  static_assert(TS == 1 || M16, "the tap split is built for the 16x16x32 loop");
+  // the one fact the MFMA form, the staging (register prefetch through buffer descriptors vs synchronous) and the LDS layout follow:
+  // 16-bit elements run on v_mfma_f32_16x16x32, f32 on v_mfma_f32_32x32x2
+  constexpr bool k16 = sizeof(T) == 2;
+  static_assert(TS == 1 || k16, "the tap split is built for the 16x16x32 loop");
   using C = ConvCfg<T, KS, STRIDE, MR, WR, WN, TS>;
   using Frag = typename FragAB<T>::type;
   constexpr int NTHR = C::NTHR;
@@ -147,7 +335,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
   // Virtual block -> tile: XCD-aware bijective remap (blocks v and v+8 share an XCD and its L2; each XCD gets a contiguous range of
   // tiles), block-uniform by construction; the readfirstlane tells the compiler so (otherwise every address product downstream
   // stays in quarter-rate vector multiplies).
-  constexpr bool kCls = (KS == 2 || KS == 1) && STRIDE == 1 && sizeof(T) == 2;
+  constexpr bool kCls = (KS == 2 || KS == 1) && STRIDE == 1 && k16;
   int cls = 0;                                                            // output-parity class of this workgroup (kCls launches)
   auto decode = [&](int vb, int& n_, int& oy_, int& ox_, int& nb_) {
     const int bid = xcd_remap(vb, a.nblocks);
@@ -179,31 +367,19 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
   // scalar registers) + 32-bit offsets inside the image (host-checked)
   const T* __restrict__ xg = nullptr;
 
-  // 16x16x32 form, stride 1: the slot swizzle is keyed on the patch COLUMN, 2*((px>>2)&1).  What keeps a 16-lane read group
-  // conflict free is that the four lanes whose pixels are 4 apart (same 64-byte position of the 256-byte bank row) alternate
-  // their slot bit, and 4 columns apart they do whatever the row start is.  The fragment address is then lane term (3 kernel
-  // columns) + wave-uniform row offset + immediate, instead of one precomputed VGPR per (row, column, pixel half) -- those 24
-  // registers pushed the 64-channel kernel over its 128 and spilled a prefetch pointer (scratch reload + vmcnt(0) inside the loop).
-  constexpr bool kColSwz = M16 && STRIDE == 1;
-  constexpr bool kDeint = M16 && STRIDE == 2;
-  constexpr int kHalf = (C::PC + 1) / 2;                  // even columns of a patch row
-  // storage pixel (within a patch row) of column 2*l + kx + 32*ph, before the lane term l: the A-fragment reads of the stride-2 forms
-  auto deint_col = [](int kx, int ph) { return (kx & 1) * kHalf + (kx >> 1) + 16 * ph; };
-  constexpr int kM16Pipe = WN == 2 ? SRGANFD_M16_PIPE : SRGANFD_M16_PIPE - 1;     // fragment read-ahead (what fits 128 VGPRs) of the 3x3 stride-1 16x16x32 loop (0 = the compiler's own schedule)
+  constexpr bool kColSwz = C::kColSwz, kDeint = C::kDeint;      // 16-bit patch layouts of stride 1 / stride 2 (see ConvCfg)
   int ldsxo[kColSwz ? C::XI : 1];
   // per-thread source offsets (elements) of the X staging items; -1 = zero padding
   int xoff[C::XI];
   // patch position of staging item i (tile-independent).  stride 2 (16x16x32 form): a patch row is stored even columns first, then
-  // the odd ones -- the 16 lanes of a fragment read want columns 2*l + kx, which interleaved sit 128 bytes apart (four 16-byte slots
-  // of the 256-byte bank row for 16 lanes: 4-way conflicts on every A read); de-interleaved they are 16 consecutive storage pixels,
-  // the stride-1 pattern the slot swizzle spreads
+  // the odd ones (ConvCfg::kDeint)
   auto item_pos = [&](int tid_, int i, int& py, int& px, int& c16) {
     const int item = tid_ + i * NTHR;
     const int pix = item / C::CPP;
     c16 = item % C::CPP;
     py = pix / C::PC;
     const int pq = pix % C::PC;
-    px = kDeint ? (pq < kHalf ? 2 * pq : 2 * (pq - kHalf) + 1) : pq;
+    px = kDeint ? (pq < C::kHalf ? 2 * pq : 2 * (pq - C::kHalf) + 1) : pq;
   };
   if constexpr (kColSwz) {
 #pragma unroll
@@ -231,22 +407,19 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
   int ldsx0;
   {
     const int pix = tid / C::CPP, c16 = tid % C::CPP;
-    if constexpr (M16) ldsx0 = lds_x16_m16_off(pix, c16);
-    else if constexpr (sizeof(T) == 2) ldsx0 = lds_x_bf16_off(pix, c16);
+    if constexpr (k16) ldsx0 = lds_x16_m16_off(pix, c16);
     else ldsx0 = pix * 128;   // f32: per-dword XOR below
   }
   const u32x4* __restrict__ wgp = nullptr;
 
-  // bf16: register prefetch of the next chunk (issue-early / write-late).  f32 (parity mode) stages
+  // 16-bit: register prefetch of the next chunk (issue-early / write-late).  f32 (parity mode) stages
   // synchronously: its 2x larger tiles would not fit the register budget next to the accumulators.
-  constexpr bool kPrefetch = sizeof(T) == 2;
-  constexpr int XR = kPrefetch ? C::XI : 1, WRG = kPrefetch ? C::WI : 1;
+  constexpr int XR = k16 ? C::XI : 1, WRG = k16 ? C::WI : 1;
   u32x4 xr[XR];
   u32x4 wrg[WRG];
   // 16-bit staging loads go through buffer descriptors: padding pixels / idle lanes carry an offset beyond the descriptor's range and
   // the hardware range check returns zeros -- no zero-initialised destination registers (32 v_mov per chunk), no exec-mask branches
   // around the loads.  Descriptors are built from wave-uniform values (image base, weight base of this output-channel block).
-  constexpr bool kBuf = sizeof(T) == 2;
   constexpr int kOob = 0x7fffffff;
   // (the base pointers are block-uniform, but 64-bit products are computed in VGPRs: without the explicit readfirstlane the backend
   // wraps every buffer load in a waterfall loop over "divergent" descriptors)
@@ -258,7 +431,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
   auto xrsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.x), (short)0, 0, 0x00020000);      // re-pointed per tile by setup_loads
   auto wrsrc = xrsrc;
   auto load_x = [&](int i, int chunk) -> u32x4 {
-    if constexpr (kBuf) {
+    if constexpr (k16) {
       typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned v4u;
       const v4u r = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, xoff[i] >= 0 ? xoff[i] * (int)sizeof(T) : kOob, chunk * a.x_cs * (int)sizeof(T), 0);
       return __builtin_bit_cast(u32x4, r);
@@ -272,7 +445,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
     const int item = tid + i * NTHR;
     // LDS slab order [n-tile][tap][kstep][lane]; global order [n-tile][chunk][tap][kstep][lane]; piece th = taps [th, th+1) * KT/TS
     const int nn = item / (C::WS_BYTES / 16), rem = item % (C::WS_BYTES / 16);
-    if constexpr (kBuf) {
+    if constexpr (k16) {
       typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned v4u;
       const bool ok = item < C::NW16;
       const v4u r = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, ok ? (nn * a.nChunks * (C::WN_BYTES / 16) + rem) * 16 : kOob,
@@ -289,7 +462,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
     if (item < C::NX) {
       if constexpr (kColSwz) {
         *(u32x4*)(ldsX + ldsxo[i]) = v;
-      } else if constexpr (sizeof(T) == 2) {
+      } else if constexpr (k16) {
         *(u32x4*)(ldsX + ldsx0 + i * (C::PIX_PER_I * C::PIXB)) = v;
       } else {
         const int pix = item / C::CPP, c16 = item % C::CPP;
@@ -305,7 +478,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
     if (item < C::NW16) *(u32x4*)(ldsW + item * 16) = v;
   };
   auto prefetch = [&](int chunk) {
-    if constexpr (kPrefetch) {
+    if constexpr (k16) {
 #pragma unroll
       for (int i = 0; i < C::XI; ++i) xr[i] = load_x(i, chunk);
 #pragma unroll
@@ -313,7 +486,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
     }
   };
   auto commit = [&](int chunk) {
-    if constexpr (kPrefetch) {
+    if constexpr (k16) {
 #pragma unroll
       for (int i = 0; i < C::XI; ++i) store_x(i, xr[i]);
 #pragma unroll
@@ -334,23 +507,23 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
     xg = (const T*)a.x + (size_t)n_ * a.Hin * a.Win * a.xC;
     const int wb_ = kCls && a.cls_sh >= 0 ? nb_ + (cls << a.cls_sh) : nb_;      // the classes' packs follow each other (host-checked)
     wgp = (const u32x4*)a.w + (size_t)wb_ * WN * a.nChunks * (C::WN_BYTES / 16);
-    if constexpr (kBuf) {
+    if constexpr (k16) {
       xrsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(xg), (short)0, (int)((unsigned)a.Hin * (unsigned)a.Win * (unsigned)a.xC * (unsigned)sizeof(T)), 0x00020000);
       wrsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(wgp), (short)0, (int)((unsigned)WN * (unsigned)a.nChunks * (unsigned)C::WN_BYTES), 0x00020000);
     }
     // the two bias values this lane's epilogue adds, requested here so that they are OLDER than the tile's staging loads: the copy at
     // the top of the tile then waits for them alone.  (Loaded at the top of the tile they were younger than the next tile's first
     // loads, and the epilogue's use of them drained those loads -- s_waitcnt vmcnt(0) -- before the tile could finish.)
-    if constexpr (sizeof(T) == 2) {
+    if constexpr (k16) {
       const int cow_ = (nb_ * WN + wn) * 32;
       bvn0 = bvn1 = 0.f;
-      if (a.bias && (EK >= 0 || a.fast_epi)) { bvn0 = a.bias[cow_ + AccSet<M16, MR>::chan(0, lane)]; bvn1 = a.bias[cow_ + AccSet<M16, MR>::chan(4, lane)]; }
+      if (a.bias && (EK >= 0 || a.fast_epi)) { bvn0 = a.bias[cow_ + AccSet<k16, MR>::chan(0, lane)]; bvn1 = a.bias[cow_ + AccSet<k16, MR>::chan(4, lane)]; }
     }
     tile_offsets(oy_, ox_);
   };
   // the first stage's loads of the tile the load side points at
   auto first_loads = [&]() {
-    if constexpr (kPrefetch) {
+    if constexpr (k16) {
 #pragma unroll
       for (int i = 0; i < C::XI; ++i) xr[i] = load_x(i, 0);
 #pragma unroll
@@ -359,9 +532,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
   };
   // tiles after the first: requested during the previous tile's last MFMA phase (the kinds whose epilogue leaves room for the 32
   // staging registers), else after its epilogue
-  constexpr bool kCross = kPrefetch && EK >= 0 && (EK & SRGANFD_CROSS_MASK) == 0;
+  constexpr bool kCross = kConvCross<T, EK>;
 
-  AccSet<M16, MR> A_;
+  AccSet<k16, MR> A_;
   auto& acc = A_.a;
 
   // this lane's A-fragment base: patch pixel (wr*MR*S, r*S), B-fragment base: n-tile wn
@@ -394,7 +567,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
   if constexpr (TS > 1) {
     // Tap-split main loop (16x16x32 form): stage (chunk, th) holds the chunk's patch and kernel rows [th*KYS, (th+1)*KYS) of its
     // weights; the patch is committed with th == 0 and stays for the chunk's TS weight pieces.  Same issue-early / write-late
-    // staging as below, one barrier pair per stage.
+    // staging as below, one barrier pair per stage.  (Its MFMA phase stays inline: as a function per piece, with the lane terms
+    // l15 / sl / pixb computed inside, the 64-channel 4x4 kernel went from 114 to 116 VGPRs.)
     constexpr int KYS = KS / TS, NR_ = (MR - 1) * STRIDE + KYS;
     const int l15 = lane & 15, sl = lane >> 4;
     const int pixb = (wr * MR * STRIDE) * C::PC + l15 * STRIDE;
@@ -429,7 +603,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
           for (int rr = 0; rr < NR_; ++rr)
 #pragma unroll
             for (int ph = 0; ph < 2; ++ph)
-              if constexpr (kDeint) av[rr][ph] = *(const Frag*)(ldsX + lds_x16_m16_off((wr * MR * STRIDE + th * KYS + rr) * C::PC + l15 + deint_col(kx, ph), sl));
+              if constexpr (kDeint) av[rr][ph] = *(const Frag*)(ldsX + lds_x16_m16_off((wr * MR * STRIDE + th * KYS + rr) * C::PC + l15 + C::deint_col(kx, ph), sl));
               else av[rr][ph] = *(const Frag*)(ldsX + lds_x16_m16_off(pixb + (th * KYS + rr) * C::PC + kx + 16 * ph * STRIDE, sl));
 #pragma unroll
           for (int kyl = 0; kyl < KYS; ++kyl) {
@@ -447,6 +621,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
       });
     }
   } else {
+  // main loop: stage the chunk between two barriers, request the next chunk (or, kCross, the next tile's first one), MFMA phase
   for (int chunk = 0; chunk < a.nChunks; ++chunk) {
     __syncthreads();
     commit(chunk);
@@ -456,185 +631,20 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
       setup_loads(vt_next);
       first_loads();
     }
-
-    auto col_body = [&](int kx, int s) {
-      if constexpr (!M16) {
-      Frag av[C::NROWS];
-#pragma unroll
-      for (int rr = 0; rr < C::NROWS; ++rr) {
-        const int pix = pix00 + rr * C::PC + kx;
-        if constexpr (sizeof(T) == 2) av[rr] = *(const Frag*)(ldsX + lds_x_bf16_off(pix, 2 * s + h));
-        else av[rr] = *(const Frag*)(ldsX + lds_x_f32_off(pix, 2 * s + h));
-      }
-#pragma unroll
-      for (int ky = 0; ky < KS; ++ky) {
-        const Frag bq = *(const Frag*)(ldsWn + ((ky * KS + kx) * C::KSTEPS + s) * 64 * C::FRAGB);
-#pragma unroll
-        for (int m = 0; m < MR; ++m) acc[m] = mfma32<T>(av[m * STRIDE + ky], bq, acc[m]);
-      }
-      }
-    };
-    if constexpr (M16) {
-      // one K step = the whole 32-channel chunk; per kernel column: (NROWS x 2 pixel halves) A fragments, (KS x 2 channel halves) B
-      const int l15 = lane & 15, sl = lane >> 4;
-      const int pixb = (wr * MR * STRIDE) * C::PC + l15 * STRIDE;
-      const char* ldsXw = ldsX + (wr * MR * STRIDE) * C::PC * 64;        // this wave's first patch row (wave-uniform)
-      __builtin_amdgcn_s_setprio(1);
-      if constexpr (kColSwz && KS == 3 && MR == 2 && kM16Pipe > 0) {
-        // software-pipelined fragment reads (see m16_need): every ds_read_b128 is issued kM16Pipe fragments ahead of the MFMA that
-        // needs it, across the three kernel columns of the chunk; same accumulation order per accumulator as the plain loop below
-        constexpr int NL = 14 * KS, NM = 24 * KS;
-        Frag F[NL];
-        static_for<NM>([&](auto ic) {
-          constexpr int i = decltype(ic)::v;
-          constexpr int c = i / 24, j = i % 24, gq = j / 4, t = j % 4;
-          constexpr int hi = m16_pipe_hi(i, kM16Pipe, NL), lo = i == 0 ? 0 : m16_pipe_hi(i - 1, kM16Pipe, NL) + 1;
-          static_for<hi - lo + 1>([&](auto jc) {
-            constexpr int n = lo + decltype(jc)::v;
-            constexpr int kx = n / 14, l = n % 14;
-            constexpr bool isB = l == 0 || l == 5 || l == 6 || l == 9 || l == 10 || l == 13;
-            if constexpr (isB) {
-              constexpr int ky = l < 6 ? 0 : (l < 10 ? 1 : 2), nh = (l == 5 || l == 9 || l == 13) ? 1 : 0;
-              F[n] = *(const Frag*)(ldsWn + ((ky * KS + kx) * 2 + nh) * 64 * C::FRAGB);
-            } else {
-              constexpr int q = l < 5 ? l - 1 : (l < 9 ? l - 3 : l - 5), rr = q >> 1, ph = q & 1;
-              F[n] = *(const Frag*)(ldsXw + colt[kx] + (rr * C::PC + 16 * ph) * 64);
-            }
-          });
-          constexpr int ky = gq >> 1, nh = gq & 1, m = t >> 1, ph = t & 1;
-          acc[m][ph][nh] = mfma16<T>(F[14 * c + m16_aidx(m + ky, ph)], F[14 * c + m16_bidx(ky, nh)], acc[m][ph][nh]);
-          __builtin_amdgcn_sched_barrier(0);
-        });
-      } else
-#pragma unroll
-      for (int kx = 0; kx < KS; ++kx) {
-        Frag av[C::NROWS][2];
-        const int colterm = (l15 + kx) * 64 + ((sl ^ ((((l15 + kx) >> 2) & 1) << 1)) << 4);     // stride 1: lane term of column kx
-#pragma unroll
-        for (int rr = 0; rr < C::NROWS; ++rr)
-#pragma unroll
-          for (int ph = 0; ph < 2; ++ph) {
-            if constexpr (kColSwz) av[rr][ph] = *(const Frag*)(ldsXw + colterm + (rr * C::PC + 16 * ph) * 64);
-            else if constexpr (kDeint) av[rr][ph] = *(const Frag*)(ldsX + lds_x16_m16_off((wr * MR * STRIDE + rr) * C::PC + l15 + deint_col(kx, ph), sl));
-            else av[rr][ph] = *(const Frag*)(ldsX + lds_x16_m16_off(pixb + rr * C::PC + kx + 16 * ph * STRIDE, sl));
-          }
-#pragma unroll
-        for (int ky = 0; ky < KS; ++ky) {
-#pragma unroll
-          for (int nh = 0; nh < 2; ++nh) {
-            const Frag bq = *(const Frag*)(ldsWn + ((ky * KS + kx) * 2 + nh) * 64 * C::FRAGB);
-#pragma unroll
-            for (int m = 0; m < MR; ++m)
-#pragma unroll
-              for (int ph = 0; ph < 2; ++ph) acc[m][ph][nh] = mfma16<T>(av[m * STRIDE + ky][ph], bq, acc[m][ph][nh]);
-          }
-        }
-      }
-      __builtin_amdgcn_s_setprio(0);
-    } else if constexpr (sizeof(T) == 2 && KS == 3 && STRIDE == 1 && MR == 2) {
-      // Software-pipelined fragment reads: the chunk's 42 ds_read_b128 and 36 MFMAs in one fixed issue order, every read kD
-      // fragments ahead of the MFMA that consumes it (the compiler's own order is read -> s_waitcnt lgkmcnt(0) -> MFMA on two
-      // fragment registers: each MFMA eats a full LDS round trip).  Same accumulation order as the plain loop below, so the
-      // results are bitwise equal; measured -4 % on the 64-channel conv, -1 % on the 32-channel one.
-      // col-body c = kx * KSTEPS + s: loads A0 B0 A1 B1 A2 B2 A3 (rows rr = j/2, taps ky = j/2), MFMAs (A0,B0)->acc0 (A1,B0)->acc1
-      // (A1,B1)->acc0 (A2,B1)->acc1 (A2,B2)->acc0 (A3,B2)->acc1.
-      constexpr int kD = WN == 2 ? 3 : 2;        // read-ahead that fits 128 VGPRs: 64-channel tiles 3 fragments, 32-channel tiles 2
-      constexpr int NL = 7 * KS * C::KSTEPS, NM = 6 * KS * C::KSTEPS;
-      Frag F[NL];
-      __builtin_amdgcn_s_setprio(1);
-      static_for<NM>([&](auto ic) {
-        constexpr int i = decltype(ic)::v;
-        constexpr int c = i / 6, j = i % 6;
-        constexpr int hi = pipe_hi(i, kD, NL), lo = i == 0 ? 0 : pipe_hi(i - 1, kD, NL) + 1;
-        static_for<hi - lo + 1>([&](auto jc) {
-          constexpr int n = lo + decltype(jc)::v;
-          constexpr int cc = n / 7, jj = n % 7, kx = cc / C::KSTEPS, ss = cc % C::KSTEPS;
-          if constexpr ((jj & 1) == 0) F[n] = *(const Frag*)(ldsX + lds_x_bf16_off(pix00 + (jj / 2) * C::PC + kx, 2 * ss + h));
-          else F[n] = *(const Frag*)(ldsWn + (((jj / 2) * KS + kx) * C::KSTEPS + ss) * 64 * C::FRAGB);
-        });
-        acc[j & 1] = mfma32<T>(F[7 * c + 2 * ((j + 1) / 2)], F[7 * c + 2 * (j / 2) + 1], acc[j & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-      });
-      __builtin_amdgcn_s_setprio(0);
-    } else if constexpr (sizeof(T) == 2) {
-      __builtin_amdgcn_s_setprio(1);   // waves in their MFMA phase win issue arbitration over waves that are staging (+1-3 %)
-#pragma unroll
-      for (int kx = 0; kx < KS; ++kx) {
-#pragma unroll
-        for (int s2 = 0; s2 < C::KSTEPS; ++s2) col_body(kx, s2);
-      }
-      __builtin_amdgcn_s_setprio(0);
-    } else {
-#pragma unroll 1
-      for (int kx = 0; kx < KS; ++kx) {
-#pragma unroll 2
-        for (int s2 = 0; s2 < C::KSTEPS; ++s2) col_body(kx, s2);
-      }
-    }
+    if constexpr (k16) mfma_chunk_16<C>(ldsX, ldsWn, wr, lane, colt, A_);
+    else mfma_chunk_f32<C>(ldsX, ldsWn, pix00, h, A_);
   }
 
   }
 
-  // ---- epilogue (see srganfd.h for the formula) ----
+  // ---- epilogue (see srganfd.h for the formula): kind-0 row tiles, else the vector epilogue through the fp32 LDS tile, else scalar ----
+  // (The immediately-invoked lambda is load-bearing for the register allocation: the same statements as a plain block with the same
+  // control flow move the VGPR / SGPR counts of 44 of the 52 kernels (the 3x3 kinds 1 / 3 / 4 from 120 to 122 VGPRs), and the vector
+  // or scalar epilogue as a function of its own moves those of the run-time-kind kernels -- the class launches by up to 4 VGPRs.
+  // Those two stay inline here until that is understood; profiles/conv_igemm_refactor_isa.txt.)
   [&]() __attribute__((always_inline)) {
-  if constexpr (EK == 0 && M16 && WN == 1 && sizeof(T) == 2) {
-    // Kind 0, 32-channel tiles (the growth convs of a dense block): bias + activation in registers, rounded to T there (the value
-    // the fp32 tile path would round after its LDS round trip: same bits), and a 16-bit CHANNEL-major LDS tile per image row --
-    // a lane's four accumulator registers of one (row, pixel half, channel half) are four consecutive pixels of one channel, so
-    // they go out as one ds_write_b64; ds_read_b64_tr_b16 hands them back pixel-major (lane i of a 16-lane group: pixel i, four
-    // channels), two reads = the 16 bytes of (pixel, 8 channels) one lane stores.  Every wave reads only the rows it wrote: one
-    // barrier (staging buffers free) instead of two, 8 LDS writes + 8 reads per lane instead of 16 + 8 wider ones, no fp32 tile
-    // unpacking / conversion after the reads.  Row tile = 32 channels x 64 bytes, dword index XOR (channel & 14): conflict-free
-    // for the ds_write_b64 (16 channels of one 8-byte column) and for the transposed reads (4 channels x 16 pixels per group).
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;
-    int lane_o = lane;
-    asm volatile("" : "+v"(lane_o));      // keeps this block's lane-only address terms out of the registers carried around the tile loop
-    const int cl = lane_o & 15, g4 = lane_o >> 4;
-    const float neg = a.act == SRGANFD_ACT_LRELU ? a.slope : (a.act == SRGANFD_ACT_RELU ? 0.f : 1.f);
-    const float ps_pos = a.post_scale, ps_neg = neg * a.post_scale;
-    char* rowt = smem + (wr * MR) * 2048;                                   // this wave's first row tile
-    const int w0 = cl * 64 + (((2 * g4) ^ (cl & 14)) << 2);                 // write: channel cl (+16 nh), pixels 4 g4 .. 4 g4 + 3 (+16 ph)
-    const int rq = 8 * g4 + ((lane_o >> 2) & 3), rp = lane_o & 3;               // read: this lane addresses channel rq (+4), pixels 4 rp .. (+16 pb)
-    const int r0 = rq * 64 + (((2 * rp) ^ (rq & 14)) << 2), r1 = (rq + 4) * 64 + (((2 * rp) ^ ((rq + 4) & 14)) << 2);
-    __syncthreads();   // all waves are done with the staging buffers
-#pragma unroll
-    for (int m = 0; m < MR; ++m)
-#pragma unroll
-      for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-        for (int nh = 0; nh < 2; ++nh) {
-          float v4[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float v = alpha * acc[m][ph][nh][i] + (nh ? bvh1 : bvh0);
-            v4[i] = v * (v > 0.f ? ps_pos : ps_neg);
-          }
-          u32x2_t pk;
-          if constexpr (Elem<T>::kDtype == SRGANFD_F16) {
-            typedef __attribute__((ext_vector_type(4))) _Float16 h4;
-            const h4 hv = {(_Float16)v4[0], (_Float16)v4[1], (_Float16)v4[2], (_Float16)v4[3]};
-            pk = __builtin_bit_cast(u32x2_t, hv);
-          } else {
-            pk = u32x2_t{(unsigned)f2bf(v4[0]) | ((unsigned)f2bf(v4[1]) << 16), (unsigned)f2bf(v4[2]) | ((unsigned)f2bf(v4[3]) << 16)};
-          }
-          *(u32x2_t*)(rowt + m * 2048 + nh * 1024 + (w0 ^ (ph << 5))) = pk;
-        }
-    const size_t img = (size_t)n * a.HoutF * a.WoutF;
-    const int cch = nb * C::NB + 8 * g4;                                    // this lane's 8 output channels
-    const int cc = a.y_c0 + cch;
-    T* ybase = (T*)a.y + img * a.yC + ((cc >> 5) * a.y_gs + (cc & 31));
-#pragma unroll
-    for (int m = 0; m < MR; ++m)
-#pragma unroll
-      for (int pb = 0; pb < 2; ++pb) {
-        const u32x2_t lo = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(rowt + m * 2048 + (r0 ^ (pb << 5)))));
-        const u32x2_t hi = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(rowt + m * 2048 + (r1 ^ (pb << 5)))));
-        const int oy = oy0 + wr * MR + m, ox = ox0 + 16 * pb + cl;
-        if (oy < a.Hout && ox < a.Wout) {
-          const int pp = (oy * a.osy + ooy()) * a.WoutF + ox * a.osx + oox();
-          *(u32x4*)(ybase + pp * a.y_ps) = u32x4{lo.x, lo.y, hi.x, hi.y};
-        }
-      }
+  if constexpr (EK == 0 && k16 && WN == 1) {
+    epilogue_rows16<C>(a, smem, lane, wr, A_, alpha, bvh0, bvh1, n, oy0, ox0, nb);
     return;
   }
   constexpr bool kR1 = EK < 0 || (EK & 1), kR2 = EK < 0 || (EK & 2), kMk = EK < 0 || (EK & 4);   // operands this instantiation can have
@@ -653,7 +663,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
     // (not in the kinds that run persistent: there the staging registers hold the next tile's first chunk through the epilogue)
     // (kinds that run persistent request them LATE, after the accumulators have gone to the LDS tile: the staging registers hold the
     // next tile's first chunk through the epilogue, the accumulators' 32 registers are what is free)
-    constexpr bool kEpiPre = sizeof(T) == 2 && EIq <= 4;
+    constexpr bool kEpiPre = k16 && EIq <= 4;
     constexpr bool kEpiLate = kEpiPre && kCross;
     u32x4 pre_r1[kEpiPre && kR1 ? EIq : 1], pre_r2[kEpiPre && kR2 ? EIq : 1], pre_m[kEpiPre && kMk ? EIq : 1];
     auto request_operands = [&]() __attribute__((always_inline)) {
@@ -686,7 +696,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
     {
       // a lane's 16 values per row cover one channel (32x32 form) or two (16x16 form: elements 0-3 / 8-11 vs 4-7 / 12-15)
       float bv0 = bvh0, bv1 = bvh1;
-      if constexpr (sizeof(T) != 2) { bv0 = a.bias ? a.bias[cow + A_.chan(0, lane)] : 0.f; bv1 = a.bias ? a.bias[cow + A_.chan(4, lane)] : 0.f; }
+      if constexpr (!k16) { bv0 = a.bias ? a.bias[cow + A_.chan(0, lane)] : 0.f; bv1 = a.bias ? a.bias[cow + A_.chan(4, lane)] : 0.f; }
       // the activation as ONE select per element: factor of the negative side = slope (LeakyReLU), 0 (ReLU), 1 (none).  Written
       // as `if (act == ...)` inside the loop the compiler emitted two scalar compares and branches per element (630 branches in this
       // epilogue's ISA), and every wave walked them.
@@ -729,7 +739,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
         auto load16 = [&](const void* base, int Cs, int c0, int ps, int gs, float* out) {
           const int cc = c0 + cch;
           const T* src = (const T*)base + img * Cs + (p * ps + (cc >> 5) * gs + (cc & 31));
-          if constexpr (sizeof(T) == 2) {
+          if constexpr (k16) {
             unpack8<T>(*(const u32x4*)src, out);
           } else {
             const f32x4 rf = *(const f32x4*)src;
@@ -739,7 +749,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
         auto store16 = [&](void* base, int Cs, int c0, int ps, int gs, const float* vv) {
           const int cc = c0 + cch;
           T* dstp = (T*)base + img * Cs + (p * ps + (cc >> 5) * gs + (cc & 31));
-          if constexpr (sizeof(T) == 2) {
+          if constexpr (k16) {
             // NT: outputs one pass cannot keep in the 256 MiB Infinity Cache (the 256^2 / 512^2 layers at batch 32) leave with non-temporal
             // stores; a template parameter, because a run-time branch around the builtin is folded into a plain store
             if constexpr (NT) __builtin_nontemporal_store(pack8<T>(vv), (u32x4*)dstp);
@@ -812,10 +822,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvK& a, char* smem) {
   }   // tiles of this workgroup
 }
 
-template <typename T, int KS, int STRIDE, int MR, int WR, int WN, bool M16 = false, int TS = 1, int EK = -1, bool NT = false>
+template <typename T, int KS, int STRIDE, int MR, int WR, int WN, int TS = 1, int EK = -1, bool NT = false>
 __global__ __launch_bounds__(64 * WR * WN, (ConvCfg<T, KS, STRIDE, MR, WR, WN, TS>::MIN_WAVES_PER_SIMD)) void conv_igemm_kernel(const ConvK a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  conv_igemm_body<T, KS, STRIDE, MR, WR, WN, M16, TS, EK, NT>(a, smem);
+  conv_igemm_body<T, KS, STRIDE, MR, WR, WN, TS, EK, NT>(a, smem);
 }
 
 // compute units of the current device (cached per device id); 256 when nothing can be asked (dry runs on the CPU)
@@ -832,14 +842,14 @@ int conv_device_cus() {
   return c;
 }
 
-template <typename T, int KS, int STRIDE, int MR, int WR, int WN, bool M16 = false, int TS = 1, int EK = -1, bool NT = false>
+template <typename T, int KS, int STRIDE, int MR, int WR, int WN, int TS = 1, int EK = -1, bool NT = false>
 static int launch_conv(const ConvK& k, int cout, hipStream_t stream) {
   using C = ConvCfg<T, KS, STRIDE, MR, WR, WN, TS>;
-  auto kern = conv_igemm_kernel<T, KS, STRIDE, MR, WR, WN, M16, TS, EK, NT>;
+  auto kern = conv_igemm_kernel<T, KS, STRIDE, MR, WR, WN, TS, EK, NT>;
   if (g_describe) {
     char ek[8] = "";
     if (EK >= 0) snprintf(ek, sizeof(ek), ",E%d", EK);
-    snprintf(g_describe, g_describe_len, "conv_igemm_kernel<%s,KS=%d,S=%d,MR=%d,WR=%d,WN=%d%s%s%s>%s", dtype_name<T>(), KS, STRIDE, MR, WR, WN, M16 ? ",M16" : "", TS > 1 ? ",TS=2" : "", ek,
+    snprintf(g_describe, g_describe_len, "conv_igemm_kernel<%s,KS=%d,S=%d,MR=%d,WR=%d,WN=%d%s%s%s>%s", dtype_name<T>(), KS, STRIDE, MR, WR, WN, sizeof(T) == 2 ? ",M16" : "", TS > 1 ? ",TS=2" : "", ek,
              k.cls_sh >= 0 ? "[4 classes]" : "");
     return SRGANFD_OK;
   }
@@ -872,7 +882,7 @@ static int launch_conv(const ConvK& k, int cout, hipStream_t stream) {
   // kinds that prefetch across tiles run as persistent workgroups: as many as the chip holds at once (a multiple of 8, so that the
   // virtual blocks v, v + grid, ... of one workgroup keep their XCD class in xcd_remap)
   long long grid = nblk;
-  if (EK >= 0 && (EK & SRGANFD_CROSS_MASK) == 0 && sizeof(T) == 2) {
+  if (kConvCross<T, EK>) {
     const long long slots = (long long)conv_device_cus() * C::WG_PER_CU;
     if (slots >= 8 && nblk > slots) grid = slots / 8 * 8;
   }
@@ -882,67 +892,52 @@ static int launch_conv(const ConvK& k, int cout, hipStream_t stream) {
 }
 
 
-
-// MFMA form of the 16-bit kernels: v_mfma_f32_16x16x32 for every kernel shape (srganfd_get_mfma16() == 3).  Same-box A/B of the training
-// steps against the 32x32x16 form (profiles/r02_mfma16_ab.txt): generator-only 78.3 -> 69.4 ms, GAN 179.6 -> 173.1 ms; the chip runs these
-// steps power-limited (1.2 kW, clock at 2.06 of 2.4 GHz) and holds a higher clock on this form.  The 32x32x16 instantiations of the
-// 16-bit kernels and the level switch live in the experiment sources (tools/experiments/r3_src).
-int g_mfma16 = 3;
-extern "C" int srganfd_get_mfma16(void) { return g_mfma16; }
+// MFMA form of the 16-bit kernels: v_mfma_f32_16x16x32 for every kernel shape (level 3 of the experiment build's switch).  Same-box A/B of
+// the training steps against the 32x32x16 form (profiles/r02_mfma16_ab.txt): generator-only 78.3 -> 69.4 ms, GAN 179.6 -> 173.1 ms; the chip
+// runs these steps power-limited (1.2 kW, clock at 2.06 of 2.4 GHz) and holds a higher clock on this form.  The 32x32x16 instantiations of
+// the 16-bit kernels and the level switch live in the experiment sources (tools/experiments/r3_src).
+extern "C" int srganfd_get_mfma16(void) { return 3; }
+// B-fragment order the kernels read a packed operand in (srganfd_pack_job.layout): the form follows the element type
+extern "C" int srganfd_pack_layout(int32_t dtype, int32_t ksize, int32_t n) { (void)ksize; (void)n; return dtype != SRGANFD_F32; }
 // non-temporal stores for outputs > 192 MB (same-box A/B switch: SRGANFD_CONV_NT=0 in the environment of the process that loads the library)
 static const bool g_conv_nt = [] { const char* e = getenv("SRGANFD_CONV_NT"); return !(e && e[0] == '0'); }();
-
-// does the kernel that consumes a packed operand of this kernel size / output width read 16x16x32 B fragments?  (pack.hip asks too)
-bool conv_uses_m16(int dtype, int ksize, int cout) {
-  (void)ksize; (void)cout;
-  return dtype != SRGANFD_F32;
-}
-extern "C" int srganfd_pack_layout(int32_t dtype, int32_t ksize, int32_t n) { return conv_uses_m16(dtype, ksize, n) ? 1 : 0; }
 
 template <typename T>
 static int dispatch_conv(const srganfd_conv_args* a, const ConvK& k, hipStream_t s) {
   const bool wide = (a->cout % 64) == 0;
-  constexpr bool bf = sizeof(T) == 2;
-  if constexpr (bf) {
-    if (conv_uses_m16(a->dtype, a->ksize, a->cout)) {
-      if (a->ksize == 3 && a->stride == 1) {
-        // epilogue kind fixed at compile time where the launch has the vectorised epilogue and no y2 (see the kernel's EK)
-        const int ek = (k.fast_epi && !k.y2) ? ((k.r1 ? 1 : 0) | (k.r2 ? 2 : 0) | (k.mask ? 4 : 0)) : -1;
-        if (wide) {
-          // outputs beyond the Infinity Cache: non-temporal stores (the discriminator / VGG / tail layers at 256^2 and 512^2; never the trunk)
-          const size_t opix_ = (size_t)a->n * (size_t)k.HoutF * (size_t)k.WoutF;
-          if (g_conv_nt && opix_ * (size_t)a->cout_store * 2 >= ((size_t)192 << 20)) {
-            if (ek == 0) return launch_conv<T, 3, 1, 2, 4, 2, true, 1, 0, true>(k, a->cout, s);
-            if (ek == 4) return launch_conv<T, 3, 1, 2, 4, 2, true, 1, 4, true>(k, a->cout, s);
-            if (ek < 0) return launch_conv<T, 3, 1, 2, 4, 2, true, 1, -1, true>(k, a->cout, s);
-          }
-          if (ek == 0) return launch_conv<T, 3, 1, 2, 4, 2, true, 1, 0>(k, a->cout, s);
-          if (ek == 1) return launch_conv<T, 3, 1, 2, 4, 2, true, 1, 1>(k, a->cout, s);
-          if (ek == 3) return launch_conv<T, 3, 1, 2, 4, 2, true, 1, 3>(k, a->cout, s);
-          if (ek == 4) return launch_conv<T, 3, 1, 2, 4, 2, true, 1, 4>(k, a->cout, s);
-          return launch_conv<T, 3, 1, 2, 4, 2, true>(k, a->cout, s);
+  if constexpr (sizeof(T) == 2) {
+    // outputs beyond the Infinity Cache leave with non-temporal stores (the discriminator / VGG / tail layers at 256^2 and 512^2; never the trunk)
+    const bool nt = wide && g_conv_nt && (size_t)a->n * (size_t)k.HoutF * (size_t)k.WoutF * (size_t)a->cout_store * 2 >= ((size_t)192 << 20);
+    if (a->ksize == 3 && a->stride == 1) {
+      // epilogue kind fixed at compile time where the launch has the vectorised epilogue and no y2 (see the kernel's EK)
+      const int ek = (k.fast_epi && !k.y2) ? ((k.r1 ? 1 : 0) | (k.r2 ? 2 : 0) | (k.mask ? 4 : 0)) : -1;
+      if (wide) {
+        if (nt) {
+          if (ek == 0) return launch_conv<T, 3, 1, 2, 4, 2, 1, 0, true>(k, a->cout, s);
+          if (ek == 4) return launch_conv<T, 3, 1, 2, 4, 2, 1, 4, true>(k, a->cout, s);
+          if (ek < 0) return launch_conv<T, 3, 1, 2, 4, 2, 1, -1, true>(k, a->cout, s);
         }
-        if (ek == 0) return launch_conv<T, 3, 1, 2, 8, 1, true, 1, 0>(k, a->cout, s);
-        if (ek == 4) return launch_conv<T, 3, 1, 2, 8, 1, true, 1, 4>(k, a->cout, s);
-        return launch_conv<T, 3, 1, 2, 8, 1, true>(k, a->cout, s);
+        if (ek == 0) return launch_conv<T, 3, 1, 2, 4, 2, 1, 0>(k, a->cout, s);
+        if (ek == 1) return launch_conv<T, 3, 1, 2, 4, 2, 1, 1>(k, a->cout, s);
+        if (ek == 3) return launch_conv<T, 3, 1, 2, 4, 2, 1, 3>(k, a->cout, s);
+        if (ek == 4) return launch_conv<T, 3, 1, 2, 4, 2, 1, 4>(k, a->cout, s);
+        return launch_conv<T, 3, 1, 2, 4, 2>(k, a->cout, s);
       }
-      if (a->ksize == 3 && a->stride == 2) return wide ? launch_conv<T, 3, 2, 1, 4, 2, true>(k, a->cout, s) : launch_conv<T, 3, 2, 1, 4, 1, true>(k, a->cout, s);
-      if (a->ksize == 2 && a->stride == 1) {
-        // the nearest-x2 + 3x3 forward as four parity classes (the class launch with a bias; the data-gradient ones have none and keep
-        // plain stores) writes the upsampled layer (1.07 GB at batch 32, 512^2): the same non-temporal rule as the 3x3 kernels
-        if (wide && g_conv_nt && k.cls_sh >= 0 && a->bias && (size_t)a->n * (size_t)k.HoutF * (size_t)k.WoutF * (size_t)a->cout_store * 2 >= ((size_t)192 << 20))
-          return launch_conv<T, 2, 1, 2, 4, 2, true, 1, -1, true>(k, a->cout, s);
-        return wide ? launch_conv<T, 2, 1, 2, 4, 2, true>(k, a->cout, s) : launch_conv<T, 2, 1, 2, 8, 1, true>(k, a->cout, s);
-      }
-      // 4x4 stride 2, 64-channel tiles: weights staged in two halves of two kernel rows -> 73 KiB of LDS, two workgroups per CU
-      if (a->ksize == 4 && a->stride == 2) return wide ? launch_conv<T, 4, 2, 1, 4, 2, true, 2>(k, a->cout, s) : launch_conv<T, 4, 2, 1, 4, 1, true>(k, a->cout, s);
-      if (a->ksize == 2 && a->stride == 2) return wide ? launch_conv<T, 2, 2, 1, 4, 2, true>(k, a->cout, s) : launch_conv<T, 2, 2, 1, 4, 1, true>(k, a->cout, s);
-      if (a->ksize == 1 && a->stride == 1) return launch_conv<T, 1, 1, 2, 4, 1, true>(k, a->cout, s);
-      return set_err(SRGANFD_EINVAL, "conv2d: unsupported ksize=%d stride=%d", a->ksize, a->stride);
+      if (ek == 0) return launch_conv<T, 3, 1, 2, 8, 1, 1, 0>(k, a->cout, s);
+      if (ek == 4) return launch_conv<T, 3, 1, 2, 8, 1, 1, 4>(k, a->cout, s);
+      return launch_conv<T, 3, 1, 2, 8, 1>(k, a->cout, s);
     }
-  }
-  if constexpr (bf) {
-    return set_err(SRGANFD_EINVAL, "conv2d: the 16-bit kernels run on v_mfma_f32_16x16x32 (ksize %d stride %d has no kernel)", a->ksize, a->stride);
+    if (a->ksize == 3 && a->stride == 2) return wide ? launch_conv<T, 3, 2, 1, 4, 2>(k, a->cout, s) : launch_conv<T, 3, 2, 1, 4, 1>(k, a->cout, s);
+    if (a->ksize == 2 && a->stride == 1) {
+      // the nearest-x2 + 3x3 forward as four parity classes (the class launch with a bias; the data-gradient ones have none and keep
+      // plain stores) writes the upsampled layer (1.07 GB at batch 32, 512^2): the same non-temporal rule as the 3x3 kernels
+      if (nt && k.cls_sh >= 0 && a->bias) return launch_conv<T, 2, 1, 2, 4, 2, 1, -1, true>(k, a->cout, s);
+      return wide ? launch_conv<T, 2, 1, 2, 4, 2>(k, a->cout, s) : launch_conv<T, 2, 1, 2, 8, 1>(k, a->cout, s);
+    }
+    // 4x4 stride 2, 64-channel tiles: weights staged in two halves of two kernel rows -> 73 KiB of LDS, two workgroups per CU
+    if (a->ksize == 4 && a->stride == 2) return wide ? launch_conv<T, 4, 2, 1, 4, 2, 2>(k, a->cout, s) : launch_conv<T, 4, 2, 1, 4, 1>(k, a->cout, s);
+    if (a->ksize == 2 && a->stride == 2) return wide ? launch_conv<T, 2, 2, 1, 4, 2>(k, a->cout, s) : launch_conv<T, 2, 2, 1, 4, 1>(k, a->cout, s);
+    if (a->ksize == 1 && a->stride == 1) return launch_conv<T, 1, 1, 2, 4, 1>(k, a->cout, s);
   } else {
     // f32 (parity mode): v_mfma_f32_32x32x2_f32, an exact fp32 fma chain
     if (a->ksize == 3 && a->stride == 1) return wide ? launch_conv<T, 3, 1, 2, 4, 2>(k, a->cout, s) : launch_conv<T, 3, 1, 2, 8, 1>(k, a->cout, s);
@@ -952,8 +947,8 @@ static int dispatch_conv(const srganfd_conv_args* a, const ConvK& k, hipStream_t
     if (a->ksize == 3 && a->stride == 2) return wide ? launch_conv<T, 3, 2, 1, 4, 2>(k, a->cout, s) : launch_conv<T, 3, 2, 1, 4, 1>(k, a->cout, s);
     if (a->ksize == 2 && a->stride == 2) return wide ? launch_conv<T, 2, 2, 1, 4, 2>(k, a->cout, s) : launch_conv<T, 2, 2, 1, 4, 1>(k, a->cout, s);
     if (a->ksize == 1 && a->stride == 1) return launch_conv<T, 1, 1, 2, 4, 1>(k, a->cout, s);
-    return set_err(SRGANFD_EINVAL, "conv2d: unsupported ksize=%d stride=%d", a->ksize, a->stride);
   }
+  return set_err(SRGANFD_EINVAL, "conv2d: unsupported ksize=%d stride=%d", a->ksize, a->stride);
 }
 
 int conv_fill_k(const srganfd_conv_args* a, ConvK& k) {

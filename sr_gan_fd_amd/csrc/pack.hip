@@ -1,8 +1,11 @@
 // pack.hip -- NCHW fp32 parameters -> MFMA B-fragment order (see srganfd.h, srganfd_pack_weights).
 // Layout of a packed operand W[tap][k][n] (k, n multiples of 32):
 //   [n/32][k/32][tap][kstep][lane 0..63][frag]   with
-//   bf16 / f16: kstep in 0..1, frag = 8 elements, k = 32*chunk + 16*kstep + 8*(lane>>5) + j, n = 32*ntile + (lane&31)
-//   f32 : kstep in 0..15, frag = 1 float, k = 32*chunk + 2*kstep + (lane>>5)
+//   bf16 / f16 (layout 1, v_mfma_f32_16x16x32: what srganfd_pack_layout asks for): the kstep index is the channel half, frag = 8
+//         elements, k = 32*chunk + 8*(lane>>4) + j, n = 32*ntile + 16*half + (lane&15)
+//   f32 (v_mfma_f32_32x32x2): kstep in 0..15, frag = 1 float, k = 32*chunk + 2*kstep + (lane>>5), n = 32*ntile + (lane&31)
+//   (layout 0 with a 16-bit dtype is the v_mfma_f32_32x32x16 order, k = 32*chunk + 16*kstep + 8*(lane>>5) + j, n = 32*ntile + (lane&31):
+//   part of the contract of srganfd_pack_weights, read by no kernel of the product library)
 // i.e. exactly the order in which conv_igemm.hip's lanes consume B fragments, so staging a
 // (chunk, n-tile) slab into LDS is a linear 16-byte copy and the fragment read is conflict free.
 #include "common.hpp"

@@ -45,7 +45,7 @@ class PackTable:
 def pack_job(dst_off: int, dtype: int, ksize: int, k: int, n: int, segs: Sequence[dict]) -> A.PackJob:
     j = A.PackJob()
     j.dst_off, j.dtype, j.ksize, j.k, j.n, j.nseg = dst_off, dtype, ksize, k, n, len(segs)
-    # B-fragment order of the MFMA form the consuming kernel runs (the library knows its own dispatch: srganfd_set_mfma16)
+    # B-fragment order the consuming kernel reads: 16x16x32 fragments for bf16 / f16, 32x32x2 for f32 (the library says which)
     j.layout = A.lib().srganfd_pack_layout(dtype, ksize, n)
     assert 1 <= len(segs) <= 5 and dst_off % 16 == 0
     for i, s in enumerate(segs):

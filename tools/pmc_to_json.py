@@ -36,7 +36,10 @@ def label(kernel: str):
     kernel = demangle(kernel)
     m = re.search(r"conv_igemm_kernel<([^,]+), (\d+), (\d+), (\d+), (\d+), (\d+)(?:, (true|false))?(?:, (\d+))?(?:, (-?\d+))?(?:, (true|false))?>", kernel)
     if m:
-        return "conv_igemm_kernel<%s,KS=%s,S=%s,MR=%s,WR=%s,WN=%s%s%s%s%s>" % (TY.get(m.group(1), m.group(1)), *m.groups()[1:6], ",M16" if m.group(7) == "true" else "",
+        # argument lists: <T, KS, S, MR, WR, WN, TS, EK, NT> (the 16-bit types run the 16x16x32 form), and in profiles taken before
+        # the form followed the element type <T, KS, S, MR, WR, WN, bool M16, TS, EK, NT>
+        m16 = m.group(7) == "true" if m.group(7) else m.group(1) != "float"
+        return "conv_igemm_kernel<%s,KS=%s,S=%s,MR=%s,WR=%s,WN=%s%s%s%s%s>" % (TY.get(m.group(1), m.group(1)), *m.groups()[1:6], ",M16" if m16 else "",
                                                                              ",TS=%s" % m.group(8) if m.group(8) and int(m.group(8)) > 1 else "",
                                                                              "",      # epilogue kinds (EK) of one tile shape: one class, as profiling.roofline groups them
                                                                              "")      # non-temporal-store twin (NT) of a kind: same class
