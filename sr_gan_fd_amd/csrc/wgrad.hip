@@ -22,12 +22,11 @@
 #include "conv_common.hpp"
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 namespace srganfd {
-
 static constexpr int kWgMagic = 0x57475244;  // 'WGRD'
-
 static constexpr int kMaxWaves = 12;
 struct WgWave { int active, ci_rel, co_rel, ks_idx, ks_n, tap0, slab_base, bias_slab; };
 struct WgGroup { int x_c0, x_units, dy_c0, dy_units;
@@ -53,16 +52,14 @@ struct WgJob { const void* x; const void* dy; float* slabs; float* bslabs; };
 struct WgK {
   WgJob job[kRedBatch];
   const WgGroup* groups;
-  int njobs, pad_;
-  int xC, x_c0v, dyC, dy_c0v;
+  int njobs, pad_;                // njobs: for the host's grid.  No kernel reads njobs, pad_, N, x_upad or dy_upad (left zero); the
+  int xC, x_c0v, dyC, dy_c0v;     // offsets of the others stay, since moving them regroups every kernel's argument loads (profiles/wgrad_refactor_isa.txt)
   int x_ps, x_gs, dy_ps, dy_gs;   // pixel / 32-channel-group strides in elements: NHWC (C, 32) or planar groups (32, H*W*32), see srganfd_view
   int N, Hin, Win, up, pad, Hout, Wout, S, x_upad, dy_upad, ntiles, tiles_x, tiles_y, ngroups;
 };
 
-
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
 // two transposed 4-element reads -> one 8-element MFMA fragment: pure register concatenation (no VALU)
 template <typename T> __device__ __forceinline__ typename FragAB<T>::type cat_frag(s16x4 lo, s16x4 hi) {
   const u32x2 l = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
@@ -90,49 +87,186 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
 #pragma clang diagnostic pop
 }
 
-template <int KS, int STRIDE> struct WgTile { static constexpr int TH = (STRIDE == 1) ? 8 : 4; };
-
-template <int KS> struct WgWaves { static constexpr int NW = (KS == 3) ? 12 : (KS == 4 ? 8 : 4); };
 // DMA builds add loader wavefronts (one per SIMD) that only issue the LDS-DMA pieces of the next tile.  Measured on the
 // dense-block launch (B=32, 128x128): register staging 357 us; every wave issuing its share right after the barrier
 // 355 us (the copy's issue time and the LDS-bound MFMA phase add up: all waves sit in the same phase between two
 // barriers); the shares spread over the MFMA rows 396 us; four specialised loaders beside the compute waves 314 us.
 static constexpr int kLoaderWaves = 4;
+static constexpr int kLdsBudget = 160 * 1024;
 
+// The tile of one launch form: the ONE description the kernel's instantiations and build_plan both read (LDS bytes, waves, loaders).
 // One wave = one (32 ci x 32 co) block x ONE kernel row (KS taps, KS*16 accumulator registers), so a
 // 3x3 workgroup runs 12 waves (3 per SIMD, <=168 VGPRs each) over the same staged tiles.
 // XP / YP = LDS row pitch of the x / dy tiles in 32-channel units (compile-time so that every LDS address in
 // the MFMA loop is table + wave-uniform row offset + immediate).
-// DMA = 1 (bf16, every group stages exactly XP / YP units): the tiles are double-buffered in LDS and filled by LDS-DMA
-// (global_load_lds_dwordx4: wave-uniform LDS base + lane*16, so the LDS image is lane-linear and the 64-byte-unit swizzle
-// is applied to the per-lane SOURCE address); tile t+1 lands while tile t is in the MFMA phase, one barrier per tile,
-// no staging registers.  DMA = 0: global -> register -> LDS staging through one buffer.
-// VAR: 0 = v_mfma_f32_32x32x16, one pair of transposed x reads per kernel column (every shape but the next); 3 = the 3x3 stride-1 16-bit
-// DMA kernel: v_mfma_f32_16x16x32 on three transposed x reads per half row whose register shifts give the three kernel columns (the
-// intermediate variants 1 / 2 of profiles/r02_wgrad_variants.txt live in tools/experiments/r3_src).
-template <typename T, int KS, int STRIDE, int XP, int YP, bool DMA, int VAR>
-__global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) void wgrad_kernel(const WgK a) {
-  constexpr int TH = WgTile<KS, STRIDE>::TH;
-  constexpr int NTHR = 64 * WgWaves<KS>::NW;
-  constexpr int NT = KS;
-  constexpr int PR = (TH - 1) * STRIDE + KS, PC = 31 * STRIDE + KS;
-  constexpr int UB = 32 * (int)sizeof(T);   // bytes of one 32-channel unit
-  constexpr int CPU = UB / 16;              // 16-byte chunks per unit (4 bf16 / 8 f32)
-  constexpr int CPU_SH = (CPU == 4) ? 2 : 3;
-  constexpr int E16 = 16 / (int)sizeof(T);
-  // staging items per thread for the largest group (2 units each side)
-  constexpr int XI = (PR * PC * 2 * CPU + NTHR - 1) / NTHR;
-  constexpr int YI = (TH * 32 * 2 * CPU + NTHR - 1) / NTHR;
+struct WgGeom {
+  int th, nw, pr, pc, ub;      // output rows of a tile (32 pixels wide); compute waves; rows / columns of the x patch; bytes of a 32-channel unit
+  int x_row, dy_row, x_bytes, buf_bytes;            // LDS row pitch (bytes per pixel) of the x / dy tile; the x tile; one (x tile, dy tile) buffer
+  int x_items, y_items, x_pieces, n_piece;          // LDS-DMA fill: 16-byte items of the two tiles; pieces of 64 items, [0, x_pieces) fill x, the rest dy
+  bool loaders;                // the shape may run the loader-wave form (two buffers, kLoaderWaves more waves)
+};
+constexpr WgGeom wg_geom(int esize, int ks, int stride, int xp, int yp) {
+  WgGeom g{};
+  g.th = stride == 1 ? 8 : 4; g.nw = ks == 3 ? 12 : (ks == 4 ? 8 : 4);
+  g.pr = (g.th - 1) * stride + ks; g.pc = 31 * stride + ks;
+  g.ub = 32 * esize; g.x_row = g.ub * xp; g.dy_row = g.ub * yp;
+  g.x_bytes = g.pr * g.pc * g.x_row; g.buf_bytes = g.x_bytes + g.th * 32 * g.dy_row;
+  g.x_items = g.x_bytes / 16; g.y_items = g.th * 32 * g.dy_row / 16;
+  g.x_pieces = (g.x_items + 63) / 64; g.n_piece = g.x_pieces + (g.y_items + 63) / 64;
+  // 16-bit only, and two buffers must fit.  Never 3x3 stride 2 (A-ESRGAN's encoder): with the four loader waves the workgroup has
+  // 1024 threads = 128 VGPRs per lane, and this shape's addressing does not fit them (10-13 spilled registers, scratch inside the
+  // loop); 12 waves with register staging have 168
+  g.loaders = esize == 2 && 2 * g.buf_bytes <= kLdsBudget && !(ks == 3 && stride == 2);
+  return g;
+}
+
+// The MFMA form follows the types: v_mfma_f32_16x16x32 for the 3x3 stride-1 16-bit loader-wave kernel, v_mfma_f32_32x32x16 for every other
+// 16-bit kernel, v_mfma_f32_32x32x2 for f32.  (The intermediate variants 1 / 2 of profiles/r02_wgrad_variants.txt live in tools/experiments/r3_src.)
+template <typename T, int KS, int STRIDE, bool DMA> constexpr bool kWgM16 = sizeof(T) == 2 && KS == 3 && STRIDE == 1 && DMA;
+// compile-time names of one instantiation's geometry
+template <typename T_, int KS_, int STRIDE_, int XP, int YP> struct WgShape {
+  static_assert(!(STRIDE_ == 2 && XP == 2), "a stride-2 workgroup stages ONE x unit (build_plan: xdiv == 1, no merged groups)");
+  using T = T_;
+  static constexpr int KS = KS_, STRIDE = STRIDE_;
+  static constexpr WgGeom g = wg_geom((int)sizeof(T), KS, STRIDE, XP, YP);
+  static constexpr int TH = g.th, NW = g.nw, NTHR = 64 * g.nw, PR = g.pr, PC = g.pc, UB = g.ub;
+  static constexpr int CPU = UB / 16, CPU_SH = (CPU == 4) ? 2 : 3, E16 = 16 / (int)sizeof(T);   // 16-byte chunks per unit (4 bf16 / 8 f32)
+  static constexpr int xp_sh = XP == 2 ? 1 : 0, yp_sh = YP == 2 ? 1 : 0;      // pitch (swizzle follows the pitch)
+  static constexpr int xRowB = g.x_row, dyRowB = g.dy_row, kXBytes = g.x_bytes, kBufBytes = g.buf_bytes;
+  static constexpr int XI = (PR * PC * 2 * CPU + NTHR - 1) / NTHR, YI = (TH * 32 * 2 * CPU + NTHR - 1) / NTHR;   // staging items per thread for the largest group (2 units each side)
+  static constexpr int XITEMS = g.x_items, YITEMS = g.y_items, XPIECES = g.x_pieces, NPIECE = g.n_piece;
+  static constexpr int NSLOT = (NPIECE + kLoaderWaves - 1) / kLoaderWaves;   // pieces per loader wave and tile
+};
+__device__ __forceinline__ int wg_swz(int ush, int pix) { return ush ? ((pix >> 1) & 1) : 0; }
+// ---- the MFMA forms: one tile-row phase and one slab epilogue each.  Plain static function templates, not __forceinline__, on purpose:
+// the ordinary inliner folds them in where it folded the lambdas they replace and every kernel keeps its instruction counts.  The staging
+// lambdas and the loader-wave role stay in the kernel for the same reason (profiles/wgrad_refactor_isa.txt) ----
+// v_mfma_f32_16x16x32 (3x3 stride 1): K = the 32 pixels of one tile row.  A (16 input channels x 32 pixels) and B (32 pixels x 16 output
+// channels): lane group g = lane>>4 supplies / receives pixels 8g..8g+7, so each 16-lane group of a transposed read takes its
+// own 4-pixel x 16-channel block.  Per row: 2 channel halves x 3 reads of x (pixels p0..p0+11 -> the three kernel columns by
+// register shifts, as in variant 1), 2 x 2 reads of dy, 12 MFMAs of 16 cycles (= the 6 of 32 cycles of the other form).
+// tx0 / tx1 / ty0: the lane's x (patch-row parity 0 / 1) and dy addresses inside a row; ones: a fragment of 1.0
+template <class S> static __device__ void wg_row_16x16x32(const WgWave& W, int ro, int ky, int tx0, int tx1, int ty0, typename FragAB<typename S::T>::type ones, const char* ldsX, const char* ldsY, f32x4_t (&acc16)[3][2][2], f32x4_t (&bacc)[2]) {
+  using T = typename S::T; constexpr int PC = S::PC, xRowB = S::xRowB, dyRowB = S::dyRowB;
+  using Fr = typename FragAB<T>::type;
+  const int prow = ro + ky;
+  const char* xb = ldsX + ((prow & 1) ? tx1 : tx0) + prow * PC * xRowB;
+  const char* yb = ldsY + ty0 + ro * 32 * dyRowB;
+  Fr bq[2];
+#pragma unroll
+  for (int nh = 0; nh < 2; ++nh) {
+    const u32x2 blo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(yb + nh * 32)));
+    const u32x2 bhi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(yb + nh * 32 + 4 * dyRowB)));
+    const u32x4 b4 = {blo.x, blo.y, bhi.x, bhi.y};
+    bq[nh] = __builtin_bit_cast(Fr, b4);
+    // bias gradient = sum over the row's 32 pixels of dy: one MFMA against a fragment of ones (every row of the result is
+    // that sum) instead of 8 conversions + 7 adds per lane -- 16 matrix-pipe cycles for ~90 VALU cycles in the one wave of
+    // three that carries it
+    if (W.bias_slab >= 0) bacc[nh] = mfma16<T>(ones, bq[nh], bacc[nh]);
+  }
+#pragma unroll
+  for (int ch = 0; ch < 2; ++ch) {
+    const u32x2 lo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb + ch * 32)));
+    const u32x2 hi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb + ch * 32 + 4 * xRowB)));
+    const u32x2 nx = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb + ch * 32 + 8 * xRowB)));
+    const u32x4 f0 = {lo.x, lo.y, hi.x, hi.y};
+    const u32x4 f1 = {__builtin_amdgcn_alignbit(lo.y, lo.x, 16), __builtin_amdgcn_alignbit(hi.x, lo.y, 16),
+                      __builtin_amdgcn_alignbit(hi.y, hi.x, 16), __builtin_amdgcn_alignbit(nx.x, hi.y, 16)};
+    const u32x4 f2 = {lo.y, hi.x, hi.y, nx.x};
+#pragma unroll
+    for (int nh = 0; nh < 2; ++nh) {
+      acc16[0][ch][nh] = mfma16<T>(__builtin_bit_cast(Fr, f0), bq[nh], acc16[0][ch][nh]);
+      acc16[1][ch][nh] = mfma16<T>(__builtin_bit_cast(Fr, f1), bq[nh], acc16[1][ch][nh]);
+      acc16[2][ch][nh] = mfma16<T>(__builtin_bit_cast(Fr, f2), bq[nh], acc16[2][ch][nh]);
+    }
+  }
+}
+// v_mfma_f32_32x32x16: one pair of transposed x reads per kernel column; tabX / tabY: the lane's address tables (see the kernel)
+template <class S> static __device__ void wg_row_32x32x16(const WgWave& W, int ro, int ky, const int (&tabX)[2][S::KS], int tabY, const char* ldsX, const char* ldsY, f32x16 (&acc)[S::KS], float& bsum) {
+  using T = typename S::T; constexpr int KS = S::KS, STRIDE = S::STRIDE, PC = S::PC, xRowB = S::xRowB, dyRowB = S::dyRowB;
+  const int prow = ro * STRIDE + ky;                       // patch row
+  const int P = ((PC & 3) == 2) ? (prow & 1) : 0;          // (prow*PC) mod 4 == 2*P
+  const int xrow_off = prow * PC * xRowB;                  // wave-uniform
+  const int yrow_off = ro * 32 * dyRowB;
+  int ax[KS];
+#pragma unroll
+  for (int dx = 0; dx < KS; ++dx) ax[dx] = (P ? tabX[1][dx] : tabX[0][dx]) + xrow_off;
+  const int ay = tabY + yrow_off;
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) {
+    const char* yb = ldsY + ay + hh * 16 * dyRowB;
+    const s16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(yb));
+    const s16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(yb + 4 * dyRowB));
+    const auto bfrag = cat_frag<T>(blo, bhi);
+    if (W.bias_slab >= 0) {
+      const u32x2 l = __builtin_bit_cast(u32x2, blo), h2 = __builtin_bit_cast(u32x2, bhi);
+      float f8[8];
+      unpack8<T>(u32x4{l.x, l.y, h2.x, h2.y}, f8);
+      bsum += ((f8[0] + f8[1]) + (f8[2] + f8[3])) + ((f8[4] + f8[5]) + (f8[6] + f8[7]));
+    }
+#pragma unroll
+    for (int dx = 0; dx < KS; ++dx) {
+      const char* xb = ldsX + ax[dx] + hh * 16 * STRIDE * xRowB;
+      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb));
+      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb + 4 * STRIDE * xRowB));
+      acc[dx] = mfma32<T>(cat_frag<T>(lo, hi), bfrag, acc[dx]);
+    }
+  }
+}
+// v_mfma_f32_32x32x2 (f32): plain ds_read_b32, channels on the lanes (r = lane & 31), two pixels a step (h = lane >> 5)
+template <class S> static __device__ void wg_row_32x32x2(const WgWave& W, int ro, int ky, int r, int h, const char* ldsX, const char* ldsY, f32x16 (&acc)[S::KS], float& bsum) {
+  constexpr int KS = S::KS, STRIDE = S::STRIDE, PC = S::PC, xRowB = S::xRowB, dyRowB = S::dyRowB;
+#pragma unroll 1
+  for (int kk = 0; kk < 16; ++kk) {
+    const int oc = 2 * kk + h;
+    const float bv = *(const float*)(ldsY + (ro * 32 + oc) * dyRowB + (W.co_rel * 32 + r) * 4);
+    if (W.bias_slab >= 0) bsum += bv;
+#pragma unroll
+    for (int dx = 0; dx < KS; ++dx) {
+      const int p = (ro * STRIDE + ky) * PC + oc * STRIDE + dx;
+      const float av = *(const float*)(ldsX + p * xRowB + (W.ci_rel * 32 + r) * 4);
+      acc[dx] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[dx], 0, 0, 0);
+    }
+  }
+}
+template <class S> static __device__ void wg_store_16x16x32(const WgWave& W, int lane, float* slab, float* bslab, const f32x4_t (&acc16)[3][2][2], const f32x4_t (&bacc)[2]) {
+  // D of 16x16x32: column = lane & 15 (output channel inside its half), row = 4 * (lane >> 4) + register (input channel)
+#pragma unroll
+  for (int tl = 0; tl < 3; ++tl)
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+      for (int nh = 0; nh < 2; ++nh)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) slab[(tl * 32 + 16 * ch + 4 * (lane >> 4) + i) * 32 + 16 * nh + (lane & 15)] = acc16[tl][ch][nh][i];
+  if (W.bias_slab >= 0) {
+    // every row of bacc holds the 32-pixel sums of channels 16 * nh + (lane & 15): take row 0 (lane group 0), slots 0..31 = channels
+    float t0 = (lane >> 4) == 0 ? bacc[0][0] : 0.f, t1 = (lane >> 4) == 0 ? bacc[1][0] : 0.f;
+    t0 += __shfl_xor(t0, 16, 64); t0 += __shfl_xor(t0, 32, 64);
+    t1 += __shfl_xor(t1, 16, 64); t1 += __shfl_xor(t1, 32, 64);
+    bslab[lane] = lane < 16 ? t0 : (lane < 32 ? t1 : 0.f);
+  }
+}
+template <class S> static __device__ void wg_store_32x32(const WgWave& W, int lane, float* slab, float* bslab, const f32x16 (&acc)[S::KS], float bsum) {
+  constexpr int NT = S::KS; const int r = lane & 31;
+#pragma unroll
+  for (int tl = 0; tl < NT; ++tl)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) slab[(tl * 32 + mfma32_row(i, lane)) * 32 + r] = acc[tl][i];
+  if (W.bias_slab >= 0) bslab[lane] = bsum;
+}
+
+// decode workgroup -> (group, split, job); role split; tile loop; epilogue.  DMA = 1: loader waves beside the compute waves, two LDS buffers
+template <typename T, int KS, int STRIDE, int XP, int YP, bool DMA>
+__global__ __launch_bounds__(64 * (wg_geom((int)sizeof(T), KS, STRIDE, XP, YP).nw + (DMA ? kLoaderWaves : 0))) void wgrad_kernel(const WgK a) {
+  using S = WgShape<T, KS, STRIDE, XP, YP>;
+  constexpr bool kM16 = kWgM16<T, KS, STRIDE, DMA>;
+  static_assert(!DMA || S::g.loaders, "this shape has no loader-wave form (wg_geom)");
   constexpr bool kPrefetch = sizeof(T) == 2 && !DMA;   // bf16 register staging: next tile's loads are issued before the MFMA phase
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // 1-D grid.  Blocks b and b+8 share an XCD (private L2): remap so that each XCD owns a contiguous range of
-  // work ids, with the channel group as the FAST index -- the workgroups that stream the same pixel tiles
-  // (different channel groups of one split) then run together on one XCD and re-read x / dy from its L2.
-  int wgid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = wgid & 7, q = nwg >> 3, rr = nwg & 7;
-    wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (wgid >> 3);
-  }
+  // 1-D grid, remapped so that each XCD (private L2) owns a contiguous range of work ids, with the channel group as the FAST index: the
+  // workgroups that stream the same pixel tiles (different channel groups of one split) run together on one XCD and re-read x / dy from its L2
+  const int wgid = xcd_remap(blockIdx.x, gridDim.x);
   // group (fastest), then split, then job: the channel groups of one (job, split) stay neighbours on one XCD
   const int grp = wgid % a.ngroups, gs = wgid / a.ngroups;
   const int split = gs % a.S;
@@ -140,42 +274,37 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
   const WgGroup& G = a.groups[grp];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const WgWave W = G.w[wave < WgWaves<KS>::NW ? wave : 0];
+  const WgWave W = G.w[wave < S::NW ? wave : 0];
   const int r = lane & 31, h = lane >> 5;
   const int xu_sh = G.x_units == 2 ? 1 : 0, yu_sh = G.dy_units == 2 ? 1 : 0;   // units staged by this group (1 or 2)
-  constexpr int xp_sh = XP == 2 ? 1 : 0, yp_sh = YP == 2 ? 1 : 0;                // pitch (swizzle follows the pitch)
-  constexpr int xRowB = UB * XP, dyRowB = UB * YP;
-  constexpr int kBufBytes = PR * PC * xRowB + TH * 32 * dyRowB;   // one (x tile, dy tile) buffer
   char* ldsX = smem;
-  char* ldsY = smem + PR * PC * xRowB;
+  char* ldsY = smem + S::kXBytes;
   const int Hl = a.Hin << a.up, Wl = a.Win << a.up;
   const int xcb = a.x_c0v + G.x_c0, ycb = a.dy_c0v + G.dy_c0;     // first channel this group stages
   const T* __restrict__ xg = (const T*)J.x + ((xcb >> 5) * (size_t)a.x_gs + (xcb & 31));
   const T* __restrict__ dyg = (const T*)J.dy + ((ycb >> 5) * (size_t)a.dy_gs + (ycb & 31));
   const int x_gs2 = a.x_gs * G.x_u1, dy_gs2 = a.dy_gs * G.dy_u1;   // distance of the group's two staged units
-
-  f32x16 acc[NT];
+  f32x16 acc[KS];
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
+  for (int t = 0; t < KS; ++t)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
   float bsum = 0.f;
-  // VAR 3 (v_mfma_f32_16x16x32): [kernel column][input-channel half][output-channel half], 48 registers like acc[3] above
+  // the 16x16x32 form: [kernel column][input-channel half][output-channel half], 48 registers like acc[3] above
   f32x4_t acc16[3][2][2];
-  float bsum16[2] = {0.f, 0.f};
-  f32x4_t bacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // VAR 3: bias sums as MFMA results (all rows equal)
-  if constexpr (VAR == 3) {
+  f32x4_t bacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // its bias sums as MFMA results (all rows equal)
+  if constexpr (kM16) {
 #pragma unroll
     for (int q = 0; q < 12; ++q)
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc16[q / 4][(q >> 1) & 1][q & 1][i] = 0.f;
   }
-
+  constexpr int TH = S::TH, NW = S::NW, NTHR = S::NTHR, PR = S::PR, PC = S::PC, UB = S::UB, CPU = S::CPU, CPU_SH = S::CPU_SH, E16 = S::E16;
+  constexpr int xp_sh = S::xp_sh, yp_sh = S::yp_sh, xRowB = S::xRowB, dyRowB = S::dyRowB, kXBytes = S::kXBytes, kBufBytes = S::kBufBytes;
+  constexpr int XI = S::XI, YI = S::YI, XITEMS = S::XITEMS, YITEMS = S::YITEMS, XPIECES = S::XPIECES, NPIECE = S::NPIECE, NSLOT = S::NSLOT;
+  const int rows_per = S::TH / W.ks_n;
   const int xItems = (PR * PC * CPU) << xu_sh;
   const int yItems = (TH * 32 * CPU) << yu_sh;
-  const int rows_per = TH / W.ks_n;
-  auto swz = [](int ush, int pix) { return ush ? ((pix >> 1) & 1) : 0; };
-
   auto tile_origin = [&](int tile, int& n, int& oy0, int& ox0) {
     const int tx = tile % a.tiles_x; tile /= a.tiles_x;
     const int ty = tile % a.tiles_y;
@@ -198,7 +327,7 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
     if (item < xItems) {
       const int pix = item >> (CPU_SH + xu_sh), c16 = item & ((CPU << xu_sh) - 1);
       const int unit = c16 >> CPU_SH, w16 = c16 & (CPU - 1);
-      const int f = sizeof(T) == 2 ? swz(xp_sh, pix) : 0;
+      const int f = sizeof(T) == 2 ? wg_swz(xp_sh, pix) : 0;
       *(u32x4*)(ldsX + pix * xRowB + ((unit ^ f) * UB) + w16 * 16) = v;
     }
   };
@@ -217,7 +346,7 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
     if (item < yItems) {
       const int pix = item >> (CPU_SH + yu_sh), c16 = item & ((CPU << yu_sh) - 1);
       const int unit = c16 >> CPU_SH, w16 = c16 & (CPU - 1);
-      const int f = sizeof(T) == 2 ? swz(yp_sh, pix) : 0;
+      const int f = sizeof(T) == 2 ? wg_swz(yp_sh, pix) : 0;
       *(u32x4*)(ldsY + pix * dyRowB + ((unit ^ f) * UB) + w16 * 16) = v;
     }
   };
@@ -248,13 +377,9 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
       for (int i = 0; i < YI; ++i) store_y(i, load_y(i, n, oy0, ox0));
     }
   };
-
   // LDS-DMA fill (DMA builds only).  Item = one 16-byte chunk; a piece = one wave instruction = 64 consecutive items =
   // 1 KiB of the lane-linear image.  Chunk (pixel, unit', w16) of the image holds source unit (unit' ^ swizzle(pixel));
   // padding chunks are zero-filled with ds_write.  Pieces [0, XPIECES) fill the x tile, the rest the dy tile.
-  constexpr int XITEMS = PR * PC * (CPU << xp_sh), YITEMS = TH * 32 * (CPU << yp_sh);
-  constexpr int XPIECES = (XITEMS + 63) / 64, NPIECE = XPIECES + (YITEMS + 63) / 64;
-  constexpr int NSLOT = (NPIECE + kLoaderWaves - 1) / kLoaderWaves;   // pieces per loader wave and tile
   // Per piece and tile the loader needs: patch pixel (py, px) of the lane's chunk, its (swizzled) source unit and 16-byte slot.  All
   // of it is tile-invariant, so it is decoded ONCE per kernel into one packed register per slot (the full decode -- pixel / unit,
   // swizzle, division by the patch width -- is ~100 instructions per piece; 19 pieces per tile and loader wave, issued at raised
@@ -265,13 +390,13 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
     constexpr int XSH = CPU_SH + xp_sh, YSH = CPU_SH + yp_sh;
 #pragma unroll
     for (int k = 0; k < NSLOT; ++k) {
-      const int piece = (wave - WgWaves<KS>::NW) + kLoaderWaves * k;
+      const int piece = (wave - NW) + kLoaderWaves * k;
       spk[k] = -1; soff[k] = 0;
       if (piece < XPIECES) {
         const int item = piece * 64 + lane;
         if (item < XITEMS) {
           const int pix = item >> XSH, c16 = item & ((CPU << xp_sh) - 1);
-          const int unit = (c16 >> CPU_SH) ^ swz(xp_sh, pix), w16 = c16 & (CPU - 1);
+          const int unit = (c16 >> CPU_SH) ^ wg_swz(xp_sh, pix), w16 = c16 & (CPU - 1);
           const int py = pix / PC, px = pix - py * PC;
           spk[k] = py | (px << 8) | (unit << 16) | (w16 << 20);
           soff[k] = (py * a.Win + px) * a.x_ps + unit * x_gs2 + w16 * E16;
@@ -280,7 +405,7 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
         const int item = (piece - XPIECES) * 64 + lane;
         if (item < YITEMS) {
           const int pix = item >> YSH, c16 = item & ((CPU << yp_sh) - 1);
-          const int unit = (c16 >> CPU_SH) ^ swz(yp_sh, pix), w16 = c16 & (CPU - 1);
+          const int unit = (c16 >> CPU_SH) ^ wg_swz(yp_sh, pix), w16 = c16 & (CPU - 1);
           spk[k] = (pix >> 5) | ((pix & 31) << 8) | (unit << 16) | (w16 << 20);
           soff[k] = ((pix >> 5) * a.Wout + (pix & 31)) * a.dy_ps + unit * dy_gs2 + w16 * E16;
         }
@@ -289,7 +414,7 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
   };
   auto dma_slots = [&](int n, int oy0, int ox0, int buf) __attribute__((always_inline)) {
     char* bx = smem + buf * kBufBytes;
-    char* by = bx + PR * PC * xRowB;
+    char* by = bx + kXBytes;
     const int gy0 = oy0 * STRIDE - a.pad, gx0 = ox0 * STRIDE - a.pad;
     const T* xi = xg + (size_t)n * a.Hin * a.Win * a.xC;            // image bases (wave-uniform)
     const T* yi = dyg + (size_t)n * a.Hout * a.Wout * a.dyC;
@@ -299,7 +424,7 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
     const bool lin = a.up == 0;
 #pragma unroll
     for (int k = 0; k < NSLOT; ++k) {
-      const int piece = (wave - WgWaves<KS>::NW) + kLoaderWaves * k;       // wave-uniform
+      const int piece = (wave - NW) + kLoaderWaves * k;       // wave-uniform
       const int q = spk[k];
       if (piece >= NPIECE || q < 0) continue;
       const int py = q & 255, px = (q >> 8) & 255, unit = (q >> 16) & 15, w16 = q >> 20;
@@ -316,8 +441,7 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
       }
     }
   };
-
-  // ---- lane-constant LDS address tables (keeps the MFMA loop almost free of address VALU work) ----
+  // ---- lane-constant LDS address tables of the 32x32x16 form (keeps the MFMA loop almost free of address VALU work) ----
   // ds_read_b64_tr_b16 lane roles inside a 16-lane group: lane 4q+p supplies row q (pixel), columns
   // 4p..4p+3 (channels); lane i receives channel i of the 4 pixels.  This lane's first block row is pixel
   // L = 8*(lane>>5) + q of the 16-pixel k-step, its channels start at byte chb inside the 32-channel unit.
@@ -335,16 +459,15 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
 #pragma unroll
       for (int dx = 0; dx < KS; ++dx) {
         const int x = 2 * P + dx + Lpix * STRIDE;   // pixel index mod 4 is what the swizzle needs
-        tabX[P][dx] = (Lpix * STRIDE + dx) * xRowB + ((W.ci_rel ^ swz(xp_sh, x)) * UB) + chb;
+        tabX[P][dx] = (Lpix * STRIDE + dx) * S::xRowB + ((W.ci_rel ^ wg_swz(S::xp_sh, x)) * S::UB) + chb;
       }
-    tabY = Lpix * dyRowB + ((W.co_rel ^ swz(yp_sh, Lpix)) * UB) + chb;
+    tabY = Lpix * S::dyRowB + ((W.co_rel ^ wg_swz(S::yp_sh, Lpix)) * S::UB) + chb;
   }
   const int ky = W.tap0 / KS;   // this wave's kernel row
-
   int tile = split;
   int cur = 0;
   if constexpr (DMA) {
-    if (wave >= WgWaves<KS>::NW) {
+    if (wave >= S::NW) {
       // ---- loader wavefronts: tile t+1 -> buffer cur^1 while the compute waves run tile t out of buffer cur ----
       int n, oy0, ox0;
       slots_setup();
@@ -368,8 +491,8 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
   for (; tile < a.ntiles; tile += a.S) {
     if constexpr (DMA) {
       __syncthreads();
-      ldsX = smem + cur * kBufBytes;
-      ldsY = ldsX + PR * PC * xRowB;
+      ldsX = smem + cur * S::kBufBytes;
+      ldsY = ldsX + S::kXBytes;
       cur ^= 1;
     } else {
       __syncthreads();  // previous tile's LDS reads done
@@ -378,127 +501,29 @@ __global__ __launch_bounds__(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))) 
       if (tile + a.S < a.ntiles) prefetch(tile + a.S);
     }
     if (W.active) {
-      if constexpr (sizeof(T) == 2 && KS == 3 && STRIDE == 1 && VAR == 3) {
-        // v_mfma_f32_16x16x32: K = the 32 pixels of one tile row.  A (16 input channels x 32 pixels) and B (32 pixels x 16 output
-        // channels): lane group g = lane>>4 supplies / receives pixels 8g..8g+7, so each 16-lane group of a transposed read takes its
-        // own 4-pixel x 16-channel block.  Per row: 2 channel halves x 3 reads of x (pixels p0..p0+11 -> the three kernel columns by
-        // register shifts, as in variant 1), 2 x 2 reads of dy, 12 MFMAs of 16 cycles (= the 6 of 32 cycles of the other variants).
+      if constexpr (kM16) {
         using Fr = typename FragAB<T>::type;
         const int Lp = 8 * g16 + lq;                                   // this lane's address row inside the 32-pixel run
-        const int tx0 = Lp * xRowB + ((W.ci_rel ^ swz(xp_sh, Lp)) * UB) + lp * 8;        // patch-row parity 0 (row start = 0 mod 4)
-        const int tx1 = Lp * xRowB + ((W.ci_rel ^ swz(xp_sh, 2 + Lp)) * UB) + lp * 8;    // parity 1 (row start = 2 mod 4)
-        const int ty0 = Lp * dyRowB + ((W.co_rel ^ swz(yp_sh, Lp)) * UB) + lp * 8;
+        const int tx0 = Lp * S::xRowB + ((W.ci_rel ^ wg_swz(S::xp_sh, Lp)) * S::UB) + lp * 8;        // patch-row parity 0 (row start = 0 mod 4)
+        const int tx1 = Lp * S::xRowB + ((W.ci_rel ^ wg_swz(S::xp_sh, 2 + Lp)) * S::UB) + lp * 8;    // parity 1 (row start = 2 mod 4)
+        const int ty0 = Lp * S::dyRowB + ((W.co_rel ^ wg_swz(S::yp_sh, Lp)) * S::UB) + lp * 8;
         const unsigned one2 = sizeof(T) == 2 && Elem<T>::kDtype == SRGANFD_F16 ? 0x3C003C00u : 0x3F803F80u;      // two 1.0 in f16 / bf16
         const Fr ones = __builtin_bit_cast(Fr, u32x4{one2, one2, one2, one2});
-        for (int rr = 0; rr < rows_per; ++rr) {
-          const int ro = W.ks_idx * rows_per + rr, prow = ro + ky;
-          const char* xb = ldsX + ((prow & 1) ? tx1 : tx0) + prow * PC * xRowB;
-          const char* yb = ldsY + ty0 + ro * 32 * dyRowB;
-          Fr bq[2];
-#pragma unroll
-          for (int nh = 0; nh < 2; ++nh) {
-            const u32x2 blo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(yb + nh * 32)));
-            const u32x2 bhi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(yb + nh * 32 + 4 * dyRowB)));
-            const u32x4 b4 = {blo.x, blo.y, bhi.x, bhi.y};
-            bq[nh] = __builtin_bit_cast(Fr, b4);
-            // bias gradient = sum over the row's 32 pixels of dy: one MFMA against a fragment of ones (every row of the result is
-            // that sum) instead of 8 conversions + 7 adds per lane -- 16 matrix-pipe cycles for ~90 VALU cycles in the one wave of
-            // three that carries it
-            if (W.bias_slab >= 0) bacc[nh] = mfma16<T>(ones, bq[nh], bacc[nh]);
-          }
-#pragma unroll
-          for (int ch = 0; ch < 2; ++ch) {
-            const u32x2 lo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb + ch * 32)));
-            const u32x2 hi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb + ch * 32 + 4 * xRowB)));
-            const u32x2 nx = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb + ch * 32 + 8 * xRowB)));
-            const u32x4 f0 = {lo.x, lo.y, hi.x, hi.y};
-            const u32x4 f1 = {__builtin_amdgcn_alignbit(lo.y, lo.x, 16), __builtin_amdgcn_alignbit(hi.x, lo.y, 16),
-                              __builtin_amdgcn_alignbit(hi.y, hi.x, 16), __builtin_amdgcn_alignbit(nx.x, hi.y, 16)};
-            const u32x4 f2 = {lo.y, hi.x, hi.y, nx.x};
-#pragma unroll
-            for (int nh = 0; nh < 2; ++nh) {
-              acc16[0][ch][nh] = mfma16<T>(__builtin_bit_cast(Fr, f0), bq[nh], acc16[0][ch][nh]);
-              acc16[1][ch][nh] = mfma16<T>(__builtin_bit_cast(Fr, f1), bq[nh], acc16[1][ch][nh]);
-              acc16[2][ch][nh] = mfma16<T>(__builtin_bit_cast(Fr, f2), bq[nh], acc16[2][ch][nh]);
-            }
-          }
-        }
+        for (int rr = 0; rr < rows_per; ++rr) wg_row_16x16x32<S>(W, W.ks_idx * rows_per + rr, ky, tx0, tx1, ty0, ones, ldsX, ldsY, acc16, bacc);
       } else
       for (int rr = 0; rr < rows_per; ++rr) {
         const int ro = W.ks_idx * rows_per + rr;
-        if constexpr (sizeof(T) == 2) {
-          const int prow = ro * STRIDE + ky;                       // patch row
-          const int P = ((PC & 3) == 2) ? (prow & 1) : 0;          // (prow*PC) mod 4 == 2*P
-          const int xrow_off = prow * PC * xRowB;                  // wave-uniform
-          const int yrow_off = ro * 32 * dyRowB;
-          int ax[KS];
-#pragma unroll
-          for (int dx = 0; dx < KS; ++dx) ax[dx] = (P ? tabX[1][dx] : tabX[0][dx]) + xrow_off;
-          const int ay = tabY + yrow_off;
-#pragma unroll
-          for (int hh = 0; hh < 2; ++hh) {
-            const char* yb = ldsY + ay + hh * 16 * dyRowB;
-            const s16x4 blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(yb));
-            const s16x4 bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(yb + 4 * dyRowB));
-            const auto bfrag = cat_frag<T>(blo, bhi);
-            if (W.bias_slab >= 0) {
-              const u32x2 l = __builtin_bit_cast(u32x2, blo), h2 = __builtin_bit_cast(u32x2, bhi);
-              float f8[8];
-              unpack8<T>(u32x4{l.x, l.y, h2.x, h2.y}, f8);
-              bsum += ((f8[0] + f8[1]) + (f8[2] + f8[3])) + ((f8[4] + f8[5]) + (f8[6] + f8[7]));
-            }
-#pragma unroll
-            for (int dx = 0; dx < KS; ++dx) {
-              const char* xb = ldsX + ax[dx] + hh * 16 * STRIDE * xRowB;
-              const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb));
-              const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(xb + 4 * STRIDE * xRowB));
-              acc[dx] = mfma32<T>(cat_frag<T>(lo, hi), bfrag, acc[dx]);
-            }
-          }
-        } else {
-#pragma unroll 1
-          for (int kk = 0; kk < 16; ++kk) {
-            const int oc = 2 * kk + h;
-            const float bv = *(const float*)(ldsY + (ro * 32 + oc) * dyRowB + (W.co_rel * 32 + r) * 4);
-            if (W.bias_slab >= 0) bsum += bv;
-#pragma unroll
-            for (int dx = 0; dx < KS; ++dx) {
-              const int p = (ro * STRIDE + ky) * PC + oc * STRIDE + dx;
-              const float av = *(const float*)(ldsX + p * xRowB + (W.ci_rel * 32 + r) * 4);
-              acc[dx] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[dx], 0, 0, 0);
-            }
-          }
-        }
+        if constexpr (sizeof(T) == 2) wg_row_32x32x16<S>(W, ro, ky, tabX, tabY, ldsX, ldsY, acc, bsum);
+        else wg_row_32x32x2<S>(W, ro, ky, r, h, ldsX, ldsY, acc, bsum);
       }
     }
   }
   if (W.active) {
-    float* slab = J.slabs + (size_t)(W.slab_base + split * W.ks_n + W.ks_idx) * (KS * KS * 1024) + W.tap0 * 1024;
-    if constexpr (VAR == 3) {
-      // D of 16x16x32: column = lane & 15 (output channel inside its half), row = 4 * (lane >> 4) + register (input channel)
-#pragma unroll
-      for (int tl = 0; tl < 3; ++tl)
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch)
-#pragma unroll
-          for (int nh = 0; nh < 2; ++nh)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) slab[(tl * 32 + 16 * ch + 4 * (lane >> 4) + i) * 32 + 16 * nh + (lane & 15)] = acc16[tl][ch][nh][i];
-      if (W.bias_slab >= 0) {
-        // every row of bacc holds the 32-pixel sums of channels 16 * nh + (lane & 15): take row 0 (lane group 0), slots 0..31 = channels
-        float t0 = (lane >> 4) == 0 ? bacc[0][0] : 0.f, t1 = (lane >> 4) == 0 ? bacc[1][0] : 0.f;
-        (void)bsum16;
-        t0 += __shfl_xor(t0, 16, 64); t0 += __shfl_xor(t0, 32, 64);
-        t1 += __shfl_xor(t1, 16, 64); t1 += __shfl_xor(t1, 32, 64);
-        J.bslabs[(size_t)(W.bias_slab + split * W.ks_n + W.ks_idx) * 64 + lane] = lane < 16 ? t0 : (lane < 32 ? t1 : 0.f);
-      }
-    } else {
-#pragma unroll
-    for (int tl = 0; tl < NT; ++tl)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) slab[(tl * 32 + mfma32_row(i, lane)) * 32 + r] = acc[tl][i];
-    if (W.bias_slab >= 0) J.bslabs[(size_t)(W.bias_slab + split * W.ks_n + W.ks_idx) * 64 + lane] = bsum;
-    }
+    const int sl = split * W.ks_n + W.ks_idx;   // this wave's slab of its task
+    float* slab = J.slabs + (size_t)(W.slab_base + sl) * (KS * KS * 1024) + W.tap0 * 1024;
+    float* bslab = W.bias_slab >= 0 ? J.bslabs + (size_t)(W.bias_slab + sl) * 64 : nullptr;
+    if constexpr (kM16) wg_store_16x16x32<S>(W, lane, slab, bslab, acc16, bacc);
+    else wg_store_32x32<S>(W, lane, slab, bslab, acc, bsum);
   }
 }
 
@@ -563,17 +588,8 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const WgRedJobs jobs
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// host side: plan construction
-// ------------------------------------------------------------------------------------------------
-static int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-
-struct PlanBuild {
-  std::vector<WgGroup> groups;
-  std::vector<WgTask> tasks;
-  WgHeader hdr;
-};
-
+// ---- host side: plan construction ----
+struct PlanBuild { std::vector<WgGroup> groups; std::vector<WgTask> tasks; WgHeader hdr; };
 static int build_plan(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* convs, PlanBuild& pb) {
   if (!s || !convs || s->nconv <= 0) return set_err(SRGANFD_EINVAL, "wgrad: null shape/convs");
   if (!((s->ksize == 3 && s->stride == 1) || (s->ksize == 4 && s->stride == 2) || (s->ksize == 1 && s->stride == 1) ||
@@ -584,8 +600,9 @@ static int build_plan(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* co
     return set_err(SRGANFD_EINVAL, "wgrad: output dims inconsistent");
   const int KT = s->ksize * s->ksize;
   const int NT = KT;                                   // taps per slab (all of them; one wave covers one kernel row)
-  const int NW = s->ksize == 3 ? 12 : (s->ksize == 4 ? 8 : 4);
-  const int cap = NW / s->ksize;                       // (ci,co) blocks per workgroup
+  const int esize = s->dtype == SRGANFD_F32 ? 4 : 2;
+  const WgGeom g1 = wg_geom(esize, s->ksize, s->stride, 1, 1);   // rows per tile and waves do not depend on the pitches
+  const int cap = g1.nw / s->ksize;                    // (ci,co) blocks per workgroup
   WgHeader& H = pb.hdr;
   memset(&H, 0, sizeof(H));
   H.magic = kWgMagic; H.dtype = s->dtype; H.N = s->n; H.Hin = s->h_in; H.Win = s->w_in; H.up = s->up ? 1 : 0;
@@ -596,8 +613,7 @@ static int build_plan(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* co
   // are bucketed by the 64-channel x range and 64-channel dy range they read (32-channel x range for the
   // 4x4 stride-2 case, whose patch is 4x larger): one workgroup stages those ranges once and its four
   // waves run the bucket's tasks (split over tile rows when a bucket holds fewer than four).
-  const int kTH = (s->stride == 1) ? 8 : 4;
-  H.tiles_y = ceil_div(s->h_out, kTH);
+  H.tiles_y = ceil_div(s->h_out, g1.th);
   H.ntiles = s->n * H.tiles_x * H.tiles_y;
   struct Bucket { int xb, yb; std::vector<int> tasks; std::vector<int> ci_abs, co_abs; };
   std::vector<Bucket> buckets;
@@ -714,27 +730,21 @@ static int build_plan(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* co
   H.bias_slab_off = slab * NT * 1024;
   H.x_upad = 1; H.dy_upad = 1;
   for (auto& g : pb.groups) { if (g.x_units > H.x_upad) H.x_upad = g.x_units; if (g.dy_units > H.dy_upad) H.dy_upad = g.dy_units; }
-  const int UB = 32 * (s->dtype == SRGANFD_F32 ? 4 : 2);
-  const int PR = (kTH - 1) * s->stride + s->ksize, PC = 31 * s->stride + s->ksize;
-  H.lds_bytes = PR * PC * H.x_upad * UB + kTH * 32 * H.dy_upad * UB;
-  if (H.lds_bytes > 160 * 1024) return set_err(SRGANFD_EINVAL, "wgrad: LDS tile %d B too large", H.lds_bytes);
-  H.dma_ok = (s->dtype != SRGANFD_F32 && 2 * H.lds_bytes <= 160 * 1024) ? 1 : 0;
-  // 3x3 stride 2 (A-ESRGAN's encoder): with the four loader waves the workgroup has 1024 threads = 128 VGPRs per lane, and this shape's
-  // addressing does not fit them (10-13 spilled registers, scratch inside the loop); 12 waves with register staging have 168
-  if (s->ksize == 3 && s->stride == 2) H.dma_ok = 0;
+  const WgGeom geom = wg_geom(esize, s->ksize, s->stride, H.x_upad, H.dy_upad);   // the pitches: the widest group's units a side
+  H.lds_bytes = geom.buf_bytes;
+  if (H.lds_bytes > kLdsBudget) return set_err(SRGANFD_EINVAL, "wgrad: LDS tile %d B too large", H.lds_bytes);
+  H.dma_ok = geom.loaders ? 1 : 0;   // loader waves: the shape has the form and every group stages the full pitch (the DMA image is lane-linear)
   for (auto& g : pb.groups) if (g.x_units != H.x_upad || g.dy_units != H.dy_upad) H.dma_ok = 0;
   H.groups_off = (sizeof(WgHeader) + 15) & ~15LL;
   H.tasks_off = (H.groups_off + (long long)sizeof(WgGroup) * H.ngroups + 15) & ~15LL;
   H.total_bytes = (H.tasks_off + (long long)sizeof(WgTask) * H.ntasks + 15) & ~15LL;
   return SRGANFD_OK;
 }
-
 extern "C" size_t srganfd_wgrad_plan_bytes(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* convs) {
   PlanBuild pb;
   if (build_plan(s, convs, pb) != SRGANFD_OK) return 0;
   return (size_t)pb.hdr.total_bytes;
 }
-
 extern "C" int srganfd_wgrad_plan_build(const srganfd_wgrad_shape* s, const srganfd_wgrad_conv* convs, void* plan_host, size_t plan_bytes,
                                         size_t* workspace_bytes) {
   PlanBuild pb;
@@ -748,13 +758,12 @@ extern "C" int srganfd_wgrad_plan_build(const srganfd_wgrad_shape* s, const srga
   if (workspace_bytes) *workspace_bytes = (size_t)(pb.hdr.bias_slab_off + pb.hdr.nbias_slabs * 64) * sizeof(float);
   return SRGANFD_OK;
 }
-
-
-template <typename T, int KS, int STRIDE, int XP, int YP, bool DMA, int VAR>
-static int launch_wgrad4(const WgHeader& H, const WgK& k, hipStream_t stream) {
-  auto kern = wgrad_kernel<T, KS, STRIDE, XP, YP, DMA, VAR>;
+template <typename T, int KS, int STRIDE, int XP, int YP, bool DMA>
+static int launch_wgrad(const WgHeader& H, const WgK& k, hipStream_t stream) {
+  auto kern = wgrad_kernel<T, KS, STRIDE, XP, YP, DMA>;
+  constexpr WgGeom g = wg_geom((int)sizeof(T), KS, STRIDE, XP, YP);
   static int attr_lds[64] = {0};   // per device: the attribute belongs to the device's code object
-  const int lds = DMA ? 2 * H.lds_bytes : H.lds_bytes;
+  const int lds = DMA ? 2 * g.buf_bytes : g.buf_bytes;
   if (!g_dry_run) {
     int dev = 0;
     SRGANFD_HIP_CHECK(hipGetDevice(&dev));
@@ -763,30 +772,28 @@ static int launch_wgrad4(const WgHeader& H, const WgK& k, hipStream_t stream) {
       attr_lds[dev & 63] = lds;
     }
   }
-  SRGANFD_LAUNCH(kern, dim3(k.njobs * H.S * H.ngroups), dim3(64 * (WgWaves<KS>::NW + (DMA ? kLoaderWaves : 0))), lds, stream, k);
+  SRGANFD_LAUNCH(kern, dim3(k.njobs * H.S * H.ngroups), dim3(64 * (g.nw + (DMA ? kLoaderWaves : 0))), lds, stream, k);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
-template <typename T, int KS, int STRIDE, int XP, int YP, bool DMA>
-static int launch_wgrad3(const WgHeader& H, const WgK& k, hipStream_t stream) {
-  if constexpr (sizeof(T) == 2 && KS == 3 && STRIDE == 1 && DMA) {
-    return launch_wgrad4<T, KS, STRIDE, XP, YP, DMA, 3>(H, k, stream);
-  } else {
-    return launch_wgrad4<T, KS, STRIDE, XP, YP, DMA, 0>(H, k, stream);
-  }
+// Every reachable (kernel size, stride, x pitch, dy pitch) once: a stride-2 plan stages one x unit.  The loader-wave kernel where the
+// plan allows it (dma_ok: the shape has the form, wg_geom, and every group stages the full pitch), register staging otherwise.
+template <typename T, int KS, int STRIDE, int XP, int YP> static int launch_wgrad_form(const WgHeader& H, const WgK& k, hipStream_t s) {
+  if constexpr (wg_geom((int)sizeof(T), KS, STRIDE, XP, YP).loaders)
+    if (H.dma_ok) return launch_wgrad<T, KS, STRIDE, XP, YP, true>(H, k, s);
+  return launch_wgrad<T, KS, STRIDE, XP, YP, false>(H, k, s);
 }
-template <typename T, int KS, int STRIDE, int XP, int YP>
-static int launch_wgrad2(const WgHeader& H, const WgK& k, hipStream_t stream) {
-  if constexpr (sizeof(T) == 2) {
-    if constexpr (!(KS == 3 && STRIDE == 2))
-      if (H.dma_ok) return launch_wgrad3<T, KS, STRIDE, XP, YP, true>(H, k, stream);
+template <typename T> static int dispatch_wgrad(const WgHeader& H, const WgK& k, hipStream_t s) {
+  switch (H.ks * 1000 + H.stride * 100 + H.x_upad * 10 + H.dy_upad) {
+    case 3111: return launch_wgrad_form<T, 3, 1, 1, 1>(H, k, s);   case 3112: return launch_wgrad_form<T, 3, 1, 1, 2>(H, k, s);
+    case 3121: return launch_wgrad_form<T, 3, 1, 2, 1>(H, k, s);   case 3122: return launch_wgrad_form<T, 3, 1, 2, 2>(H, k, s);
+    case 3211: return launch_wgrad_form<T, 3, 2, 1, 1>(H, k, s);   case 3212: return launch_wgrad_form<T, 3, 2, 1, 2>(H, k, s);
+    case 4211: return launch_wgrad_form<T, 4, 2, 1, 1>(H, k, s);   case 4212: return launch_wgrad_form<T, 4, 2, 1, 2>(H, k, s);
+    case 2211: return launch_wgrad_form<T, 2, 2, 1, 1>(H, k, s);   case 2212: return launch_wgrad_form<T, 2, 2, 1, 2>(H, k, s);
+    case 1111: return launch_wgrad_form<T, 1, 1, 1, 1>(H, k, s);   case 1112: return launch_wgrad_form<T, 1, 1, 1, 2>(H, k, s);
+    case 1121: return launch_wgrad_form<T, 1, 1, 2, 1>(H, k, s);   case 1122: return launch_wgrad_form<T, 1, 1, 2, 2>(H, k, s);
   }
-  return launch_wgrad3<T, KS, STRIDE, XP, YP, false>(H, k, stream);
-}
-template <typename T, int KS, int STRIDE>
-static int launch_wgrad(const WgHeader& H, const WgK& k, hipStream_t stream) {
-  if (H.x_upad == 2) return H.dy_upad == 2 ? launch_wgrad2<T, KS, STRIDE, 2, 2>(H, k, stream) : launch_wgrad2<T, KS, STRIDE, 2, 1>(H, k, stream);
-  return H.dy_upad == 2 ? launch_wgrad2<T, KS, STRIDE, 1, 2>(H, k, stream) : launch_wgrad2<T, KS, STRIDE, 1, 1>(H, k, stream);
+  return set_err(SRGANFD_EINVAL, "wgrad: no kernel for ksize=%d stride=%d with x / dy pitches %d / %d", H.ks, H.stride, H.x_upad, H.dy_upad);
 }
 
 // the MFMA launch of njobs jobs (1 for srganfd_conv2d_wgrad and srganfd_conv2d_wgrad_partial); jobs past the first were checked by the caller
@@ -812,17 +819,11 @@ static int wgrad_launch_jobs(const srganfd_wgrad_partial_job* jobs, int njobs, h
     return set_err(SRGANFD_EINVAL, "wgrad: a planar view needs c0 and cstride multiples of 32");
   k.x_ps = x.planar ? 32 : x.cstride; k.x_gs = x.planar ? H.Hin * H.Win * 32 : 32;
   k.dy_ps = dy.planar ? 32 : dy.cstride; k.dy_gs = dy.planar ? H.Hout * H.Wout * 32 : 32;
-  k.N = H.N; k.Hin = H.Hin; k.Win = H.Win; k.up = H.up; k.pad = H.pad; k.Hout = H.Hout; k.Wout = H.Wout; k.S = H.S;
-  k.ngroups = H.ngroups; k.x_upad = H.x_upad; k.dy_upad = H.dy_upad; k.ntiles = H.ntiles; k.tiles_x = H.tiles_x; k.tiles_y = H.tiles_y;
-  int rc;
-#define WG_BY_TYPE(KS_, S_) (H.dtype == SRGANFD_BF16 ? launch_wgrad<bf16_t, KS_, S_>(H, k, stream) : H.dtype == SRGANFD_F16 ? launch_wgrad<f16_t, KS_, S_>(H, k, stream) : launch_wgrad<float, KS_, S_>(H, k, stream))
-  if (H.ks == 3 && H.stride == 1) rc = WG_BY_TYPE(3, 1);
-  else if (H.ks == 3) rc = WG_BY_TYPE(3, 2);
-  else if (H.ks == 4) rc = WG_BY_TYPE(4, 2);
-  else if (H.ks == 2) rc = WG_BY_TYPE(2, 2);
-  else rc = WG_BY_TYPE(1, 1);
-#undef WG_BY_TYPE
-  return rc;
+  k.Hin = H.Hin; k.Win = H.Win; k.up = H.up; k.pad = H.pad; k.Hout = H.Hout; k.Wout = H.Wout; k.S = H.S;
+  k.ngroups = H.ngroups; k.ntiles = H.ntiles; k.tiles_x = H.tiles_x; k.tiles_y = H.tiles_y;
+  if (H.dtype == SRGANFD_BF16) return dispatch_wgrad<bf16_t>(H, k, stream);
+  if (H.dtype == SRGANFD_F16) return dispatch_wgrad<f16_t>(H, k, stream);
+  return dispatch_wgrad<float>(H, k, stream);
 }
 
 // shared by srganfd_conv2d_wgrad (grads != NULL) and srganfd_conv2d_wgrad_partial (grads == NULL)
@@ -866,7 +867,6 @@ extern "C" int srganfd_conv2d_wgrad(const void* plan_host, const void* plan_dev,
   if (!grads) return srganfd::set_err(SRGANFD_EINVAL, "wgrad: null gradient pointer (srganfd_conv2d_wgrad_partial is the reduce-later form)");
   return wgrad_impl(plan_host, plan_dev, x, dy, grads, scalars, workspace, workspace_bytes, (hipStream_t)stream);
 }
-
 extern "C" int srganfd_wgrad_reduce_batch(const srganfd_wgrad_reduce_job* jobs, int32_t njobs, void* stream) {
   if (!jobs || njobs <= 0 || njobs > kRedBatch) return set_err(SRGANFD_EINVAL, "wgrad_reduce_batch: 1..%d jobs", kRedBatch);
   WgRedJobs J;

@@ -189,6 +189,40 @@ def test_conv2d_dgrad_orientation(dtype, mfma16):
     _assert_close(dxb.permute(0, 3, 1, 2), x.grad, dtype, "dgrad")
 
 
+def _wg(k, s, p, cin, cout, **kw):
+    """a weight-gradient case whose OUTPUT image is 9 x 35: rows and columns both ragged against the 8- (stride 1) or 4-row (stride 2)
+    by 32-pixel tile"""
+    return dict(n=1, h=9 * s, w=35 * s, cin=cin, cout=cout, k=k, s=s, p=p, **kw)
+
+
+# One case per path of the plan's arithmetic (cin / cout are the padded channel counts the plan sees).  A 64-channel range that holds
+# one 32-channel unit beside ranges that hold two ("mixed units") keeps a 16-bit launch off the loader waves: register staging.
+_WGRAD_PATH_CASES = [
+    _wg(3, 1, 1, 32, 32),      # x pitch 1 / dy pitch 1, loader waves
+    _wg(3, 2, 1, 32, 32),      # dy pitch 1 (3x3 stride 2 never takes the loader waves)
+    _wg(3, 2, 1, 64, 64),      # dy pitch 2
+    _wg(3, 2, 1, 32, 96),      # mixed dy units
+    _wg(4, 2, 1, 64, 32),      # dy pitch 1, loader waves
+    _wg(4, 2, 1, 64, 96),      # mixed units: register staging in 16-bit
+    _wg(2, 2, 0, 32, 32),      # dy pitch 1
+    _wg(2, 2, 0, 64, 64),      # dy pitch 2
+    _wg(2, 2, 0, 32, 96),      # mixed dy units
+    _wg(1, 1, 0, 32, 32),      # pitches 1 / 1
+    _wg(1, 1, 0, 64, 64),      # pitches 2 / 2
+    _wg(1, 1, 0, 32, 64),      # pitches 1 / 2
+    _wg(1, 1, 0, 96, 32),      # x pitch 2, mixed units
+]
+# Several tiles per workgroup (12 tiles at stride 1, 18 at stride 2): with one split a workgroup goes round the double buffer many
+# times, with two each makes half the trips.  Per kernel shape one case with equal units everywhere (the loader waves, where the shape
+# has them) and one with mixed units.
+_WGRAD_MULTI_TILE_CASES = [
+    dict(_wg(k, s, p, cin, cout), n=3, splits=splits)
+    for k, s, p, cin, cout in [(3, 1, 1, 64, 64), (3, 1, 1, 96, 32), (3, 2, 1, 64, 64), (3, 2, 1, 32, 96), (4, 2, 1, 64, 32),
+                               (4, 2, 1, 64, 96), (2, 2, 0, 64, 64), (2, 2, 0, 32, 96), (1, 1, 0, 64, 64), (1, 1, 0, 96, 32)]
+    for splits in (1, 2)
+]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", [
     dict(n=2, h=16, w=16, cin=64, cout=32),
@@ -200,13 +234,13 @@ def test_conv2d_dgrad_orientation(dtype, mfma16):
     dict(n=1, h=16, w=16, cin=64, cout=3),
     dict(n=1, h=16, w=24, cin=64, cout=128, k=4, s=2),
     dict(n=3, h=8, w=8, cin=256, cout=128, splits=3),
-])
+] + _WGRAD_PATH_CASES + _WGRAD_MULTI_TILE_CASES)
 def test_conv2d_wgrad(dtype, case):
     from sr_gan_fd_amd import _abi as A, ops
     torch.manual_seed(3)
     dt = ops.DT[dtype]
     n, h, w, cin, cout = case["n"], case["h"], case["w"], case["cin"], case["cout"]
-    k, s, p, up = case.get("k", 3), case.get("s", 1), 1, case.get("up", 0)
+    k, s, p, up = case.get("k", 3), case.get("s", 1), case.get("p", 1), case.get("up", 0)
     x = torch.randn(n, cin, h, w)
     wt = torch.zeros(cout, cin, k, k, dtype=torch.float64, requires_grad=True)
     b = torch.zeros(cout, dtype=torch.float64, requires_grad=True)

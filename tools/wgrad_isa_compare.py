@@ -1,0 +1,122 @@
+"""Device assembly of wgrad.hip, one tree against another, per kernel (the method of profiles/conv_igemm_refactor_isa.txt).
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I. --offload-device-only -S -o parent.s <parent>/wgrad.hip      (same for the branch)
+    python tools/wgrad_isa_compare.py parent.s branch.s > profiles/wgrad_refactor_isa.txt
+
+Kernels are matched by template arguments <T, KS, STRIDE, XP, YP, DMA>; a seventh argument (the parent's VAR) is dropped.  Per kernel:
+the .amdhsa_kernel block, and the counts of MFMA, LDS, global / flat / scratch memory, buffer, s_waitcnt and s_barrier instructions.
+A working tool, not a test."""
+import collections
+import re
+import sys
+
+NAME = re.compile(r"wgrad_kernelI(t|DF16_|f)Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E(?:Li(\d+)E)?E")
+TYPES = {"t": "bf16", "DF16_": "f16", "f": "f32"}
+CLASSES = [("mfma", r"v_mfma"), ("lds", r"ds_"), ("global", r"(global|flat|scratch)_"), ("buffer", r"buffer_"), ("s_waitcnt", r"s_waitcnt"),
+           ("s_barrier", r"s_barrier")]
+WAVE_STEPS = [64, 72, 80, 96, 128, 168, 256, 512]   # VGPRs per lane at which one more wave per SIMD is lost (512 registers, granule 8)
+
+
+def waves(v):
+    return 8 - next(i for i, s in enumerate(WAVE_STEPS) if v <= s)
+
+
+def label(sym):
+    m = NAME.search(sym)
+    if not m:
+        return sym, None
+    t, ks, st, xp, yp, dma, var = m.groups()
+    return "wgrad_kernel<%s, KS=%s, STRIDE=%s, XP=%s, YP=%s, DMA=%s>" % (TYPES[t], ks, st, xp, yp, dma), var
+
+
+def parse(path):
+    out, cur, body, meta, in_meta = {}, None, [], [], False
+    for line in open(path):
+        s = line.strip()
+        m = re.match(r"^(_ZN7srganfd\w+):", line)
+        if m:
+            cur, body, meta = m.group(1), [], []
+            continue
+        if cur is None:
+            continue
+        if s.startswith(".amdhsa_kernel "):
+            in_meta = True
+            continue
+        if s == ".end_amdhsa_kernel":
+            name, var = label(cur)
+            ops = [re.sub(r"\s*;.*$", "", b).replace(cur, "@") for b in body]
+            ops = [re.sub(r"\.LBB\d+_", ".LBB_", o) for o in ops]
+            md = dict(x.split(None, 1) for x in meta)
+            out[name] = dict(var=var, ops=ops, meta=md)
+            cur, in_meta = None, False
+            continue
+        if in_meta:
+            meta.append(s)
+        elif s and not s.startswith((".", ";")) and not s.endswith(":"):
+            body.append(s)
+    return out
+
+
+def counts(ops):
+    c = collections.OrderedDict((k, 0) for k, _ in CLASSES)
+    for o in ops:
+        for k, pat in CLASSES:
+            if re.match(pat, o):
+                c[k] += 1
+                break
+    return c
+
+
+def res(md):
+    return "vgpr %s sgpr %s scratch %s lds %s kernarg %s" % (md[".amdhsa_next_free_vgpr"], md[".amdhsa_next_free_sgpr"],
+                                                          md[".amdhsa_private_segment_fixed_size"], md[".amdhsa_group_segment_fixed_size"],
+                                                          md[".amdhsa_kernarg_size"])
+
+
+def main():
+    P, B = parse(sys.argv[1]), parse(sys.argv[2])
+    only_p, only_b = sorted(set(P) - set(B)), sorted(set(B) - set(P))
+    print("# parent: %d kernels, branch: %d kernels; only in parent: %d, only in branch: %d" % (len(P), len(B), len(only_p), len(only_b)))
+    for n in only_p:
+        print("only in parent: %s (VAR %s): %s" % (n, P[n]["var"], res(P[n]["meta"])))
+    for n in only_b:
+        print("only in branch: %s: %s" % (n, res(B[n]["meta"])))
+    print("# per kernel: instruction stream / .amdhsa_kernel block (kernarg size aside) / resources parent | branch")
+    bad = []
+    n_same, n_meta = 0, 0
+    for n in sorted(set(P) & set(B)):
+        p, b = P[n], B[n]
+        same = p["ops"] == b["ops"]
+        mp = {k: v for k, v in p["meta"].items() if k != ".amdhsa_kernarg_size"}
+        mb = {k: v for k, v in b["meta"].items() if k != ".amdhsa_kernarg_size"}
+        msame = mp == mb
+        n_same += same
+        n_meta += msame
+        var = " (parent VAR %s)" % p["var"] if p["var"] is not None else ""
+        print("%s%s: stream %s, metadata %s, %s | %s" % (n, var, "identical" if same else "DIFFERS", "identical" if msame else "DIFFERS",
+                                                         res(p["meta"]), res(b["meta"])))
+        cp, cb = counts(p["ops"]), counts(b["ops"])
+        vp, vb = int(p["meta"][".amdhsa_next_free_vgpr"]), int(b["meta"][".amdhsa_next_free_vgpr"])
+        sp, sb = int(p["meta"][".amdhsa_private_segment_fixed_size"]), int(b["meta"][".amdhsa_private_segment_fixed_size"])
+        if cp != cb:
+            bad.append(n + ": instruction-class counts differ")
+        if sb > sp:
+            bad.append(n + ": gains scratch")
+        if waves(vb) < waves(vp):
+            bad.append(n + ": crosses a wave-occupancy step (%d -> %d VGPRs)" % (vp, vb))
+        if "DMA=1" in n and vb > 128 and vb > vp:
+            bad.append(n + ": loader-wave kernel above 128 VGPRs")
+        if not same:
+            print("    instructions %d | %d" % (len(p["ops"]), len(b["ops"])))
+            for k in cp:
+                print("    %s %d | %d" % (k, cp[k], cb[k]))
+            op, ob = collections.Counter(o.split()[0] for o in p["ops"]), collections.Counter(o.split()[0] for o in b["ops"])
+            print("    per opcode (differing only): " + ", ".join("%s %d|%d" % (k, op[k], ob[k]) for k in sorted(set(op) | set(ob)) if op[k] != ob[k]))
+    print("# identical streams: %d of %d; identical metadata (kernarg size aside): %d of %d" % (n_same, len(set(P) & set(B)), n_meta, len(set(P) & set(B))))
+    print("# requirements not met: %d" % len(bad))
+    for x in bad:
+        print("#   " + x)
+
+
+if __name__ == "__main__":
+    main()
