@@ -77,21 +77,37 @@ template <int RPW> struct DcGeo {
   static constexpr int StageHalo = (WaveItems > 64 ? WaveItems : 64) * 16;       // per wave: its halo items (a full 64-lane piece first), ...
   static constexpr int StageWave = StageHalo + 256;                 // ... then one flag word per lane
   static constexpr int CtlOff = StageOff + 4 * StageWave;           // float alpha[8]; float bias[6][32]; int tab[6][32]
-  static constexpr int Lds = CtlOff + 32 + kDcMaxLayers * 32 * 4 + kDcMaxLayers * 128;      // 162,080 / 124,000 B
+  static constexpr int CtlBiasOff = CtlOff + 32, CtlTabOff = CtlBiasOff + kDcMaxLayers * 32 * 4;
+  static constexpr int Lds = CtlTabOff + kDcMaxLayers * 128;      // 162,080 / 124,000 B
 };
 constexpr int kDcThreads = 384;      // waves 0-3 compute, 4-5 weight loaders
 constexpr int kDcMaxTiles = 16384;   // tiles of one call (flags: 4 growth layers x tiles)
 
-struct DcLayer {
+struct DcLayer {             // what the kernel reads of a layer straight from the kernel arguments (the loader waves, the prologue)
   const char* w;             // this 32-channel n-tile of the packed operand: [chunk][tap][channel half][64 lanes x 16 B]
   const float* bias;         // its 32 bias values, or null
   const float* alpha_dev;
-  char* y; const char* r1; const char* r2; const char* mask;       // image-0 bases
-  int yC, y_c0, y_ps, y_gs, r1C, r1_c0, r1_ps, r1_gs, r2C, r2_c0, r2_ps, r2_gs, mC, m_c0, m_ps, m_gs;    // elements (see ConvK)
+  int nChunks; float alpha;
+};
+// A view of an image-0 base as the table holds it: the pointer's two halves, then elements (see ConvK)
+struct DcView { unsigned lo, hi; int C, ps, gs, c0; };
+// One layer's row of the per-layer table: 32 words, copied to LDS once (kernel-argument loads in the layer loop measured ~0.7k cycles
+// per dependent round) and read there in 16-byte groups (DcWords): words [0, 8) the scalars, [8, 20) the output view and operand A,
+// [20, 28) operand B.  Floats are held as such: the copy moves words.
+struct DcTab {
   int nChunks;
   int dst_group;             // >= 0: growth layer -- the output is also group dst_group of the resident patch and its halo is exchanged
-  float alpha, neg, post_scale, r1s, r2s, mask_slope;     // neg: factor of the negative side of the activation (slope / 0 / 1)
+  int kind;                  // epilogue kind, see DcKind
+  float ps_pos, ps_neg;      // post_scale (the activation's positive side), post_scale * (slope / 0 / 1) (its negative side)
+  float r1s, r2s, mask_slope;
+  DcView y, opA, opB;        // output; operand A = r1 or mask; operand B = r2.  An absent operand holds the output's view: any valid one
+  int unused[6];
 };
+constexpr int kDcTabWords = sizeof(DcTab) / 4;
+#define DC_W(field) ((int)(offsetof(DcTab, field) / 4))       // word index of a field of the row
+static_assert(sizeof(DcTab) == 128 && sizeof(DcView) == 24, "a table row is 32 words, a view 6");
+static_assert(DC_W(mask_slope) == 7 && DC_W(y) == 8 && DC_W(opA) + 6 == 20 && DC_W(opB) == 20 && DC_W(opB) + 6 <= 28,
+              "the 16-byte groups the kernel reads: scalars [0, 8), y + operand A [8, 20), operand B [20, 28)");
 struct DcK {
   DcLayer L[kDcMaxLayers];
   const char* x;             // image-0 base of the block input (groups 0, 1)
@@ -101,69 +117,49 @@ struct DcK {
   int rpw;                   // rows per compute wave: 4 (16 x 16 tiles) or 2 (8 x 16 tiles), see DcGeo
   int ipl;                   // images per pass (the grid is ipl * tpi workgroups)
   int totalTiles;            // N * tpi
-  int tab[kDcMaxLayers][32]; // per layer, copied to LDS once (kernel-argument loads in the layer loop measured ~0.7k cycles per dependent round):
-                             // 0 nChunks, 1 dst_group, 2 epilogue kind, 3 post_scale (+), 4 post_scale * neg (-), 5 r1s, 6 r2s, 7 mask_slope (floats as bits),
-                             // 8-9 y, 10 yC, 11 y_ps, 12 y_gs, 13 y_c0, 14-15 operand A (r1 or mask), 16 its C, 17 ps, 18 gs, 19 c0, 20-21 r2, 22 r2C, 23 r2_ps, 24 r2_gs, 25 r2_c0
+  DcTab tab[kDcMaxLayers];
   int* hdr;                  // [0] hand-off waits that gave up, [1] epoch of the last finished launch, [2] workgroups finished in this launch
   int* flags;                // [growth layer][tile of the batch], epoch-valued
 };
 
 __device__ __forceinline__ unsigned dc_lds_addr(const void* p) { return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
 // One LDS-DMA piece (see wgrad.hip glds16): 64 lanes x 16 bytes, per-lane source, wave-uniform LDS destination; outside the
 // compiler's wait-count bookkeeping, the loader waves count vmcnt themselves.
-__device__ __forceinline__ void dc_glds16(const void* gsrc, unsigned lds_dst) {
+// BYTES per lane: 16 or 4.  SC1: the hand-off's loads, with the sc1 policy (served by memory, never a stale L1 / L2 line).
+template <int BYTES, bool SC1> __device__ __forceinline__ void dc_glds(const void* gsrc, unsigned lds_dst) {
+  static_assert(BYTES == 16 || (BYTES == 4 && SC1), "the forms the kernel uses");
   const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(gsrc), "s"(dst) : "m0", "memory");
-#pragma clang diagnostic pop
-}
-// the hand-off's loads: the same LDS-DMA with the sc1 policy (served by memory, never a stale L1 / L2 line); 16 bytes or one dword per lane
-__device__ __forceinline__ void dc_glds16_sc1(const void* gsrc, unsigned lds_dst) {
-  const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc1" : : "v"(gsrc), "s"(dst) : "m0", "memory");
-#pragma clang diagnostic pop
-}
-__device__ __forceinline__ void dc_glds4_sc1(const void* gsrc, unsigned lds_dst) {
-  const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off sc1" : : "v"(gsrc), "s"(dst) : "m0", "memory");
-#pragma clang diagnostic pop
+#define DC_GLDS(OP, POLICY) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_" OP " %0, off" POLICY : : "v"(gsrc), "s"(dst) : "m0", "memory")
+  if constexpr (BYTES == 4) DC_GLDS("dword", " sc1");
+  else if constexpr (SC1) DC_GLDS("dwordx4", " sc1");
+  else DC_GLDS("dwordx4", "");
+#undef DC_GLDS
 }
 // 16-byte write-through store (no 16-byte atomic store exists; inline assembly, so the compiler's vmcnt bookkeeping does not see it:
 // the hand-off drains with an explicit vmcnt(0) before the flag is published, and a kernel's stores are complete when it ends)
 __device__ __forceinline__ void dc_store16_sc1(void* dst, const u32x4 v) {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
   // the s_nop is the gfx9 wait state between a store of more than 8 bytes and a VALU write of its data registers (the hazard
   // recognizer inserts it for its own stores; it cannot see into this one, and the epilogue reuses the registers at once)
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-#pragma clang diagnostic pop
 }
 template <int N> __device__ __forceinline__ void dc_wait_vm() {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#pragma clang diagnostic pop
 }
 // at most 3 * younger_steps of this loader's pieces may still be in flight (the ring holds the step being read and SLOTS - 1 more:
 // when step t + 1 must have landed, steps t + 2 .. t + SLOTS - 1 are younger)
-template <int SLOTS> __device__ __forceinline__ void dc_wait_pieces(int younger_steps) {
-  constexpr int kMax = SLOTS - 2;
-  if (younger_steps >= kMax) dc_wait_vm<3 * kMax>();
-  else if (younger_steps == 5) dc_wait_vm<15>(); else if (younger_steps == 4) dc_wait_vm<12>(); else if (younger_steps == 3) dc_wait_vm<9>();
-  else if (younger_steps == 2) dc_wait_vm<6>(); else if (younger_steps == 1) dc_wait_vm<3>(); else dc_wait_vm<0>();
+// SLOTS - 2 or more younger steps in the stream's body; SLOTS - 3, ... 1, none in its tail: one case per N, down from SLOTS - 2.
+template <int SLOTS, int N = SLOTS - 2> __device__ __forceinline__ void dc_wait_pieces(int younger_steps) {
+  if constexpr (N == 0) dc_wait_vm<0>();
+  else if (N == SLOTS - 2 ? younger_steps >= N : younger_steps == N) dc_wait_vm<3 * N>();
+  else dc_wait_pieces<SLOTS, N - 1>(younger_steps);
 }
 // workgroup barrier that leaves vector-memory operations in flight (LDS operations of this wave are complete when it is passed)
 __device__ __forceinline__ void dc_barrier() {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma clang diagnostic pop
 }
+#pragma clang diagnostic pop
 // byte position of (patch row, patch column, 16-byte slot) inside one group: pixel-major, slot XOR 2 * ((column >> 2) & 1) -- the
 // column-keyed swizzle of conv_igemm.hip's 16x16x32 fragment reads (conflict-free ds_read_b128 for every kernel column)
 __device__ __forceinline__ int dc_pos(int prow, int pcol, int slot) { return (prow * kDcPC + pcol) * 64 + ((slot ^ (((pcol >> 2) & 1) << 1)) << 4); }
@@ -172,8 +168,30 @@ template <int TR> __device__ __forceinline__ void dc_halo_rc(int hp, int& prow, 
   prow = hp < 18 ? 0 : (hp < 36 ? TR + 1 : (hp < 36 + TR ? 1 + hp - 36 : 1 + hp - 36 - TR));
   pcol = hp < 18 ? hp : (hp < 36 ? hp - 18 : (hp < 36 + TR ? 0 : 17));
 }
-
-typedef unsigned long long dc_u64;
+// words [W0, W0 + 4 N) of a table row in LDS, read as N 16-byte loads; at<DC_W(field)>() is the field's word, wave-uniform (an SGPR)
+template <int W0, int N> struct DcWords {
+  static_assert(W0 % 4 == 0 && W0 + 4 * N <= kDcTabWords, "whole 16-byte groups of one row");
+  int w[4 * N];
+  __device__ __forceinline__ explicit DcWords(const int* row) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) { const int4 v = *(const int4*)(row + W0 + 4 * q); w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
+  }
+  template <int W> __device__ __forceinline__ int at() const {
+    static_assert(W >= W0 && W < W0 + 4 * N, "a word of another group");
+    return __builtin_amdgcn_readfirstlane(w[W - W0]);
+  }
+  template <int W> __device__ __forceinline__ float f() const { return __builtin_bit_cast(float, at<W>()); }
+  // the view's pointer, in the global address space spelled out: a pointer assembled from two table words is generic to the compiler,
+  // and a FLAT load also counts on lgkmcnt -- the next barrier's lgkmcnt(0) would wait for the operands' whole memory latency
+  template <typename GT, int W> __device__ __forceinline__ GT* ptr() const { return (GT*)(((unsigned long long)(unsigned)at<W + 1>() << 32) | (unsigned)at<W>()); }
+};
+#define DC_V(field) ((int)(offsetof(DcView, field) / 4))
+// element (image at element offset img * C, pixel p0, 16-byte slot sl16 of the view's first 32 channels) of the view at words W .. W + 5
+// (channel offsets are multiples of 32, checked on the host: the second channel half is 16 elements on)
+template <int W, class Words, typename GT> __device__ __forceinline__ GT* dc_view_at(const Words& tw, GT* base, size_t img, int p0, int sl16) {
+  const int ps = tw.template at<W + DC_V(ps)>();
+  return base + img * tw.template at<W + DC_V(C)>() + ((size_t)p0 * ps + (size_t)(tw.template at<W + DC_V(c0)>() >> 5) * tw.template at<W + DC_V(gs)>() + 8 * sl16);
+}
 typedef __attribute__((ext_vector_type(2))) unsigned int dc_u32x2;
 
 template <typename T> __device__ __forceinline__ void dc_widen4(const dc_u32x2 q, float* f) {
@@ -196,6 +214,99 @@ template <typename T> __device__ __forceinline__ dc_u32x2 dc_narrow4(const float
     return dc_u32x2{(unsigned)f2bf(v4[0]) | ((unsigned)f2bf(v4[1]) << 16), (unsigned)f2bf(v4[2]) | ((unsigned)f2bf(v4[3]) << 16)};
   }
 }
+
+// The epilogue kind of a layer (DcTab::kind, dense_chain_fill) as its three compile-time constants.
+template <int KIND> struct DcKind {
+  static constexpr int OPS = KIND & 3;                // operands: 0 none, 1 mask, 2 r1, 3 r1 + r2
+  static constexpr bool GROWTH = (KIND & 4) != 0;     // also group dst_group of the patch and a write-through store
+  static constexpr bool MAXACT = (KIND & 8) != 0;     // the activation as max(v * pos, v * neg)
+};
+// what a lane's epilogue of one layer reads beside its accumulators and operand registers
+template <typename T> struct DcEpi {
+  float alpha, ps_pos, ps_neg, r1s, r2s, mslope;
+  f32x4_t b0, b1;                                     // bias of the lane's channel quad in the two 16-channel halves
+  char* lds_out;                                      // its 16-byte slot of its first row in the patch group a growth layer writes
+  __attribute__((address_space(1))) T* y;             // its first output element (row RPW cw, 16-byte slot {0, 2, 1, 3}[g4] of its pixel)
+  int yrow;                                           // elements per image row of the output
+  bool col_ok; int orow0, H;                          // its column lies in the image; its first row; the image's rows
+};
+// lane = pixel l15 of rows RPW cw + m, channels 16 nh + 4 g4 .. + 3 per accumulator.  The two 8-byte channel quads of a lane
+// (nh = 0 / 1) are turned into ONE 16-byte slot by v_permlane16_swap (lane row g4 ends up with slot {0, 2, 1, 3}[g4] of its pixel): one
+// 16-byte LDS write and one 16-byte store per pixel instead of two 8-byte ones each
+template <typename T, int RPW, bool GROWTH, int OPS, bool MAXACT>
+__device__ __forceinline__ void dc_epilogue(const f32x4_t (&acc)[RPW][2], const u32x4* rA, const u32x4* rB, const DcEpi<T>& e) {
+#pragma unroll
+  for (int m = 0; m < RPW; ++m) {
+    const bool ok = e.col_ok && e.orow0 + m < e.H;
+    dc_u32x2 pk[2], eA[2], eB[2];
+    if constexpr (OPS >= 1) {
+      const dc_u32x2 ux = __builtin_amdgcn_permlane16_swap(rA[m].x, rA[m].z, false, false), uy = __builtin_amdgcn_permlane16_swap(rA[m].y, rA[m].w, false, false);
+      eA[0] = dc_u32x2{ux.x, uy.x}; eA[1] = dc_u32x2{ux.y, uy.y};
+    }
+    if constexpr (OPS == 3) {
+      const dc_u32x2 ux = __builtin_amdgcn_permlane16_swap(rB[m].x, rB[m].z, false, false), uy = __builtin_amdgcn_permlane16_swap(rB[m].y, rB[m].w, false, false);
+      eB[0] = dc_u32x2{ux.x, uy.x}; eB[1] = dc_u32x2{ux.y, uy.y};
+    }
+#pragma unroll
+    for (int nh = 0; nh < 2; ++nh) {
+      float v4[4], t4[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float v = __builtin_fmaf(e.alpha, acc[m][nh][i], nh ? e.b1[i] : e.b0[i]);
+        // v * (v > 0 ? pos : neg); with pos >= neg >= 0 that is max(v * pos, v * neg): two multiplies and a max, no compare / select pair
+        if constexpr (MAXACT) v4[i] = __builtin_fmaxf(v * e.ps_pos, v * e.ps_neg);
+        else v4[i] = v * (v > 0.f ? e.ps_pos : e.ps_neg);
+      }
+      if constexpr (OPS >= 2) { dc_widen4<T>(eA[nh], t4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v4[i] = __builtin_fmaf(e.r1s, t4[i], v4[i]); }
+      if constexpr (OPS == 3) { dc_widen4<T>(eB[nh], t4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v4[i] = __builtin_fmaf(e.r2s, t4[i], v4[i]); }
+      if constexpr (OPS == 1) { dc_widen4<T>(eA[nh], t4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v4[i] *= t4[i] > 0.f ? 1.f : e.mslope; }
+      pk[nh] = dc_narrow4<T>(v4);
+      if (!ok) pk[nh] = dc_u32x2{0u, 0u};      // pixels beyond the image are zero padding for the layers that follow
+    }
+    const dc_u32x2 sx = __builtin_amdgcn_permlane16_swap(pk[0].x, pk[1].x, false, false);
+    const dc_u32x2 sy = __builtin_amdgcn_permlane16_swap(pk[0].y, pk[1].y, false, false);
+    const u32x4 q = {sx.x, sy.x, sx.y, sy.y};      // lower quad (both dwords), then upper quad of this lane's 16-byte slot
+    if constexpr (GROWTH) *(u32x4*)(e.lds_out + m * (kDcPC * 64)) = q;
+    if (ok) {
+      __attribute__((address_space(1))) T* dst = e.y + (size_t)m * e.yrow;
+      // growth layers: write-through (sc1), the neighbours read the halo from memory inside this launch
+      if constexpr (GROWTH) dc_store16_sc1((void*)dst, q);
+      else *(__attribute__((address_space(1))) u32x4*)dst = q;
+    }
+  }
+}
+// Control-table prologue of compute wave cw: the per-layer table, alpha and bias from the kernel arguments and memory into LDS, once.
+template <int RPW> __device__ __forceinline__ void dc_ctl_prologue(const DcK& a, char* smem, int cw, int lane) {
+  float* const ctl_alpha = (float*)(smem + DcGeo<RPW>::CtlOff);
+  float* const ctl_bias = (float*)(smem + DcGeo<RPW>::CtlBiasOff);
+  int* const ctl_tab = (int*)(smem + DcGeo<RPW>::CtlTabOff);
+  if (cw == 3) {      // the per-layer table: one dword per lane and round straight from the kernel-argument segment
+#pragma unroll
+    for (int r = 0; r < kDcMaxLayers * kDcTabWords / 64; ++r)
+      ctl_tab[lane + 64 * r] = ((const __attribute__((address_space(4))) int*)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(DcK, tab) / 4 + lane + 64 * r];
+  }
+  // all six layers' loads first, then the LDS writes: one memory round trip instead of one per layer
+  float bv[kDcMaxLayers], av[kDcMaxLayers];
+#pragma unroll
+  for (int l = 0; l < kDcMaxLayers; ++l) {
+    const bool mine = l < a.nLayers && cw == (l & 3);
+    bv[l] = mine && lane < 32 && a.L[l].bias ? a.L[l].bias[lane] : 0.f;
+    av[l] = mine && lane == 32 && a.L[l].alpha_dev ? *a.L[l].alpha_dev : 1.f;
+  }
+#pragma unroll
+  for (int l = 0; l < kDcMaxLayers; ++l) {
+    if (l < a.nLayers && cw == (l & 3)) {
+      if (lane < 32) ctl_bias[l * 32 + lane] = bv[l];
+      if (lane == 32) ctl_alpha[l] = a.L[l].alpha * av[l];
+    }
+  }
+}
 }  // namespace
 
 template <typename T, int RPW>
@@ -208,8 +319,8 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
   char* const patch = smem;
   char* const ring = smem + Geo::RingOff;
   float* const ctl_alpha = (float*)(smem + Geo::CtlOff);
-  float* const ctl_bias = (float*)(smem + Geo::CtlOff + 32);
-  int* const ctl_tab = (int*)(smem + Geo::CtlOff + 32 + kDcMaxLayers * 32 * 4);
+  float* const ctl_bias = (float*)(smem + Geo::CtlBiasOff);
+  int* const ctl_tab = (int*)(smem + Geo::CtlTabOff);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, g4 = lane >> 4;
@@ -252,7 +363,7 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
 
   if (wave >= 4) {
     // =====================================================  LOADER WAVES  =====================================================
-    // the weight stream: per kernel-column step this wave's three 1 KB pieces of the 6 KB slot, five steps ahead of the step that reads them
+    // the weight stream: per kernel-column step this wave's three 1 KB pieces of the 6 KB slot, Slots - 1 steps ahead of the step that reads them
     const int ld = wave - 4;               // pieces {0, 1, 2} / {3, 4, 5}: piece q = (kernel row q >> 1, channel half q & 1)
     int pl = 0, pc = 0, pk = 0, pt = 0;    // producer cursor = the next step to request
     auto issue_next = [&]() {
@@ -262,7 +373,7 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           const int q = 3 * ld + j;
-          dc_glds16(wl + ((q >> 1) * 6144 + (q & 1) * 1024), dst + q * 1024);
+          dc_glds<16, false>(wl + ((q >> 1) * 6144 + (q & 1) * 1024), dst + q * 1024);
         }
         ++pt;
         if (++pk == 3) { pk = 0; if (++pc == a.L[pl].nChunks) { pc = 0; if (++pl == a.nLayers) pl = 0; } }
@@ -278,7 +389,7 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
       dc_barrier();
 #pragma unroll 1
       for (int i = 0; i < a.stepsPerPass; ++i) {
-        dc_wait_pieces<kDcSlots>(totalSteps - 2 - t);   // this wave's pieces of step t + 1 have landed: only those of steps t + 2 .. t + 4 are younger
+        dc_wait_pieces<kDcSlots>(totalSteps - 2 - t);   // this wave's pieces of step t + 1 have landed: only those of steps t + 2 .. t + Slots - 1 are younger
         dc_barrier();                         // slot t + 1 is complete for everybody; slot t is free (its fragments are in registers)
         issue_next();                         // step t + SLOTS into it
         ++t;
@@ -289,28 +400,7 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
     const int cw = wave;                   // rows RPW cw .. RPW cw + RPW - 1 of the tile
     // launch constants: epoch (polls and the publish use it), bias / alpha table
     const int epoch = __hip_atomic_load(a.hdr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-    if (cw == 3) {      // the per-layer table: one dword per lane and round straight from the kernel-argument segment
-#pragma unroll
-      for (int r = 0; r < kDcMaxLayers * 32 / 64; ++r)
-        ctl_tab[lane + 64 * r] = ((const __attribute__((address_space(4))) int*)__builtin_amdgcn_kernarg_segment_ptr())[offsetof(DcK, tab) / 4 + lane + 64 * r];
-    }
-    {
-      // all six layers' loads first, then the LDS writes: one memory round trip instead of one per layer
-      float bv[kDcMaxLayers], av[kDcMaxLayers];
-#pragma unroll
-      for (int l = 0; l < kDcMaxLayers; ++l) {
-        const bool mine = l < a.nLayers && cw == (l & 3);
-        bv[l] = mine && lane < 32 && a.L[l].bias ? a.L[l].bias[lane] : 0.f;
-        av[l] = mine && lane == 32 && a.L[l].alpha_dev ? *a.L[l].alpha_dev : 1.f;
-      }
-#pragma unroll
-      for (int l = 0; l < kDcMaxLayers; ++l) {
-        if (l < a.nLayers && cw == (l & 3)) {
-          if (lane < 32) ctl_bias[l * 32 + lane] = bv[l];
-          if (lane == 32) ctl_alpha[l] = a.L[l].alpha * av[l];
-        }
-      }
-    }
+    dc_ctl_prologue<RPW>(a, smem, cw, lane);
     const int rowoff = (RPW * cw) * kDcPC * 64;
     // this wave's share of a group's halo ring: items 68 cw .. 68 cw + 67 (item = 4 * halo pixel + 16-byte slot), two rounds of lanes
     int h_off[2], h_gp[2], h_slot[2]; bool h_in[2];
@@ -345,7 +435,7 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
     };
 
     __builtin_amdgcn_s_setprio(2);
-    int t = 0;        // kernel-column steps consumed so far (all passes): ring slot t % 6
+    int t = 0;        // kernel-column steps consumed so far (all passes): step t reads ring slot t % Geo::Slots
     int giveups = 0;
     const int orow0 = oy0 + RPW * cw, ocol = ox0 + l15;
     const bool col_ok = ocol < a.W;
@@ -361,14 +451,14 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
 
 #pragma unroll 1
       for (int l = 0; l < a.nLayers; ++l) {
-        const int* const tl = ctl_tab + 32 * l;
-        const int4 tb0 = *(const int4*)(tl), tb1 = *(const int4*)(tl + 4);
-        const int nCh = __builtin_amdgcn_readfirstlane(tb0.x), ns = 3 * nCh;
-        const int dst_group = __builtin_amdgcn_readfirstlane(tb0.y), epi_kind = __builtin_amdgcn_readfirstlane(tb0.z);
-        const float ps_pos = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(tb0.w)), ps_neg = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(tb1.x));
-        const float r1s = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(tb1.y)), r2s = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(tb1.z));
-        const float mslope = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(tb1.w));
-        const bool prev_growth = l > 0 && __builtin_amdgcn_readfirstlane(ctl_tab[32 * (l > 0 ? l - 1 : 0) + 1]) >= 0;
+        const int* const tl = ctl_tab + kDcTabWords * l;       // this layer's row; tl - kDcTabWords: the previous layer's
+        const DcWords<0, 2> ts(tl);
+        const int nCh = ts.at<DC_W(nChunks)>(), ns = 3 * nCh;
+        const int dst_group = ts.at<DC_W(dst_group)>(), epi_kind = ts.at<DC_W(kind)>();
+        const float ps_pos = ts.f<DC_W(ps_pos)>(), ps_neg = ts.f<DC_W(ps_neg)>();
+        const float r1s = ts.f<DC_W(r1s)>(), r2s = ts.f<DC_W(r2s)>();
+        const float mslope = ts.f<DC_W(mask_slope)>();
+        const bool prev_growth = l > 0 && __builtin_amdgcn_readfirstlane(ctl_tab[kDcTabWords * (l > 0 ? l - 1 : 0) + DC_W(dst_group)]) >= 0;
         // hand-off of the previous layer's output (group nCh - 1, first read by the fragments requested behind barrier 3 (nCh - 1) - 1): three
         // dependent round trips of 1.5-2.5k cycles (store acknowledgement, flag visible + poll, halo read) beside steps of ~650 cycles.
         // Stores drained behind step 1, flag published behind barrier 2, neighbours' flags requested behind barrier s_poll (a poll right
@@ -392,11 +482,11 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
             // the tile.  Behind barrier s_poll every wave asks for its neighbours' flags (lane j < 8: neighbour j; the other lanes read this tile's own word)
             if (cw == 0 && lane == 0) __hip_atomic_store(a.flags + (size_t)(l - 1) * a.totalTiles + gtile, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           } else if (s == s_poll) {
-            dc_glds4_sc1(a.flags + (size_t)(l - 1) * a.totalTiles + gtile + noff, stage_lds + kDcStageHalo);
+            dc_glds<4, true>(a.flags + (size_t)(l - 1) * a.totalTiles + gtile + noff, stage_lds + kDcStageHalo);
           } else if (s == s_chk) {
-            const int4 q2 = *(const int4*)(tl - 32 + 8), q3 = *(const int4*)(tl - 32 + 12);      // the previous layer's output view
-            const int PyC = __builtin_amdgcn_readfirstlane(q2.z), Py_ps = __builtin_amdgcn_readfirstlane(q2.w), Py_gs = __builtin_amdgcn_readfirstlane(q3.x), Py_c0 = __builtin_amdgcn_readfirstlane(q3.y);
-            const T* const Py = (const T*)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(q2.y) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(q2.x));
+            const DcWords<DC_W(y), 2> prev(tl - kDcTabWords);      // the previous layer's output view
+            const int PyC = prev.at<DC_W(y.C)>(), Py_ps = prev.at<DC_W(y.ps)>(), Py_gs = prev.at<DC_W(y.gs)>(), Py_c0 = prev.at<DC_W(y.c0)>();
+            const T* const Py = prev.ptr<const T, DC_W(y)>();
             // all neighbours have published?  (normally yes at the first look: they run the same schedule)
             for (int spins = 0;; ++spins) {
               dc_wait_vm<0>();
@@ -404,22 +494,22 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
               if (__builtin_amdgcn_ballot_w64(nvalid && pv != epoch) == 0ull) break;
               if (spins > (1 << 21)) { ++giveups; break; }      // seconds: never in a correct run; wrong results, no hang
               __builtin_amdgcn_s_sleep(2);
-              dc_glds4_sc1(a.flags + (size_t)(l - 1) * a.totalTiles + gtile + noff, stage_lds + kDcStageHalo);
+              dc_glds<4, true>(a.flags + (size_t)(l - 1) * a.totalTiles + gtile + noff, stage_lds + kDcStageHalo);
             }
             // this wave's 68 halo items of the previous layer's output: 16 bytes per lane, lanes 0 .. 63 and 0 .. 3
             const T* yi = Py + img * PyC;
             {
               const int cc = Py_c0 + 8 * h_slot[0];
-              dc_glds16_sc1(yi + ((size_t)h_gp[0] * Py_ps + (size_t)(cc >> 5) * Py_gs + (cc & 31)), stage_lds);
+              dc_glds<16, true>(yi + ((size_t)h_gp[0] * Py_ps + (size_t)(cc >> 5) * Py_gs + (cc & 31)), stage_lds);
             }
             if (Geo::WaveItems > 64 && lane < Geo::WaveItems - 64) {
               const int cc = Py_c0 + 8 * h_slot[1];
-              dc_glds16_sc1(yi + ((size_t)h_gp[1] * Py_ps + (size_t)(cc >> 5) * Py_gs + (cc & 31)), stage_lds + 1024);
+              dc_glds<16, true>(yi + ((size_t)h_gp[1] * Py_ps + (size_t)(cc >> 5) * Py_gs + (cc & 31)), stage_lds + 1024);
             }
           }
           if (prev_growth && s == s_wr) {
             dc_wait_vm<0>();       // the halo items have landed in the staging area
-            char* pg = patch + __builtin_amdgcn_readfirstlane(tl[1 - 32]) * kDcGroupBytes;
+            char* pg = patch + __builtin_amdgcn_readfirstlane(tl[DC_W(dst_group) - kDcTabWords]) * kDcGroupBytes;
             if (h_in[0]) *(u32x4*)(pg + h_off[0]) = *(const u32x4*)(stage + 16 * lane);
             if (Geo::WaveItems > 64 && h_in[1]) *(u32x4*)(pg + h_off[1]) = *(const u32x4*)(stage + 1024 + 16 * lane);
           }
@@ -462,35 +552,29 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
         DC_STEP(0, Aw, Ap, Bw, Bp)
         DC_STEP(1, Bw, Bp, Aw, Ap)
         if (prev_growth) dc_wait_vm<0>();      // the previous layer's write-through stores are acknowledged (issued two steps ago: free); barrier 2 follows
-        // epilogue operands of this lane's 4 pixels: slot A = r1 or mask, slot B = r2.  Loaded as ONE 16-byte slot per pixel (slot
+        // epilogue operands of this lane's RPW pixels: slot A = r1 or mask, slot B = r2.  Loaded as ONE 16-byte slot per pixel (slot
         // {0, 2, 1, 3}[g4], the layout the epilogue stores in) and turned into this lane's two channel quads by v_permlane16_swap in the
-        // epilogue (the swap is its own inverse): 4 load instructions per operand instead of 8 (16 requests of 8 bytes per wave took ~2.7k cycles to issue)
+        // epilogue (the swap is its own inverse): RPW loads per operand instead of 2 RPW (16 requests of 8 bytes per wave took ~2.7k cycles to issue).
+        // The operand registers have ONE definition: a zero-initialised array assigned under an `if` is a merge of two, and the compiler settles such
+        // a merge by WAITING for the loads -- a whole memory latency per layer; rA / rB stay undefined without the operand and are never read then.
+        // (Both requests are written out, each with its own first-pixel index: as one function or lambda, or with the index hoisted out of the
+        // layer loop, the kernels gain s_waitcnt instructions: profiles/dense_chain_refactor_isa.txt.)
         u32x4 rA[RPW], rB[RPW];
-        T* ydst;                 // this lane's first output element (row 4 cw, 16-byte slot {0, 2, 1, 3}[g4] of its pixel)
+        GT* ydst;                // this lane's first output element (row RPW cw, 16-byte slot {0, 2, 1, 3}[g4] of its pixel)
         int yrow;                // elements per image row of the output
         {
-          // output address and epilogue operands (residuals, mask) of this lane: in registers long before the epilogue
-          // (channel offsets are multiples of 32, checked on the host: the second channel half is 16 elements on)
-          auto rfl = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
-          // (global address space spelled out: a pointer assembled from two table words is generic to the compiler, and a FLAT load also counts
-          // on lgkmcnt -- the next barrier's lgkmcnt(0) would wait for the operands' whole memory latency)
-          auto ptr_of = [&](int lo, int hi) { return (const GT*)(((unsigned long long)(unsigned)rfl(hi) << 32) | (unsigned)rfl(lo)); };
-          const int4 t2 = *(const int4*)(tl + 8), t3 = *(const int4*)(tl + 12), t4 = *(const int4*)(tl + 16);
+          // output address and first operand: in registers long before the epilogue
+          const DcWords<DC_W(y), 3> tw(tl);
           const int p0 = col_ok && orow0 < a.H ? orow0 * a.W + ocol : 0;       // a lane without an output pixel reads pixel 0 (a valid address) and drops it
           const int sl16 = ((g4 & 1) << 1) | (g4 >> 1);
-          ydst = (T*)(unsigned long long)ptr_of(t2.x, t2.y) + img * rfl(t2.z) + ((size_t)p0 * rfl(t2.w) + (size_t)(rfl(t3.y) >> 5) * rfl(t3.x) + 8 * sl16);
-          yrow = a.W * rfl(t2.w);
-          // (the operand registers have ONE definition: a zero-initialised array assigned under an `if` is a merge of two, and the compiler
-          // settles such a merge by WAITING for the loads -- measured as a whole memory latency per layer)
-          const GT* opA = ptr_of(t3.z, t3.w);
-          if ((epi_kind & 3) != 0) {      // (rA stays undefined otherwise -- never read: the merge has one definition, nothing to settle)
-            const int a_ps = rfl(t4.y);
-            const GT* pa = opA + img * rfl(t4.x) + ((size_t)p0 * a_ps + (size_t)(rfl(t4.w) >> 5) * rfl(t4.z) + 8 * sl16);
+          ydst = dc_view_at<DC_W(y)>(tw, tw.ptr<GT, DC_W(y)>(), img, p0, sl16);
+          yrow = a.W * tw.at<DC_W(y.ps)>();
+          const GT* const opA = tw.ptr<const GT, DC_W(opA)>();
+          if ((epi_kind & 3) != 0) {
+            const int a_ps = tw.at<DC_W(opA.ps)>();
+            const GT* const pa = dc_view_at<DC_W(opA)>(tw, opA, img, p0, sl16);
 #pragma unroll
-            for (int m = 0; m < RPW; ++m) {
-              const GT* pm = orow0 + m < a.H ? pa + (size_t)m * a.W * a_ps : pa;
-              rA[m] = *(const __attribute__((address_space(1))) u32x4*)pm;
-            }
+            for (int m = 0; m < RPW; ++m) rA[m] = *(const __attribute__((address_space(1))) u32x4*)(orow0 + m < a.H ? pa + (size_t)m * a.W * a_ps : pa);
           }
         }
         // steps 2 and 3, then the second operand (one burst of requests per CU overruns the L1's miss queue and stalls the issuing wave
@@ -498,24 +582,17 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
         DC_STEP(2, Aw, Ap, Bw, Bp)
         DC_STEP(3, Bw, Bp, Aw, Ap)
         {
-          auto rfl = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
-          // (global address space spelled out: a pointer assembled from two table words is generic to the compiler, and a FLAT load also counts
-          // on lgkmcnt -- the next barrier's lgkmcnt(0) would wait for the operands' whole memory latency)
-          auto ptr_of = [&](int lo, int hi) { return (const GT*)(((unsigned long long)(unsigned)rfl(hi) << 32) | (unsigned)rfl(lo)); };
-          const int4 t5 = *(const int4*)(tl + 20), t6 = *(const int4*)(tl + 24);
+          const DcWords<DC_W(opB), 2> tw(tl);
           const int p0 = col_ok && orow0 < a.H ? orow0 * a.W + ocol : 0;
           const int sl16 = ((g4 & 1) << 1) | (g4 >> 1);
-          const GT* opB = ptr_of(t5.x, t5.y);
+          const GT* const opB = tw.ptr<const GT, DC_W(opB)>();
           if ((epi_kind & 3) == 3) {
-            const int b_ps = rfl(t5.w);
-            const GT* pb = opB + img * rfl(t5.z) + ((size_t)p0 * b_ps + (size_t)(rfl(t6.y) >> 5) * rfl(t6.x) + 8 * sl16);
+            const int b_ps = tw.at<DC_W(opB.ps)>();
+            const GT* const pb = dc_view_at<DC_W(opB)>(tw, opB, img, p0, sl16);
 #pragma unroll
-            for (int m = 0; m < RPW; ++m) {
-              const GT* pm = orow0 + m < a.H ? pb + (size_t)m * a.W * b_ps : pb;
-              rB[m] = *(const __attribute__((address_space(1))) u32x4*)pm;
-            }
+            for (int m = 0; m < RPW; ++m) rB[m] = *(const __attribute__((address_space(1))) u32x4*)(orow0 + m < a.H ? pb + (size_t)m * a.W * b_ps : pb);
           }
-                }
+        }
         int s = 4;
 #pragma unroll 1
         for (; s + 1 < ns; s += 2) {
@@ -530,83 +607,17 @@ __global__ __launch_bounds__(kDcThreads) void dense_chain_kernel(const DcK a) {
           for (int q = 0; q < RPW + 2; ++q) Ap[q] = Bp[q];
         }
 #undef DC_STEP
-
-        // ---- epilogue: lane = pixel l15 of rows 4 cw + m, channels 16 nh + 4 g4 .. + 3 per accumulator.  The operand combination is a
-        // compile-time kind (one switch per layer): OPS 0 none, 1 mask, 2 r1, 3 r1 + r2; GROWTH: also group dst_group of the patch and a
-        // write-through store; MAXACT: activation as max(v * pos, v * neg).  The two 8-byte channel quads of a lane (nh = 0 / 1) are turned
-        // into ONE 16-byte slot by v_permlane16_swap (lane row g4 ends up with slot {0, 2, 1, 3}[g4] of its pixel): one 16-byte LDS write and
-        // one 16-byte store per pixel instead of two 8-byte ones each ----
-        const float alpha = ctl_alpha[l];
-        const f32x4_t b0 = *(const f32x4_t*)(ctl_bias + l * 32 + 4 * g4), b1 = *(const f32x4_t*)(ctl_bias + l * 32 + 16 + 4 * g4);
-        const int sl16 = ((g4 & 1) << 1) | (g4 >> 1);
-        char* const lds_out = patch + (growth ? dst_group : 0) * kDcGroupBytes + dc_pos(RPW * cw + 1, l15 + 1, sl16);
-        T* const y16 = ydst;
-        auto epilogue = [&](auto growth_c, auto ops_c, auto max_c) {
-          constexpr bool GROWTH = decltype(growth_c)::v != 0, MAXACT = decltype(max_c)::v != 0;
-          constexpr int OPS = decltype(ops_c)::v;
-#pragma unroll
-          for (int m = 0; m < RPW; ++m) {
-            const bool ok = col_ok && orow0 + m < a.H;
-            dc_u32x2 pk[2], eA[2], eB[2];
-            if constexpr (OPS >= 1) {
-              const dc_u32x2 ux = __builtin_amdgcn_permlane16_swap(rA[m].x, rA[m].z, false, false), uy = __builtin_amdgcn_permlane16_swap(rA[m].y, rA[m].w, false, false);
-              eA[0] = dc_u32x2{ux.x, uy.x}; eA[1] = dc_u32x2{ux.y, uy.y};
-            }
-            if constexpr (OPS == 3) {
-              const dc_u32x2 ux = __builtin_amdgcn_permlane16_swap(rB[m].x, rB[m].z, false, false), uy = __builtin_amdgcn_permlane16_swap(rB[m].y, rB[m].w, false, false);
-              eB[0] = dc_u32x2{ux.x, uy.x}; eB[1] = dc_u32x2{ux.y, uy.y};
-            }
-#pragma unroll
-            for (int nh = 0; nh < 2; ++nh) {
-              float v4[4], t4[4];
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                const float v = __builtin_fmaf(alpha, acc[m][nh][i], nh ? b1[i] : b0[i]);
-                // v * (v > 0 ? pos : neg); with pos >= neg >= 0 that is max(v * pos, v * neg): two multiplies and a max, no compare / select pair
-                if constexpr (MAXACT) v4[i] = __builtin_fmaxf(v * ps_pos, v * ps_neg);
-                else v4[i] = v * (v > 0.f ? ps_pos : ps_neg);
-              }
-              if constexpr (OPS >= 2) { dc_widen4<T>(eA[nh], t4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v4[i] = __builtin_fmaf(r1s, t4[i], v4[i]); }
-              if constexpr (OPS == 3) { dc_widen4<T>(eB[nh], t4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v4[i] = __builtin_fmaf(r2s, t4[i], v4[i]); }
-              if constexpr (OPS == 1) { dc_widen4<T>(eA[nh], t4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v4[i] *= t4[i] > 0.f ? 1.f : mslope; }
-              pk[nh] = dc_narrow4<T>(v4);
-              if (!ok) pk[nh] = dc_u32x2{0u, 0u};      // pixels beyond the image are zero padding for the layers that follow
-            }
-            const dc_u32x2 sx = __builtin_amdgcn_permlane16_swap(pk[0].x, pk[1].x, false, false);
-            const dc_u32x2 sy = __builtin_amdgcn_permlane16_swap(pk[0].y, pk[1].y, false, false);
-            const u32x4 q = {sx.x, sy.x, sx.y, sy.y};      // lower quad (both dwords), then upper quad of this lane's 16-byte slot
-            if constexpr (GROWTH) *(u32x4*)(lds_out + m * (kDcPC * 64)) = q;
-            if (ok) {
-              T* dst = y16 + (size_t)m * yrow;
-              // growth layers: write-through (sc1), the neighbours read the halo from memory inside this launch
-              if constexpr (GROWTH) dc_store16_sc1(dst, q);
-              else *(u32x4*)dst = q;
-            }
-          }
-        };
+        // ---- epilogue, by compile-time kind: one multi-way branch per layer ----
+        const DcEpi<T> e = {ctl_alpha[l], ps_pos, ps_neg, r1s, r2s, mslope,
+                            *(const f32x4_t*)(ctl_bias + l * 32 + 4 * g4), *(const f32x4_t*)(ctl_bias + l * 32 + 16 + 4 * g4),
+                            patch + (growth ? dst_group : 0) * kDcGroupBytes + dc_pos(RPW * cw + 1, l15 + 1, ((g4 & 1) << 1) | (g4 >> 1)),
+                            ydst, yrow, col_ok, orow0, a.H};
+        auto epi = [&](auto k) { using K = DcKind<decltype(k)::v>; dc_epilogue<T, RPW, K::GROWTH, K::OPS, K::MAXACT>(acc, rA, rB, e); };
         switch (epi_kind) {
-          case 0: epilogue(IC<0>{}, IC<0>{}, IC<0>{}); break;
-          case 1: epilogue(IC<0>{}, IC<1>{}, IC<0>{}); break;
-          case 2: epilogue(IC<0>{}, IC<2>{}, IC<0>{}); break;
-          case 3: epilogue(IC<0>{}, IC<3>{}, IC<0>{}); break;
-          case 4: epilogue(IC<1>{}, IC<0>{}, IC<0>{}); break;
-          case 5: epilogue(IC<1>{}, IC<1>{}, IC<0>{}); break;
-          case 6: epilogue(IC<1>{}, IC<2>{}, IC<0>{}); break;
-          case 7: epilogue(IC<1>{}, IC<3>{}, IC<0>{}); break;
-          case 8: epilogue(IC<0>{}, IC<0>{}, IC<1>{}); break;
-          case 9: epilogue(IC<0>{}, IC<1>{}, IC<1>{}); break;
-          case 10: epilogue(IC<0>{}, IC<2>{}, IC<1>{}); break;
-          case 11: epilogue(IC<0>{}, IC<3>{}, IC<1>{}); break;
-          case 12: epilogue(IC<1>{}, IC<0>{}, IC<1>{}); break;
-          case 13: epilogue(IC<1>{}, IC<1>{}, IC<1>{}); break;
-          case 14: epilogue(IC<1>{}, IC<2>{}, IC<1>{}); break;
-          default: epilogue(IC<1>{}, IC<3>{}, IC<1>{}); break;
+          case 0: epi(IC<0>{}); break;   case 1: epi(IC<1>{}); break;   case 2: epi(IC<2>{}); break;   case 3: epi(IC<3>{}); break;
+          case 4: epi(IC<4>{}); break;   case 5: epi(IC<5>{}); break;   case 6: epi(IC<6>{}); break;   case 7: epi(IC<7>{}); break;
+          case 8: epi(IC<8>{}); break;   case 9: epi(IC<9>{}); break;   case 10: epi(IC<10>{}); break; case 11: epi(IC<11>{}); break;
+          case 12: epi(IC<12>{}); break; case 13: epi(IC<13>{}); break; case 14: epi(IC<14>{}); break; default: epi(IC<15>{}); break;
         }
       }
     }
@@ -652,29 +663,20 @@ static int dense_chain_fill(const srganfd_conv_args* layers, int n, DcK& K) {
       L.w = (const char*)a.w_packed + (size_t)h * k.nChunks * 18432;
       L.bias = a.bias ? a.bias + 32 * h : nullptr;
       L.alpha_dev = a.alpha_dev;
-      L.y = (char*)a.y.ptr; L.r1 = (const char*)a.r1.ptr; L.r2 = (const char*)a.r2.ptr; L.mask = (const char*)a.mask.ptr;
-      L.yC = k.yC; L.y_c0 = k.y_c0 + 32 * h; L.y_ps = k.y_ps; L.y_gs = k.y_gs;
-      L.r1C = k.r1C; L.r1_c0 = k.r1_c0 + 32 * h; L.r1_ps = k.r1_ps; L.r1_gs = k.r1_gs;
-      L.r2C = k.r2C; L.r2_c0 = k.r2_c0 + 32 * h; L.r2_ps = k.r2_ps; L.r2_gs = k.r2_gs;
-      L.mC = k.mC; L.m_c0 = k.m_c0 + 32 * h; L.m_ps = k.m_ps; L.m_gs = k.m_gs;
       L.nChunks = k.nChunks;
-      L.dst_group = last ? -1 : a.cin / 32;
-      L.alpha = a.alpha; L.neg = a.act == SRGANFD_ACT_LRELU ? a.slope : (a.act == SRGANFD_ACT_RELU ? 0.f : 1.f);
-      L.post_scale = a.post_scale; L.r1s = a.r1_scale; L.r2s = a.r2_scale; L.mask_slope = a.mask_slope;
-      {
-        const float ps_pos = L.post_scale, ps_neg = L.neg * L.post_scale;
-        const int ops = L.r1 ? (L.r2 ? 3 : 2) : (L.mask ? 1 : 0);
-        const int kind = (L.dst_group >= 0 ? 4 : 0) + ops + (ps_neg >= 0.f && ps_pos >= ps_neg ? 8 : 0);
-        int* t = K.tab[nl - 1];
-        t[0] = L.nChunks; t[1] = L.dst_group; t[2] = kind;
-        memcpy(&t[3], &ps_pos, 4); memcpy(&t[4], &ps_neg, 4); memcpy(&t[5], &L.r1s, 4); memcpy(&t[6], &L.r2s, 4); memcpy(&t[7], &L.mask_slope, 4);
-        memcpy(&t[8], &L.y, 8); t[10] = L.yC; t[11] = L.y_ps; t[12] = L.y_gs; t[13] = L.y_c0;
-        if (L.r1) { memcpy(&t[14], &L.r1, 8); t[16] = L.r1C; t[17] = L.r1_ps; t[18] = L.r1_gs; t[19] = L.r1_c0; }
-        else if (L.mask) { memcpy(&t[14], &L.mask, 8); t[16] = L.mC; t[17] = L.m_ps; t[18] = L.m_gs; t[19] = L.m_c0; }
-        else { memcpy(&t[14], &L.y, 8); t[16] = L.yC; t[17] = L.y_ps; t[18] = L.y_gs; t[19] = L.y_c0; }      // absent: any valid view (the requests are unconditional)
-        if (L.r2) { memcpy(&t[20], &L.r2, 8); t[22] = L.r2C; t[23] = L.r2_ps; t[24] = L.r2_gs; t[25] = L.r2_c0; }
-        else { memcpy(&t[20], &L.y, 8); t[22] = L.yC; t[23] = L.y_ps; t[24] = L.y_gs; t[25] = L.y_c0; }
-      }
+      L.alpha = a.alpha;
+      DcTab& t = K.tab[nl - 1];
+      t.nChunks = k.nChunks;
+      t.dst_group = last ? -1 : a.cin / 32;
+      const float neg = a.act == SRGANFD_ACT_LRELU ? a.slope : (a.act == SRGANFD_ACT_RELU ? 0.f : 1.f);      // factor of the activation's negative side
+      t.ps_pos = a.post_scale; t.ps_neg = neg * a.post_scale;
+      t.r1s = a.r1_scale; t.r2s = a.r2_scale; t.mask_slope = a.mask_slope;
+      const int ops = a.r1.ptr ? (a.r2.ptr ? 3 : 2) : (a.mask.ptr ? 1 : 0);
+      t.kind = (last ? 0 : 4) + ops + (t.ps_neg >= 0.f && t.ps_pos >= t.ps_neg ? 8 : 0);
+      auto view = [h](const void* p, int C, int ps, int gs, int c0) { return DcView{(unsigned)(uintptr_t)p, (unsigned)((uintptr_t)p >> 32), C, ps, gs, c0 + 32 * h}; };
+      t.y = view(a.y.ptr, k.yC, k.y_ps, k.y_gs, k.y_c0);
+      t.opA = a.r1.ptr ? view(a.r1.ptr, k.r1C, k.r1_ps, k.r1_gs, k.r1_c0) : (a.mask.ptr ? view(a.mask.ptr, k.mC, k.m_ps, k.m_gs, k.m_c0) : t.y);
+      t.opB = a.r2.ptr ? view(a.r2.ptr, k.r2C, k.r2_ps, k.r2_gs, k.r2_c0) : t.y;
       steps += 3 * k.nChunks;
     }
   }
@@ -698,6 +700,22 @@ static int dense_chain_limits(const DcK& K) {
   return SRGANFD_OK;
 }
 
+// One launch of dense_chain_kernel<T, RPW>; its dynamic-LDS limit is raised once per device.
+template <typename T, int RPW> static int dc_launch(const DcK& K, hipStream_t stream) {
+  static unsigned long long attr_done = 0;      // bit per device
+  if (!g_dry_run) {
+    int dev = 0;
+    SRGANFD_HIP_CHECK(hipGetDevice(&dev));
+    if (!(attr_done >> (dev & 63) & 1ULL)) {
+      SRGANFD_HIP_CHECK(hipFuncSetAttribute((const void*)dense_chain_kernel<T, RPW>, hipFuncAttributeMaxDynamicSharedMemorySize, DcGeo<RPW>::Lds));
+      attr_done |= 1ULL << (dev & 63);
+    }
+  }
+  SRGANFD_LAUNCH((dense_chain_kernel<T, RPW>), dim3((unsigned)(K.ipl * K.tpi)), dim3(kDcThreads), DcGeo<RPW>::Lds, stream, K);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+
 extern "C" int srganfd_dense_chain_check(const srganfd_conv_args* layers, int32_t n) {
   DcK K;
   const int rc = dense_chain_fill(layers, n, K);
@@ -714,30 +732,11 @@ extern "C" int srganfd_dense_chain(const srganfd_conv_args* layers, int32_t n, v
   K.hdr = (int*)workspace;
   K.flags = (int*)((char*)workspace + 64);
   const bool f16 = layers[0].dtype == SRGANFD_F16;
-  const int variant = (f16 ? 1 : 0) + 2 * (4 - K.rpw);       // rows per wave 4, 3, 2 x {bf16, f16}
-  const void* const kerns[6] = {(const void*)dense_chain_kernel<bf16_t, 4>, (const void*)dense_chain_kernel<f16_t, 4>, (const void*)dense_chain_kernel<bf16_t, 3>,
-                                (const void*)dense_chain_kernel<f16_t, 3>, (const void*)dense_chain_kernel<bf16_t, 2>, (const void*)dense_chain_kernel<f16_t, 2>};
-  const int lds = K.rpw == 2 ? DcGeo<2>::Lds : (K.rpw == 3 ? DcGeo<3>::Lds : DcGeo<4>::Lds);
-  static unsigned long long attr_done[6] = {0, 0, 0, 0, 0, 0};
-  if (!g_dry_run) {
-    int dev = 0;
-    SRGANFD_HIP_CHECK(hipGetDevice(&dev));
-    if (!(attr_done[variant] >> (dev & 63) & 1ULL)) {
-      SRGANFD_HIP_CHECK(hipFuncSetAttribute(kerns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      attr_done[variant] |= 1ULL << (dev & 63);
-    }
+  switch (K.rpw) {
+    case 2: return f16 ? dc_launch<f16_t, 2>(K, (hipStream_t)stream) : dc_launch<bf16_t, 2>(K, (hipStream_t)stream);
+    case 3: return f16 ? dc_launch<f16_t, 3>(K, (hipStream_t)stream) : dc_launch<bf16_t, 3>(K, (hipStream_t)stream);
+    default: return f16 ? dc_launch<f16_t, 4>(K, (hipStream_t)stream) : dc_launch<bf16_t, 4>(K, (hipStream_t)stream);
   }
-  const unsigned grid = (unsigned)(K.ipl * K.tpi);
-  switch (variant) {
-    case 0: SRGANFD_LAUNCH((dense_chain_kernel<bf16_t, 4>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
-    case 1: SRGANFD_LAUNCH((dense_chain_kernel<f16_t, 4>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
-    case 2: SRGANFD_LAUNCH((dense_chain_kernel<bf16_t, 3>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
-    case 3: SRGANFD_LAUNCH((dense_chain_kernel<f16_t, 3>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
-    case 4: SRGANFD_LAUNCH((dense_chain_kernel<bf16_t, 2>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
-    default: SRGANFD_LAUNCH((dense_chain_kernel<f16_t, 2>), dim3(grid), dim3(kDcThreads), lds, (hipStream_t)stream, K); break;
-  }
-  SRGANFD_HIP_CHECK(hipGetLastError());
-  return SRGANFD_OK;
 }
 
 }  // namespace srganfd

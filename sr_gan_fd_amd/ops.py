@@ -359,8 +359,9 @@ _DC_WS = {}
 
 
 def dense_chain_workspace(device) -> torch.Tensor:
-    """hand-off flags + error word of the dense-chain launches of one device (zeroed once here; the launches re-zero the flags they use
-    on the stream, and they run in stream order, so every chain of a device can share it)"""
+    """hand-off flags + header (give-up count, epoch, finished-workgroup count) of the dense-chain launches of one device, zeroed once
+    here.  The flags are epoch-valued: the last workgroup of a launch advances the epoch, so nothing is zeroed per launch, a captured
+    graph replays correctly, and -- the launches running in stream order -- every chain of a device can share it"""
     ws = _DC_WS.get(str(device))
     if ws is None:
         ws = _DC_WS[str(device)] = torch.zeros(int(A.lib().srganfd_dense_chain_workspace_bytes()), dtype=torch.uint8, device=device)

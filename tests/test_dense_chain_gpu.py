@@ -81,7 +81,7 @@ def test_dense_chain_equals_the_separate_launches(dtype, backward, shape, rows, 
     # here, mul + add where the compiler chose so in conv_igemm) and propagates through the later layers
     tol = 4e-3 if dtype == torch.float16 else 3e-2
     assert torch.isfinite(out_dc.float()).all() and e_buf < tol and e_out < tol
-    # a second run over the same buffers (flags re-zeroed on the stream) gives the same bits: the launch is deterministic
+    # a second run over the same buffers (flags are epoch-valued: the launch before advanced the epoch) gives the same bits: the launch is deterministic
     snap_b, snap_o = buf_dc.clone(), out_dc.clone()
     chain.run()
     torch.cuda.synchronize()
@@ -187,3 +187,148 @@ def test_generator_iteration_at_the_reference_crops_through_the_launch_meets_the
           f"Adam-update rel L2 err {err_w:.2e}; per-layer launches: loss {res['0'][0]:.6f}, SR diff {d_sr:.2e}")
     assert abs(loss - want_loss) < 1e-3 * abs(want_loss) and err_sr < 1e-3 and err_w < 2e-2
     assert d_sr < 2e-4 and abs(loss - res["0"][0]) < 1e-4 * abs(want_loss)
+
+
+# ---- every epilogue kind against the float64 formula, layer by layer ----
+# dense_chain.hip promises conv_igemm.hip's arithmetic contract, so each layer of a chain is held to the bound tests/test_conv_paths_gpu.py
+# holds conv_igemm to (conv_oracle.bound, unchanged): layer k's stored output against conv_oracle.conv2d over the chain's OWN stored
+# channels [0, 64 + 32 k), so no error carries from layer to layer.  n = 2 images of 35 x 37 pixels: ragged both ways, at least 3 x 3
+# tiles in every tile form (a tile with all eight neighbours, every border kind), one pass.
+# SRGANFD_DC_KINDS_REPORT=<file> appends the worst err / bound per epilogue kind and dtype (profiles/dense_chain_kinds_fp64.txt).
+KN, KH, KW = 2, 35, 37
+_FWD = dict(bias=True, act=1, slope=0.2, alpha=1.0, alpha_dev=None, post_scale=1.0, ops="none")       # act: conv_oracle.ACT_*
+_OPS = {"none": 0, "mask": 1, "r1": 2, "r1r2": 3}
+
+
+def _L(**kw):
+    return dict(_FWD, **kw)
+
+
+# name -> layers (the last one closes the chain: 64 channels into its own buffer; the others grow the block buffer by 32 channels)
+KIND_CHAINS = {
+    # the eight growth kinds: operands none / mask / r1 / r1 + r2, max form (LeakyReLU 0.2, post_scale 1) and select form
+    "grow_max": [_L(alpha=1.5), _L(ops="mask"), _L(ops="r1", bias=False), _L(ops="r1r2", alpha_dev=0.6), _L(act=0, post_scale=0.04, ops="r1r2")],
+    "grow_select": [_L(post_scale=-0.5), _L(slope=1.5, ops="mask", alpha=0.75), _L(post_scale=-0.5, ops="r1", bias=False), _L(slope=1.5, ops="r1r2"),
+                    _L(act=0, post_scale=-0.5, ops="mask", alpha_dev=1.75)],
+    # the eight closing kinds behind 1, 2 and 3 growth layers
+    "close2_max_none": [_L(alpha=1.25), _L(act=2, post_scale=0.5)],
+    "close3_max_mask": [_L(), _L(alpha=0.75, bias=False), _L(act=0, bias=False, ops="mask")],
+    "close4_max_r1": [_L(), _L(ops="mask"), _L(alpha=1.5), _L(act=0, post_scale=0.04, ops="r1", alpha=2.0)],
+    "close2_max_r1r2": [_L(alpha_dev=0.7), _L(act=0, post_scale=0.04, ops="r1r2", alpha=0.5)],
+    "close3_select_none": [_L(), _L(alpha=1.5), _L(act=1, slope=1.5, alpha=0.75)],
+    "close4_select_mask": [_L(alpha=0.5), _L(), _L(ops="r1"), _L(act=0, post_scale=-0.5, bias=False, ops="mask")],
+    "close2_select_r1": [_L(alpha=1.5, alpha_dev=1.25), _L(act=1, post_scale=-0.5, ops="r1")],
+    "close3_select_r1r2": [_L(), _L(alpha=0.75), _L(act=1, slope=1.5, ops="r1r2", alpha=1.25)],
+}
+
+
+def epilogue_kind(layer, last):
+    """dense_chain_fill's formula: 4 (growth layer) + operands (3 r1 + r2, 2 r1, 1 mask, 0 none) + 8 (activation in max form)"""
+    neg = layer["slope"] if layer["act"] == 1 else (0.0 if layer["act"] == 2 else 1.0)
+    ps_pos, ps_neg = layer["post_scale"], neg * layer["post_scale"]
+    return 4 * (not last) + _OPS[layer["ops"]] + 8 * (ps_neg >= 0 and ps_pos >= ps_neg)
+
+
+def test_kind_chains_cover_every_epilogue_kind():
+    kinds = {epilogue_kind(l, i == len(ls) - 1) for ls in KIND_CHAINS.values() for i, l in enumerate(ls)}
+    assert kinds == set(range(16)), sorted(kinds)
+    assert {epilogue_kind(l, False) for l in KIND_CHAINS["grow_max"][:4]} == {12, 13, 14, 15}
+    assert {epilogue_kind(l, False) for l in KIND_CHAINS["grow_select"][:4]} == {4, 5, 6, 7}
+    closing = [ls for nm, ls in KIND_CHAINS.items() if nm.startswith("close")]
+    assert sorted(epilogue_kind(ls[-1], True) for ls in closing) == [0, 1, 2, 3, 8, 9, 10, 11]
+    assert all(sum(len(ls) == k for ls in closing) >= 2 for k in (2, 3, 4))
+    assert all(any(l["alpha"] != 1.0 for l in ls) for ls in KIND_CHAINS.values())
+    assert sum(any(l["alpha_dev"] for l in ls) for ls in KIND_CHAINS.values()) >= 2
+    assert any(not l["bias"] for ls in KIND_CHAINS.values() for l in ls[:-1])
+
+
+KIND_RATIOS = {}       # (epilogue kind, dtype) -> worst err / bound seen
+
+
+@pytest.fixture(scope="module")
+def kinds_report():
+    import os
+    yield
+    lines = ["%8.4f  kind %2d  %s" % (r, k, dt) for (k, dt), r in sorted(KIND_RATIOS.items())]
+    print("\nworst err / bound per epilogue kind\n" + "\n".join(lines))
+    path = os.environ.get("SRGANFD_DC_KINDS_REPORT")
+    if path:
+        with open(path, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+_KIND_DATA = {}        # (chain, dtype) -> host data, made once for the three tile forms and both layouts
+
+
+def _kind_data(name, dtype):
+    from tests.test_conv_paths_gpu import f32r
+    key = (name, dtype)
+    if key not in _KIND_DATA:
+        _KIND_DATA.clear()
+        g = torch.Generator().manual_seed(4321 + 7 * len(name) + sorted(KIND_CHAINS).index(name))
+        rnd = lambda *s: torch.randn(*s, generator=g)
+        D = dict(x0=(rnd(KN, KH, KW, 64) * 0.6).to(dtype), layers=[])
+        for k, l in enumerate(KIND_CHAINS[name]):
+            last = k == len(KIND_CHAINS[name]) - 1
+            cin, cout = 64 + 32 * k, (64 if last else 32)
+            d = dict(wt=rnd(cout, cin, 3, 3) / (3.0 * cin ** 0.5), bias=rnd(cout) * 0.1 if l["bias"] else None,
+                     alpha_dev=torch.tensor([l["alpha_dev"]], dtype=torch.float32) if l["alpha_dev"] else None)
+            for nm in {"none": (), "mask": ("mask",), "r1": ("r1",), "r1r2": ("r1", "r2")}[l["ops"]]:
+                d[nm] = rnd(KN, KH, KW, cout).to(dtype)
+            d["scalars"] = dict(act=l["act"], slope=f32r(l["slope"]), alpha=f32r(l["alpha"]), post_scale=f32r(l["post_scale"]),
+                                r1_scale=f32r(0.2 if "r1" in d else 0.0), r2_scale=f32r(-1.0 if "r2" in d else 0.0), mask_slope=f32r(0.25))
+            D["layers"].append(d)
+        _KIND_DATA[key] = D
+    return _KIND_DATA[key]
+
+
+@pytest.mark.parametrize("rows", [8, 12, 16], ids=lambda r: "tile-rows-%d" % r)
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("name", list(KIND_CHAINS))
+def test_every_epilogue_kind_layer_by_layer_against_fp64(name, dtype, rows, monkeypatch, kinds_report):
+    from sr_gan_fd_amd import _abi as A, ops
+    from tests import conv_oracle as O
+    monkeypatch.setenv("SRGANFD_DC_RPW", str(rows // 4))
+    dt, layers, D = ops.DT[dtype], KIND_CHAINS[name], _kind_data(name, dtype)
+    nl = len(layers)
+    for planar in (0, 1):
+        what = f"{name} {dtype} {rows} x 16 tiles {'planar' if planar else 'nhwc'}"
+        g = torch.Generator().manual_seed(99)
+        blk = O.Buf(KN, KH, KW, 192, dtype, planar)
+        blk.put(0, D["x0"])
+        blk.upload()
+        out = O.Buf(KN, KH, KW, 128, dtype, planar).upload()             # the closing layer writes channels [32, 96)
+        keep, args = [], []
+        for k, (l, d) in enumerate(zip(layers, D["layers"])):
+            last = k == nl - 1
+            cin, cout = 64 + 32 * k, (64 if last else 32)
+            wp = ops.pack_single(d["wt"].cuda(), dt)
+            kw = dict(d["scalars"], bias=d["bias"].cuda() if d["bias"] is not None else None, alpha_dev=d["alpha_dev"].cuda() if d["alpha_dev"] is not None else None)
+            for j, nm in enumerate(("r1", "r2", "mask")):
+                if nm in d:        # a slice at a non-zero multiple-of-32 offset of a wider tensor of other values
+                    b = O.Buf(KN, KH, KW, 128, dtype, planar, fill="garbage", gen=g)
+                    c0 = 32 if last else 32 * (1 + (k + j) % 3)
+                    b.put(c0, d[nm])
+                    kw[nm] = b.upload().view(A, c0)
+                    keep.append(b)
+            keep += [wp, kw["bias"], kw["alpha_dev"]]
+            args.append(ops.conv_args(dt, blk.view(A), out.view(A, 32) if last else blk.view(A, cin), wp, KN, KH, KW, cin, cout, **kw))
+        chain = ops.DenseChain(args, "cuda")
+        assert chain.ok, what
+        chain.run()
+        torch.cuda.synchronize()
+        assert chain.errors() == 0, what
+        got_blk, got_out = blk.download(), out.download()
+        blk.assert_outside_untouched(got_blk, 64, 32 * (nl - 1), what + " block buffer")
+        out.assert_outside_untouched(got_out, 32, 64, what + " closing output")
+        for k, (l, d) in enumerate(zip(layers, D["layers"])):
+            last = k == nl - 1
+            cin, cout = 64 + 32 * k, (64 if last else 32)
+            ref, _, mag = O.conv2d(got_blk[..., :cin], d["wt"].to(dtype), bias=d["bias"], alpha_dev=d["alpha_dev"], r1=d.get("r1"), r2=d.get("r2"),
+                                   mask=d.get("mask"), **d["scalars"])
+            got = got_out[..., 32:96] if last else got_blk[..., cin:cin + 32]
+            ratio, at = O.worst_ratio(got, ref, mag, 9 * cin, dtype)
+            kind = epilogue_kind(l, last)
+            print(f"{what} layer {k} kind {kind}: worst err / bound {ratio:.4f}")
+            KIND_RATIOS[(kind, str(dtype))] = max(KIND_RATIOS.get((kind, str(dtype)), 0.0), ratio)
+            assert ratio <= 1.0, f"{what} layer {k} (kind {kind}): element {at} is {ratio:.3f} times its bound"

@@ -1,19 +1,23 @@
-"""Device assembly of wgrad.hip, one tree against another, per kernel (the method of profiles/conv_igemm_refactor_isa.txt).
+"""Device assembly of wgrad.hip or dense_chain.hip, one tree against another, per kernel (the method of profiles/conv_igemm_refactor_isa.txt).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I. --offload-device-only -S -o parent.s <parent>/wgrad.hip      (same for the branch)
     python tools/wgrad_isa_compare.py parent.s branch.s > profiles/wgrad_refactor_isa.txt
+    python tools/wgrad_isa_compare.py --kernel dense_chain parent.s branch.s > profiles/dense_chain_refactor_isa.txt
 
-Kernels are matched by template arguments <T, KS, STRIDE, XP, YP, DMA>; a seventh argument (the parent's VAR) is dropped.  Per kernel:
-the .amdhsa_kernel block, and the counts of MFMA, LDS, global / flat / scratch memory, buffer, s_waitcnt and s_barrier instructions.
-A working tool, not a test."""
+wgrad kernels are matched by template arguments <T, KS, STRIDE, XP, YP, DMA>; a seventh argument (the parent's VAR) is dropped;
+dense-chain kernels by <T, RPW>.  Per kernel: the .amdhsa_kernel block, and the counts of MFMA, LDS, global / flat / scratch memory,
+buffer, s_waitcnt and s_barrier instructions, which must be equal; --kernel dense_chain also counts v_readlane / v_writelane (SGPR
+spills to lanes), which must not rise.  A working tool, not a test."""
 import collections
 import re
 import sys
 
 NAME = re.compile(r"wgrad_kernelI(t|DF16_|f)Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E(?:Li(\d+)E)?E")
+DC_NAME = re.compile(r"dense_chain_kernelI(t|DF16_)Li(\d+)EE")
 TYPES = {"t": "bf16", "DF16_": "f16", "f": "f32"}
 CLASSES = [("mfma", r"v_mfma"), ("lds", r"ds_"), ("global", r"(global|flat|scratch)_"), ("buffer", r"buffer_"), ("s_waitcnt", r"s_waitcnt"),
            ("s_barrier", r"s_barrier")]
+AT_MOST = []                                        # classes whose count may fall but not rise
 WAVE_STEPS = [64, 72, 80, 96, 128, 168, 256, 512]   # VGPRs per lane at which one more wave per SIMD is lost (512 registers, granule 8)
 
 
@@ -22,6 +26,9 @@ def waves(v):
 
 
 def label(sym):
+    m = DC_NAME.search(sym)
+    if m:
+        return "dense_chain_kernel<%s, RPW=%s>" % (TYPES[m.group(1)], m.group(2)), None
     m = NAME.search(sym)
     if not m:
         return sym, None
@@ -74,7 +81,15 @@ def res(md):
 
 
 def main():
-    P, B = parse(sys.argv[1]), parse(sys.argv[2])
+    argv = sys.argv[1:]
+    if argv[:1] == ["--kernel"]:
+        if argv[1] == "dense_chain":
+            CLASSES.append(("lane spills", r"v_(readlane|writelane)"))
+            AT_MOST.append("lane spills")
+        elif argv[1] != "wgrad":
+            sys.exit("--kernel: wgrad or dense_chain, not %r" % argv[1])
+        argv = argv[2:]
+    P, B = parse(argv[0]), parse(argv[1])
     only_p, only_b = sorted(set(P) - set(B)), sorted(set(B) - set(P))
     print("# parent: %d kernels, branch: %d kernels; only in parent: %d, only in branch: %d" % (len(P), len(B), len(only_p), len(only_b)))
     for n in only_p:
@@ -98,7 +113,7 @@ def main():
         cp, cb = counts(p["ops"]), counts(b["ops"])
         vp, vb = int(p["meta"][".amdhsa_next_free_vgpr"]), int(b["meta"][".amdhsa_next_free_vgpr"])
         sp, sb = int(p["meta"][".amdhsa_private_segment_fixed_size"]), int(b["meta"][".amdhsa_private_segment_fixed_size"])
-        if cp != cb:
+        if any(cb[k] > cp[k] if k in AT_MOST else cb[k] != cp[k] for k in cp):
             bad.append(n + ": instruction-class counts differ")
         if sb > sp:
             bad.append(n + ": gains scratch")
