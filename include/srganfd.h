@@ -720,6 +720,54 @@ int srganfd_attention_bwd(const srganfd_attn_args* a, void* stream);
 int srganfd_pixel_gate(int32_t bwd, srganfd_view x, srganfd_view a, srganfd_view z_or_dz, srganfd_view dx, srganfd_view da,
                        int32_t dtype, int64_t npix, int32_t c, void* stream);
 
+/* ---- post-norm transformer encoder layer (nn.TransformerEncoderLayer with norm_first=False, as A-ESRGAN/model.py:673-674 builds it):
+ * the pieces that are no 1x1 convolution.  Tensors are contiguous token-major rows in `dtype` (F32 / F16 / BF16); keep-masks are
+ * uint8 of the tensor's shape, 1 = keep, drawn by the caller; every accumulation is fp32; one owner per output element and fixed
+ * summation orders throughout: no atomics, bit-reproducible, nothing waits on the host (graph capture is fine). ---- */
+
+/* Residual add with its dropout, fused into LayerNorm over the last axis (csrc/layernorm.hip); x, r, z, y: (ntok, e).
+ *   fwd   z = x + r * keep * keep_scale (keep NULL: z = x + r), stored in `dtype`; over the STORED z of a token: mean and
+ *         rstd = 1 / sqrt(biased variance + eps), stored per token in fp32; y = (z - mean) * rstd * gamma + beta.
+ *   bwd   from dy, z, mean, rstd: dz = rstd * (g - mean(g) - x^ * mean(g x^)) with g = dy * gamma, x^ = (z - mean) * rstd; dx = dz
+ *         (the gradient of x) and dr = dz * keep * keep_scale (the gradient of r), both in `dtype`.  With dgamma and dbeta (fp32, e
+ *         each; both or neither): dgamma = sum_t dy x^, dbeta = sum_t dy, overwritten, in two phases through `workspace`
+ *         (srganfd_add_layernorm_workspace_bytes bytes; the query returns 0 for a shape the entry points refuse).
+ * SRGANFD_EINVAL: a bad dtype; ntok outside 1 .. 2^31; e no multiple of 32 in 32 .. 2048; a null pointer other than keep (and
+ * dgamma / dbeta / workspace together); x, r, z, y, dy, dx, dr or the workspace not 16-byte aligned, keep not 8-byte aligned; an output
+ * that aliases an input or another output; eps <= 0; a workspace that is too small. */
+int srganfd_add_layernorm_fwd(int32_t dtype, const void* x, const void* r, const uint8_t* keep, float keep_scale, const float* gamma,
+                              const float* beta, float eps, void* z, void* y, float* mean, float* rstd, int64_t ntok, int32_t e, void* stream);
+size_t srganfd_add_layernorm_workspace_bytes(int64_t ntok, int32_t e);
+int srganfd_add_layernorm_bwd(int32_t dtype, const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma,
+                              const uint8_t* keep, float keep_scale, void* dx, void* dr, float* dgamma, float* dbeta, void* workspace,
+                              size_t workspace_bytes, int64_t ntok, int32_t e, void* stream);
+/* y = x * keep * scale over numel elements (the feed-forward dropout; the same call runs on the gradient).  y may be x itself.
+ * SRGANFD_EINVAL: a bad dtype; a null pointer; numel no positive multiple of 8; x or y not 16-byte, keep not 8-byte aligned. */
+int srganfd_dropout_apply(int32_t dtype, const void* x, const uint8_t* keep, float scale, void* y, int64_t numel, void* stream);
+
+/* Multi-head self-attention over short sequences stored with a token stride, with dropout on the probabilities
+ * (csrc/attention_seq.hip): the attention of a batch_first=False encoder layer on its (seq, nseq, C) tensor as it lies in memory.
+ * qkv (seq, nseq, 3 C): the row of token s of sequence n at s * nseq + n, q | k | v and the heads within a row as in
+ * srganfd_attn_args; out / d_out (seq, nseq, C) and d_qkv likewise; lse (nseq, heads, seq) fp32; keep (nseq, heads, seq, seq)
+ * uint8 or NULL.  head_dim 16, 32 or 64; 1 <= seq <= 128 (every row sweeps the whole sequence).
+ *   fwd   S = (q k^T) / sqrt(head_dim), P = softmax rows in fp32, rounded once to `dtype`; out = (P * keep * keep_scale) v; writes lse.
+ *   bwd   from qkv, out, lse, d_out (and the same keep): d_qkv.  One launch, no workspace.
+ * SRGANFD_EINVAL: null arguments or a null pointer among those the entry point uses; a bad dtype or head_dim; a non-positive
+ * size; seq > 128; a pointer not 16-byte aligned; out aliasing qkv, d_qkv aliasing an input; keep with keep_scale <= 0. */
+typedef struct srganfd_seq_attn_args {
+  int32_t dtype;                 /* SRGANFD_F32 / F16 / BF16 */
+  int32_t seq, nseq, heads, head_dim;
+  float keep_scale;              /* 1 / (1 - p); read only with keep */
+  const void* qkv;
+  void* out;
+  float* lse;
+  const void* d_out;
+  void* d_qkv;
+  const uint8_t* keep;
+} srganfd_seq_attn_args;
+int srganfd_seq_attention_fwd(const srganfd_seq_attn_args* a, void* stream);
+int srganfd_seq_attention_bwd(const srganfd_seq_attn_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,14 @@ class AttnArgs(C.Structure):
     ]
 
 
+class SeqAttnArgs(C.Structure):
+    C_NAME = "srganfd_seq_attn_args"
+    _fields_ = [
+        ("dtype", C.c_int32), ("seq", C.c_int32), ("nseq", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("keep_scale", C.c_float),
+        ("qkv", C.c_void_p), ("out", C.c_void_p), ("lse", C.c_void_p), ("d_out", C.c_void_p), ("d_qkv", C.c_void_p), ("keep", C.c_void_p),
+    ]
+
+
 # symbol -> (restype, argtypes).  tests/test_host_logic.py checks that the library exports every one of these, and has a C++ compiler
 # check each entry's argument and return classes, every Structure above (C_NAME: the header's struct; size, field offsets and sizes) and
 # the constants this file repeats against include/srganfd.h
@@ -257,6 +265,14 @@ SYMBOLS = {
     "srganfd_attention_weights": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
     "srganfd_attention_bwd": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
     "srganfd_pixel_gate": (C.c_int, [C.c_int32, View, View, View, View, View, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    "srganfd_add_layernorm_fwd": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "srganfd_add_layernorm_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "srganfd_add_layernorm_bwd": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int32, C.c_void_p]),
+    "srganfd_dropout_apply": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "srganfd_seq_attention_fwd": (C.c_int, [C.POINTER(SeqAttnArgs), C.c_void_p]),
+    "srganfd_seq_attention_bwd": (C.c_int, [C.POINTER(SeqAttnArgs), C.c_void_p]),
 }
 
 LOSS_WS_FLOATS = 2049

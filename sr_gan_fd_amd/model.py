@@ -34,6 +34,7 @@ __all__ = [
     "Discriminator", "discriminator",
     "SelfAttention", "BSRGANsa", "bsrgansa_x2",
     "RPA", "US", "Generator_RPA", "gen_rpa2x",
+    "TransformerEncoderLayer", "TransformerEncoder",
 ]
 
 
@@ -162,6 +163,60 @@ class SelfAttention(nn.Module):
     def forward(self, x: Tensor):
         from .attention import self_attention_apply
         return self_attention_apply(self, x)
+
+
+class TransformerEncoderLayer(nn.TransformerEncoderLayer):
+    """The layer of the reference's transformer block (A-ESRGAN/model.py:673: ``TransformerEncoderLayer(d_model=channels, nhead=4)``
+    with torch's defaults -- post-norm, ReLU, dim_feedforward 2048, dropout 0.1, batch_first=False, LayerNorm eps 1e-5, biases).
+    torch's class is the parameter container (its state-dict keys, shapes and seeded initial values); ``forward(src)`` runs the HIP
+    engine (transformer.py) on a ``(S, N, E)`` fp32 GPU tensor -- S is the sequence axis -- and returns the same shape in fp32,
+    differentiable in ``src`` and every parameter.  In ``.train()`` mode with ``dropout > 0`` all four dropout sites are live;
+    ``dropout_masks()`` returns the keep-masks of the last training forward.
+
+    Deviations: ``norm_first=True``, an activation other than ReLU, ``batch_first=True``, ``bias=False``, any mask or ``is_causal``
+    argument, ``d_model % 32 != 0``, a head size outside {16, 32, 64}, ``dim_feedforward % 32 != 0``, sequences longer than 128, CPU
+    tensors and a wrong last dimension raise ``SrganfdError``."""
+
+    def __init__(self, *args: Any, **kwargs: Any) -> None:
+        super().__init__(*args, **kwargs)
+        from .transformer import check_layer
+        check_layer(self)
+        self.compute_dtype = None
+
+    def forward(self, src: Tensor, src_mask=None, src_key_padding_mask=None, is_causal=False) -> Tensor:
+        from .transformer import check_no_masks, transformer_apply
+        check_no_masks("TransformerEncoderLayer", src_mask=src_mask, src_key_padding_mask=src_key_padding_mask, is_causal=is_causal)
+        return transformer_apply(self, src)
+
+    def dropout_masks(self) -> dict:
+        from .transformer import transformer_engine
+        return transformer_engine(self).dropout_masks()
+
+
+class TransformerEncoder(nn.TransformerEncoder):
+    """A-ESRGAN/model.py:674: ``TransformerEncoder(encoder_layer, num_layers)``, torch's class as the parameter container
+    (``layers.{i}.*``, ``_get_clones`` copies of the layer given); ``forward(src)`` runs the whole stack as ONE engine (transformer.py).
+    ``encoder_layer`` is a TransformerEncoderLayer of this module; a final ``norm`` raises ``SrganfdError``, as does everything the layer
+    refuses.  ``dropout_masks()``: the keep-masks of the last training forward, keys ``layers.{i}.<site>``."""
+
+    def __init__(self, encoder_layer: nn.Module, num_layers: int, *args: Any, **kwargs: Any) -> None:
+        from ._abi import SrganfdError
+        if not isinstance(encoder_layer, TransformerEncoderLayer):
+            raise SrganfdError("TransformerEncoder: encoder_layer must be a sr_gan_fd_amd TransformerEncoderLayer")
+        kwargs.setdefault("enable_nested_tensor", False)        # torch's fast path, which this class never takes
+        super().__init__(encoder_layer, num_layers, *args, **kwargs)
+        if self.norm is not None:
+            raise SrganfdError("TransformerEncoder: a final norm has no kernel (the reference's stack has none)")
+        self.compute_dtype = None
+
+    def forward(self, src: Tensor, mask=None, src_key_padding_mask=None, is_causal=None) -> Tensor:
+        from .transformer import check_no_masks, transformer_apply
+        check_no_masks("TransformerEncoder", mask=mask, src_key_padding_mask=src_key_padding_mask, is_causal=is_causal)
+        return transformer_apply(self, src)
+
+    def dropout_masks(self) -> dict:
+        from .transformer import transformer_engine
+        return transformer_engine(self).dropout_masks()
 
 
 class RRDBNet(_RRDBGenerator):

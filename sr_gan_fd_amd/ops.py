@@ -198,7 +198,7 @@ def conv2d(args: A.ConvArgs, rec=None, what: str = "conv2d", L=None, st=None) ->
 # ---- launch items: what the engines' per-shape launch lists (sp.fw / sp.bw) hold.  Every item has ``launch(run)`` and ``run_items`` is
 # the one loop over a list; ``kind`` names the class for tests and debugging, nothing dispatches on it.  Here: Conv, Call, Wgrad,
 # WgradPartial / WgradPartialBatch / WgradReduce (the generator's dense blocks: batched MFMA launch, batched slab reduction), Ready (the generator's gradient buckets), PerCall (a
-# layer that writes the pass's own output) and, further down, DenseChain, ThinLaunch, Attention and PixelGate; the engines define the items only they launch
+# layer that writes the pass's own output) and, further down, DenseChain, ThinLaunch, Attention, PixelGate, SeqAttention, AddLayerNorm and DropoutApply; the engines define the items only they launch
 # beside themselves (BatchNorm, the spectral-norm gradient, the loss taps).  An item holds structs and addresses, never a closure:
 # what the addresses point to is kept alive by the plan's buffers.
 class Run:
@@ -733,6 +733,85 @@ class PixelGate(_Bracketed):
 def pixel_gate(args: tuple, rec=None) -> None:
     """one launch on the current stream, outside a launch list (tests, tools)"""
     launch_alone(PixelGate(args), rec)
+
+
+# ---- post-norm transformer encoder layer (csrc/layernorm.hip, csrc/attention_seq.hip): what is no 1x1 convolution ----
+SEQ_ATTN_MAX_SEQ = 128
+
+
+def seq_attn_args(dtype: int, seq: int, nseq: int, heads: int, head_dim: int, *, qkv=None, out=None, lse=None, d_out=None, d_qkv=None,
+                  keep=None, keep_scale: float = 1.0) -> A.SeqAttnArgs:
+    """qkv (seq, nseq, 3 * heads * head_dim), out / d_out (seq, nseq, heads * head_dim) in ``dtype``; lse (nseq, heads, seq) fp32;
+    keep (nseq, heads, seq, seq) uint8 or None; tensors or device addresses, None for what the entry point at hand does not use"""
+    a = A.SeqAttnArgs()
+    a.dtype, a.seq, a.nseq, a.heads, a.head_dim, a.keep_scale = dtype, seq, nseq, heads, head_dim, keep_scale
+    a.qkv, a.out, a.lse, a.d_out, a.d_qkv, a.keep = _ptr(qkv), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(d_qkv), _ptr(keep)
+    return a
+
+
+class SeqAttention(_Bracketed):
+    """one srganfd_seq_attention_fwd / _bwd launch (``op`` "fwd" | "bwd") over ``args`` (seq_attn_args').  Algorithmic work as
+    attn_work's: 4 N H S^2 D forward, 10 backward."""
+    kind = "seq_attention"
+
+    def __init__(self, op: str, args: A.SeqAttnArgs):
+        self.op, self.args = op, args
+        es, c = esize(args.dtype), args.heads * args.head_dim
+        unit, tok = 2.0 * args.nseq * args.heads * args.seq * args.seq * args.head_dim, float(args.nseq) * args.seq
+        self.label = "seq_attn_%s_kernel<%s,D=%d%s>" % (op, A.DT_NAME[args.dtype], args.head_dim, ",keep" if args.keep else "")
+        self.work = (2 * unit, tok * (4 * c * es + 4 * args.heads)) if op == "fwd" else (5 * unit, tok * (8 * c * es + 4 * args.heads))
+
+    def _issue(self, run: Run) -> None:
+        A.check(getattr(run.L, "srganfd_seq_attention_" + self.op)(C.byref(self.args), run.st), "seq_attention_" + self.op)
+
+
+def add_layernorm_workspace_bytes(ntok: int, e: int) -> int:
+    n = int(A.lib().srganfd_add_layernorm_workspace_bytes(ntok, e))
+    if n == 0:
+        raise A.SrganfdError("add_layernorm_workspace_bytes: " + A.lib().srganfd_last_error().decode())
+    return n
+
+
+class AddLayerNorm(_Bracketed):
+    """one srganfd_add_layernorm_fwd launch -- ``x``, ``r``, ``z``, ``y`` (ntok, e) in ``dtype``, ``mean`` / ``rstd`` (ntok) fp32,
+    ``gamma`` / ``beta``: addresses in the flat parameters, ``keep``: uint8 mask or None -- or, with ``dy``, ``dx`` and ``dr``, its
+    backward: dgamma / dbeta go to elements ``dg_off`` / ``db_off`` of the pass's flat gradient through ``ws``, and are skipped by a
+    pass with frozen parameters.  Tensors or device addresses.  Algorithmic work: bytes only."""
+    kind = "add_layernorm"
+
+    def __init__(self, dtype: int, ntok: int, e: int, *, z, mean, rstd, gamma: int, keep=None, keep_scale: float = 1.0, eps: float = 1e-5,
+                 x=None, r=None, y=None, beta: int = 0, dy=None, dx=None, dr=None, dg_off: int = -1, db_off: int = -1,
+                 ws: Optional[torch.Tensor] = None):
+        self.bwd = dy is not None
+        self.dtype, self.ntok, self.e, self.eps, self.keep_scale = dtype, ntok, e, eps, keep_scale
+        self.z, self.mean, self.rstd, self.gamma, self.beta, self.keep = _ptr(z), _ptr(mean), _ptr(rstd), gamma, beta, _ptr(keep)
+        self.x, self.r, self.y, self.dy, self.dx, self.dr = _ptr(x), _ptr(r), _ptr(y), _ptr(dy), _ptr(dx), _ptr(dr)
+        self.dg_off, self.db_off, self.ws = dg_off, db_off, ws
+        self.label = "add_layernorm_%s_kernel<%s%s>" % ("bwd" if self.bwd else "fwd", A.DT_NAME[dtype], ",keep" if keep is not None else "")
+        self.work = (0.0, float(ntok) * e * (esize(dtype) * 4 + (1 if keep is not None else 0)))
+
+    def _issue(self, run: Run) -> None:
+        if not self.bwd:
+            A.check(run.L.srganfd_add_layernorm_fwd(self.dtype, self.x, self.r, self.keep, self.keep_scale, self.gamma, self.beta, self.eps, self.z,
+                                                    self.y, self.mean, self.rstd, self.ntok, self.e, run.st), "add_layernorm_fwd")
+            return
+        params = run.need_wgrad and self.dg_off >= 0
+        A.check(run.L.srganfd_add_layernorm_bwd(self.dtype, self.dy, self.z, self.mean, self.rstd, self.gamma, self.keep, self.keep_scale, self.dx,
+                                                self.dr, run.grad + 4 * self.dg_off if params else None, run.grad + 4 * self.db_off if params else None,
+                                                self.ws.data_ptr() if params else None, self.ws.numel() if params else 0, self.ntok, self.e, run.st),
+                "add_layernorm_bwd")
+
+
+class DropoutApply(_Bracketed):
+    """one srganfd_dropout_apply launch: y = x * keep * scale over ``numel`` elements (y may be x)"""
+    kind = "dropout_apply"
+
+    def __init__(self, dtype: int, x, keep, scale: float, y, numel: int):
+        self.args = (dtype, _ptr(x), _ptr(keep), scale, _ptr(y), numel)
+        self.label, self.work = "dropout_apply_kernel<%s>" % A.DT_NAME[dtype], (0.0, float(numel) * (2 * esize(dtype) + 1))
+
+    def _issue(self, run: Run) -> None:
+        A.check(run.L.srganfd_dropout_apply(*self.args, run.st), "dropout_apply")
 
 
 # same-box A/B switch (0: one group of launches per layer, the round-1 form); both forms run in the HIP library and agree to the bit
