@@ -86,6 +86,7 @@ class FlatParams:
         self.index = {n: i for i, n in enumerate(self.names)}
         self.flat: Optional[Tensor] = None
         self.version = 0                       # bumped by whoever writes the flat buffer behind autograd's back (touch())
+        self.unwritten = False                 # True: some parameter's range of the flat gradient is written by no launch (new_grad zeroes)
 
     def off(self, name: str) -> int:
         return self.offsets[self.index[name]]
@@ -132,7 +133,7 @@ class FlatParams:
         """Flat gradient buffer.  Tensors whose size is not a multiple of 4 leave alignment gaps that no kernel writes: zero
         them (the optimizer walks the whole buffer), otherwise the gaps of the parameter buffer pick up allocator garbage and
         two identical runs stop being bitwise equal (found by tests/test_fullsize_gpu.py)."""
-        if self.total == sum(self.numels):
+        if self.total == sum(self.numels) and not self.unwritten:
             return torch.empty(self.total, dtype=torch.float32, device=device)
         return torch.zeros(self.total, dtype=torch.float32, device=device)
 
@@ -389,6 +390,7 @@ class TrunkEngine(EngineBase):
                 pb.add(("b", i, step), 3, kdim, n, segs)
         if self.full:
             fwd(("f", "conv1"), "conv1.weight", Cc, self.in_ch)
+            self._stage_pack(pb, dtc)
             ups = [f"upsampling{u}.0" for u in range(1, self.n_up + 1)]
             for nm in ["conv2"] + ups + ["conv3.0"]:
                 if nm in ups and self._parity(dtc):
@@ -405,7 +407,7 @@ class TrunkEngine(EngineBase):
     # -- per-shape plan -----------------------------------------------------------------------
     def _plan(self, N: int, H: int, W: int, dt: torch.dtype, dtc: int, device, pk: dict, train: bool) -> _Shape:
         # the launch lists bake absolute pointers into the packed buffer AND the flat parameter buffer (biases): both are in the key
-        key = (N, H, W, dtc, train, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
+        key = (N, H, W, dtc, train, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr()) + self._plan_key()
         sp = self.shapes.get(key)
         if sp is not None:
             return sp
@@ -465,8 +467,9 @@ class TrunkEngine(EngineBase):
             # small batches (the reference's own crop sizes): the five launches as ONE LDS-resident launch (csrc/dense_chain.hip)
             fw.extend(ops.dense_chain_or_launches(blk, device) if (Cc, G) == (64, 32) else [ops.Conv(a) for a in blk])
         if self.full:
-            tout = catb(R)
-            fw.append(ops.Conv(ops.conv_args(dtc, VC(tout), V(sp.f0), wptr + pk["offs"][("f", "conv2")], N, H, W, Cc, Cc, bias=bias("conv2.bias"),
+            # what conv2 reads: the trunk's output, or the output of a stage between the two (BSRGANtrans, engine_trans.py)
+            sp.conv2_in = self._stage_forward(sp, pk, fw, VC(catb(R)), N, H, W, dt, dtc, device, train)
+            fw.append(ops.Conv(ops.conv_args(dtc, sp.conv2_in, V(sp.f0), wptr + pk["offs"][("f", "conv2")], N, H, W, Cc, Cc, bias=bias("conv2.bias"),
                                              r1=VC(catb(0)), r1_scale=1.0)))
             src, h, w = sp.f0, H, W
             for u in range(1, self.n_up + 1):
@@ -596,11 +599,14 @@ class TrunkEngine(EngineBase):
             d_f0 = cur if self.n_up else sp.gB
             sp.d_f0 = d_f0
             # conv2: f0 = out1 + conv2(trunk_out)
-            bw.append(ops.Wgrad(wplans.plan(H, W, Cc, Cc, one("conv2", Cc, Cc)), VC(sp.catb(R)), V(d_f0)))
-            bw.append(cv(V(d_f0), VD(dyb(R - 1)), wptr + pk["offs"][("b", "conv2")], N, H, W, Cc, Cc))
+            bw.append(ops.Wgrad(wplans.plan(H, W, Cc, Cc, one("conv2", Cc, Cc)), sp.conv2_in, V(d_f0)))
+            dst2, epi2 = self._conv2_dgrad_target(sp, VD(dyb(R - 1)))
+            bw.append(cv(V(d_f0), dst2, wptr + pk["offs"][("b", "conv2")], N, H, W, Cc, Cc, **epi2))
             # gradient buckets for the data-parallel exchange (parallel.BucketReducer): parameters sit in named_parameters() order --
             # conv1, the dense blocks, conv2 and the tail -- so "everything from conv2 on" is one contiguous range, final here
             bw.append(ops.Ready(self._poff("conv2.weight"), self.fp.total))
+            # a stage between trunk and conv2: its backward ends in the last dense block's stacked-gradient buffer, its parameters are final
+            bw.extend(self._stage_backward(sp, pk, wplans, VD(dyb(R - 1))))
         # dense blocks, last to first
         rdb_names = ["conv%d" % k for k in range(1, 6)]
         for i in range(R - 1, -1, -1):
@@ -622,7 +628,7 @@ class TrunkEngine(EngineBase):
             blk.append(ops.conv_args(dtc, VD(di), dst, wptr + pk["offs"][("b", i, 4)], N, H, W, Ccat, Cc, **kw))
             chain = ops.dense_chain_or_launches(blk, sp.device) if (Cc, G) == (64, 32) else [ops.Conv(a) for a in blk]
             wg = ops.Wgrad(dense_plan(s5), VC(ci), VD(di), dw_off=self._poff(pre + "conv1.weight"), block=i)     # the plan's offsets are relative to the block
-            ready = [ops.Ready(self._poff(pre + "conv1.weight"), self._poff("conv2.weight"))] if self.full and R >= 4 and i == R // 2 else []     # upper half of the trunk is final: second bucket
+            ready = [ops.Ready(self._poff(pre + "conv1.weight"), self._trunk_end())] if self.full and R >= 4 and i == R // 2 else []     # upper half of the trunk is final: second bucket
             # the weight gradient reads what the four growth layers of the data gradient wrote and follows them (or the one launch for all five convs)
             bw.extend(chain[:4] + [wg] + ready + chain[4:])
         if self.full:
@@ -632,6 +638,7 @@ class TrunkEngine(EngineBase):
         # last bucket: whatever the earlier markers did not cover
         covered = min([it.lo for it in bw if isinstance(it, ops.Ready)], default=self.fp.total)
         bw.append(ops.Ready(0, covered))
+        self._finish_backward(sp, pk)
         sp.wg_ws = wplans.workspace()
         # four more workspaces of the dense-block plan's size for the batched slab reduction (34 MB each at B=32, 128x128)
         dense_ws = max((p_.workspace_bytes for p_ in plans.values()), default=0)
@@ -643,6 +650,33 @@ class TrunkEngine(EngineBase):
             sp.bw = batch_wgrads(bw, sp.wg_ws4, lambda wg, n: wg.plan if n == 1 else dense_plan(block_s5(wg.block), max(1, p0.splits // n)))
         else:
             sp.bw = batch_reductions(bw, sp.wg_ws4)
+
+    # -- what a generator with a stage between the trunk and conv2 overrides (engine_trans.py); here: no stage -----------------
+    def _plan_key(self) -> tuple:
+        """what a plan depends on besides shape, dtype, buffers and ``train``"""
+        return ()
+
+    def _stage_pack(self, pb: "ops.PackBuilder", dtc: int) -> None:
+        """the stage's packed operands"""
+
+    def _stage_forward(self, sp: _Shape, pk: dict, fw: list, trunk_out: A.View, N: int, H: int, W: int, dt, dtc: int, device, train: bool) -> A.View:
+        """appends the stage's forward items to ``fw``; returns the view conv2 reads"""
+        return trunk_out
+
+    def _conv2_dgrad_target(self, sp: _Shape, trunk_grad: A.View) -> Tuple[A.View, dict]:
+        """(where conv2's data gradient goes, its epilogue keywords)"""
+        return trunk_grad, {}
+
+    def _stage_backward(self, sp: _Shape, pk: dict, wplans: "ops.WgradPlans", trunk_grad: A.View) -> list:
+        """the stage's backward items, from conv2's data gradient to channels [0, Cc) of ``trunk_grad``, and their bucket marker"""
+        return []
+
+    def _trunk_end(self) -> int:
+        """offset of the first parameter behind the trunk's"""
+        return self._poff("conv2.weight")
+
+    def _finish_backward(self, sp: _Shape, pk: dict) -> None:
+        """last step of _plan_backward, before the workspaces are sized"""
 
     # -- execution ----------------------------------------------------------------------------
     def trunk_size(self, shape) -> Tuple[int, int, int]:
@@ -787,6 +821,9 @@ class _EngineFn(torch.autograd.Function):
     def backward(ctx, dout, *_):
         g, dx = ctx.eng.backward(ctx.sp, ctx.token, dout, ctx.need_w, ctx.need_dx)
         grads = tuple(ctx.eng.fp.grad_views(g)) if g is not None else (None,) * len(ctx.eng.fp.params)
+        unused = getattr(ctx.eng, "unused_params", None)          # registered parameters the forward never reads: None, as autograd gives
+        if unused:
+            grads = tuple(None if i in unused else t for i, t in enumerate(grads))
         return (dx, None, None) + grads
 
 
@@ -823,6 +860,10 @@ def generator_engine(owner: nn.Module) -> TrunkEngine:
         rdbs = []
         for blk in owner.trunk:
             rdbs += [blk.rdb1, blk.rdb2, blk.rdb3]
+        from . import model as M
+        if isinstance(owner, M.BSRGANtrans):              # (a subclass too: a plain TrunkEngine would silently skip the stage)
+            from .engine_trans import TransGeneratorEngine
+            return TransGeneratorEngine(owner, rdbs)
         return TrunkEngine(owner, rdbs, rrdb=True, full=True)
     return _engine(owner, make)
 

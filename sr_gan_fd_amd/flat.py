@@ -44,6 +44,34 @@ def flat_span(tensors: Sequence[Optional[Tensor]]) -> Optional[Tuple[Tensor, Lis
     return flat, [(p - lo) // 4 for p in ptrs]
 
 
+def engine_grad_span(params: Sequence[Tensor]) -> Optional[Tuple[Tensor, List[int]]]:
+    """flat_span of the gradients of ``params`` when some of them are None BY DESIGN: the parameters are exactly those of one engine
+    that registers parameters its forward never reads (BSRGANtrans's ``transformer_layer.*``: ``unused_params``), the None gradients
+    are exactly those parameters', and every other gradient is the view of ONE flat gradient at its parameter's offset.  That
+    engine's flat gradient is zero over the unread parameters' ranges (FlatParams.unwritten), so a whole-buffer Adam step with zero
+    moments and no weight decay leaves them bit-unchanged -- what torch does by skipping them.  Else None."""
+    from . import engine as E
+    for eng in list(E._ENGINES.values()):
+        fp, unused = eng.fp, getattr(eng, "unused_params", None)
+        if not unused or len(fp.params) != len(params) or any(a is not b for a, b in zip(fp.params, params)):
+            continue
+        grads = [p.grad for p in params]
+        if {i for i, g in enumerate(grads) if g is None} != set(unused):
+            return None
+        i0 = next(i for i, g in enumerate(grads) if g is not None)
+        g0 = grads[i0]
+        st0, base = g0.untyped_storage().data_ptr(), g0.data_ptr() - 4 * fp.offsets[i0]
+        if g0.dtype != torch.float32 or base < st0 or base + 4 * fp.total > st0 + g0.untyped_storage().nbytes():
+            return None
+        for g, o in zip(grads, fp.offsets):
+            if g is not None and (g.dtype != torch.float32 or not g.is_contiguous() or g.untyped_storage().data_ptr() != st0 or g.data_ptr() != base + 4 * o):
+                return None
+        n = fp.offsets[-1] + fp.numels[-1]          # as flat_span: up to the last tensor's end, without its alignment padding
+        flat = torch.empty(0, dtype=torch.float32, device=g0.device).set_(g0.untyped_storage(), (base - st0) // 4, (n,))
+        return flat, list(fp.offsets)
+    return None
+
+
 def engine_flatten(module) -> None:
     """If ``module`` is one of this package's networks on a GPU, make its parameters views of the engine's flat buffer now (the engines
     do this at the first forward; an optimizer or EMA copy built before it would otherwise see 702 separate tensors once)."""
@@ -56,7 +84,7 @@ def engine_flatten(module) -> None:
     if not p.is_cuda:
         return
     eng = None
-    if isinstance(module, M._RRDBGenerator):
+    if isinstance(module, (M._RRDBGenerator, M.BSRGANtrans)):
         eng = E.generator_engine(module)
     elif isinstance(module, M.DiscriminatorUNet):
         from .engine_d import discriminator_engine

@@ -21,7 +21,7 @@ from .engine import generator_engine
 from .engine_a import aesrgan_engine
 from .engine_d import discriminator_engine
 from .parallel import SideStreamReducer, SyncBatchNormReduce
-from .trainer import FlatAdamEMA, FusedTrainer, check_loss_scaling, check_targets, pin_training_dtype
+from .trainer import FlatAdamEMA, FusedTrainer, check_generator, check_loss_scaling, check_targets, pin_training_dtype
 
 
 class GanTrainer(FusedTrainer):
@@ -36,6 +36,7 @@ class GanTrainer(FusedTrainer):
         # (A-ESRGAN/train_aesrgan.py:396-483 runs the same statements around it); both engines share one interface
         d_engine = aesrgan_engine if type(d_model).__name__ == "UNetDiscriminatorAesrgan" else discriminator_engine
         self.ge, self.de = generator_engine(g_model), d_engine(d_model)
+        check_generator("GanTrainer", self.ge, weight_decay, process_group)
         dev = next(g_model.parameters()).device
         self.dev = dev
         self.g_opt = FlatAdamEMA(self.ge.fp.sync(dev), g_lr, betas, eps, weight_decay, ema_decay, layout=self.ge.fp)

@@ -35,6 +35,7 @@ __all__ = [
     "SelfAttention", "BSRGANsa", "bsrgansa_x2",
     "RPA", "US", "Generator_RPA", "gen_rpa2x",
     "TransformerEncoderLayer", "TransformerEncoder",
+    "BSRGANtrans", "bsrgantrans_x2",
 ]
 
 
@@ -217,6 +218,64 @@ class TransformerEncoder(nn.TransformerEncoder):
     def dropout_masks(self) -> dict:
         from .transformer import transformer_engine
         return transformer_engine(self).dropout_masks()
+
+
+class BSRGANtrans(nn.Module):
+    """A-ESRGAN/model.py:643-746, the generator A-ESRGAN's configuration names (aesrgan_config.py:50): conv1, the RRDB trunk, a 3x3
+    stride-2 conv + LeakyReLU (``downsamplingTrans``), two post-norm transformer layers over the half-size map read as ``(B, h w, C)``
+    with batch_first=False -- the sequence axis is the BATCH: one sample's SR depends on the rest of its batch --, nearest x2 + conv
+    + LeakyReLU (``upsamplingTrans``), conv2, ``+ out1`` (the trunk's own output is not added back), the tail, clamp to [0, 1].
+    Same constructor arguments, state-dict keys and shapes, construction order and therefore seeded initial values: the init loop
+    re-draws the nn.Conv2d weights only, the transformer keeps torch's initialisation.  ``transformer_layer`` is registered and never
+    called (``transformer_encoder`` holds copies of it): its gradients stay ``None``.  The sub-modules are parameter containers; the
+    whole network is ONE HIP engine (engine_trans.py).  In ``.train()`` mode all eight dropout sites are live; ``dropout_masks()``
+    returns the last training forward's keep-masks under ``transformer_encoder.layers.{i}.<site>``.
+
+    Deviations: odd H or W (the reference's ``view`` fails there too), a batch above 128, ``channels`` that is no multiple of 32 or
+    whose quarter is no attention head size (16, 32, 64), ``growth_channels % 32``, a wrong channel count, CPU tensors and everything
+    TransformerEncoderLayer refuses raise ``SrganfdError``."""
+
+    def __init__(self, in_channels: int = 3, out_channels: int = 3, channels: int = 64, growth_channels: int = 32,
+                 num_rrdb: int = 23, upscale_factor: int = 4) -> None:
+        super().__init__()
+        self.upscale_factor = upscale_factor
+        self.channels = channels
+        conv = lambda cin, cout, stride=1: nn.Conv2d(cin, cout, (3, 3), (stride, stride), (1, 1))
+        act_conv = lambda stride=1: nn.Sequential(conv(channels, channels, stride), nn.LeakyReLU(0.2, True))
+        # the reference's order: it fixes the named_parameters() order and the random stream of a seeded construction
+        self.conv1 = conv(in_channels, channels)
+        self.trunk = nn.Sequential(*[_ResidualResidualDenseBlock(channels, growth_channels) for _ in range(num_rrdb)])
+        self.downsamplingTrans = act_conv(2)
+        self.transformer_layer = TransformerEncoderLayer(d_model=channels, nhead=4)
+        self.transformer_encoder = TransformerEncoder(self.transformer_layer, num_layers=2)
+        self.upsamplingTrans = act_conv()
+        self.conv2 = conv(channels, channels)
+        self.upsampling1 = act_conv()
+        if upscale_factor == 4:
+            self.upsampling2 = act_conv()
+        self.conv3 = act_conv()
+        self.conv4 = conv(channels, out_channels)
+        for module in self.modules():
+            if isinstance(module, nn.Conv2d):
+                nn.init.kaiming_normal_(module.weight)
+                module.weight.data *= 0.1
+                if module.bias is not None:
+                    nn.init.constant_(module.bias, 0)
+        self.compute_dtype = None
+
+    def n_upsample(self) -> int:
+        return 2 if self.upscale_factor == 4 else 1
+
+    def forward(self, x: Tensor) -> Tensor:
+        return self._forward_impl(x)
+
+    def _forward_impl(self, x: Tensor) -> Tensor:
+        from .engine import generator_apply
+        return generator_apply(self, x)
+
+    def dropout_masks(self) -> dict:
+        from .engine import generator_engine
+        return generator_engine(self).dropout_masks()
 
 
 class RRDBNet(_RRDBGenerator):
@@ -480,6 +539,12 @@ def bsrgansa_x2(**kwargs: Any) -> BSRGANsa:
 
 def bsrgan_x2(**kwargs: Any) -> BSRGAN:
     return BSRGAN(upscale_factor=2, **kwargs)
+
+
+def bsrgantrans_x2(**kwargs: Any) -> BSRGANtrans:
+    """A-ESRGAN/model.py:749-753"""
+    print("* BSRGAN TRANSFORMER 2x")
+    return BSRGANtrans(upscale_factor=2, **kwargs)
 
 
 def bsrgan_x4(**kwargs: Any) -> BSRGAN:

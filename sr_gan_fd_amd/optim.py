@@ -16,7 +16,7 @@ import torch
 from torch.optim import lr_scheduler  # noqa: F401  (the scripts use optim.lr_scheduler.MultiStepLR)
 
 from . import _abi as A
-from .flat import flat_span
+from .flat import engine_grad_span, flat_span
 
 
 class Adam(torch.optim.Adam):
@@ -39,6 +39,10 @@ class Adam(torch.optim.Adam):
             return False
         pf = flat_span([p.data for p in ps])
         gf = flat_span([p.grad for p in ps])
+        if gf is None and not group["weight_decay"] and any(p.grad is None for p in ps):
+            # a generator whose engine registers parameters its forward never reads: their gradients are None, their range of the one
+            # flat gradient is zero, and without weight decay the whole-buffer step leaves them unchanged, as torch's skipping does
+            gf = engine_grad_span(ps)
         if pf is None or gf is None or pf[1] != gf[1] or pf[0].numel() != gf[0].numel():
             return False
         flat, offs = pf

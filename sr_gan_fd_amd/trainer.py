@@ -235,6 +235,24 @@ def check_targets(what: str, eng, lr_img: Tensor, **targets: Optional[Tensor]) -
                                  f"{tuple(lr_img.shape)}")
 
 
+def check_generator(what: str, eng, weight_decay: float, process_group) -> None:
+    """What the fused trainers refuse of a generator whose engine carries parameters its forward never reads (``eng.unused_params``:
+    BSRGANtrans's registered ``transformer_layer``) or whose forward couples the samples of a batch (``eng.batch_coupled``: its
+    transformer block attends across the local batch):
+      * weight_decay != 0 -- the unread parameters' range of the flat gradient is zero, so the fused Adam would decay what torch.optim.Adam
+        (which skips a parameter whose .grad is None) leaves alone;
+      * a process group of more than one rank -- a sharded batch is another function than the single-process step on the whole batch,
+        and the trainers' "identical maths" promise would be false."""
+    if getattr(eng, "unused_params", None) and weight_decay != 0:
+        raise A.SrganfdError(f"{what}: weight_decay != 0 is not supported with {eng.what} (its transformer_layer.* parameters have no gradient: "
+                             "torch skips them, a fused step over the flat buffer would decay them)")
+    if getattr(eng, "batch_coupled", False) and process_group is not None:
+        import torch.distributed as dist
+        if dist.get_world_size(process_group) > 1:
+            raise A.SrganfdError(f"{what}: {eng.what} cannot be trained data-parallel (its transformer block attends across the local batch: "
+                                 "a sharded batch computes another function than the single-process step)")
+
+
 class FlatAdamEMA:
     """torch.optim.Adam maths (amsgrad=False) + AveragedModel(avg_fn=(1-d)*ema + d*p) over one flat buffer."""
 
@@ -457,6 +475,7 @@ class GeneratorTrainer(FusedTrainer):
         self.g = g_model
         pin_training_dtype(g_model)
         self.eng = generator_engine(g_model)
+        check_generator("GeneratorTrainer", self.eng, weight_decay, process_group)
         dev = next(g_model.parameters()).device
         self.flat = self.eng.fp.sync(dev)
         self.opt = FlatAdamEMA(self.flat, lr, betas, eps, weight_decay, ema_decay, layout=self.eng.fp)
