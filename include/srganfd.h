@@ -387,6 +387,10 @@ int srganfd_conv2d_thin_out(const srganfd_thin_args* a, void* stream);
  * w_big_is_cout, else cs) or NULL.  Deterministic (slabs + ordered reduction); workspace >= srganfd_conv2d_thin_wgrad_workspace(). */
 size_t srganfd_conv2d_thin_wgrad_workspace(void);
 int srganfd_conv2d_thin_wgrad(const srganfd_thin_args* a, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+/* Name of the kernel instantiation one of the three entry points above launches for these arguments (validates them as that entry point
+ * does, launches nothing, reads no gradient or workspace): op 0 = thin_in, 1 = thin_out, 2 = thin_wgrad.  thin_in's label ends in ",NT"
+ * when the output is large enough for non-temporal stores. */
+int srganfd_conv2d_thin_describe(const srganfd_thin_args* a, int32_t op, char* out, size_t out_len);
 
 /* ---- A-ESRGAN attention U-Net discriminator (A-ESRGAN/model.py:228-345) ---- */
 /* F.interpolate(size=..., mode="bilinear", align_corners=False) (model.py:245,250): bwd=0: a (hi x wi) -> b (ho x wo);

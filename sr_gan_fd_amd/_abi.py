@@ -177,6 +177,7 @@ SYMBOLS = {
     "srganfd_conv2d_thin_out": (C.c_int, [C.POINTER(ThinArgs), C.c_void_p]),
     "srganfd_conv2d_thin_wgrad_workspace": (C.c_size_t, []),
     "srganfd_conv2d_thin_wgrad": (C.c_int, [C.POINTER(ThinArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "srganfd_conv2d_thin_describe": (C.c_int, [C.POINTER(ThinArgs), C.c_int32, C.c_char_p, C.c_size_t]),
     "srganfd_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "srganfd_pack_weights": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "srganfd_wgrad_plan_bytes": (C.c_size_t, [C.POINTER(WgradShape), C.POINTER(WgradConv)]),

@@ -10,15 +10,17 @@
 //   * thin_in  (1..4 -> 64 channels; also the data gradient of a 64 -> 1..4 conv, with the LeakyReLU' mask): all 9 taps x 4 channels
 //     are ONE K: k = 4 * tap + c, 36 products = two v_mfma_f32_16x16x32 steps (taps 0-7, tap 8) per 16 pixels x
 //     16 output channels instead of 9 taps x 32 padded channels.  Operands are swapped (A = weights, B = pixels) so that a lane ends
-//     up with 8 CONSECUTIVE output channels of one pixel: bias (as the accumulator's initial value), activation, mask and the 16-byte
-//     store all happen in registers.  No LDS, no barrier: a wave owns a 16-column strip and walks down the image; its B fragments are
-//     8-byte loads of the thin tensor (L1 / L2 hits: every thin pixel is needed by 9 taps), its weights live in 24 registers.
+//     up with 8 CONSECUTIVE output channels of one pixel: bias (as the accumulator's initial value) and activation happen in
+//     registers.  A wave owns a 16-column strip and walks down the image; its B fragments are 8-byte loads of the thin tensor (L1 /
+//     L2 hits: every thin pixel is needed by 9 taps), its weights live in 24 registers.  LDS: the fp32 weights once (the prologue's
+//     one workgroup barrier), then every row's 16 x 64 tile through a wave-private 2 KiB image that turns the accumulator layout
+//     into whole-pixel stores (wave barriers only); the mask is applied in that store layout.
 //   * thin_out (64 -> 1..4 channels; also the data gradient of a 1..4 -> 64 conv): the three kernel COLUMNS are folded into the MFMA's
 //     M side: row (kx, co) of D' = sum over (ky, ci) of W[co][ky][kx][ci] * X[y + ky][x'][ci] for 16 patch columns x' -- K = 3 x 64 =
 //     192 = six 16x16x32 MFMAs per 14 output pixels instead of eighteen on 31/32-zero columns -- and the output is
-//     out[x] = D'[kx=0][x] + D'[1][x+1] + D'[2][x+2], three ds_bpermute'd registers.  B fragments are 16-byte global loads of the
-//     64-channel tensor (read exactly once per strip row, kept in registers for the three output rows that use them), ring-buffered
-//     four rows ahead.  No LDS, no barrier.
+//     out[x] = D'[kx=0][x] + D'[1][x+1] + D'[2][x+2], two lane gathers (__shfl) per accumulator register.  B fragments are 16-byte
+//     global loads of the 64-channel tensor (read exactly once per strip row, kept in registers for the three output rows that use
+//     them), ring-buffered four rows ahead.  No LDS and no barrier after the weight prologue.
 //   * thin_wgrad: dW[b][tap][s] = sum_p BIG[p][b] * THIN[p + tap][s] as a 64 x 48 output (M = the 64 channels, N = 4 * tap + s, plus
 //     a column of ones that yields the bias gradient), K = pixels.  Both operands need K (pixels) along a lane's register, i.e. a
 //     transpose of NHWC data: tiles go through a wave-private LDS image and come back through ds_read_b64_tr_b16 (for the thin
@@ -34,22 +36,42 @@ namespace srganfd {
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2v;
 typedef __attribute__((address_space(3))) s16x4 lds_tr_t;
 
+// A 64-channel operand (srganfd_view): element (pixel p, channel c of the view) of an image of H*W*C elements at p * ps + offset(c) --
+// NHWC ps = C, gs = 32; planar 32-channel groups ps = 32, gs = H*W*32
+struct ThinView {
+  const void* ptr;
+  int C, c0, ps, gs;
+  __device__ __forceinline__ int offset(int c) const { c += c0; return (c >> 5) * gs + (c & 31); }
+};
+
 struct ThinK {
-  const void* thin;         // NHWC4 16-bit tensor (thin_in input / thin_wgrad small operand)
+  const void* thin;         // NHWC4 16-bit tensor (thin_in input)
   float* thin_f32;          // thin_out output (fp32)
   int thin_pitch;           // its pixel pitch in floats (4, or 1 when cs == 1)
-  const void* big; const void* mask;
-  int bigC, big_c0, big_ps, big_gs;      // element (pixel p, channel c) at p * ps + (c >> 5) * gs + (c & 31) inside an image of H*W*bigC elements
-  int mC, m_c0, m_ps, m_gs;
+  ThinView big, mask;
   const float* w; const float* bias;
   int cs, big_is_cout, flip;
-  int N, H, W;
+  int H, W;
   float neg, mask_slope;    // activation as one select: v * (v > 0 ? 1 : neg)
-  int nt;                   // non-temporal output stores (large outputs)
   int tiles_x, tiles_y;
 };
 
 constexpr int kThinOob = 0x7fffffff;
+
+// the launch's raw fp32 weights -> LDS, where the fragment prologues pick them
+__device__ __forceinline__ void thin_stage_weights(float* wl, const ThinK& a, int tid) {
+  const int nw = 64 * a.cs * 9;
+  for (int i = tid; i < nw; i += 256) wl[i] = a.w[i];
+  __syncthreads();
+}
+
+// tile of this workgroup: block index -> (tile column, tile row, image)
+struct ThinTile { int tx, ty, img; };
+__device__ __forceinline__ ThinTile thin_tile(const ThinK& a) {
+  int bid = blockIdx.x;
+  const int tx = bid % a.tiles_x; bid /= a.tiles_x;
+  return {tx, bid % a.tiles_y, bid / a.tiles_y};
+}
 
 template <typename T> __device__ __forceinline__ unsigned short to_bits16(float f) {
   if constexpr (Elem<T>::kDtype == SRGANFD_F16) return __builtin_bit_cast(unsigned short, (_Float16)f);
@@ -85,11 +107,7 @@ __global__ __launch_bounds__(256) void thin_in_kernel(const ThinK a) {
   __shared__ __attribute__((aligned(16))) char tl_all[4 * 2048];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  {
-    const int nw = 64 * a.cs * 9;
-    for (int i = tid; i < nw; i += 256) wl[i] = a.w[i];
-  }
-  __syncthreads();
+  thin_stage_weights(wl, a, tid);
   const int n16 = lane & 15, kg = lane >> 4;
   // A fragments: D row m = lane & 15 of tile t is output channel 32 * (t >> 1) + 8 * (m >> 2) + 4 * (t & 1) + (m & 3), so that after
   // the MFMA lane (pixel, kg) holds channels 32 u + 8 kg + [0, 8) in tiles 2u, 2u + 1
@@ -98,6 +116,7 @@ __global__ __launch_bounds__(256) void thin_in_kernel(const ThinK a) {
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int b = 32 * (t >> 1) + 8 * (n16 >> 2) + 4 * (t & 1) + (n16 & 3);
+    // (the packing stays written out here and in thin_out: on pack8<T> or behind one builder this kernel's registers moved, see profiles/conv_thin_refactor_isa.txt)
     unsigned short e[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) e[j] = to_bits16<T>(thin_weight(wl, a.big_is_cout, a.cs, a.flip, b, j & 3, 2 * kg + (j >> 2)));
@@ -116,36 +135,30 @@ __global__ __launch_bounds__(256) void thin_in_kernel(const ThinK a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) bv[t][r] = a.bias ? a.bias[32 * (t >> 1) + 8 * kg + 4 * (t & 1) + r] : 0.f;
   }
-  // tile of this workgroup
-  int bid = blockIdx.x;
-  const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int img = bid / a.tiles_y;
+  const ThinTile tile = thin_tile(a);
+  const int tx = tile.tx, ty = tile.ty, img = tile.img;
   const int ox = tx * 64 + wave * 16 + n16;
   const int y0 = ty * kThinInRows, y1 = min(y0 + kThinInRows, a.H);
   if (tx * 64 + wave * 16 >= a.W) return;              // whole wave outside the image (ragged width)
   // thin operand: 8-byte loads through a buffer descriptor of this image (padding = offset beyond the range -> zeros)
   const T* timg = (const T*)a.thin + (size_t)img * a.H * a.W * 4;
   auto rsrc = __builtin_amdgcn_make_buffer_rsrc(thin_uniform_ptr(timg), (short)0, (int)((unsigned)a.H * (unsigned)a.W * 8u), 0x00020000);
-  // taps of this lane: K32 fragment taps 2 kg, 2 kg + 1; K16 fragment tap 8
+  // taps of this lane: first K32 step taps 2 kg, 2 kg + 1; second K32 step tap 8
   const int tA = 2 * kg, tB = 2 * kg + 1;
   const int dyA = tA / 3 - 1, dxA = tA % 3 - 1, dyB = tB / 3 - 1, dxB = tB % 3 - 1;
   const int xA = ox + dxA, xB = ox + dxB, xC = ox + 1;
   const bool okA = xA >= 0 && xA < a.W, okB = xB >= 0 && xB < a.W, okC = xC < a.W;
   auto ldx = [&](int gy, int gx, bool okx) -> u32x2v {
-    typedef __attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned v2u;
     const bool ok = okx && gy >= 0 && gy < a.H;
-    const v2u r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, ok ? (gy * a.W + gx) * 8 : kThinOob, 0, 0);
-    return __builtin_bit_cast(u32x2v, r);
+    return __builtin_bit_cast(u32x2v, __builtin_amdgcn_raw_buffer_load_b64(rsrc, ok ? (gy * a.W + gx) * 8 : kThinOob, 0, 0));
   };
-  const T* yimg = (const T*)a.big + (size_t)img * a.H * a.W * a.bigC;
-  const T* mimg = MASK ? (const T*)a.mask + (size_t)img * a.H * a.W * a.mC : nullptr;
+  const T* yimg = (const T*)a.big.ptr + (size_t)img * a.H * a.W * a.big.C;
+  const T* mimg = MASK ? (const T*)a.mask.ptr + (size_t)img * a.H * a.W * a.mask.C : nullptr;
   // store layout: piece u (0, 1) of a lane is pixel (lane >> 3) + 8 u of the wave's 16, channels c0 + 8 (lane & 7) .. + 7
   char* tl = tl_all + wave * 2048;
   const int sp8 = lane >> 3, ss8 = lane & 7;
   const int ox_t0 = tx * 64 + wave * 16 + sp8;             // image column of piece 0 (piece 1: + 8)
-  const int cy = a.big_c0 + 8 * ss8, cm = a.m_c0 + 8 * ss8;
-  const int yoff = (cy >> 5) * a.big_gs + (cy & 31), moff = (cm >> 5) * a.m_gs + (cm & 31);
+  const int yoff = a.big.offset(8 * ss8), moff = a.mask.offset(8 * ss8);
   // rows of loads in flight ahead of the row being computed (4 and 8 measured the same: the kernel is bound by its stores, and 2 leaves
   // registers for four / three waves per SIMD)
   constexpr int D = 2;
@@ -159,7 +172,7 @@ __global__ __launch_bounds__(256) void thin_in_kernel(const ThinK a) {
       if (oy < y1) {
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-          if (ox_t0 + 8 * u < a.W) mk[slot][u] = *(const u32x4*)(mimg + (size_t)(oy * a.W + ox_t0 + 8 * u) * a.m_ps + moff);
+          if (ox_t0 + 8 * u < a.W) mk[slot][u] = *(const u32x4*)(mimg + (size_t)(oy * a.W + ox_t0 + 8 * u) * a.mask.ps + moff);
       }
     }
   };
@@ -209,7 +222,7 @@ __global__ __launch_bounds__(256) void thin_in_kernel(const ThinK a) {
             o = pack8<T>(v);
           }
           if (ox_t0 + 8 * u < a.W) {
-            u32x4* dst = (u32x4*)((T*)yimg + (size_t)(oy * a.W + ox_t0 + 8 * u) * a.big_ps + yoff);
+            u32x4* dst = (u32x4*)((T*)yimg + (size_t)(oy * a.W + ox_t0 + 8 * u) * a.big.ps + yoff);
             // (NT is a template parameter: behind a run-time `if` the two stores are merged into one plain store)
             if constexpr (NT) __builtin_nontemporal_store(o, dst);
             else *dst = o;
@@ -234,11 +247,7 @@ __global__ __launch_bounds__(256) void thin_out_kernel(const ThinK a) {
   __shared__ float wl[64 * 4 * 9];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  {
-    const int nw = 64 * a.cs * 9;
-    for (int i = tid; i < nw; i += 256) wl[i] = a.w[i];
-  }
-  __syncthreads();
+  thin_stage_weights(wl, a, tid);
   const int n16 = lane & 15, kg = lane >> 4;
   // A fragments [ky][half]: row m = (kx = m >> 2, co = m & 3), k = 8 kg + j -> input channel 32 half + 8 kg + j
   Frag wa[3][2];
@@ -259,31 +268,22 @@ __global__ __launch_bounds__(256) void thin_out_kernel(const ThinK a) {
   float bs[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) bs[r] = (a.bias && r < a.cs) ? a.bias[r] : 0.f;
-  int bid = blockIdx.x;
-  const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int img = bid / a.tiles_y;
+  const ThinTile tile = thin_tile(a);
+  const int tx = tile.tx, ty = tile.ty, img = tile.img;
   const int x0 = (tx * 4 + wave) * 14;                   // first output column of this wave's strip
   if (x0 >= a.W) return;
   const int y0 = ty * kThinOutRows, y1 = min(y0 + kThinOutRows, a.H);
   const int gx = x0 - 1 + n16;                            // image column of this lane's patch column
   const bool okx = gx >= 0 && gx < a.W;
-  const T* ximg = (const T*)a.big + (size_t)img * a.H * a.W * a.bigC;
-  auto rsrc = __builtin_amdgcn_make_buffer_rsrc(thin_uniform_ptr(ximg), (short)0, (int)((unsigned)a.H * (unsigned)a.W * (unsigned)a.bigC * 2u), 0x00020000);
-  int coff[2];
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf) {
-    const int c = a.big_c0 + 32 * hf + 8 * kg;
-    coff[hf] = ((c >> 5) * a.big_gs + (c & 31)) * 2;
-  }
+  const T* ximg = (const T*)a.big.ptr + (size_t)img * a.H * a.W * a.big.C;
+  auto rsrc = __builtin_amdgcn_make_buffer_rsrc(thin_uniform_ptr(ximg), (short)0, (int)((unsigned)a.H * (unsigned)a.W * (unsigned)a.big.C * 2u), 0x00020000);
+  const int coff[2] = {a.big.offset(8 * kg) * 2, a.big.offset(32 + 8 * kg) * 2};      // bytes: the lane's two channel octets
   auto ldrow = [&](int gy, u32x4* out) {
-    typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned v4u;
     const bool ok = okx && gy >= 0 && gy < a.H;
-    const int base = ok ? (gy * a.W + gx) * a.big_ps * 2 : kThinOob;
+    const int base = ok ? (gy * a.W + gx) * a.big.ps * 2 : kThinOob;
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
-      const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, ok ? base + coff[hf] : kThinOob, 0, 0);
-      out[hf] = __builtin_bit_cast(u32x4, r);
+      out[hf] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, ok ? base + coff[hf] : kThinOob, 0, 0));
     }
   };
   constexpr int D = 4;
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(256) void thin_out_kernel(const ThinK a) {
   for (int d = 0; d < D; ++d) ldrow(pr0 + d, ring[d]);
   f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
   // gather lanes of the kx = 1 / kx = 2 partial sums: output column i (lane i, kg == 0) needs row group 1 of column i + 1 and row group 2 of i + 2
-  const int src1 = 4 * min(16 + n16 + 1, 63), src2 = 4 * min(32 + n16 + 2, 63);
+  const int src1 = min(16 + n16 + 1, 63), src2 = min(32 + n16 + 2, 63);
   const int ox = x0 + n16;
   const bool st_ok = kg == 0 && n16 < 14 && ox < a.W;
   float* yimg = a.thin_f32 + (size_t)img * a.H * a.W * a.thin_pitch;
@@ -315,14 +315,8 @@ __global__ __launch_bounds__(256) void thin_out_kernel(const ThinK a) {
       const int oy = pr - 1;
       if (oy >= y0) {            // (oy < y1 holds: pr <= pr1 = y1)
         float o[4];
-        const float c0 = acc0[0], c1 = acc0[1], c2 = acc0[2], c3 = acc0[3];
-        const float cv[4] = {c0, c1, c2, c3};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v1 = __shfl(cv[r], src1 >> 2, 64);
-          const float v2 = __shfl(cv[r], src2 >> 2, 64);
-          o[r] = (cv[r] + v1) + v2 + bs[r];
-        }
+        for (int r = 0; r < 4; ++r) o[r] = (acc0[r] + __shfl(acc0[r], src1, 64)) + __shfl(acc0[r], src2, 64) + bs[r];
         if (st_ok) {
           float* dst = yimg + (size_t)(oy * a.W + ox) * a.thin_pitch;
           if (a.thin_pitch == 4) *(f32x4*)dst = f32x4{o[0], o[1], o[2], o[3]};
@@ -349,15 +343,22 @@ constexpr int kTwSlab = 64 * 48 + 16;             // floats per workgroup slab: 
 constexpr int kTwLds = (kTwWaves * kTwWaveBytes > 4 * 64 * 48 * 4 ? kTwWaves * kTwWaveBytes : 4 * 64 * 48 * 4) + 64;
 
 struct ThinWgK {
-  const void* big; const void* thin; float* slabs;
-  int bigC, big_c0, big_ps, big_gs;
-  int N, H, W, cbx;         // cbx = column blocks of 32 per row
-  long long nunits;         // N * H * cbx K steps
+  ThinView big;
+  const void* thin;         // NHWC4 16-bit tensor (the thin operand)
+  float* slabs;
+  int H, W, cbx;         // cbx = column blocks of 32 per row
+  long long nunits;         // n * H * cbx K steps
 };
 
 // swizzled byte offset of 8-byte chunk `ch` (0..15: channels 4 ch .. 4 ch + 3) of pixel `pix` (0..31) in the BIG tile
 __device__ __forceinline__ int tw_big_off(int pix, int ch) { return pix * 128 + ((ch ^ (4 * (((pix >> 1) & 1) | (((pix >> 3) & 1) << 1)))) << 3); }
 
+// one MFMA operand from the wave's LDS image: two transposing reads, K = the lane group's pixels 0-3 (off[0]) and 4-7 (off[1])
+template <typename T> __device__ __forceinline__ typename FragAB<T>::type tw_read_frag(char* img, const int (&off)[2]) {
+  const u32x2v lo = __builtin_bit_cast(u32x2v, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(img + off[0])));
+  const u32x2v hi = __builtin_bit_cast(u32x2v, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(img + off[1])));
+  return __builtin_bit_cast(typename FragAB<T>::type, u32x4{lo.x, lo.y, hi.x, hi.y});
+}
 template <typename T>
 __global__ __launch_bounds__(64 * kTwWaves) void thin_wgrad_kernel(const ThinWgK a) {
   using Frag = typename FragAB<T>::type;
@@ -367,10 +368,7 @@ __global__ __launch_bounds__(64 * kTwWaves) void thin_wgrad_kernel(const ThinWgK
   char* lbig = smem + wave * kTwWaveBytes;
   char* lthin = lbig + kTwBigBytes;
   char* lone = lthin + kTwPatchBytes;              // {1, 0, 0, 0} in the element type, then 8 zero bytes
-  if (lane == 0) {
-    *(unsigned*)(lone) = (unsigned)to_bits16<T>(1.f);
-    *(unsigned*)(lone + 4) = 0u; *(unsigned*)(lone + 8) = 0u; *(unsigned*)(lone + 12) = 0u;
-  }
+  if (lane == 0) *(u32x4*)lone = u32x4{(unsigned)__builtin_bit_cast(unsigned short, Elem<T>::from_f(1.f)), 0u, 0u, 0u};
   const int i16 = lane & 15, kg = lane >> 4, q = i16 >> 2, p4 = i16 & 3;
   // transposing-read addresses (bytes from the wave's LDS base): A = BIG^T, m-tile mt, first half (pixels 8 kg + q), second + 4 pixels
   int aoff[4][2];
@@ -389,14 +387,12 @@ __global__ __launch_bounds__(64 * kTwWaves) void thin_wgrad_kernel(const ThinWgK
       else boff[nt][hh] = kTwBigBytes + kTwPatchBytes + (tap == 9 ? 0 : 8);     // ones column (bias gradient) / zeros
     }
   }
-  f32x4_t acc[4][3];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 3; ++nt) acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  f32x4_t acc[4][3] = {};
   float tsum[4] = {0.f, 0.f, 0.f, 0.f};
-  // staging roles: BIG piece j (0..3): pixel 8 j + (lane >> 3), 16-byte slot lane & 7; THIN items lane, lane + 64 (< 102): row item / 34, col item % 34
+  // staging roles.  BIG piece j (0..3): pixel 8 j + bpix, 16-byte slot bslot.  THIN item j (0, 1) = lane + 64 j of the 3 x 34 patch: patch
+  // row trow[j] (3: no item), patch column tcol[j]
   const int bpix = lane >> 3, bslot = lane & 7;
+  const int trow[2] = {lane / 34, (lane + 64) / 34}, tcol[2] = {lane % 34, (lane + 64) % 34};
   const long long nw = (long long)gridDim.x * kTwWaves;
   const long long gw = (long long)blockIdx.x * kTwWaves + wave;
   u32x4 rb[4];
@@ -406,25 +402,23 @@ __global__ __launch_bounds__(64 * kTwWaves) void thin_wgrad_kernel(const ThinWgK
     const long long t = u / a.cbx;
     const int row = (int)(t % a.H), img = (int)(t / a.H);
     const int c0 = cb * 32;
-    const T* bimg = (const T*)a.big + (size_t)img * a.H * a.W * a.bigC;
+    const T* bimg = (const T*)a.big.ptr + (size_t)img * a.H * a.W * a.big.C;
     const T* timg = (const T*)a.thin + (size_t)img * a.H * a.W * 4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int px = c0 + 8 * j + bpix;
-      const int c = a.big_c0 + 8 * bslot;
+      const int c = a.big.c0 + 8 * bslot;
       u32x4 v = {0u, 0u, 0u, 0u};
       // (non-temporal: read once, 229 -> 218 us; the same hint on thin_out's ring loads cost 254 -> 321 us -- its strips re-read 2 of 16 columns
       // and 2 of 34 rows from the caches -- and on thin_in's mask loads 410 -> 423)
-      if (px < a.W) v = __builtin_nontemporal_load((const u32x4*)(bimg + (size_t)(row * a.W + px) * a.big_ps + (c >> 5) * a.big_gs + (c & 31)));
+      if (px < a.W) v = __builtin_nontemporal_load((const u32x4*)(bimg + (size_t)(row * a.W + px) * a.big.ps + (c >> 5) * a.big.gs + (c & 31)));
       rb[j] = v;
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int item = lane + 64 * j;
-      const int pr = item / 34, pc = item % 34;
-      const int gy = row - 1 + pr, gx = c0 - 1 + pc;
+      const int gy = row - 1 + trow[j], gx = c0 - 1 + tcol[j];
       u32x2v v = {0u, 0u};
-      if (item < 102 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) v = *(const u32x2v*)(timg + (size_t)(gy * a.W + gx) * 4);
+      if (trow[j] < 3 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) v = *(const u32x2v*)(timg + (size_t)(gy * a.W + gx) * 4);
       rt[j] = v;
     }
   };
@@ -437,10 +431,9 @@ __global__ __launch_bounds__(64 * kTwWaves) void thin_wgrad_kernel(const ThinWgK
     for (int j = 0; j < 4; ++j) *(u32x4*)(lbig + tw_big_off(8 * j + bpix, 2 * bslot)) = rb[j];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int item = lane + 64 * j;
-      if (item < 102) {
-        *(u32x2v*)(lthin + ((item / 34) * kTwPatchCols + item % 34) * 8) = rt[j];
-        if (item / 34 == 1 && item % 34 >= 1 && item % 34 <= 32) {      // centre row, own pixels: the thin side's channel sums
+      if (trow[j] < 3) {
+        *(u32x2v*)(lthin + (trow[j] * kTwPatchCols + tcol[j]) * 8) = rt[j];
+        if (trow[j] == 1 && tcol[j] >= 1 && tcol[j] <= 32) {      // centre row, own pixels: the thin side's channel sums
           float f[8];
           unpack8<T>(u32x4{rt[j].x, rt[j].y, 0u, 0u}, f);
 #pragma unroll
@@ -454,17 +447,11 @@ __global__ __launch_bounds__(64 * kTwWaves) void thin_wgrad_kernel(const ThinWgK
     Frag bf[3];
 #pragma unroll
     for (int nt = 0; nt < 3; ++nt) {
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(lbig + boff[nt][0]));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(lbig + boff[nt][1]));
-      const u32x2v l = __builtin_bit_cast(u32x2v, lo), h2 = __builtin_bit_cast(u32x2v, hi);
-      bf[nt] = __builtin_bit_cast(Frag, u32x4{l.x, l.y, h2.x, h2.y});
+      bf[nt] = tw_read_frag<T>(lbig, boff[nt]);
     }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(lbig + aoff[mt][0]));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(lbig + aoff[mt][1]));
-      const u32x2v l = __builtin_bit_cast(u32x2v, lo), h2 = __builtin_bit_cast(u32x2v, hi);
-      const Frag af = __builtin_bit_cast(Frag, u32x4{l.x, l.y, h2.x, h2.y});
+      const Frag af = tw_read_frag<T>(lbig, aoff[mt]);
 #pragma unroll
       for (int nt = 0; nt < 3; ++nt) acc[mt][nt] = mfma16<T>(af, bf[nt], acc[mt][nt]);
     }
@@ -476,6 +463,7 @@ __global__ __launch_bounds__(64 * kTwWaves) void thin_wgrad_kernel(const ThinWgK
   float* red = (float*)smem;          // [4][64 * 48]
   // D layout: lane (column n = i16, rows 4 kg + r): acc[mt][nt][r] = D[16 mt + 4 kg + r][16 nt + i16]
   auto red_idx = [&](int mt, int nt, int r) { return (16 * mt + 4 * kg + r) * 48 + 16 * nt + i16; };
+  // (three written-out walks of acc: behind one loop helper the compiler pairs these LDS writes and the counts move, same file)
   for (int stride = 4; stride >= 1; stride >>= 1) {
     if (wave >= stride && wave < 2 * stride) {
 #pragma unroll
@@ -574,59 +562,60 @@ static int thin_check(const srganfd_thin_args* a, const char* what, bool need_th
   return SRGANFD_OK;
 }
 
-static void thin_fill(const srganfd_thin_args* a, ThinK& k) {
-  const long long ipix = (long long)a->h * a->w;
-  k.thin = a->thin; k.thin_f32 = a->thin_out; k.thin_pitch = a->thin_out_pitch;
-  k.big = a->big.ptr; k.mask = a->mask.ptr;
-  k.bigC = a->big.cstride; k.big_c0 = a->big.c0; k.big_ps = a->big.planar ? 32 : a->big.cstride; k.big_gs = a->big.planar ? (int)(ipix * 32) : 32;
-  k.mC = a->mask.cstride; k.m_c0 = a->mask.c0; k.m_ps = a->mask.planar ? 32 : a->mask.cstride; k.m_gs = a->mask.planar ? (int)(ipix * 32) : 32;
-  k.w = a->weight; k.bias = a->bias; k.cs = a->cs; k.big_is_cout = a->w_big_is_cout ? 1 : 0; k.flip = a->flip ? 1 : 0;
-  k.N = a->n; k.H = a->h; k.W = a->w;
-  k.neg = a->act == SRGANFD_ACT_LRELU ? a->slope : (a->act == SRGANFD_ACT_RELU ? 0.f : 1.f);
-  k.mask_slope = a->mask_slope;
-  // Non-temporal stores for outputs that one pass cannot keep in the caches anyway (> the 256 MiB Infinity Cache): the write-only
-  // 3 -> 64 launch at 512 x 512, batch 32 (1.07 GB) ran 321 -> 240 us with them, the masked launch unchanged (same-box, alternating).
-  // (The same switch in conv_igemm's epilogue moved neither training step: 58.8 / 141.0 ms with and without.)
-  k.nt = (long long)a->n * ipix * a->big.cstride * 2 >= (192LL << 20) ? 1 : 0;
+static ThinView thin_view(const srganfd_view& v, int h, int w) {
+  return ThinView{v.ptr, v.cstride, v.c0, v.planar ? 32 : v.cstride, v.planar ? (int)((long long)h * w * 32) : 32};
 }
 
+static void thin_fill(const srganfd_thin_args* a, ThinK& k) {
+  k.thin = a->thin; k.thin_f32 = a->thin_out; k.thin_pitch = a->thin_out_pitch;
+  k.big = thin_view(a->big, a->h, a->w); k.mask = thin_view(a->mask, a->h, a->w);
+  k.w = a->weight; k.bias = a->bias; k.cs = a->cs; k.big_is_cout = a->w_big_is_cout ? 1 : 0; k.flip = a->flip ? 1 : 0;
+  k.H = a->h; k.W = a->w;
+  k.neg = a->act == SRGANFD_ACT_LRELU ? a->slope : (a->act == SRGANFD_ACT_RELU ? 0.f : 1.f);
+  k.mask_slope = a->mask_slope;
+}
+
+// An instantiation and its label side by side: the launch and srganfd_conv2d_thin_describe read the same table entry
+template <typename K> struct ThinKernel { void (*fn)(const K); const char* label; };
+template <typename K> static int thin_launch(const ThinKernel<K>& kn, long long grid, int block, int lds, hipStream_t s, const K& k) {
+  if (grid > 0x7fffffffLL) return set_err(SRGANFD_EINVAL, "%s: grid too large", kn.label);
+  if (g_describe) { snprintf(g_describe, g_describe_len, "%s", kn.label); return SRGANFD_OK; }
+  SRGANFD_LAUNCH(kn.fn, dim3((unsigned)grid), dim3(block), lds, s, k);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+
+// Non-temporal stores for outputs that one pass cannot keep in the caches anyway (> the 256 MiB Infinity Cache): the write-only
+// 3 -> 64 launch at 512 x 512, batch 32 (1.07 GB) ran 321 -> 240 us with them, the masked launch unchanged (same-box, alternating).
+// (The same switch in conv_igemm's epilogue moved neither training step: 58.8 / 141.0 ms with and without.)
+constexpr long long kThinNtBytes = 192LL << 20;     // bytes of n * h * w * big.cstride 16-bit elements from which thin_in stores non-temporally
+
+static const ThinKernel<ThinK> kThinIn[2][2][2] = {      // [f16][mask][non-temporal]
+    {{{thin_in_kernel<bf16_t, false, false>, "thin_in_kernel<bf16>"}, {thin_in_kernel<bf16_t, false, true>, "thin_in_kernel<bf16,NT>"}},
+     {{thin_in_kernel<bf16_t, true, false>, "thin_in_kernel<bf16,mask>"}, {thin_in_kernel<bf16_t, true, true>, "thin_in_kernel<bf16,mask,NT>"}}},
+    {{{thin_in_kernel<f16_t, false, false>, "thin_in_kernel<f16>"}, {thin_in_kernel<f16_t, false, true>, "thin_in_kernel<f16,NT>"}},
+     {{thin_in_kernel<f16_t, true, false>, "thin_in_kernel<f16,mask>"}, {thin_in_kernel<f16_t, true, true>, "thin_in_kernel<f16,mask,NT>"}}}};
+static const ThinKernel<ThinK> kThinOut[2] = {{thin_out_kernel<bf16_t>, "thin_out_kernel<bf16>"}, {thin_out_kernel<f16_t>, "thin_out_kernel<f16>"}};
+static const ThinKernel<ThinWgK> kThinWgrad[2] = {{thin_wgrad_kernel<bf16_t>, "thin_wgrad_kernel<bf16>"}, {thin_wgrad_kernel<f16_t>, "thin_wgrad_kernel<f16>"}};
+
 extern "C" int srganfd_conv2d_thin_in(const srganfd_thin_args* a, void* stream) {
-  const hipStream_t s = (hipStream_t)stream;
   const int rc = thin_check(a, "conv2d_thin_in", true, false);
   if (rc != SRGANFD_OK) return rc;
   ThinK k;
   thin_fill(a, k);
   k.tiles_x = ceil_div(a->w, 64); k.tiles_y = ceil_div(a->h, kThinInRows);
-  const long long grid = (long long)a->n * k.tiles_x * k.tiles_y;
-  if (grid > 0x7fffffffLL) return set_err(SRGANFD_EINVAL, "conv2d_thin_in: grid too large");
-  if (g_describe) { snprintf(g_describe, g_describe_len, "thin_in_kernel<%s%s>", a->dtype == SRGANFD_F16 ? "f16" : "bf16", a->mask.ptr ? ",mask" : ""); return SRGANFD_OK; }
-#define THIN_IN_LAUNCH(TT, MK) do { if (k.nt) SRGANFD_LAUNCH((thin_in_kernel<TT, MK, true>), dim3((unsigned)grid), dim3(256), 0, s, k); \
-                                    else SRGANFD_LAUNCH((thin_in_kernel<TT, MK, false>), dim3((unsigned)grid), dim3(256), 0, s, k); } while (0)
-  if (a->dtype == SRGANFD_F16) {
-    if (a->mask.ptr) THIN_IN_LAUNCH(f16_t, true); else THIN_IN_LAUNCH(f16_t, false);
-  } else {
-    if (a->mask.ptr) THIN_IN_LAUNCH(bf16_t, true); else THIN_IN_LAUNCH(bf16_t, false);
-  }
-#undef THIN_IN_LAUNCH
-  SRGANFD_HIP_CHECK(hipGetLastError());
-  return SRGANFD_OK;
+  const bool nt = (long long)a->n * a->h * a->w * a->big.cstride * 2 >= kThinNtBytes;
+  return thin_launch(kThinIn[a->dtype == SRGANFD_F16][a->mask.ptr != nullptr][nt], (long long)a->n * k.tiles_x * k.tiles_y, 256, 0, (hipStream_t)stream, k);
 }
 
 extern "C" int srganfd_conv2d_thin_out(const srganfd_thin_args* a, void* stream) {
-  const hipStream_t s = (hipStream_t)stream;
   const int rc = thin_check(a, "conv2d_thin_out", false, true);
   if (rc != SRGANFD_OK) return rc;
   if (a->big.planar) return set_err(SRGANFD_EINVAL, "conv2d_thin_out: NHWC input views only");
   ThinK k;
   thin_fill(a, k);
   k.tiles_x = ceil_div(ceil_div(a->w, 14), 4); k.tiles_y = ceil_div(a->h, kThinOutRows);
-  const long long grid = (long long)a->n * k.tiles_x * k.tiles_y;
-  if (grid > 0x7fffffffLL) return set_err(SRGANFD_EINVAL, "conv2d_thin_out: grid too large");
-  if (g_describe) { snprintf(g_describe, g_describe_len, "thin_out_kernel<%s>", a->dtype == SRGANFD_F16 ? "f16" : "bf16"); return SRGANFD_OK; }
-  if (a->dtype == SRGANFD_F16) SRGANFD_LAUNCH((thin_out_kernel<f16_t>), dim3((unsigned)grid), dim3(256), 0, s, k);
-  else SRGANFD_LAUNCH((thin_out_kernel<bf16_t>), dim3((unsigned)grid), dim3(256), 0, s, k);
-  SRGANFD_HIP_CHECK(hipGetLastError());
-  return SRGANFD_OK;
+  return thin_launch(kThinOut[a->dtype == SRGANFD_F16], (long long)a->n * k.tiles_x * k.tiles_y, 256, 0, (hipStream_t)stream, k);
 }
 
 static int thin_wgrad_grid() { return 2 * conv_device_cus(); }
@@ -638,18 +627,28 @@ extern "C" int srganfd_conv2d_thin_wgrad(const srganfd_thin_args* a, float* dw, 
   if (rc != SRGANFD_OK) return rc;
   if (!dw || !ws || ws_bytes < srganfd_conv2d_thin_wgrad_workspace()) return set_err(SRGANFD_EINVAL, "conv2d_thin_wgrad: null gradient / workspace below srganfd_conv2d_thin_wgrad_workspace()");
   ThinWgK k;
-  const long long ipix = (long long)a->h * a->w;
-  k.big = a->big.ptr; k.thin = a->thin; k.slabs = (float*)ws;
-  k.bigC = a->big.cstride; k.big_c0 = a->big.c0; k.big_ps = a->big.planar ? 32 : a->big.cstride; k.big_gs = a->big.planar ? (int)(ipix * 32) : 32;
-  k.N = a->n; k.H = a->h; k.W = a->w; k.cbx = ceil_div(a->w, 32);
+  k.big = thin_view(a->big, a->h, a->w); k.thin = a->thin; k.slabs = (float*)ws;
+  k.H = a->h; k.W = a->w; k.cbx = ceil_div(a->w, 32);
   k.nunits = (long long)a->n * a->h * k.cbx;
   const int grid = thin_wgrad_grid();
-  if (g_describe) { snprintf(g_describe, g_describe_len, "thin_wgrad_kernel<%s>", a->dtype == SRGANFD_F16 ? "f16" : "bf16"); return SRGANFD_OK; }
-  if (a->dtype == SRGANFD_F16) SRGANFD_LAUNCH((thin_wgrad_kernel<f16_t>), dim3((unsigned)grid), dim3(64 * kTwWaves), kTwLds, s, k);
-  else SRGANFD_LAUNCH((thin_wgrad_kernel<bf16_t>), dim3((unsigned)grid), dim3(64 * kTwWaves), kTwLds, s, k);
+  const int rl = thin_launch(kThinWgrad[a->dtype == SRGANFD_F16], grid, 64 * kTwWaves, kTwLds, s, k);
+  if (rl != SRGANFD_OK || g_describe) return rl;
   SRGANFD_LAUNCH(thin_wgrad_reduce_kernel, dim3((unsigned)ceil_div(kTwSlab, 64)), dim3(256), 0, s, (const float*)ws, grid, dw, db, a->cs, a->w_big_is_cout ? 1 : 0);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
+}
+
+// op 0 / 1 / 2 = thin_in / thin_out / thin_wgrad: the label of the instantiation that entry point launches for these arguments
+extern "C" int srganfd_conv2d_thin_describe(const srganfd_thin_args* a, int32_t op, char* out, size_t out_len) {
+  if (!out || !out_len) return set_err(SRGANFD_EINVAL, "conv2d_thin_describe: no buffer");
+  if (op < 0 || op > 2) return set_err(SRGANFD_EINVAL, "conv2d_thin_describe: op %d is none of 0 (in), 1 (out), 2 (wgrad)", op);
+  out[0] = 0;
+  g_describe = out; g_describe_len = out_len;
+  float unused;           // a non-null gradient and workspace for thin_wgrad's argument check: the label is written before either is used
+  const int rc = op == 0 ? srganfd_conv2d_thin_in(a, nullptr) : op == 1 ? srganfd_conv2d_thin_out(a, nullptr)
+                                                             : srganfd_conv2d_thin_wgrad(a, &unused, nullptr, &unused, srganfd_conv2d_thin_wgrad_workspace(), nullptr);
+  g_describe = nullptr; g_describe_len = 0;
+  return rc;
 }
 
 }  // namespace srganfd

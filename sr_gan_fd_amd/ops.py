@@ -482,6 +482,16 @@ def thin_wgrad(a: A.ThinArgs, dw, db, workspace: torch.Tensor) -> None:
                                               A.stream_ptr()), "conv2d_thin_wgrad")
 
 
+THIN_OPS = ("thin_in", "thin_out", "thin_wgrad")
+
+
+def thin_describe(a: A.ThinArgs, op) -> str:
+    """label of the kernel instantiation srganfd_conv2d_<op> launches for these arguments (op: 0 / 1 / 2 or a name of THIN_OPS); nothing runs"""
+    buf = C.create_string_buffer(96)
+    A.check(A.lib().srganfd_conv2d_thin_describe(C.byref(a), op if isinstance(op, int) else THIN_OPS.index(op), buf, 96), "conv2d_thin_describe")
+    return buf.value.decode()
+
+
 class ThinLaunch(_Bracketed):
     """One thin-side launch in an engine's launch list.  op: "thin_in" / "thin_out" / "thin_wgrad" (the latter writes the weight and
     bias gradient at element offsets ``dw_off`` / ``db_off`` of the pass's flat gradient, and is skipped by a pass with frozen parameters)."""

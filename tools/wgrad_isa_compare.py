@@ -1,12 +1,15 @@
-"""Device assembly of wgrad.hip or dense_chain.hip, one tree against another, per kernel (the method of profiles/conv_igemm_refactor_isa.txt).
+"""Device assembly of wgrad.hip, dense_chain.hip or conv_thin.hip, one tree against another, per kernel (the method of
+profiles/conv_igemm_refactor_isa.txt).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I. --offload-device-only -S -o parent.s <parent>/wgrad.hip      (same for the branch)
     python tools/wgrad_isa_compare.py parent.s branch.s > profiles/wgrad_refactor_isa.txt
     python tools/wgrad_isa_compare.py --kernel dense_chain parent.s branch.s > profiles/dense_chain_refactor_isa.txt
+    python tools/wgrad_isa_compare.py --kernel thin parent.s branch.s > profiles/conv_thin_refactor_isa.txt
 
 wgrad kernels are matched by template arguments <T, KS, STRIDE, XP, YP, DMA>; a seventh argument (the parent's VAR) is dropped;
-dense-chain kernels by <T, RPW>.  Per kernel: the .amdhsa_kernel block, and the counts of MFMA, LDS, global / flat / scratch memory,
-buffer, s_waitcnt and s_barrier instructions, which must be equal; --kernel dense_chain also counts v_readlane / v_writelane (SGPR
+dense-chain kernels by <T, RPW>; the thin-side kernels by <T, MASK, NT> (thin_in) and <T> (thin_out, thin_wgrad), the slab reduction by
+its symbol.  Per kernel: the .amdhsa_kernel block, and the counts of MFMA, LDS, global / flat / scratch memory,
+buffer, s_waitcnt and s_barrier instructions, which must be equal; --kernel dense_chain and --kernel thin also count v_readlane / v_writelane (SGPR
 spills to lanes), which must not rise.  A working tool, not a test."""
 import collections
 import re
@@ -14,6 +17,7 @@ import sys
 
 NAME = re.compile(r"wgrad_kernelI(t|DF16_|f)Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E(?:Li(\d+)E)?E")
 DC_NAME = re.compile(r"dense_chain_kernelI(t|DF16_)Li(\d+)EE")
+THIN_NAME = re.compile(r"(thin_in|thin_out|thin_wgrad)_kernelI(t|DF16_)(?:Lb(\d)ELb(\d)E)?E")
 TYPES = {"t": "bf16", "DF16_": "f16", "f": "f32"}
 CLASSES = [("mfma", r"v_mfma"), ("lds", r"ds_"), ("global", r"(global|flat|scratch)_"), ("buffer", r"buffer_"), ("s_waitcnt", r"s_waitcnt"),
            ("s_barrier", r"s_barrier")]
@@ -29,6 +33,12 @@ def label(sym):
     m = DC_NAME.search(sym)
     if m:
         return "dense_chain_kernel<%s, RPW=%s>" % (TYPES[m.group(1)], m.group(2)), None
+    m = THIN_NAME.search(sym)
+    if m:
+        extra = ", MASK=%s, NT=%s" % (m.group(3), m.group(4)) if m.group(3) is not None else ""
+        return "%s_kernel<%s%s>" % (m.group(1), TYPES[m.group(2)], extra), None
+    if "thin_wgrad_reduce_kernel" in sym:
+        return "thin_wgrad_reduce_kernel", None
     m = NAME.search(sym)
     if not m:
         return sym, None
@@ -83,11 +93,11 @@ def res(md):
 def main():
     argv = sys.argv[1:]
     if argv[:1] == ["--kernel"]:
-        if argv[1] == "dense_chain":
+        if argv[1] in ("dense_chain", "thin"):
             CLASSES.append(("lane spills", r"v_(readlane|writelane)"))
             AT_MOST.append("lane spills")
         elif argv[1] != "wgrad":
-            sys.exit("--kernel: wgrad or dense_chain, not %r" % argv[1])
+            sys.exit("--kernel: wgrad, dense_chain or thin, not %r" % argv[1])
         argv = argv[2:]
     P, B = parse(argv[0]), parse(argv[1])
     only_p, only_b = sorted(set(P) - set(B)), sorted(set(B) - set(P))
