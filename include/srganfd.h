@@ -256,6 +256,12 @@ int srganfd_resample(int32_t op, srganfd_view a, srganfd_view b, int32_t dtype, 
  * LeakyReLU output of the upsampled layer.  dx_raw.ptr may be NULL; dx_masked may alias nothing it reads. */
 int srganfd_resample_bwd_lrelu(srganfd_view dy, srganfd_view dx_raw, srganfd_view act, srganfd_view dx_masked,
                                int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, float slope, void* stream);
+/* Name of the kernel instantiation one of the two entry points above launches for these arguments, as "<kernel>/<dtype>" (validates
+ * them as that entry point does, launches nothing): entry 0 = srganfd_resample(op, a, b), with act and b2 unused (NULL views);
+ * entry 1 = srganfd_resample_bwd_lrelu(dy = a, dx_raw = b, act, dx_masked = b2), with op unused.  Results of 192 MiB or more leave
+ * entry 1 through non-temporal stores: its label then ends in "<NT>". */
+int srganfd_resample_describe(int32_t entry, int32_t op, srganfd_view a, srganfd_view b, srganfd_view act, srganfd_view b2,
+                              int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, char* out, size_t out_len);
 /* Entry points on channel-slice views outside the convolutions (this group, the L1 losses on views, the attention gate's pieces and
  * BatchNorm below) refuse with SRGANFD_EINVAL, before anything is launched: a planar view; a slice that ends past its buffer
  * (c0 < 0 or c0 + c > cstride); c <= 0; npix <= 0 (BatchNorm states its own rule for npix).  A view that may be NULL passes these.

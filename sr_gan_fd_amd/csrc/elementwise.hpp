@@ -53,6 +53,20 @@ template <typename T> __device__ __forceinline__ void stv(void* p, size_t i, con
   }
 }
 
+// width-generic access for a kernel body written once on float[N]: the 16-byte vector at N = VecN<T>::N, ld / st at N = 1
+// (a plain store there: the non-temporal form is for vectors)
+template <typename T, int N> __device__ __forceinline__ void ldn(const void* p, size_t i, float* o) {
+  if constexpr (N == 1) o[0] = ld<T>(p, i); else ldv<T>(p, i, o);
+}
+template <typename T, int N, bool NT = false> __device__ __forceinline__ void stn(void* p, size_t i, const float* v) {
+  if constexpr (N == 1) st<T>(p, i, v[0]); else if constexpr (NT) stv_nt<T>(p, i, v); else stv<T>(p, i, v);
+}
+// f(q) for each of the N lanes of such a body
+template <int N, typename F> __device__ __forceinline__ void each(F f) {
+#pragma unroll
+  for (int q = 0; q < N; ++q) f(q);
+}
+
 // raw 16-byte vector (8 halves or 4 floats), widened to floats where it is used
 template <typename T> __device__ __forceinline__ u32x4 ldraw(const void* p, size_t i) { return *(const u32x4*)((const T*)p + i); }
 template <typename T> __device__ __forceinline__ void widen(const u32x4 raw, float* o) {

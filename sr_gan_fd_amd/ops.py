@@ -492,6 +492,16 @@ def thin_describe(a: A.ThinArgs, op) -> str:
     return buf.value.decode()
 
 
+def resample_describe(dtype: int, n: int, h: int, w: int, c: int, a: A.View, b: A.View, op=None, *, act: A.View = A.NULL_VIEW,
+                      b2: A.View = A.NULL_VIEW) -> str:
+    """label, "<kernel>/<dtype>", of the kernel instantiation srganfd_resample(op, a, b, ...) launches for these arguments -- or, with
+    ``op`` None, srganfd_resample_bwd_lrelu(dy=a, dx_raw=b, act, dx_masked=b2, ...); nothing runs"""
+    buf = C.create_string_buffer(96)
+    entry, op = (1, 2) if op is None else (0, op)
+    A.check(A.lib().srganfd_resample_describe(entry, op, a, b, act, b2, dtype, n, h, w, c, buf, 96), "resample_describe")
+    return buf.value.decode()
+
+
 class ThinLaunch(_Bracketed):
     """One thin-side launch in an engine's launch list.  op: "thin_in" / "thin_out" / "thin_wgrad" (the latter writes the weight and
     bias gradient at element offsets ``dw_off`` / ``db_off`` of the pass's flat gradient, and is skipped by a pass with frozen parameters)."""

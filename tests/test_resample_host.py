@@ -72,6 +72,31 @@ def test_the_x2_matrix_holds_the_kernels_taps():
     assert torch.equal(O.resize_matrix(1, 2), torch.ones(2, 1, dtype=torch.float64))
 
 
+def _closed_form_adjoint_taps(k, n):
+    """csrc/resample.hip's bil_bwd_taps4: low-res k collects high-res 2k-1 .. 2k+2 with (.25, .75, .75, .25); a tap outside [0, 2n) is
+    dropped, and the end that loses one to the clamp takes its inner neighbour with weight 1"""
+    wt = [0.25, 0.75, 0.75, 0.25]
+    if k == 0:
+        wt[1] = 1.0
+    if k == n - 1:
+        wt[2] = 1.0
+    return [(2 * k - 1 + j, wt[j]) for j in range(4) if 0 <= 2 * k - 1 + j < 2 * n]
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 7])
+def test_the_adjoints_weights_are_the_kernels_closed_form_tap_table(n):
+    """the sizes at which a row meets both borders (1), one border in every row (2), and one border or none (3, 7)"""
+    want = torch.zeros(n, 2 * n, dtype=torch.float64)
+    for k in range(n):
+        for d, w in _closed_form_adjoint_taps(k, n):
+            want[k, d] = w
+    got = O._up2_axis_adjoint(torch.eye(2 * n, dtype=torch.float64), 0)          # column d: what high-res d gives to each low-res k
+    assert torch.equal(got, want)
+    assert torch.equal(got, O.resize_matrix(n, 2 * n).T)
+    borders = [sum(1 for k in range(n) for d, w in _closed_form_adjoint_taps(k, n) if w == 1.0 and k == e) for e in (0, n - 1)]
+    assert borders == ([2, 2] if n == 1 else [1, 1])
+
+
 @pytest.mark.parametrize("shape", O.X2_SHAPES, ids=O.X2_IDS)
 def test_nearest_x2_backward_equals_autograd(shape):
     n, h, w, c = _shape(shape)

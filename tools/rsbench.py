@@ -1,5 +1,6 @@
 """Timing + output digests of the bilinear x2 resampling entry points at the U-Net discriminator's three up-block shapes (B=32, 512x512
-input: 512ch@64^2, 256ch@128^2, 128ch@256^2 low-res).  Run twice (SRGANFD_LIB=<other build>) and compare digests for bit-equality."""
+input: 512ch@64^2, 256ch@128^2, 128ch@256^2 low-res).  Run twice (SRGANFD_LIB=<other build>) and compare digests for bit-equality.
+The bwd+ rows are srganfd_resample_bwd_lrelu, the launch csrc/resample.hip's rows-per-thread and non-temporal choices were measured on."""
 import hashlib
 import os
 import sys
