@@ -1,151 +1,104 @@
 // layout.hip -- layout / dtype conversion at the module boundary: NCHW fp32 <-> NHWC bf16/f16/f32 views, the clamp's gradient mask
-// folded into the relayout, the batch crop and the uint8 HWC ingest of the data side.
+// folded into the relayout, the batch crop and the uint8 HWC ingest of the data side.  NCHW -> NHWC has three forms: one per-pixel
+// kernel for c <= 4 image planes into a whole 16-bit buffer (rgb_to_nhwc_kernel, with or without the clamp mask, chosen by rgb_ok /
+// whole_pitch of elementwise.hpp), and the generic body's vector and scalar widths (vec_ok).
 #include "elementwise.hpp"
 
 namespace srganfd {
 
-// ---- NCHW fp32 -> NHWC T view, zero padded to cpad channels (BSRGAN.forward input, model.py:366) ----
-template <typename T>
-__global__ void nchw_to_nhwc_kernel(const float* __restrict__ src, void* dst, int dC, int d0, int n, int c, int hw, int cpad,
-                                    const float* __restrict__ mean, const float* __restrict__ stdv) {
-  const size_t total = (size_t)n * hw * cpad;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % cpad);
-    const size_t p = i / cpad;
-    const size_t img = p / hw, pix = p % hw;
-    float v = 0.f;
-    if (ch < c) {
-      v = src[(img * c + ch) * hw + pix];
-      if (mean) v = (v - mean[ch]) / stdv[ch];
-    }
-    st<T>(dst, p * dC + d0 + ch, v);
-  }
-}
+// What the relayouts take: an NCHW fp32 batch (n images of c planes of hw pixels) on one side, an NHWC view on the other, zero padded
+// to cpad channels where it is written.  nchw_to_nhwc: src -> view, with (x - mean[ch]) / stdv[ch] when mean is given.  clamp_grad:
+// src = d sr, pre = the pre-clamp SR (fp32), view = the gradient.  nhwc_to_nchw (+ scaled): view -> dst.
+struct LayK { const float* src; float* dst; View view, pre; int n, c, hw, cpad; const float *mean, *stdv, *ch_div; int clamp01; };
 
-template <typename T>
-__global__ __launch_bounds__(256) void nchw_to_nhwc_vec_kernel(const float* __restrict__ src, void* dst, int dC, int d0, int n, int c, int hw, int cpad,
-                                                               const float* __restrict__ mean, const float* __restrict__ stdv) {
-  constexpr int N = VecN<T>::N;
-  const int cv = cpad / N;
-  const size_t total = (size_t)n * hw * cv;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int ck = (int)(i % cv) * N;
-    const size_t p = i / cv;
-    const size_t img = p / hw, pix = p % hw;
+// ---- NCHW fp32 -> NHWC T view, zero padded to cpad channels (BSRGAN.forward input, model.py:366): vector form N = VecN<T>::N, scalar N = 1 ----
+template <typename T, int N>
+__global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const LayK k) {
+  for_each_group<N>((size_t)k.n * k.hw, k.cpad, [&](size_t p, int ck) {
+    const size_t img = p / k.hw, pix = p % k.hw;
     float v[N];
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
+    each<N>([&](int q) {
       const int ch = ck + q;
       float t = 0.f;
-      if (ch < c) {
-        t = src[(img * c + ch) * hw + pix];
-        if (mean) t = (t - mean[ch]) / stdv[ch];
+      if (ch < k.c) {
+        t = k.src[(img * k.c + ch) * k.hw + pix];
+        if (k.mean) t = (t - k.mean[ch]) / k.stdv[ch];
       }
       v[q] = t;
-    }
-    stv<T>(dst, p * dC + d0 + ck, v);
-  }
+    });
+    stn<T, N>(k.view.p, k.view.at(p, ck), v);
+  });
 }
 
 // ---- NHWC view (T or fp32) -> NCHW fp32, optional clamp to [0,1] (model.py:379) ----
 template <typename T>
-__global__ void nhwc_to_nchw_kernel(const void* __restrict__ src, int sC, int s0, float* __restrict__ dst, int n, int c, int hw, int clamp01) {
-  const size_t total = (size_t)n * c * hw;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t pix = i % hw;
-    const size_t t = i / hw;
-    const int ch = (int)(t % c);
-    const size_t img = t / c;
-    float v = ld<T>(src, (img * hw + pix) * sC + s0 + ch);
-    if (clamp01) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);       // torch's clamp_: a NaN stays a NaN (fminf(fmaxf(v, 0), 1) made it 0), -0 stays -0
-    dst[i] = v;
-  }
+__global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const LayK k) {
+  grid_stride((size_t)k.n * k.c * k.hw, [&](size_t i) {
+    const size_t pix = i % k.hw;
+    const size_t t = i / k.hw;
+    const int ch = (int)(t % k.c);
+    const size_t img = t / k.c;
+    float v = ld<T>(k.view.p, k.view.at(img * k.hw + pix, ch));
+    if (k.clamp01) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);       // torch's clamp_: a NaN stays a NaN (fminf(fmaxf(v, 0), 1) made it 0), -0 stays -0
+    k.dst[i] = v;
+  });
 }
 
 // ---- gradient of clamp_(0,1) + NCHW fp32 -> NHWC T (zero padded): d pre = (0 <= pre <= 1) ? d sr : 0 ----
 template <typename T>
-__global__ void clamp_grad_kernel(const float* __restrict__ dsr, const float* __restrict__ pre, int pC, int p0, void* dst, int dC, int d0,
-                                  int n, int c, int hw, int cpad) {
-  const size_t total = (size_t)n * hw * cpad;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % cpad);
-    const size_t p = i / cpad;
-    const size_t img = p / hw, pix = p % hw;
+__global__ __launch_bounds__(256) void clamp_grad_kernel(const LayK k) {
+  for_each_group<1>((size_t)k.n * k.hw, k.cpad, [&](size_t p, int ch) {
+    const size_t img = p / k.hw, pix = p % k.hw;
     float v = 0.f;
-    if (ch < c) {
-      const float q = pre[p * pC + p0 + ch];
-      if (q >= 0.f && q <= 1.f) v = dsr[(img * c + ch) * hw + pix];
+    if (ch < k.c) {
+      const float q = ((const float*)k.pre.p)[k.pre.at(p, ch)];
+      if (q >= 0.f && q <= 1.f) v = k.src[(img * k.c + ch) * k.hw + pix];
     }
-    st<T>(dst, p * dC + d0 + ch, v);
-  }
+    st<T>(k.view.p, k.view.at(p, ch), v);
+  });
 }
 
-// the generator's case (3 image channels, fp32 pre-clamp SR with a 4-channel pitch, 16-bit gradient padded to 32 channels): one thread
-// per pixel, one 16-byte read of the pre-clamp pixel, three coalesced plane reads, four 16-byte stores (the 29 padding channels are
-// zeros the data-gradient conv multiplies by padded weights)
-template <typename T>
-__global__ __launch_bounds__(256) void clamp_grad_rgb16_kernel(const float* __restrict__ dsr, const f32x4* __restrict__ pre, u32x4* __restrict__ dst,
-                                                               size_t npix, size_t hw, int c) {
-  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (size_t)gridDim.x * 256) {
+// ---- the per-pixel forms: c <= 4 image planes into a 16-bit view that is a whole buffer.  One thread per pixel, c coalesced plane reads,
+// the pixel packed once.  CLAMP: the clamp's gradient mask, from one 16-byte read of the pre-clamp pixel (fp32, 4-channel pitch); without
+// it the input normalisation.  WIDE = false: a 4-channel pitch ("NHWC4", the thin-side kernels' operand, conv_thin.hip), one 8-byte store.
+// WIDE = true: the generator's gradient padded to 32 channels, four 16-byte stores (the 29 padding channels are zeros the data-gradient
+// conv multiplies by padded weights).
+template <typename T, bool CLAMP, bool WIDE>
+__global__ __launch_bounds__(256) void rgb_to_nhwc_kernel(const LayK k) {
+  static_assert(CLAMP || !WIDE, "the input side has the 4-channel pitch only");
+  const size_t hw = k.hw;
+  grid_stride((size_t)k.n * hw, [&](size_t p) {
     const size_t img = p / hw, pix = p % hw;
-    const f32x4 q = pre[p];
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < c && q[k] >= 0.f && q[k] <= 1.f) v[k] = dsr[(img * c + k) * hw + pix];
-    const float v8[8] = {v[0], v[1], v[2], v[3], 0.f, 0.f, 0.f, 0.f};
-    const u32x4 w0 = pack8<T>(v8);
-    const u32x4 z = {0u, 0u, 0u, 0u};
-    dst[p * 4 + 0] = w0; dst[p * 4 + 1] = z; dst[p * 4 + 2] = z; dst[p * 4 + 3] = z;
-  }
-}
-
-// the same into a 4-channel pitch ("NHWC4", 8 bytes per pixel): the thin-side kernels' operand (conv_thin.hip)
-template <typename T>
-__global__ __launch_bounds__(256) void clamp_grad_rgb4_kernel(const float* __restrict__ dsr, const f32x4* __restrict__ pre, unsigned long long* __restrict__ dst,
-                                                              size_t npix, size_t hw, int c) {
-  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (size_t)gridDim.x * 256) {
-    const size_t img = p / hw, pix = p % hw;
-    const f32x4 q = pre[p];
+    f32x4 q = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (CLAMP) q = ((const f32x4*)k.pre.p)[p];
     float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < c && q[k] >= 0.f && q[k] <= 1.f) v[k] = dsr[(img * c + k) * hw + pix];
-    const u32x4 w0 = pack8<T>(v);
-    dst[p] = (unsigned long long)w0[0] | ((unsigned long long)w0[1] << 32);
-  }
-}
-
-// NCHW fp32 (c <= 4 planes) -> NHWC4 16-bit: one thread per pixel, c coalesced plane reads, one 8-byte store
-template <typename T>
-__global__ __launch_bounds__(256) void nchw_to_nhwc4_kernel(const float* __restrict__ src, unsigned long long* __restrict__ dst, size_t npix, size_t hw, int c,
-                                                            const float* __restrict__ mean, const float* __restrict__ stdv) {
-  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (size_t)gridDim.x * 256) {
-    const size_t img = p / hw, pix = p % hw;
-    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < c) {
-        float t = src[(img * c + k) * hw + pix];
-        if (mean) t = (t - mean[k]) / stdv[k];
-        v[k] = t;
+    for (int j = 0; j < 4; ++j)
+      if (j < k.c && (!CLAMP || (q[j] >= 0.f && q[j] <= 1.f))) {
+        float t = k.src[(img * k.c + j) * hw + pix];
+        if constexpr (!CLAMP) { if (k.mean) t = (t - k.mean[j]) / k.stdv[j]; }
+        v[j] = t;
       }
     const u32x4 w0 = pack8<T>(v);
-    dst[p] = (unsigned long long)w0[0] | ((unsigned long long)w0[1] << 32);
-  }
+    if constexpr (WIDE) {
+      u32x4* dst = (u32x4*)k.view.p;
+      const u32x4 z = {0u, 0u, 0u, 0u};
+      dst[p * 4 + 0] = w0; dst[p * 4 + 1] = z; dst[p * 4 + 2] = z; dst[p * 4 + 3] = z;
+    } else {
+      ((unsigned long long*)k.view.p)[p] = (unsigned long long)w0[0] | ((unsigned long long)w0[1] << 32);
+    }
+  });
 }
 
 // the differentiable VGG tap's relayout (ESRGAN/model.py:281-292): NHWC fp32 -> NCHW that also undoes the 1/std of the input normalisation
-__global__ __launch_bounds__(256) void nhwc_to_nchw_scaled_kernel(const float* __restrict__ src, int sC, int s0, float* __restrict__ dst, int n, int c,
-                                                                  int hw, const float* __restrict__ ch_div) {
-  const size_t total = (size_t)n * c * hw;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const size_t pix = i % hw;
-    const size_t t = i / hw;
-    const int ch = (int)(t % c);
-    const size_t img = t / c;
-    dst[i] = src[(img * hw + pix) * sC + s0 + ch] / ch_div[ch];
-  }
+__global__ __launch_bounds__(256) void nhwc_to_nchw_scaled_kernel(const LayK k) {
+  grid_stride((size_t)k.n * k.c * k.hw, [&](size_t i) {
+    const size_t pix = i % k.hw;
+    const size_t t = i / k.hw;
+    const int ch = (int)(t % k.c);
+    const size_t img = t / k.c;
+    k.dst[i] = ((const float*)k.view.p)[k.view.at(img * k.hw + pix, ch)] / k.ch_div[ch];
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -191,25 +144,13 @@ extern "C" int srganfd_nchw_to_nhwc(const float* src, int32_t n, int32_t c, int3
   const hipStream_t s = (hipStream_t)stream;
   if (!src || !dst.ptr || n <= 0 || c <= 0 || cpad < c || dst.c0 + cpad > dst.cstride) return set_err(SRGANFD_EINVAL, "nchw_to_nhwc: bad args");
   if (dst.planar) return set_err(SRGANFD_EINVAL, "nchw_to_nhwc: NHWC views only, not planar ones");
-  const size_t total = (size_t)n * h * w * cpad;
-  if (dtype != SRGANFD_F32 && c <= 4 && cpad == 4 && dst.cstride == 4 && dst.c0 == 0 && ((uintptr_t)dst.ptr & 7) == 0) {
-    const size_t npix = (size_t)n * h * w;
-    if (dtype == SRGANFD_BF16) SRGANFD_LAUNCH(nchw_to_nhwc4_kernel<bf16_t>, dim3(grid_for(npix)), dim3(256), 0, s, src, (unsigned long long*)dst.ptr, npix, (size_t)h * w, c, mean, stdv);
-    else SRGANFD_LAUNCH(nchw_to_nhwc4_kernel<f16_t>, dim3(grid_for(npix)), dim3(256), 0, s, src, (unsigned long long*)dst.ptr, npix, (size_t)h * w, c, mean, stdv);
-    SRGANFD_HIP_CHECK(hipGetLastError());
-    return SRGANFD_OK;
+  const size_t npix = (size_t)n * h * w;
+  const LayK k = {src, nullptr, dev_view(dst), {}, n, c, h * w, cpad, mean, stdv, nullptr, 0};
+  if (rgb_ok(dtype, c, cpad, 4) && whole_pitch(dst, 4, 8)) {
+    DISPATCH_T16(dtype, SRGANFD_LAUNCH((rgb_to_nhwc_kernel<TT, false, false>), dim3(grid_for(npix)), dim3(256), 0, s, k));
+  } else {
+    DISPATCH_TN(dtype, vec_ok(dtype, cpad, {dst}), SRGANFD_LAUNCH((nchw_to_nhwc_kernel<TT, NN>), group_grid(npix * cpad, NN), dim3(256), 0, s, k));
   }
-  {
-    const int vn = dtype == SRGANFD_F32 ? 4 : 8;
-    if (cpad % vn == 0 && dst.c0 % vn == 0 && dst.cstride % vn == 0 && ((uintptr_t)dst.ptr & 15) == 0) {
-      DISPATCH_T(dtype,
-                 SRGANFD_LAUNCH(nchw_to_nhwc_vec_kernel<TT>, dim3(grid_for(total / vn, 256, 65536)), dim3(256), 0, s, src, dst.ptr, dst.cstride, dst.c0, n, c, h * w, cpad, mean, stdv));
-      SRGANFD_HIP_CHECK(hipGetLastError());
-      return SRGANFD_OK;
-    }
-  }
-  DISPATCH_T(dtype,
-             SRGANFD_LAUNCH(nchw_to_nhwc_kernel<TT>, dim3(grid_for(total)), dim3(256), 0, s, src, dst.ptr, dst.cstride, dst.c0, n, c, h * w, cpad, mean, stdv));
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
@@ -217,9 +158,8 @@ extern "C" int srganfd_nhwc_to_nchw(srganfd_view src, int32_t dtype, int32_t n, 
   const hipStream_t s = (hipStream_t)stream;
   if (!src.ptr || !dst || src.c0 + c > src.cstride) return set_err(SRGANFD_EINVAL, "nhwc_to_nchw: bad args");
   if (src.planar) return set_err(SRGANFD_EINVAL, "nhwc_to_nchw: NHWC views only, not planar ones");
-  const size_t total = (size_t)n * h * w * c;
-  DISPATCH_T(dtype,
-             SRGANFD_LAUNCH(nhwc_to_nchw_kernel<TT>, dim3(grid_for(total)), dim3(256), 0, s, src.ptr, src.cstride, src.c0, dst, n, c, h * w, clamp01));
+  const LayK k = {nullptr, dst, dev_view(src), {}, n, c, h * w, 0, nullptr, nullptr, nullptr, clamp01};
+  DISPATCH_T(dtype, SRGANFD_LAUNCH(nhwc_to_nchw_kernel<TT>, dim3(grid_for((size_t)n * h * w * c)), dim3(256), 0, s, k));
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
@@ -228,25 +168,15 @@ extern "C" int srganfd_clamp_grad_to_nhwc(const float* dsr, srganfd_view pre, in
   const hipStream_t s = (hipStream_t)stream;
   if (!dsr || !pre.ptr || !dst.ptr || dst.c0 + cpad > dst.cstride) return set_err(SRGANFD_EINVAL, "clamp_grad: bad args");
   if (pre.planar || dst.planar) return set_err(SRGANFD_EINVAL, "clamp_grad: NHWC views only, not planar ones");
-  const size_t total = (size_t)n * h * w * cpad;
-  if (dtype != SRGANFD_F32 && c <= 4 && cpad == 4 && pre.cstride == 4 && pre.c0 == 0 && dst.cstride == 4 && dst.c0 == 0 &&
-      ((uintptr_t)pre.ptr & 15) == 0 && ((uintptr_t)dst.ptr & 7) == 0) {
-    const size_t npix = (size_t)n * h * w;
-    if (dtype == SRGANFD_BF16) SRGANFD_LAUNCH(clamp_grad_rgb4_kernel<bf16_t>, dim3(grid_for(npix)), dim3(256), 0, s, dsr, (const f32x4*)pre.ptr, (unsigned long long*)dst.ptr, npix, (size_t)h * w, c);
-    else SRGANFD_LAUNCH(clamp_grad_rgb4_kernel<f16_t>, dim3(grid_for(npix)), dim3(256), 0, s, dsr, (const f32x4*)pre.ptr, (unsigned long long*)dst.ptr, npix, (size_t)h * w, c);
-    SRGANFD_HIP_CHECK(hipGetLastError());
-    return SRGANFD_OK;
+  const size_t npix = (size_t)n * h * w;
+  const LayK k = {dsr, nullptr, dev_view(dst), dev_view(pre), n, c, h * w, cpad, nullptr, nullptr, nullptr, 0};
+  if (rgb_ok(dtype, c, cpad, 4) && whole_pitch(pre, 4, 16) && whole_pitch(dst, 4, 8)) {
+    DISPATCH_T16(dtype, SRGANFD_LAUNCH((rgb_to_nhwc_kernel<TT, true, false>), dim3(grid_for(npix)), dim3(256), 0, s, k));
+  } else if (rgb_ok(dtype, c, cpad, 32) && whole_pitch(pre, 4, 16) && whole_pitch(dst, 32, 16)) {
+    DISPATCH_T16(dtype, SRGANFD_LAUNCH((rgb_to_nhwc_kernel<TT, true, true>), dim3(grid_for(npix)), dim3(256), 0, s, k));
+  } else {
+    DISPATCH_T(dtype, SRGANFD_LAUNCH(clamp_grad_kernel<TT>, dim3(grid_for(npix * cpad)), dim3(256), 0, s, k));
   }
-  if (dtype != SRGANFD_F32 && c <= 4 && cpad == 32 && pre.cstride == 4 && pre.c0 == 0 && dst.cstride == 32 && dst.c0 == 0 &&
-      ((uintptr_t)pre.ptr & 15) == 0 && ((uintptr_t)dst.ptr & 15) == 0) {
-    const size_t npix = (size_t)n * h * w;
-    if (dtype == SRGANFD_BF16) SRGANFD_LAUNCH(clamp_grad_rgb16_kernel<bf16_t>, dim3(grid_for(npix)), dim3(256), 0, s, dsr, (const f32x4*)pre.ptr, (u32x4*)dst.ptr, npix, (size_t)h * w, c);
-    else SRGANFD_LAUNCH(clamp_grad_rgb16_kernel<f16_t>, dim3(grid_for(npix)), dim3(256), 0, s, dsr, (const f32x4*)pre.ptr, (u32x4*)dst.ptr, npix, (size_t)h * w, c);
-    SRGANFD_HIP_CHECK(hipGetLastError());
-    return SRGANFD_OK;
-  }
-  DISPATCH_T(dtype,
-             SRGANFD_LAUNCH(clamp_grad_kernel<TT>, dim3(grid_for(total)), dim3(256), 0, s, dsr, (const float*)pre.ptr, pre.cstride, pre.c0, dst.ptr, dst.cstride, dst.c0, n, c, h * w, cpad));
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
@@ -254,7 +184,8 @@ extern "C" int srganfd_nhwc_to_nchw_scaled(srganfd_view src, int32_t n, int32_t 
   const hipStream_t s = (hipStream_t)stream;
   if (!src.ptr || !dst || !ch_div || n <= 0 || c <= 0) return set_err(SRGANFD_EINVAL, "nhwc_to_nchw_scaled: bad args");
   if (src.planar) return set_err(SRGANFD_EINVAL, "nhwc_to_nchw_scaled: NHWC views only, not planar ones");
-  SRGANFD_LAUNCH(nhwc_to_nchw_scaled_kernel, dim3(grid_for((size_t)n * c * h * w)), dim3(256), 0, s, (const float*)src.ptr, src.cstride, src.c0, dst, n, c, h * w, ch_div);
+  const LayK k = {nullptr, dst, dev_view(src), {}, n, c, h * w, 0, nullptr, nullptr, ch_div, 0};
+  SRGANFD_LAUNCH(nhwc_to_nchw_scaled_kernel, dim3(grid_for((size_t)n * c * h * w)), dim3(256), 0, s, k);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }

@@ -4,7 +4,9 @@
 
 namespace srganfd {
 
-// ---- losses.  out[slot] (+)= weight * mean(...) ; two-stage deterministic reduction ----
+// ---- losses.  out[slot] (+)= weight * mean(...) ; two-stage deterministic reduction (store_block_sum, finish_kernel: elementwise.hpp) ----
+// The four partial kernels on flat arrays share the tail and spell their loops out: through grid_stride's lambda l1_partial_kernel and
+// bce_rel_partial_kernel compiled to other code (profiles/view_kernels_refactor_isa.txt).
 // L1 (nn.L1Loss, train_bsrgan.py:297,450) on flat fp32 arrays, optional gradient wrt a.
 __global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n, float gscale,
                                                          const float* __restrict__ gscale_dev, float* __restrict__ grad, float* __restrict__ partial) {
@@ -16,49 +18,35 @@ __global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict
     s += fabsf(d);
     if (grad) grad[i] = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f);      // torch.sign: 0 at 0 and at a NaN
   }
-  const float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+  store_block_sum(s, sh, partial);
 }
-// L1 between two NHWC T views (VGG feature taps, model.py:548-550), no gradient (detached in the reference)
-template <typename T>
-__global__ __launch_bounds__(256) void l1_views_partial_kernel(const void* __restrict__ a, int aC, int a0, const void* __restrict__ b, int bC, int b0,
-                                                               size_t npix, int c, int relu, float* __restrict__ partial) {
+// L1 between two NHWC T views (VGG feature taps, model.py:548-550), no gradient (detached in the reference): vector form N = VecN<T>::N,
+// scalar form N = 1.  l1_grad_views_kernel below is the differentiable tap's gradient (ESRGAN/model.py:281-292): that of mean |a - b|
+// w.r.t. a, into out; it has the scalar form only.
+struct L1K { View a, b, out; size_t npix; int c, relu; float* partial; const float* upstream; float scale; };
+template <typename T, int N>
+__global__ __launch_bounds__(256) void l1_views_partial_kernel(const L1K k) {
   __shared__ float sh[4];
   float s = 0.f;
-  const size_t total = npix * c;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int ch = (int)(i % c);
-    const size_t p = i / c;
-    float va = ld<T>(a, p * aC + a0 + ch), vb = ld<T>(b, p * bC + b0 + ch);
-    if (relu) { va = va < 0.f ? 0.f : va; vb = vb < 0.f ? 0.f : vb; }      // torch's relu: a NaN stays one (fmaxf would turn it into 0)
-    s += fabsf(va - vb);
-  }
-  const float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-template <typename T>
-__global__ __launch_bounds__(256) void l1_views_vec_partial_kernel(const void* __restrict__ a, int aC, int a0, const void* __restrict__ b, int bC, int b0,
-                                                                   size_t npix, int c, int relu, float* __restrict__ partial) {
-  constexpr int N = VecN<T>::N;
-  __shared__ float sh[4];
-  float s = 0.f;
-  const int cv = c / N;
-  const size_t total = npix * cv;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int ch = (int)(i % cv) * N;
-    const size_t p = i / cv;
+  for_each_group<N>(k.npix, k.c, [&](size_t p, int ch) {
     float va[N], vb[N];
-    ldv<T>(a, p * aC + a0 + ch, va);
-    ldv<T>(b, p * bC + b0 + ch, vb);
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
+    ldn<T, N>(k.a.p, k.a.at(p, ch), va);
+    ldn<T, N>(k.b.p, k.b.at(p, ch), vb);
+    each<N>([&](int q) {
       float x = va[q], y = vb[q];
-      if (relu) { x = x < 0.f ? 0.f : x; y = y < 0.f ? 0.f : y; }
+      if (k.relu) { x = x < 0.f ? 0.f : x; y = y < 0.f ? 0.f : y; }      // torch's relu: a NaN stays one (fmaxf would turn it into 0)
       s += fabsf(x - y);
-    }
-  }
-  const float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+    });
+  });
+  store_block_sum(s, sh, k.partial);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void l1_grad_views_kernel(const L1K k) {
+  const float sc = k.scale * (k.upstream ? *k.upstream : 1.f);
+  for_each_group<1>(k.npix, k.c, [&](size_t p, int ch) {
+    const float d = ld<T>(k.a.p, k.a.at(p, ch)) - ld<T>(k.b.p, k.b.at(p, ch));
+    st<T>(k.out.p, k.out.at(p, ch), d > 0.f ? sc : (d < 0.f ? -sc : 0.f));     // torch.sign: 0 at 0 and at a NaN
+  });
 }
 // BCE-with-logits against a constant label map (train_bsrgan.py:301,403-404): loss and sigmoid mean
 __global__ __launch_bounds__(256) void bce_partial_kernel(const float* __restrict__ x, size_t n, float target, float gscale,
@@ -74,37 +62,30 @@ __global__ __launch_bounds__(256) void bce_partial_kernel(const float* __restric
     sg += sig;
     if (grad) grad[i] = (sig - target) * gscale;
   }
-  float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = r;
-  r = block_reduce_sum(sg, sh);
-  if (threadIdx.x == 0) partial_sig[blockIdx.x] = r;
+  store_block_sum(s, sh, partial);
+  store_block_sum(sg, sh, partial_sig);
 }
-__global__ __launch_bounds__(256) void finish_sum_kernel(const float* __restrict__ partial, int nblk, float scale, float* out, int accumulate) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
-  const float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) *out = (accumulate ? *out : 0.f) + r * scale;
-}
-// sigmoid(mean(logits)): the D(x) probability as ESRGAN / Real-ESRGAN log it (train_esrgan.py:430-431, train_realesrgan.py:475-476;
-// BSRGAN / A-ESRGAN log mean(sigmoid(logits)) instead -- bce_partial_kernel's second output)
+// the plain sum: stage one of sigmoid(mean(logits)) and of the relativistic form's mean(other)
 __global__ __launch_bounds__(256) void sum_partial_kernel(const float* __restrict__ x, size_t n, float* __restrict__ partial) {
   __shared__ float sh[4];
   float s = 0.f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) s += x[i];
-  const float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+  store_block_sum(s, sh, partial);
 }
+// The epilogues of finish_kernel.  FinAxpy: out (+)= sum * scale, every loss.  FinMean: out = sum / n, the relativistic form's mean(other).
+// FinSigmoidMean: out = sigmoid(sum / n), the D(x) probability as ESRGAN / Real-ESRGAN log it (train_esrgan.py:430-431,
+// train_realesrgan.py:475-476; BSRGAN / A-ESRGAN log mean(sigmoid(logits)) instead -- bce_partial_kernel's second output).
+struct FinBase {
+  const float* table; int n; float scale; float* out;
+  __device__ const float* partial() const { return table; }
+  __device__ int nblk() const { return n; }
+};
+struct FinAxpy : FinBase { int accumulate; __device__ void store(float r) const { *out = (accumulate ? *out : 0.f) + r * scale; } };
+struct FinMean : FinBase { __device__ void store(float r) const { *out = r * scale; } };
+struct FinSigmoidMean : FinBase { __device__ void store(float r) const { *out = 1.f / (1.f + expf(-r * scale)); } };
 // ---- relativistic-average BCE (ESRGAN/train_esrgan.py:378-380,404,412): mean_i BCE(x_i - mean(other), target) ----
-// stage 0: mean(other) -> ws[2 * kRedBlocks] (sum_partial_kernel + this finish); stage 1: per-element loss, d/dx_i, partial sums of the loss
+// stage 0: mean(other) -> ws[2 * kRedBlocks] (sum_partial_kernel + FinMean); stage 1: per-element loss, d/dx_i, partial sums of the loss
 // and of (sigmoid - target); stage 2: finishes -- loss, and d/d(other_j) = -(1/n_other) * mean_i(sigmoid_i - target), the same for every j.
-__global__ __launch_bounds__(256) void finish_mean_kernel(const float* __restrict__ partial, int nblk, float inv_n, float* out) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
-  const float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) *out = r * inv_n;
-}
 __global__ __launch_bounds__(256) void bce_rel_partial_kernel(const float* __restrict__ x, size_t n, const float* __restrict__ other_mean, float target,
                                                               float gscale, const float* __restrict__ gscale_dev, float* __restrict__ grad_x,
                                                               int accumulate_x, float* __restrict__ partial, float* __restrict__ partial_d) {
@@ -119,46 +100,20 @@ __global__ __launch_bounds__(256) void bce_rel_partial_kernel(const float* __res
     sd += d;
     if (grad_x) grad_x[i] = (accumulate_x ? grad_x[i] : 0.f) + d * gscale;
   }
-  float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = r;
-  r = block_reduce_sum(sd, sh);
-  if (threadIdx.x == 0) partial_d[blockIdx.x] = r;
+  store_block_sum(s, sh, partial);
+  store_block_sum(sd, sh, partial_d);
 }
 // grad_other[j] (+)= -gscale * sum_d / n_other for every j (gscale already carries weight / n_x)
 __global__ __launch_bounds__(256) void bce_rel_other_kernel(const float* __restrict__ partial_d, int nblk, float gscale, const float* __restrict__ gscale_dev,
                                                             float* __restrict__ grad_other, size_t n_other, int accumulate) {
   __shared__ float sh[4];
   __shared__ float tot;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256) s += partial_d[i];      // every block re-reduces the (<= 1024) partials: same order, same value
-  const float r = block_reduce_sum(s, sh);
+  const float r = sum_partials(partial_d, nblk, sh);      // every block re-reduces the (<= 1024) partials: same order, same value
   if (threadIdx.x == 0) tot = r;
   __syncthreads();
   if (gscale_dev) gscale *= *gscale_dev;
   const float g = -gscale * tot / (float)n_other;
-  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < n_other; j += (size_t)gridDim.x * 256)
-    grad_other[j] = (accumulate ? grad_other[j] : 0.f) + g;
-}
-__global__ __launch_bounds__(256) void finish_sigmoid_mean_kernel(const float* __restrict__ partial, int nblk, float inv_n, float* out) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
-  const float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) *out = 1.f / (1.f + expf(-r * inv_n));
-}
-
-// ---- differentiable VGG tap (ESRGAN/model.py:281-292): gradient of mean |a - b| w.r.t. a ----
-template <typename T>
-__global__ __launch_bounds__(256) void l1_grad_views_kernel(const void* __restrict__ a, int aC, int a0, const void* __restrict__ b, int bC, int b0,
-                                                            void* out, int oC, int o0, size_t npix, int c, const float* __restrict__ upstream, float scale) {
-  const float sc = scale * (upstream ? *upstream : 1.f);
-  const size_t total = npix * c;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int ch = (int)(i % c);
-    const size_t p = i / c;
-    const float d = ld<T>(a, p * aC + a0 + ch) - ld<T>(b, p * bC + b0 + ch);
-    st<T>(out, p * oC + o0 + ch, d > 0.f ? sc : (d < 0.f ? -sc : 0.f));     // torch.sign: 0 at 0 and at a NaN
-  }
+  grid_stride(n_other, [&](size_t j) { grad_other[j] = (accumulate ? grad_other[j] : 0.f) + g; });
 }
 
 // flag = 1 if any element of x is inf or NaN (the found_inf of torch.cuda.amp.GradScaler.unscale_, train_bsrgan.py:436,466)
@@ -204,7 +159,7 @@ extern "C" int srganfd_l1_loss(const float* a, const float* b, int64_t numel, fl
   if (numel <= 0) return set_err(SRGANFD_EINVAL, "l1_loss: numel <= 0");
   const unsigned g = grid_for(n, 256, kRedBlocks);
   SRGANFD_LAUNCH(l1_partial_kernel, dim3(g), dim3(256), 0, s, a, b, n, grad_scale / (float)n, grad_scale_dev, grad, ws);
-  SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, out, accumulate);
+  SRGANFD_LAUNCH(finish_kernel<FinAxpy>, dim3(1), dim3(256), 0, s, FinAxpy{{ws, (int)g, weight / (float)n, out}, accumulate});
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
@@ -216,14 +171,9 @@ extern "C" int srganfd_l1_loss_views(srganfd_view a, srganfd_view b, int32_t dty
   if (const char* why = views_bad(npix64, c, {a, b})) return set_err(SRGANFD_EINVAL, "l1_views: %s", why);      // npix * c == 0 would store weight / 0 * 0 = NaN
   const size_t n = npix * c;
   const unsigned g = grid_for(n, 256, kRedBlocks);
-  const int vn = dtype == SRGANFD_F32 ? 4 : 8;
-  if (c % vn == 0 && a.c0 % vn == 0 && b.c0 % vn == 0 && a.cstride % vn == 0 && b.cstride % vn == 0 && ((uintptr_t)a.ptr & 15) == 0 && ((uintptr_t)b.ptr & 15) == 0) {
-    DISPATCH_T(dtype,
-               SRGANFD_LAUNCH(l1_views_vec_partial_kernel<TT>, dim3(g), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, npix, c, relu, ws));
-  } else
-  DISPATCH_T(dtype,
-             SRGANFD_LAUNCH(l1_views_partial_kernel<TT>, dim3(g), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, npix, c, relu, ws));
-  SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, out, accumulate);
+  const L1K k = {dev_view(a), dev_view(b), {}, npix, c, relu, ws, nullptr, 0.f};
+  DISPATCH_TN(dtype, vec_ok(dtype, c, {a, b}), SRGANFD_LAUNCH((l1_views_partial_kernel<TT, NN>), dim3(g), dim3(256), 0, s, k));
+  SRGANFD_LAUNCH(finish_kernel<FinAxpy>, dim3(1), dim3(256), 0, s, FinAxpy{{ws, (int)g, weight / (float)n, out}, accumulate});
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
@@ -233,8 +183,8 @@ extern "C" int srganfd_l1_grad_views(srganfd_view a, srganfd_view b, srganfd_vie
   const hipStream_t s = (hipStream_t)stream;
   if (!a.ptr || !b.ptr || !out.ptr) return set_err(SRGANFD_EINVAL, "l1_grad_views: bad args");
   if (const char* why = views_bad(npix64, c, {a, b, out})) return set_err(SRGANFD_EINVAL, "l1_grad_views: %s", why);
-  DISPATCH_T(dtype,
-             SRGANFD_LAUNCH(l1_grad_views_kernel<TT>, dim3(grid_for(npix * c)), dim3(256), 0, s, a.ptr, a.cstride, a.c0, b.ptr, b.cstride, b.c0, out.ptr, out.cstride, out.c0, npix, c, upstream, scale));
+  const L1K k = {dev_view(a), dev_view(b), dev_view(out), npix, c, 0, nullptr, upstream, scale};
+  DISPATCH_T(dtype, SRGANFD_LAUNCH(l1_grad_views_kernel<TT>, dim3(grid_for(npix * c)), dim3(256), 0, s, k));
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
@@ -246,8 +196,8 @@ extern "C" int srganfd_bce_logits(const float* x, int64_t numel, float target, f
   if (numel <= 0) return set_err(SRGANFD_EINVAL, "bce: numel <= 0");
   const unsigned g = grid_for(n, 256, kRedBlocks);
   SRGANFD_LAUNCH(bce_partial_kernel, dim3(g), dim3(256), 0, s, x, n, target, grad_scale / (float)n, grad_scale_dev, grad, ws, ws + kRedBlocks);
-  SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, loss_out, accumulate);
-  if (sig_mean_out) SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)(ws + kRedBlocks), (int)g, 1.f / (float)n, sig_mean_out, 0);
+  SRGANFD_LAUNCH(finish_kernel<FinAxpy>, dim3(1), dim3(256), 0, s, FinAxpy{{ws, (int)g, weight / (float)n, loss_out}, accumulate});
+  if (sig_mean_out) SRGANFD_LAUNCH(finish_kernel<FinAxpy>, dim3(1), dim3(256), 0, s, FinAxpy{{ws + kRedBlocks, (int)g, 1.f / (float)n, sig_mean_out}, 0});
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
@@ -257,7 +207,7 @@ extern "C" int srganfd_sigmoid_of_mean(const float* x, int64_t numel, float* out
   if (!x || !out || !ws || n == 0) return set_err(SRGANFD_EINVAL, "sigmoid_of_mean: bad args");
   const unsigned g = grid_for(n, 256, kRedBlocks);
   SRGANFD_LAUNCH(sum_partial_kernel, dim3(g), dim3(256), 0, s, x, n, ws);
-  SRGANFD_LAUNCH(finish_sigmoid_mean_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, 1.f / (float)n, out);
+  SRGANFD_LAUNCH(finish_kernel<FinSigmoidMean>, dim3(1), dim3(256), 0, s, FinSigmoidMean{{ws, (int)g, 1.f / (float)n, out}});
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
@@ -271,10 +221,10 @@ extern "C" int srganfd_bce_logits_relativistic(const float* x, int64_t numel, co
   float* mean = ws + 2 * kRedBlocks;
   const unsigned go = grid_for(n_other, 256, kRedBlocks), g = grid_for(n, 256, kRedBlocks);
   SRGANFD_LAUNCH(sum_partial_kernel, dim3(go), dim3(256), 0, s, other, n_other, ws);
-  SRGANFD_LAUNCH(finish_mean_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)go, 1.f / (float)n_other, mean);
+  SRGANFD_LAUNCH(finish_kernel<FinMean>, dim3(1), dim3(256), 0, s, FinMean{{ws, (int)go, 1.f / (float)n_other, mean}});
   SRGANFD_LAUNCH(bce_rel_partial_kernel, dim3(g), dim3(256), 0, s, x, n, (const float*)mean, target, grad_scale / (float)n, grad_scale_dev, grad_x,
                  accumulate_x, ws, ws + kRedBlocks);
-  SRGANFD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, (int)g, weight / (float)n, loss_out, accumulate);
+  SRGANFD_LAUNCH(finish_kernel<FinAxpy>, dim3(1), dim3(256), 0, s, FinAxpy{{ws, (int)g, weight / (float)n, loss_out}, accumulate});
   if (grad_other)
     SRGANFD_LAUNCH(bce_rel_other_kernel, dim3(grid_for(n_other, 256, 256)), dim3(256), 0, s, (const float*)(ws + kRedBlocks), (int)g, grad_scale / (float)n,
                    grad_scale_dev, grad_other, n_other, accumulate_other);

@@ -1,5 +1,7 @@
 // norm.hip -- the normalisations: spectral norm (power iteration, sigma) and its gradient, single and batched over layers;
 // BatchNorm2d forward / backward with the fused LeakyReLU and the two-phase data-parallel (SyncBN) forms; the per-channel affine map.
+// The BatchNorm kernels take one struct of views and scalars each; the two directions share their refusals (bn_refuse) and the loop over
+// channel blocks and phases (bn_blocks).
 #include "elementwise.hpp"
 
 namespace srganfd {
@@ -94,15 +96,14 @@ __global__ __launch_bounds__(256) void sn_dot_partial_kernel(const SnGradJobs jo
   const float r = block_reduce_sum(s, sh);
   if (threadIdx.x == 0) J.workspace[blockIdx.x] = r;
 }
-__global__ __launch_bounds__(256) void sn_dot_finish_kernel(const SnGradJobs jobs) {
-  __shared__ float sh[4];
-  const srganfd_sn_grad_job& J = jobs.j[blockIdx.x];
-  const int nblk = (int)sn_grad_blocks((size_t)J.rows * J.cols);
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256) s += J.workspace[i];
-  const float r = block_reduce_sum(s, sh);
-  if (threadIdx.x == 0) J.workspace[kSnGradBlocks] = 0.f + r * 1.f;
-}
+// finish_kernel's epilogue for <G, W_orig>: block b sums layer b's partials into workspace[kSnGradBlocks]  (0.f + r: a sum of -0 is stored as +0)
+struct SnDotFin {
+  SnGradJobs jobs;
+  __device__ const srganfd_sn_grad_job& job() const { return jobs.j[blockIdx.x]; }
+  __device__ const float* partial() const { return job().workspace; }
+  __device__ int nblk() const { return (int)sn_grad_blocks((size_t)job().rows * job().cols); }
+  __device__ void store(float r) const { job().workspace[kSnGradBlocks] = 0.f + r; }
+};
 __global__ __launch_bounds__(256) void sn_grad_kernel(const SnGradJobs jobs, float beta) {
   const srganfd_sn_grad_job& J = jobs.j[blockIdx.y];
   const int cols = J.cols;
@@ -120,33 +121,35 @@ __global__ __launch_bounds__(256) void sn_grad_kernel(const SnGradJobs jobs, flo
 // BatchNorm2d.  Statistics: 16-byte loads, thread = one channel chunk, pixels strided over the grid (coalesced);
 // each block writes partial[block][2][C]; the finish kernel (one 1024-thread block) reduces them in a fixed order
 // (deterministic), turns them into mean / invstd / (scale, shift) and updates the running statistics.
+struct BnPartialK { View x, g, act; const float* save; size_t npix; int c; float* partial; float act_slope; };
 template <typename T>
-__global__ __launch_bounds__(256) void bn_partial_kernel(const void* __restrict__ x, int xC, int x0, const void* __restrict__ g, int gC, int g0,
-                                                         const float* __restrict__ save, size_t npix, int c, float* __restrict__ partial,
-                                                         const void* __restrict__ act, int actC, int act0, float act_slope) {
+__global__ __launch_bounds__(256) void bn_partial_kernel(const BnPartialK k) {
   // act (optional, backward only): output of the LeakyReLU that followed the BatchNorm; dy is scaled by its derivative
-  // forward statistics (g == nullptr): sum x, sum x^2.  backward (g = dy): sum dy, sum dy * xhat (xhat from save)
+  // forward statistics (g absent): sum x, sum x^2.  backward (g = dy): sum dy, sum dy * xhat (xhat from save)
+  const View &x = k.x, &g = k.g, &act = k.act;
+  const float* __restrict__ save = k.save; float* __restrict__ partial = k.partial;
+  const size_t npix = k.npix; const int c = k.c; const float act_slope = k.act_slope;
   constexpr int N = VecN<T>::N;
   __shared__ float sh[2][256 * N];
   const int cv = c / N;                                 // 16-byte chunks per pixel (host: 256 % cv == 0)
   const int lanes = 256 / cv;                           // pixels per block pass
   const int chunk = threadIdx.x % cv, pl = threadIdx.x / cv, ch = chunk * N;
-  float s0[N], s1[N], mean[N], invstd[N];
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-    s0[q] = 0.f; s1[q] = 0.f;
-    mean[q] = (g && save) ? save[ch + q] : 0.f;
-    invstd[q] = (g && save) ? save[c + ch + q] : 1.f;
-  }
+  float s0[N], s1[N];
+  each<N>([&](int q) { s0[q] = 0.f; s1[q] = 0.f; });
   const size_t step = (size_t)gridDim.x * lanes;
-  if (g) {
+  if (g.p) {
+    // the saved statistics, read under one guard: guarded per channel they cost a load and a wait each, or two more VGPRs than a wave step
+    // allows (profiles/view_kernels_refactor_isa.txt)
+    float mean[N], invstd[N];
+    each<N>([&](int q) { mean[q] = 0.f; invstd[q] = 1.f; });
+    if (save) each<N>([&](int q) { mean[q] = save[ch + q]; invstd[q] = save[c + ch + q]; });
     for (size_t p = (size_t)blockIdx.x * lanes + pl; p < npix; p += step) {
       float xv[N], dv[N];
-      ldv<T>(x, p * xC + x0 + ch, xv);
-      ldv<T>(g, p * gC + g0 + ch, dv);
-      if (act) {
+      ldv<T>(x.p, x.at(p, ch), xv);
+      ldv<T>(g.p, g.at(p, ch), dv);
+      if (act.p) {
         float av[N];
-        ldv<T>(act, p * actC + act0 + ch, av);
+        ldv<T>(act.p, act.at(p, ch), av);
 #pragma unroll
         for (int q = 0; q < N; ++q) dv[q] *= av[q] > 0.f ? 1.f : act_slope;
       }
@@ -157,14 +160,14 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const void* __restrict_
     size_t p = (size_t)blockIdx.x * lanes + pl;
     for (; p + step < npix; p += 2 * step) {            // two loads in flight
       float xa[N], xb[N];
-      ldv<T>(x, p * xC + x0 + ch, xa);
-      ldv<T>(x, (p + step) * xC + x0 + ch, xb);
+      ldv<T>(x.p, x.at(p, ch), xa);
+      ldv<T>(x.p, x.at(p + step, ch), xb);
 #pragma unroll
       for (int q = 0; q < N; ++q) { s0[q] += xa[q] + xb[q]; s1[q] += xa[q] * xa[q] + xb[q] * xb[q]; }
     }
     if (p < npix) {
       float xa[N];
-      ldv<T>(x, p * xC + x0 + ch, xa);
+      ldv<T>(x.p, x.at(p, ch), xa);
 #pragma unroll
       for (int q = 0; q < N; ++q) { s0[q] += xa[q]; s1[q] += xa[q] * xa[q]; }
     }
@@ -245,29 +248,30 @@ __global__ __launch_bounds__(1024) void bn_bwd_finish_kernel(const float* __rest
 }
 // out = a*ca[c] + b*cb[c] + c0[c]  (b, cb optional): BatchNorm apply (forward: a=x, ca=scale, c0=shift) and backward.
 // Thread = one fixed channel chunk (coefficients live in registers), pixels strided over the grid.
+struct AffineK { View a, b, out, act; const float *ca, *cb, *c0; size_t npix; int c; float post_slope, act_slope; };
 template <typename T>
-__global__ __launch_bounds__(256) void chan_affine_kernel(const void* __restrict__ a, int aC, int a0, const void* __restrict__ b, int bC, int b0,
-                                                          void* out, int oC, int o0, const float* __restrict__ ca, const float* __restrict__ cb,
-                                                          const float* __restrict__ c0, size_t npix, int c, float post_slope,
-                                                          const void* __restrict__ act, int actC, int act0, float act_slope) {
+__global__ __launch_bounds__(256) void chan_affine_kernel(const AffineK k) {
   // post_slope: LeakyReLU applied to the result (1 = none).  act (optional): `a` is scaled by LeakyReLU'(act) first.
+  const View &a = k.a, &b = k.b, &out = k.out, &act = k.act;
+  const float* __restrict__ ca = k.ca; const float* __restrict__ cb = k.cb; const float* __restrict__ c0 = k.c0;
+  const size_t npix = k.npix; const int c = k.c; const float post_slope = k.post_slope, act_slope = k.act_slope;
   constexpr int N = VecN<T>::N;
   const int cv = c / N, lanes = 256 / cv;               // host: 256 % cv == 0
   const int ch = (threadIdx.x % cv) * N, pl = threadIdx.x / cv;
   float fa[N], fb[N], f0[N];
 #pragma unroll
-  for (int q = 0; q < N; ++q) { fa[q] = ca[ch + q]; fb[q] = b ? cb[ch + q] : 0.f; f0[q] = c0[ch + q]; }
+  for (int q = 0; q < N; ++q) { fa[q] = ca[ch + q]; fb[q] = b.p ? cb[ch + q] : 0.f; f0[q] = c0[ch + q]; }
   const size_t step = (size_t)gridDim.x * lanes;
   for (size_t p = (size_t)blockIdx.x * lanes + pl; p < npix; p += step) {
     float va[N], vb[N];
-    ldv<T>(a, p * aC + a0 + ch, va);
-    if (act) {
-      ldv<T>(act, p * actC + act0 + ch, vb);
+    ldv<T>(a.p, a.at(p, ch), va);
+    if (act.p) {
+      ldv<T>(act.p, act.at(p, ch), vb);
 #pragma unroll
       for (int q = 0; q < N; ++q) va[q] *= vb[q] > 0.f ? 1.f : act_slope;
     }
-    if (b) {
-      ldv<T>(b, p * bC + b0 + ch, vb);
+    if (b.p) {
+      ldv<T>(b.p, b.at(p, ch), vb);
 #pragma unroll
       for (int q = 0; q < N; ++q) va[q] = va[q] * fa[q] + vb[q] * fb[q] + f0[q];
     } else {
@@ -278,7 +282,7 @@ __global__ __launch_bounds__(256) void chan_affine_kernel(const void* __restrict
 #pragma unroll
       for (int q = 0; q < N; ++q) va[q] = va[q] > 0.f ? va[q] : va[q] * post_slope;
     }
-    stv<T>(out, p * oC + o0 + ch, va);
+    stv<T>(out.p, out.at(p, ch), va);
   }
 }
 
@@ -331,7 +335,7 @@ extern "C" int srganfd_spectral_norm_grad_batch(const srganfd_sn_grad_job* jobs,
     }
     for (int i = nb; i < kSnBatch; ++i) J.j[i] = J.j[0];
     SRGANFD_LAUNCH(sn_dot_partial_kernel, dim3(grid_for(max_n, 256, kRedBlocks), nb), dim3(256), 0, s, J);
-    SRGANFD_LAUNCH(sn_dot_finish_kernel, dim3(nb), dim3(256), 0, s, J);
+    SRGANFD_LAUNCH(finish_kernel<SnDotFin>, dim3(nb), dim3(256), 0, s, SnDotFin{J});
     SRGANFD_LAUNCH(sn_grad_kernel, dim3(grid_for(max_n), nb), dim3(256), 0, s, J, beta);
   }
   SRGANFD_HIP_CHECK(hipGetLastError());
@@ -346,7 +350,7 @@ extern "C" int srganfd_spectral_norm_grad(const float* G, const float* W, const 
 
 static constexpr int kBnBlocks = 1024;  // workspace: kBnBlocks * 2 * c floats (+ 3c for the backward coefficients)
 extern "C" int64_t srganfd_batchnorm_partial_floats(int32_t c) { return (long long)kBnBlocks * 2 * c; }
-static inline bool bn_chunks_ok(int dtype, int c) { const int cv = c / (dtype == SRGANFD_F32 ? 4 : 8); return cv > 0 && 256 % cv == 0; }
+static inline bool bn_chunks_ok(int dtype, int c) { const int cv = c / vec_width(dtype); return cv > 0 && 256 % cv == 0; }
 // every channel block of <= 256, checked before the first launch: a refused call has written nothing.  Returns the bad block's size or 0.
 static inline int bn_bad_block(int dtype, int c) {
   for (int cb = 0; cb < c; cb += 256) {
@@ -355,70 +359,88 @@ static inline int bn_bad_block(int dtype, int c) {
   }
   return 0;
 }
-static inline unsigned bn_grid(size_t npix, int dtype, int c) { const int lanes = 256 / (c / (dtype == SRGANFD_F32 ? 4 : 8)); return grid_for((npix + lanes - 1) / lanes, 1, 16384); }
+static inline unsigned bn_grid(size_t npix, int dtype, int c) { const int lanes = 256 / (c / vec_width(dtype)); return grid_for((npix + lanes - 1) / lanes, 1, 16384); }
 // Channels are processed in blocks of <= 256 (the statistics kernels map one thread to one channel); `save` is
-// [block][mean | invstd | scale | shift] and is only read back by batchnorm_bwd_impl with the same blocking.
+// [block][mean | invstd | scale | shift], written by the forward pass and read back by the backward pass with the same blocking.
 // phase (data-parallel SyncBN): 0 = statistics, finish and apply in one call; 1 = this rank's partial sums into ws only (the caller
-// all-reduces the first batchnorm_partial_floats(c) floats of ws over the ranks); 2 = finish + apply from ws with total_npix pixels.
+// all-reduces the first batchnorm_partial_floats(c) floats of ws over the ranks); 2 = finish + apply from the summed table with total_npix
+// pixels (backward: ws_global is that table, ws keeps this rank's own).
+// What both directions refuse after their own null / alignment check (phase_why: the direction's own rule for the two-phase form, or NULL)
+static int bn_refuse(const char* who, int dtype, int c, std::initializer_list<srganfd_view> views, const char* phase_why) {
+  if (const char* why = views_bad(c, views)) return set_err(SRGANFD_EINVAL, "%s: %s", who, why);
+  if (phase_why) return set_err(SRGANFD_EINVAL, "%s: %s", who, phase_why);
+  if (const int bad = bn_bad_block(dtype, c)) return set_err(SRGANFD_EINVAL, "%s: channel block of %d is not a power-of-two number of 16-byte chunks", who, bad);
+  return SRGANFD_OK;
+}
+// The block loop and the phases, once: stats(cb, cc) launches the partial sums of channels [cb, cb + cc) (not in phase 2, and not where
+// the running statistics are used), apply(cb, cc) the finish kernel and the affine map (not in phase 1).  Both return an error code.
+template <typename S, typename A>
+static int bn_blocks(int c, int phase, bool want_stats, S stats, A apply) {
+  for (int cb = 0; cb < c; cb += 256) {
+    const int cc = c - cb < 256 ? c - cb : 256;
+    if (want_stats && phase != 2)
+      if (const int rc = stats(cb, cc)) return rc;
+    if (phase == 1) continue;
+    if (const int rc = apply(cb, cc)) return rc;
+  }
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
 // Shared by the three forward entry points (plain, fused activation, two-phase).
 static int batchnorm_fwd_impl(srganfd_view x, srganfd_view y, int dtype, size_t npix, int c, const float* gamma, const float* beta, float* rm, float* rv,
                               float momentum, float eps, int training, float* save, float* ws, float act_slope, hipStream_t s, int phase,
                               size_t total_npix) {
   if (!x.ptr || !y.ptr || !gamma || !beta || !rm || !rv || !save || !ws || c <= 0 || !vec_ok(dtype, c, {x, y}))
     return set_err(SRGANFD_EINVAL, "batchnorm_fwd: bad args (16-byte aligned views)");
-  if (const char* why = views_bad(c, {x, y})) return set_err(SRGANFD_EINVAL, "batchnorm_fwd: %s", why);
-  if (phase && (c > 256 || !training)) return set_err(SRGANFD_EINVAL, "batchnorm_fwd: the two-phase form takes training mode and at most 256 channels");
-  if (const int bad = bn_bad_block(dtype, c)) return set_err(SRGANFD_EINVAL, "batchnorm_fwd: channel block of %d is not a power-of-two number of 16-byte chunks", bad);
+  if (const int rc = bn_refuse("batchnorm_fwd", dtype, c, {x, y},
+                               phase && (c > 256 || !training) ? "the two-phase form takes training mode and at most 256 channels" : nullptr))
+    return rc;
   // the unbiased running variance is var * n / (n - 1): one value per channel has none (torch refuses it as well)
-  if (training && phase != 1 && (phase == 2 ? total_npix : npix) < 2)
-    return set_err(SRGANFD_EINVAL, "batchnorm_fwd: training mode needs more than one value per channel (npix = %lld)", (long long)(phase == 2 ? total_npix : npix));
-  const float count = (float)(phase == 2 ? total_npix : npix);
-  for (int cb = 0; cb < c; cb += 256) {
-    const int cc = c - cb < 256 ? c - cb : 256;
-    const srganfd_view xs = sub_view(x, cb), ys = sub_view(y, cb);
-    float* sv = save + 4 * cb;
-    if (training && phase != 2) {
-      DISPATCH_T(dtype,
-                 SRGANFD_LAUNCH(bn_partial_kernel<TT>, dim3(kBnBlocks), dim3(256), 0, s, xs.ptr, xs.cstride, xs.c0, (const void*)nullptr, 0, 0, (const float*)nullptr, npix, cc, ws, (const void*)nullptr, 0, 0, 1.f));
-    }
-    if (phase == 1) continue;
-    SRGANFD_LAUNCH(bn_fwd_finish_kernel, dim3(1), dim3(1024), 0, s, (const float*)ws, kBnBlocks, cc, count, gamma + cb, beta + cb, rm + cb, rv + cb, momentum, eps, training, sv);
-    DISPATCH_T(dtype,
-               SRGANFD_LAUNCH(chan_affine_kernel<TT>, dim3(bn_grid(npix, dtype, cc)), dim3(256), 0, s, xs.ptr, xs.cstride, xs.c0, (const void*)nullptr, 0, 0,
-                              ys.ptr, ys.cstride, ys.c0, (const float*)(sv + 2 * cc), (const float*)nullptr, (const float*)(sv + 3 * cc), npix, cc, act_slope, (const void*)nullptr, 0, 0, 1.f));
-  }
-  SRGANFD_HIP_CHECK(hipGetLastError());
-  return SRGANFD_OK;
+  const size_t count = phase == 2 ? total_npix : npix;
+  if (training && phase != 1 && count < 2)
+    return set_err(SRGANFD_EINVAL, "batchnorm_fwd: training mode needs more than one value per channel (npix = %lld)", (long long)count);
+  return bn_blocks(
+      c, phase, training != 0,
+      [&](int cb, int cc) {
+        const BnPartialK k = {dev_view(sub_view(x, cb)), {}, {}, nullptr, npix, cc, ws, 1.f};
+        DISPATCH_T(dtype, SRGANFD_LAUNCH(bn_partial_kernel<TT>, dim3(kBnBlocks), dim3(256), 0, s, k));
+        return (int)SRGANFD_OK;
+      },
+      [&](int cb, int cc) {
+        float* sv = save + 4 * cb;
+        SRGANFD_LAUNCH(bn_fwd_finish_kernel, dim3(1), dim3(1024), 0, s, (const float*)ws, kBnBlocks, cc, (float)count, gamma + cb, beta + cb, rm + cb, rv + cb, momentum, eps, training, sv);
+        const AffineK k = {dev_view(sub_view(x, cb)), {}, dev_view(sub_view(y, cb)), {}, sv + 2 * cc, nullptr, sv + 3 * cc, npix, cc, act_slope, 1.f};
+        DISPATCH_T(dtype, SRGANFD_LAUNCH(chan_affine_kernel<TT>, dim3(bn_grid(npix, dtype, cc)), dim3(256), 0, s, k));
+        return (int)SRGANFD_OK;
+      });
 }
-// phase as in batchnorm_fwd_impl; phase 2 takes ws_global = the partial table summed over the ranks (ws keeps this rank's own)
+// Shared by the three backward entry points.  act (optional): the output of the LeakyReLU fused into the forward pass.
 static int batchnorm_bwd_impl(srganfd_view x, srganfd_view dy, srganfd_view dx, int dtype, size_t npix, int c, const float* gamma, const float* save,
                               float* dgamma, float* dbeta, float acc, float* ws, srganfd_view act, float act_slope, hipStream_t s, int phase,
                               const float* ws_global, size_t total_npix) {
   if (!x.ptr || !dy.ptr || !dx.ptr || !gamma || !save || !dgamma || !dbeta || !ws || c <= 0 || !vec_ok(dtype, c, {x, dy, dx, act}))
     return set_err(SRGANFD_EINVAL, "batchnorm_bwd: bad args");
-  if (const char* why = views_bad(c, {x, dy, dx, act})) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: %s", why);
-  if (phase && c > 256) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: the two-phase form takes at most 256 channels");
-  if (phase == 2 && !ws_global) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: phase 2 needs the all-reduced table");
-  if (const int bad = bn_bad_block(dtype, c)) return set_err(SRGANFD_EINVAL, "batchnorm_bwd: channel block of %d is not a power-of-two number of 16-byte chunks", bad);
+  if (const int rc = bn_refuse("batchnorm_bwd", dtype, c, {x, dy, dx, act},
+                               phase && c > 256 ? "the two-phase form takes at most 256 channels"
+                                                : phase == 2 && !ws_global ? "phase 2 needs the all-reduced table" : nullptr))
+    return rc;
   const float count = (float)(phase == 2 ? total_npix : npix);
-  for (int cb = 0; cb < c; cb += 256) {
-    const int cc = c - cb < 256 ? c - cb : 256;
-    const srganfd_view xs = sub_view(x, cb), dys = sub_view(dy, cb), dxs = sub_view(dx, cb), as = sub_view(act, cb);
-    const float* sv = save + 4 * cb;
-    float* coef = ws + (size_t)kBnBlocks * 2 * cc;
-    if (phase != 2) {
-      DISPATCH_T(dtype,
-                 SRGANFD_LAUNCH(bn_partial_kernel<TT>, dim3(kBnBlocks), dim3(256), 0, s, xs.ptr, xs.cstride, xs.c0, (const void*)dys.ptr, dys.cstride, dys.c0, sv, npix, cc, ws, (const void*)as.ptr, as.cstride, as.c0, act_slope));
-    }
-    if (phase == 1) continue;
-    SRGANFD_LAUNCH(bn_bwd_finish_kernel, dim3(1), dim3(1024), 0, s, (const float*)ws, kBnBlocks, cc, count, gamma + cb, sv, dgamma + cb, dbeta + cb, acc, coef,
-                   phase == 2 ? ws_global : (const float*)nullptr);
-    DISPATCH_T(dtype,
-               SRGANFD_LAUNCH(chan_affine_kernel<TT>, dim3(bn_grid(npix, dtype, cc)), dim3(256), 0, s, dys.ptr, dys.cstride, dys.c0, (const void*)xs.ptr, xs.cstride, xs.c0,
-                              dxs.ptr, dxs.cstride, dxs.c0, (const float*)coef, (const float*)(coef + cc), (const float*)(coef + 2 * cc), npix, cc, 1.f, (const void*)as.ptr, as.cstride, as.c0, act_slope));
-  }
-  SRGANFD_HIP_CHECK(hipGetLastError());
-  return SRGANFD_OK;
+  return bn_blocks(
+      c, phase, true,
+      [&](int cb, int cc) {
+        const BnPartialK k = {dev_view(sub_view(x, cb)), dev_view(sub_view(dy, cb)), dev_view(sub_view(act, cb)), save + 4 * cb, npix, cc, ws, act_slope};
+        DISPATCH_T(dtype, SRGANFD_LAUNCH(bn_partial_kernel<TT>, dim3(kBnBlocks), dim3(256), 0, s, k));
+        return (int)SRGANFD_OK;
+      },
+      [&](int cb, int cc) {
+        float* coef = ws + (size_t)kBnBlocks * 2 * cc;
+        SRGANFD_LAUNCH(bn_bwd_finish_kernel, dim3(1), dim3(1024), 0, s, (const float*)ws, kBnBlocks, cc, count, gamma + cb, save + 4 * cb, dgamma + cb, dbeta + cb, acc, coef,
+                       phase == 2 ? ws_global : (const float*)nullptr);
+        const AffineK k = {dev_view(sub_view(dy, cb)), dev_view(sub_view(x, cb)), dev_view(sub_view(dx, cb)), dev_view(sub_view(act, cb)),
+                           coef, coef + cc, coef + 2 * cc, npix, cc, 1.f, act_slope};
+        DISPATCH_T(dtype, SRGANFD_LAUNCH(chan_affine_kernel<TT>, dim3(bn_grid(npix, dtype, cc)), dim3(256), 0, s, k));
+        return (int)SRGANFD_OK;
+      });
 }
 extern "C" int srganfd_batchnorm_fwd(srganfd_view x, srganfd_view y, int32_t dtype, int64_t npix, int32_t c, const float* gamma, const float* beta,
                                      float* running_mean, float* running_var, float momentum, float eps, int32_t training, float* save, float* workspace,

@@ -5,14 +5,9 @@
 
 namespace srganfd {
 
-// an NHWC channel slice as the kernels see it; at() = element index of channel ch of a pixel
-struct RsView {
-  void* p; int cs, c0;
-  __device__ __forceinline__ size_t at(size_t pixel, int ch) const { return pixel * (size_t)cs + c0 + ch; }
-};
 // what every kernel of this file takes.  x2 ops: a -> b, (h, w) as the ABI states them; act, b2, slope: the fused adjoint's LeakyReLU'
 // (below).  resize: (h, w) -> (ho, wo).  maxpool2_relu_bwd: a = x, act = dy, b = dx.  No pointer is __restrict__: the ReLU copy runs in place.
-struct RsK { RsView a, b; int h, w, c, cv_shift; RsView act, b2; float slope; int n, ho, wo; };
+struct RsK { View a, b; int h, w, c, cv_shift; View act, b2; float slope; int n, ho, wo; };
 
 // flat index -> (image, y, x, first channel) over extents (hh, ww) and c / N channel groups; pix = the flat pixel (img * hh + y) * ww + x
 struct RsPix { size_t img, pix; int y, x, ch; };
@@ -320,7 +315,7 @@ __global__ __launch_bounds__(256) void resize_bwd_kernel(const RsK k) {   // a =
 // that maximum is not positive (ReLU').
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool2_relu_bwd_kernel(const RsK k) {
-  const RsView &x = k.a, &dy = k.act, &dx = k.b;
+  const View &x = k.a, &dy = k.act, &dx = k.b;
   const int h = k.h, w = k.w, ho = h / 2, wo = w / 2;
   const size_t total = (size_t)k.n * ho * wo * k.c;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -360,7 +355,6 @@ static const RsKernel kResize[2] = {{0, true, false, false, {resize_fwd_kernel<b
                                     {1, true, false, false, {resize_bwd_kernel<bf16_t>, resize_bwd_kernel<f16_t>, resize_bwd_kernel<float>}, "resize_bwd_kernel"}};
 static const RsKernel kMaxpoolBwd = {0, false, false, false, {maxpool2_relu_bwd_kernel<bf16_t>, maxpool2_relu_bwd_kernel<f16_t>, maxpool2_relu_bwd_kernel<float>}, "maxpool2_relu_bwd_kernel"};
 
-static RsView rs_view(const srganfd_view& v) { return {v.ptr, v.cstride, v.c0}; }
 // launches kn for the dtype, or writes "<label>/<dtype>" where srganfd_resample_describe asked for it
 static int rs_launch(const RsKernel& kn, int dtype, dim3 grid, hipStream_t s, const RsK& k) {
   const int t = dtype == SRGANFD_BF16 ? 0 : dtype == SRGANFD_F16 ? 1 : dtype == SRGANFD_F32 ? 2 : -1;
@@ -371,13 +365,10 @@ static int rs_launch(const RsKernel& kn, int dtype, dim3 grid, hipStream_t s, co
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }
-// grids of the grid-stride kernels: the scalar forms stop at grid_for's 8192 blocks, the vector forms (1/4 or 1/8 of the threads per
-// element) at 65536
-static dim3 rs_grid(size_t total, int vn) { return dim3(vn > 1 ? grid_for(total / vn, 256, 65536) : grid_for(total)); }
 
 // the x2 ops' dispatch.  may_nt: the fused entry's results may leave through non-temporal stores.
 static int rs_dispatch(int op, bool vec, bool may_nt, int dtype, RsK& k, hipStream_t s) {
-  const int vn = !vec ? 1 : dtype == SRGANFD_F32 ? 4 : 8, esize = dtype == SRGANFD_F32 ? 4 : 2;
+  const int vn = !vec ? 1 : vec_width(dtype), esize = dtype == SRGANFD_F32 ? 4 : 2;
   const size_t lo = (size_t)k.n * k.h * k.w * k.c;
   // row-grid forms of the two bilinear ops, grid (column blocks, groups of low-res rows, images): a grid's y and z extents end at 65535,
   // and the column decode is 32-bit
@@ -391,7 +382,7 @@ static int rs_dispatch(int op, bool vec, bool may_nt, int dtype, RsK& k, hipStre
     k.cv_shift = (cv & (cv - 1)) == 0 ? __builtin_ctz(cv) : -1;
     grid = dim3((unsigned)(((size_t)k.w * cv + 255) / 256), (unsigned)((k.h + kBilRows - 1) / kBilRows), (unsigned)k.n);
   } else {
-    grid = rs_grid(op == 1 ? lo * 4 : op == 3 ? lo / 4 : lo, vn);
+    grid = group_grid(op == 1 ? lo * 4 : op == 3 ? lo / 4 : lo, vn);
   }
   for (const RsKernel& kn : kResample)
     if (kn.op == op && kn.vec == vec && kn.rows == rows && kn.nt == nt) return rs_launch(kn, dtype, grid, s, k);
@@ -402,7 +393,7 @@ static int rs_dispatch(int op, bool vec, bool may_nt, int dtype, RsK& k, hipStre
 extern "C" int srganfd_resample(int32_t op, srganfd_view a, srganfd_view b, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, void* stream) {
   if (!a.ptr || !b.ptr) return set_err(SRGANFD_EINVAL, "resample: null view");
   if (const char* bad = views_bad(c, {a, b})) return set_err(SRGANFD_EINVAL, "resample: %s", bad);
-  RsK k = {rs_view(a), rs_view(b), h, w, c, 0, {}, {}, 0.f, n, 0, 0};
+  RsK k = {dev_view(a), dev_view(b), h, w, c, 0, {}, {}, 0.f, n, 0, 0};
   return rs_dispatch(op, vec_ok(dtype, c, {a, b}), false, dtype, k, (hipStream_t)stream);
 }
 // bilinear-x2 backward fused with the LeakyReLU' of the upsampled layer: dx_raw (optional) = adjoint of the upsampling applied to dy,
@@ -412,7 +403,7 @@ extern "C" int srganfd_resample_bwd_lrelu(srganfd_view dy, srganfd_view dx_raw, 
   if (!dy.ptr || !act.ptr || !dx_masked.ptr) return set_err(SRGANFD_EINVAL, "resample_bwd_lrelu: null view");
   if (const char* bad = views_bad(c, {dy, dx_raw, act, dx_masked})) return set_err(SRGANFD_EINVAL, "resample_bwd_lrelu: %s", bad);
   if (!vec_ok(dtype, c, {dy, dx_raw, act, dx_masked})) return set_err(SRGANFD_EINVAL, "resample_bwd_lrelu: views must be 16-byte aligned NHWC slices");
-  RsK k = {rs_view(dy), rs_view(dx_raw), h, w, c, 0, rs_view(act), rs_view(dx_masked), slope, n, 0, 0};
+  RsK k = {dev_view(dy), dev_view(dx_raw), h, w, c, 0, dev_view(act), dev_view(dx_masked), slope, n, 0, 0};
   return rs_dispatch(2, true, true, dtype, k, (hipStream_t)stream);
 }
 // entry 0: srganfd_resample(op, a, b) ; entry 1: srganfd_resample_bwd_lrelu(dy = a, dx_raw = b, act = act, dx_masked = b2).  Writes the
@@ -431,16 +422,16 @@ extern "C" int srganfd_resize_bilinear(int32_t bwd, srganfd_view a, srganfd_view
                                        int32_t c, void* stream) {
   if (!a.ptr || !b.ptr || !vec_ok(dtype, c, {a, b})) return set_err(SRGANFD_EINVAL, "resize_bilinear: views must be 16-byte aligned channel multiples");
   if (const char* bad = views_bad(c, {a, b})) return set_err(SRGANFD_EINVAL, "resize_bilinear: %s", bad);
-  RsK k = {rs_view(a), rs_view(b), hi, wi, c, 0, {}, {}, 0.f, n, ho, wo};
+  RsK k = {dev_view(a), dev_view(b), hi, wi, c, 0, {}, {}, 0.f, n, ho, wo};
   const size_t total = bwd ? (size_t)n * hi * wi * c : (size_t)n * ho * wo * c;
-  return rs_launch(kResize[bwd ? 1 : 0], dtype, rs_grid(total, dtype == SRGANFD_F32 ? 4 : 8), (hipStream_t)stream, k);
+  return rs_launch(kResize[bwd ? 1 : 0], dtype, group_grid(total, vec_width(dtype)), (hipStream_t)stream, k);
 }
 extern "C" int srganfd_maxpool2_relu_bwd(srganfd_view x, srganfd_view dy, srganfd_view dx, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c,
                                          void* stream) {
   if (!x.ptr || !dy.ptr || !dx.ptr || n <= 0 || h <= 0 || w <= 0 || (h & 1) || (w & 1)) return set_err(SRGANFD_EINVAL, "maxpool2_relu_bwd: bad args");
   if (const char* bad = views_bad(c, {x, dy, dx})) return set_err(SRGANFD_EINVAL, "maxpool2_relu_bwd: %s", bad);
-  RsK k = {rs_view(x), rs_view(dx), h, w, c, 0, rs_view(dy), {}, 0.f, n, 0, 0};
-  return rs_launch(kMaxpoolBwd, dtype, rs_grid((size_t)n * (h / 2) * (w / 2) * c, 1), (hipStream_t)stream, k);
+  RsK k = {dev_view(x), dev_view(dx), h, w, c, 0, dev_view(dy), {}, 0.f, n, 0, 0};
+  return rs_launch(kMaxpoolBwd, dtype, group_grid((size_t)n * (h / 2) * (w / 2) * c, 1), (hipStream_t)stream, k);
 }
 
 }  // namespace srganfd

@@ -7,14 +7,15 @@ Views sit at different channel offsets of padded buffers filled with sentinels; 
 told about.  Stored maps are held to norm_oracle.assert_stored (TOL_BWD for the backward maps, TOL_FWD for the forward ones); where a
 value is only selected it is bit for bit the input.
 
-Which test reaches which launch (SRGANFD_LAUNCH lines of csrc/elementwise.hip):
-  lrelu_bwd_vec_kernel        test_lrelu_bwd_vector_form, test_lrelu_bwd_in_place, test_lrelu_bwd_forms_agree_bit_for_bit,
-                              test_lrelu_bwd_vector_grid_second_trip
-  lrelu_bwd_kernel            test_lrelu_bwd_scalar_form, test_lrelu_bwd_in_place, test_lrelu_bwd_forms_agree_bit_for_bit,
+Which test reaches which launch (SRGANFD_LAUNCH lines of csrc/elementwise.hip; N = the 16-byte vector, or 1 for the scalar form):
+  lrelu_bwd_kernel<T, N>      test_lrelu_bwd_vector_form, test_lrelu_bwd_in_place, test_lrelu_bwd_forms_agree_bit_for_bit,
+                              test_lrelu_bwd_one_stride_off_the_vector_takes_the_scalar_form, test_lrelu_bwd_vector_grid_second_trip
+  lrelu_bwd_kernel<T, 1>      test_lrelu_bwd_scalar_form, test_lrelu_bwd_in_place, test_lrelu_bwd_forms_agree_bit_for_bit,
+                              test_lrelu_bwd_one_stride_off_the_vector_takes_the_scalar_form, test_scalar_grids_second_trip
+  axpby_kernel<T, N>          test_axpby_vector_form, test_axpby_forms_agree_bit_for_bit, test_axpby_one_view_off_the_vector_takes_the_scalar_form
+  axpby_kernel<T, 1>          test_axpby_scalar_form, test_axpby_flat_form_of_the_trainers, test_axpby_single_element,
+                              test_axpby_forms_agree_bit_for_bit, test_axpby_one_view_off_the_vector_takes_the_scalar_form,
                               test_scalar_grids_second_trip
-  axpby_vec_kernel            test_axpby_vector_form, test_axpby_forms_agree_bit_for_bit
-  axpby_kernel                test_axpby_scalar_form, test_axpby_flat_form_of_the_trainers, test_axpby_single_element,
-                              test_axpby_forms_agree_bit_for_bit, test_scalar_grids_second_trip
   sigmoid_kernel              test_sigmoid_saturates_without_nan, test_scalar_grids_second_trip
   sigmoid_bwd_kernel          test_sigmoid_bwd_in_place_and_not, test_scalar_grids_second_trip
   add_relu_kernel, gate_fwd_kernel, gate_bwd_kernel             tests/test_attention_gate_gpu.py"""
@@ -146,6 +147,20 @@ def test_lrelu_bwd_forms_agree_bit_for_bit(dtype, with_skip):
     O.assert_bits(vec, sca, "lrelu_bwd: vector against scalar form")
 
 
+@pytest.mark.parametrize("which", range(4), ids=["dy", "act", "skip", "out"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_lrelu_bwd_one_stride_off_the_vector_takes_the_scalar_form(dtype, which):
+    """c and every c0 a multiple of the vector, every base pointer aligned, and exactly one buffer one channel wider than a multiple of the
+    vector: its second pixel is no longer aligned, so the whole call has to take the scalar form.  Same bits as the vector form."""
+    v = O.vn(dtype)
+    dy, act, skip = _lrelu_case(dtype, NPIX, 2 * v, True, seed=15)
+    vec = _lrelu_bwd(dtype, dy, act, skip, _geo(v))
+    geo = _geo(v)
+    geo[which] = (geo[which][0] + 1, geo[which][1])
+    sca = _lrelu_bwd(dtype, dy, act, skip, geo)
+    O.assert_bits(vec, sca, "lrelu_bwd: vector form against the scalar form a stride forces")
+
+
 # ---- axpby ----
 def _axpby(dtype, x, y, geo, alpha, beta, flat=False):
     A, L, st = O.abi()
@@ -199,6 +214,21 @@ def test_axpby_forms_agree_bit_for_bit(dtype, ab):
     vec = _axpby(dtype, x, y, [(2 * v, v), (v, 0)], *ab)
     sca = _axpby(dtype, x, y, [(2 * v, v), (v, 1)], *ab)
     O.assert_bits(vec, sca, "axpby: vector against scalar form")
+
+
+@pytest.mark.parametrize("how", ["c0 one channel off", "cstride off the vector"])
+@pytest.mark.parametrize("which", [0, 1], ids=["x", "y"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_axpby_one_view_off_the_vector_takes_the_scalar_form(dtype, which, how):
+    """c a multiple of the vector and the base pointers aligned; exactly one term of the eligibility test fails, for exactly one view"""
+    v = O.vn(dtype)
+    x, y = _axpby_case(dtype, NPIX, 2 * v, seed=16)
+    geo = [(2 * v, v), (v, 0)]                                 # (pad, c0) of x and y: the vector form's
+    vec = _axpby(dtype, x, y, geo, *AB[0])
+    pad, c0 = geo[which]
+    geo[which] = (pad, c0 + 1) if how.startswith("c0") else (pad + 1, c0)
+    sca = _axpby(dtype, x, y, geo, *AB[0])
+    O.assert_bits(vec, sca, "axpby: vector form against the scalar form one view forces")
 
 
 def _axpby_flat(x, y, alpha, beta):

@@ -697,7 +697,7 @@ def test_content_loss_gradient_matches_oracle(mode):
     # the loss is ONE number (see SCALAR_FLOOR's note; measured against the un-floored rule: f32 1.06, f16 1.30, bf16 0.66 of it).  It is
     # pinned in two sharper ways instead: the two halves of the stored tap map it is computed from are held to the rule as tensors, and it
     # equals the float64 mean |sr_f - gt_f| of the STORED halves within the roundoff of its fp32 sum of non-negative terms
-    # (csrc/loss.hip, l1_views_vec_partial_kernel + finish_sum_kernel over min(ceil(n / 256), 1024) blocks: the difference -- exact for
+    # (csrc/loss.hip, l1_views_partial_kernel's vector form + finish_kernel<FinAxpy> over min(ceil(n / 256), 1024) blocks: the difference -- exact for
     # 16-bit values, one rounding in f32 --, a thread's serial chain over its vectors of at most 8 elements, at most 10 additions of
     # block_reduce_sum, the finish kernel's chain over the blocks' partials and its block_reduce_sum, the rounding of 1 / n and the
     # scaling: each one rounding of at most 2^-24).  Its floor under the rule is what the rule's bounds on the two halves allow:

@@ -8,11 +8,12 @@ to the bounds of tests/norm_oracle.py.  Outputs sit in channel slices between se
 has to keep its sentinels too.
 
 Which test reaches which launch:
-  nchw_to_nhwc4_kernel                               test_nchw_to_nhwc_nhwc4_packer, test_nchw_to_nhwc4_second_trip_of_the_grid
-  nchw_to_nhwc_vec_kernel, nchw_to_nhwc_kernel       test_nchw_to_nhwc_vector_path, test_nchw_to_nhwc_scalar_path
+  rgb_to_nhwc_kernel<T, CLAMP=0, WIDE=0>             test_nchw_to_nhwc_nhwc4_packer, test_nchw_to_nhwc4_second_trip_of_the_grid
+  nchw_to_nhwc_kernel<T, N> (vector and N = 1)       test_nchw_to_nhwc_vector_path, test_nchw_to_nhwc_scalar_path,
+                                                     test_nchw_to_nhwc_view_off_the_vector_takes_the_scalar_path (N = 1)
   nhwc_to_nchw_kernel                                test_nhwc_to_nchw_generator_output, _from_a_channel_slice, _second_trip_of_the_grid
   nhwc_to_nchw_scaled_kernel                         test_nhwc_to_nchw_scaled_from_a_channel_slice
-  clamp_grad_rgb4_kernel, _rgb16_kernel, clamp_grad_kernel            test_clamp_grad_three_paths_agree_with_the_definition_and_each_other,
+  rgb_to_nhwc_kernel<T, CLAMP=1, WIDE=0 / 1>, clamp_grad_kernel       test_clamp_grad_three_paths_agree_with_the_definition_and_each_other,
                                                      test_clamp_grad_generic_path_in_fp32, test_clamp_grad_rgb4_second_trip_of_the_grid"""
 import pytest
 import torch
@@ -94,6 +95,17 @@ def test_nchw_to_nhwc_scalar_path(dtype, norm):
         _nchw_to_nhwc(dtype, 3, 6, 2, 1, norm)
     else:
         _nchw_to_nhwc(dtype, 3, 8, 8, 4, norm)
+
+
+@pytest.mark.parametrize("how", ["c0 one channel off", "cstride off the vector"])
+@pytest.mark.parametrize("norm", [False, True], ids=["plain", "normalised"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_nchw_to_nhwc_view_off_the_vector_takes_the_scalar_path(dtype, norm, how):
+    """cpad two whole vectors and the base pointer aligned; the view alone is off: it starts one channel into its buffer, or its buffer is
+    one channel wider than a multiple of the vector (every pixel but the first is then off 16 bytes)"""
+    v = O.vn(dtype)
+    pad, c0 = (v, 1) if how.startswith("c0") else (v + 1, v)
+    _nchw_to_nhwc(dtype, 3, 2 * v, pad, c0, norm)
 
 
 # ---- NHWC -> NCHW ----

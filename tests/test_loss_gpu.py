@@ -18,12 +18,13 @@ at a NaN difference are 0, because torch.sign is (0 < d) - (d < 0) and gives 0 t
 it): the kernels already did that, and test_l1_loss_nan_is_torchs holds them to torch's gradient bit for bit.
 
 Which test reaches which launch (SRGANFD_LAUNCH lines of csrc/loss.hip):
-  l1_partial_kernel, finish_sum_kernel                   test_l1_loss, test_l1_loss_nan_is_torchs
-  l1_views_vec_partial_kernel, l1_views_partial_kernel   test_l1_loss_views, test_l1_loss_views_keeps_a_nan_through_relu
+  l1_partial_kernel, finish_kernel<FinAxpy>              test_l1_loss, test_l1_loss_nan_is_torchs
+  l1_views_partial_kernel<T, N> (vector and N = 1)       test_l1_loss_views, test_l1_loss_views_keeps_a_nan_through_relu,
+                                                         test_l1_loss_views_one_view_off_the_vector_takes_the_scalar_form (N = 1)
   l1_grad_views_kernel                                   test_l1_grad_views, test_l1_grad_views_second_trip
-  bce_partial_kernel, finish_sum_kernel (both uses)      test_bce_logits
-  sum_partial_kernel, finish_sigmoid_mean_kernel         test_sigmoid_of_mean
-  sum_partial_kernel, finish_mean_kernel, bce_rel_partial_kernel, finish_sum_kernel, bce_rel_other_kernel       test_bce_logits_relativistic
+  bce_partial_kernel, finish_kernel<FinAxpy> (both uses) test_bce_logits
+  sum_partial_kernel, finish_kernel<FinSigmoidMean>      test_sigmoid_of_mean
+  sum_partial_kernel, finish_kernel<FinMean>, bce_rel_partial_kernel, finish_kernel<FinAxpy>, bce_rel_other_kernel       test_bce_logits_relativistic
   nonfinite_flag_kernel                                  test_nonfinite_flag
   loss_scale_update_kernel                               test_loss_scale_update_word_for_word"""
 import numpy as np
@@ -182,6 +183,33 @@ def test_l1_loss_views_keeps_a_nan_through_relu(dtype, form, c):
             k.done("l1_loss_views")
             out.assert_fences("loss")
             assert torch.isnan(out.val).all(), f"NaN at {where}, relu={relu}: the loss is {out.val.item()}"
+
+
+@pytest.mark.parametrize("how", ["c0 one channel off", "cstride off the vector"])
+@pytest.mark.parametrize("which", [0, 1], ids=["a", "b"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_l1_loss_views_one_view_off_the_vector_takes_the_scalar_form(dtype, which, how):
+    """c a multiple of the vector and the base pointers aligned; exactly one term of the eligibility test fails, for exactly one view.  The
+    vector form would read that view's pixels at addresses that are no multiple of 16 bytes (the sum is the check: the two forms add in
+    different orders, so they are not held to each other's bits)."""
+    k = _Call()
+    v = O.vn(dtype)
+    npix, c = 37 * 29, 2 * v
+    g = _gen(7)
+    a, b = torch.randn(npix, c, generator=g).to(dtype), torch.randn(npix, c, generator=g).to(dtype)
+    geo = [(2 * v, v), (v, 0)]
+    pad, c0 = geo[which]
+    geo[which] = (pad, c0 + 1) if how.startswith("c0") else (pad + 1, c0)
+    sa, sb = Slot((npix, c), dtype, a, *geo[0]), Slot((npix, c), dtype, b, *geo[1])
+    for relu in (0, 1):
+        ref = O.l1_views(a, b, bool(relu))
+        what = f"l1_loss_views, {'ab'[which]} {how}, relu={relu}"
+        out = k.slot(0.25)
+        k.A.check(k.L.srganfd_l1_loss_views(sa.view(k.A), sb.view(k.A), O.code(k.A, dtype), npix, c, relu, 0.1, out.ptr(), 1, k.ws.ptr(), k.st), what)
+        k.done(what)
+        sa.assert_untouched("a")
+        sb.assert_untouched("b")
+        _assert_loss(out, 0.25, O.f32(0.1) * ref, 0.1, ref, what)
 
 
 def _l1_grad_views(dtype, npix, c, geo, upstream, seed, device="cpu"):

@@ -1,4 +1,4 @@
-"""Device assembly of wgrad.hip, dense_chain.hip, conv_thin.hip or resample.hip, one tree against another, per kernel (the method of
+"""Device assembly of wgrad.hip, dense_chain.hip, conv_thin.hip, resample.hip or the view kernels' files, one tree against another, per kernel (the method of
 profiles/conv_igemm_refactor_isa.txt).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I. --offload-device-only -S -o parent.s <parent>/wgrad.hip      (same for the branch)
@@ -6,6 +6,8 @@ profiles/conv_igemm_refactor_isa.txt).
     python tools/wgrad_isa_compare.py --kernel dense_chain parent.s branch.s > profiles/dense_chain_refactor_isa.txt
     python tools/wgrad_isa_compare.py --kernel thin parent.s branch.s > profiles/conv_thin_refactor_isa.txt
     python tools/wgrad_isa_compare.py --kernel resample parent.s branch.s > profiles/resample_refactor_isa.txt
+    cat <parent>/{elementwise,loss,layout,norm,resample}.s > parent.s  (same for the branch)
+    python tools/wgrad_isa_compare.py --kernel views parent.s branch.s > profiles/view_kernels_refactor_isa.txt
 
 wgrad kernels are matched by template arguments <T, KS, STRIDE, XP, YP, DMA>; a seventh argument (the parent's VAR) is dropped;
 dense-chain kernels by <T, RPW>; the thin-side kernels by <T, MASK, NT> (thin_in) and <T> (thin_out, thin_wgrad), the slab reduction by
@@ -13,7 +15,12 @@ its symbol.  Per kernel: the .amdhsa_kernel block, and the counts of MFMA, LDS, 
 buffer, s_waitcnt and s_barrier instructions, which must be equal; --kernel dense_chain and --kernel thin also count v_readlane / v_writelane (SGPR
 spills to lanes), which must not rise.  --kernel resample matches resample_vec_kernel<T, OP> / relu_copy_vec_kernel<T> and the five
 scalar kernels of the old file to resample_kernel<T, N, OP>, the row-grid kernels by <T> and <T, NT>; the scalar forms (N = 1) are
-reported as what they became, not held to the counts.  A working tool, not a test."""
+reported as what they became, not held to the counts.  --kernel views (elementwise.hip, loss.hip, layout.hip, norm.hip, and resample.hip,
+whose labels are those of --kernel resample) matches the scalar / vector pairs of the old files (x_kernel<T> / x_vec_kernel<T>) to
+x_kernel<T, N>, the three per-pixel RGB kernels to rgb_to_nhwc_kernel<T, CLAMP, WIDE>, the four one-block sums to finish_kernel<E>, and
+every other kernel by name and element type, whatever its arguments became; scalar forms are reported, axpby_kernel<f32, scalar> aside
+(the trainers run it); an s_waitcnt count that moved is listed, and fails only if the waits on vector memory (vmcnt) moved.
+A working tool, not a test."""
 import collections
 import re
 import sys
@@ -32,7 +39,41 @@ RS_NAMES = [   # (pattern, label format): groups are (T, ...)
     (re.compile(r"bilinear_up2_bwd_rows_kernel" + RS_T + r"(?:Li4E)?Lb(\d)EE"), lambda g: "bilinear_up2_bwd_rows_kernel<%s, NT=%s>" % (TYPES[g[0]], g[1])),
     (re.compile(r"(resize_fwd|resize_bwd|maxpool2_relu_bwd)_kernel" + RS_T + "E"), lambda g: "%s_kernel<%s>" % (g[0], TYPES[g[1]])),
 ]
-REPORT_ONLY = ", scalar,"                           # resample: kernels whose label holds this are reported, not held to the counts
+REPORT_ONLY = ", scalar"                            # resample, views: kernels whose label holds this are reported, not held to the counts
+HELD_SCALAR = "axpby_kernel<f32, scalar>"           # views: the one scalar form the product runs (the trainers' flat fp32 gradient sums)
+VIEWS = False
+VIEW_PAIRS = ("lrelu_bwd", "axpby", "l1_views", "nchw_to_nhwc")      # old: x_kernel / x_vec_kernel (l1_views: x_partial_kernel / x_vec_partial_kernel)
+VIEW_SCALAR_ONLY = ("clamp_grad_kernel", "nhwc_to_nchw_kernel", "l1_grad_views_kernel")
+VIEW_RENAMED = {"clamp_grad_rgb16_kernel": "rgb_to_nhwc_kernel<%s, CLAMP=1, WIDE=1>", "clamp_grad_rgb4_kernel": "rgb_to_nhwc_kernel<%s, CLAMP=1, WIDE=0>",
+                "nchw_to_nhwc4_kernel": "rgb_to_nhwc_kernel<%s, CLAMP=0, WIDE=0>", "finish_sum_kernel": "finish_kernel<FinAxpy>",
+                "finish_mean_kernel": "finish_kernel<FinMean>", "finish_sigmoid_mean_kernel": "finish_kernel<FinSigmoidMean>",
+                "sn_dot_finish_kernel": "finish_kernel<SnDotFin>"}
+VIEW_SYM = re.compile(r"_ZN7srganfd\d+?([a-z][a-z0-9_]*_kernel)(?:I(t|DF16_|f)((?:L[ib]\d+E)*)E|INS_\d+([A-Za-z]+)EE)?E")
+
+
+def views_label(sym):
+    """one label for a kernel of elementwise / loss / layout / norm .hip on either side of the refactor"""
+    m = VIEW_SYM.match(sym)
+    if not m:
+        return None
+    name, t, args, epi = m.groups()
+    if epi:
+        return "%s<%s>" % (name, epi)
+    if name in VIEW_RENAMED:
+        return VIEW_RENAMED[name] % TYPES[t] if "%s" in VIEW_RENAMED[name] else VIEW_RENAMED[name]
+    if name == "rgb_to_nhwc_kernel":
+        clamp, wide = re.findall(r"Lb(\d)E", args)
+        return "rgb_to_nhwc_kernel<%s, CLAMP=%s, WIDE=%s>" % (TYPES[t], clamp, wide)
+    for base in VIEW_PAIRS:
+        tail = "_partial_kernel" if base == "l1_views" else "_kernel"
+        if name == base + "_vec" + tail:
+            return "%s%s<%s, vec>" % (base, tail, TYPES[t])
+        if name == base + tail:
+            n = re.findall(r"Li(\d+)E", args)
+            return "%s%s<%s, %s>" % (base, tail, TYPES[t], "vec" if n and n[0] != "1" else "scalar")
+    if name in VIEW_SCALAR_ONLY:
+        return "%s<%s, scalar>" % (name, TYPES[t])
+    return "%s<%s>" % (name, TYPES[t]) if t else name
 TYPES = {"t": "bf16", "DF16_": "f16", "f": "f32"}
 CLASSES = [("mfma", r"v_mfma"), ("lds", r"ds_"), ("global", r"(global|flat|scratch)_"), ("buffer", r"buffer_"), ("s_waitcnt", r"s_waitcnt"),
            ("s_barrier", r"s_barrier")]
@@ -44,11 +85,17 @@ def waves(v):
     return 8 - next(i for i, s in enumerate(WAVE_STEPS) if v <= s)
 
 
+def report_only(n):
+    return REPORT_ONLY in n and n != HELD_SCALAR
+
+
 def label(sym):
     for pat, fmt in RS_NAMES:
         m = pat.search(sym)
         if m:
             return fmt(m.groups()), None
+    if VIEWS and views_label(sym):
+        return views_label(sym), None
     m = DC_NAME.search(sym)
     if m:
         return "dense_chain_kernel<%s, RPW=%s>" % (TYPES[m.group(1)], m.group(2)), None
@@ -115,8 +162,11 @@ def main():
         if argv[1] in ("dense_chain", "thin"):
             CLASSES.append(("lane spills", r"v_(readlane|writelane)"))
             AT_MOST.append("lane spills")
+        elif argv[1] == "views":
+            global VIEWS
+            VIEWS = True
         elif argv[1] not in ("wgrad", "resample"):
-            sys.exit("--kernel: wgrad, dense_chain, thin or resample, not %r" % argv[1])
+            sys.exit("--kernel: wgrad, dense_chain, thin, resample or views, not %r" % argv[1])
         argv = argv[2:]
     P, B = parse(argv[0]), parse(argv[1])
     only_p, only_b = sorted(set(P) - set(B)), sorted(set(B) - set(P))
@@ -126,7 +176,7 @@ def main():
     for n in only_b:
         print("only in branch: %s: %s" % (n, res(B[n]["meta"])))
     print("# per kernel: instruction stream / .amdhsa_kernel block (kernarg size aside) / resources parent | branch")
-    bad = []
+    bad, moved = [], []
     n_same, n_meta = 0, 0
     for n in sorted(set(P) & set(B)):
         p, b = P[n], B[n]
@@ -142,13 +192,17 @@ def main():
         cp, cb = counts(p["ops"]), counts(b["ops"])
         vp, vb = int(p["meta"][".amdhsa_next_free_vgpr"]), int(b["meta"][".amdhsa_next_free_vgpr"])
         sp, sb = int(p["meta"][".amdhsa_private_segment_fixed_size"]), int(b["meta"][".amdhsa_private_segment_fixed_size"])
-        if REPORT_ONLY in n:
+        wv = [sum("vmcnt" in o for o in x["ops"] if o.startswith("s_waitcnt")) for x in (p, b)]
+        waits_moved = VIEWS and cp["s_waitcnt"] != cb["s_waitcnt"] and wv[0] == wv[1]      # scalar (kernel-argument) waits alone: listed
+        if report_only(n):
             print("    a scalar form: reported, not held to the parent's counts")
-        elif any(cb[k] > cp[k] if k in AT_MOST else cb[k] != cp[k] for k in cp):
+        elif any(cb[k] > cp[k] if k in AT_MOST else cb[k] != cp[k] for k in cp if not (waits_moved and k == "s_waitcnt")):
             bad.append(n + ": instruction-class counts differ")
+        if waits_moved and not report_only(n):
+            moved.append("%s: s_waitcnt %d -> %d, those on vector memory %d on both sides" % (n, cp["s_waitcnt"], cb["s_waitcnt"], wv[0]))
         if sb > sp:
             bad.append(n + ": gains scratch")
-        if waves(vb) < waves(vp) and REPORT_ONLY not in n:
+        if waves(vb) < waves(vp) and not report_only(n):
             bad.append(n + ": crosses a wave-occupancy step (%d -> %d VGPRs)" % (vp, vb))
         if "DMA=1" in n and vb > 128 and vb > vp:
             bad.append(n + ": loader-wave kernel above 128 VGPRs")
@@ -157,11 +211,14 @@ def main():
             for k in cp:
                 print("    %s %d | %d" % (k, cp[k], cb[k]))
             if cp["s_waitcnt"] != cb["s_waitcnt"]:      # which waits moved: those on vector memory, or those on scalar (kernel-argument) loads alone
-                wv = [sum("vmcnt" in o for o in x["ops"] if o.startswith("s_waitcnt")) for x in (p, b)]
                 print("    s_waitcnt with vmcnt %d | %d, without (scalar loads, LDS) %d | %d" % (wv[0], wv[1], cp["s_waitcnt"] - wv[0], cb["s_waitcnt"] - wv[1]))
             op, ob = collections.Counter(o.split()[0] for o in p["ops"]), collections.Counter(o.split()[0] for o in b["ops"])
             print("    per opcode (differing only): " + ", ".join("%s %d|%d" % (k, op[k], ob[k]) for k in sorted(set(op) | set(ob)) if op[k] != ob[k]))
     print("# identical streams: %d of %d; identical metadata (kernarg size aside): %d of %d" % (n_same, len(set(P) & set(B)), n_meta, len(set(P) & set(B))))
+    if VIEWS:
+        print("# s_waitcnt counts that moved with the kernel-argument layout (waits on vector memory equal): %d" % len(moved))
+        for x in moved:
+            print("#   " + x)
     print("# requirements not met: %d" % len(bad))
     for x in bad:
         print("#   " + x)
