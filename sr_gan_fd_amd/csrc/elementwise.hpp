@@ -118,6 +118,8 @@ inline unsigned grid_for(size_t total, int block = 256, unsigned cap = 8192) {
   if (g > cap) g = cap;
   return (unsigned)g;
 }
+// the refusal the entry points on plain fp32 buffers share, under the entry point's name: a null pointer or a size that is not positive
+inline int refuse_empty(const char* name) { return set_err(SRGANFD_EINVAL, "%s: null / empty argument", name); }
 // CALL (the rest of the arguments: a launch's own commas pass through) names the element type as TT
 #define DISPATCH_T(dtype, ...)                                                                                                          \
   if ((dtype) == SRGANFD_BF16) { using TT = bf16_t; __VA_ARGS__; } else if ((dtype) == SRGANFD_F16) { using TT = f16_t; __VA_ARGS__; } \

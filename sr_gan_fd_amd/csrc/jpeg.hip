@@ -1,8 +1,13 @@
-// jpeg.hip -- a real baseline JPEG round trip (encode at a quality, decode) on NCHW fp32 RGB batches: the integer pipeline of libjpeg's
-// defaults (4:2:0, the slow-but-accurate integer DCT, fancy chroma upsampling), which BSRGAN's blind degradation runs per image on the
-// host through cv2.imencode / cv2.imdecode (BSRGAN/imgproc.py:284-293).  Entropy coding is lossless, so it is not there; what is left is
-// integer arithmetic in int32, and the result equals the library's byte for byte (tests/jpeg_oracle.py is the same restated in numpy).
-//   jpeg_mcu_kernel     one wave per 16 x 16 MCU, four MCUs per workgroup: quantise to bytes, RGB -> YCbCr (16-bit fixed point), 2 x 2 chroma
+// jpeg.hip -- the two JPEG round trips (encode at a quality, decode) of the degradation pipelines on NCHW fp32 RGB batches.  They share the
+// frame (McuLane: one wavefront per 16 x 16 MCU = 4 luma blocks + Cb + Cr, four MCUs per 256-thread workgroup) and the standard
+// quantisation tables.  The arithmetic of each is its own, and with it the LDS layout that arithmetic wants (fp32: luma as one 16 x 16 plane;
+// int32: six blocks of row pitch 9).
+//
+// srganfd_jpeg_roundtrip: a real baseline JPEG, the integer pipeline of libjpeg's defaults (4:2:0, the slow-but-accurate integer DCT, fancy
+// chroma upsampling), which BSRGAN's blind degradation runs per image on the host through cv2.imencode / cv2.imdecode
+// (BSRGAN/imgproc.py:284-293).  Entropy coding is lossless, so it is not there; what is left is integer arithmetic in int32, and the
+// result equals the library's byte for byte (tests/jpeg_oracle.py is the same restated in numpy).
+//   jpeg_mcu_kernel     one wave per MCU: quantise to bytes, RGB -> YCbCr (16-bit fixed point), 2 x 2 chroma
 //                       average (bias 1, 2, 1, 2 ... along a row), then for the four luma and two chroma blocks the forward DCT, the
 //                       quantiser (|c| + 4 q) / (8 q), the product with q, the inverse DCT and the + 128 clamp, rows and columns through LDS;
 //                       decoded Y (full size) and Cb / Cr (half size) go to a byte workspace.
@@ -11,7 +16,10 @@
 // Edges as the library pads them: columns are replicated before the chroma average, rows after it (an odd height's last row is doubled
 // first), so the last chroma row of an even height is a true average of two rows, repeated downwards.
 // quality[b] lives in device memory; 0 leaves that image's planes as they are (copied through, bit for bit).
-#include "common.hpp"
+//
+// srganfd_diff_jpeg: Real-ESRGAN's DiffJPEG (Real_ESRGAN/imgproc.py:1198-1497), fp32 throughout; see diff_jpeg_kernel.
+#include <math.h>
+#include "elementwise.hpp"
 
 namespace srganfd {
 
@@ -20,12 +28,37 @@ static constexpr int kJpgPitch = 9;          // ints per block row in LDS: rows 
 static constexpr int kJpgBlock = 8 * kJpgPitch;
 static constexpr int kJpgMcuBytes = 384;     // 256 Y + 64 Cb + 64 Cr of workspace per MCU
 
-__device__ static const unsigned char kJpgLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
-                                                      69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55,  64,
-                                                      81, 104, 113, 92, 49, 64,  78,  87,  103, 121, 120, 101, 72, 92, 95,  98,  112, 100, 103, 99};
-__device__ static const unsigned char kJpgChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
-                                                        99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
-                                                        99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+// the standard luminance and chrominance quantisation tables (JPEG Annex K), in libjpeg's natural order: [frequency row][frequency column]
+static constexpr unsigned char kJpgLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
+                                               69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55,  64,
+                                               81, 104, 113, 92, 49, 64,  78,  87,  103, 121, 120, 101, 72, 92, 95,  98,  112, 100, 103, 99};
+static constexpr unsigned char kJpgChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                                                 99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+
+// A lane's place in a grid of ceil(b * mcus_y * mcus_x / 4) workgroups of 256: wave -> MCU (img, my, mx), live = there is one; lane l owns the
+// 2 x 2 pixel quad (qy, qx) = (l / 8, l % 8) of the MCU on the way in and out, and coefficient / sample (qy, qx) of each 8 x 8 block in between.
+struct McuLane {
+  int wave, lane, qy, qx, img, my, mx;
+  long long per_img;
+  bool live;
+  __device__ __forceinline__ McuLane(int b, int mcus_x, int mcus_y)
+      : wave(threadIdx.x >> 6), lane(threadIdx.x & 63), qy(lane >> 3), qx(lane & 7), img(0), my(0), mx(0), per_img((long long)mcus_x * mcus_y) {
+    const long long mcu = (long long)blockIdx.x * kJpgWaves + wave;
+    live = mcu < b * per_img;
+    if (live) {
+      img = (int)(mcu / per_img);
+      const int rem = (int)(mcu % per_img);
+      my = rem / mcus_x;
+      mx = rem % mcus_x;
+    }
+  }
+  // pixel j = 0 .. 3 of the quad (row-major): its row and column inside the MCU; + 16 * my / mx = in the image padded to whole MCUs
+  __device__ __forceinline__ int quad_y(int j) const { return qy * 2 + (j >> 1); }
+  __device__ __forceinline__ int quad_x(int j) const { return qx * 2 + (j & 1); }
+  // the luma block (raster order, 0..3) that pixel (ly, lx) of the MCU falls in; Cb is block 4, Cr block 5
+  __device__ static __forceinline__ int luma_block(int ly, int lx) { return (ly >> 3) * 2 + (lx >> 3); }
+};
 
 // 13-bit constants of the integer DCT
 #define JF_0_298 2446
@@ -97,51 +130,39 @@ __device__ __forceinline__ void jpeg_idct8(int* p, int stride) {
 
 __device__ __forceinline__ int jpeg_u8(float v) { return (int)rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f); }
 
-// grid: ceil(b * mcus_y * mcus_x / 4) workgroups of 256
 __global__ __launch_bounds__(64 * kJpgWaves) void jpeg_mcu_kernel(const float* __restrict__ src, int b, int h, int w, int mcus_x, int mcus_y,
                                                                   const int* __restrict__ quality, unsigned char* __restrict__ ws) {
   __shared__ int lds[kJpgWaves][6 * kJpgBlock];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long long mcu = (long long)blockIdx.x * kJpgWaves + wave;
-  const int per_img = mcus_x * mcus_y;
-  bool live = mcu < (long long)b * per_img;
-  int img = 0, my = 0, mx = 0, q = 0;
+  const McuLane m(b, mcus_x, mcus_y);
+  const int lane = m.lane, qy = m.qy, qx = m.qx, my = m.my, mx = m.mx;
+  bool live = m.live;
+  int q = 0;
   if (live) {
-    img = (int)(mcu / per_img);
-    const int rem = (int)(mcu - (long long)img * per_img);
-    my = rem / mcus_x;
-    mx = rem - my * mcus_x;
-    q = quality[img];
+    q = quality[m.img];
     live = q != 0;                       // the whole image is copied through by jpeg_finish_kernel
     q = min(max(q, 1), 100);             // as the library clamps it; the host refuses such values where it sees them
   }
-  int* blk = lds[wave];
+  int* blk = lds[m.wave];
   const size_t plane = (size_t)h * w;
-  const float* ps = src + (size_t)img * 3 * plane;
-  const int qy = lane >> 3, qx = lane & 7;
+  const float* ps = src + (size_t)m.img * 3 * plane;
   if (live) {
     // this lane's 2 x 2 quad: luma at the pixel itself (clamped into the image), chroma from the rows the library averages
     const int h2 = (h + 1) >> 1;
     const int cyc = min(my * 8 + qy, h2 - 1);
     int cbs = 0, crs = 0;
 #pragma unroll
-    for (int dy = 0; dy < 2; ++dy) {
-      const int ly = qy * 2 + dy;
-      const int y = min(my * 16 + ly, h - 1), yc = min(2 * cyc + dy, h - 1);
-#pragma unroll
-      for (int dx = 0; dx < 2; ++dx) {
-        const int lx = qx * 2 + dx;
-        const int x = min(mx * 16 + lx, w - 1);
-        size_t o = (size_t)y * w + x;
-        int r = jpeg_u8(ps[o]), g = jpeg_u8(ps[plane + o]), bl = jpeg_u8(ps[2 * plane + o]);
-        blk[((ly >> 3) * 2 + (lx >> 3)) * kJpgBlock + (ly & 7) * kJpgPitch + (lx & 7)] = ((19595 * r + 38470 * g + 7471 * bl + 32768) >> 16) - 128;
-        if (yc != y) {                   // below the last chroma row: its samples repeat that row's
-          o = (size_t)yc * w + x;
-          r = jpeg_u8(ps[o]); g = jpeg_u8(ps[plane + o]); bl = jpeg_u8(ps[2 * plane + o]);
-        }
-        cbs += (-11059 * r - 21709 * g + 32768 * bl + (128 << 16) + 32767) >> 16;
-        crs += (32768 * r - 27439 * g - 5329 * bl + (128 << 16) + 32767) >> 16;
+    for (int j = 0; j < 4; ++j) {
+      const int ly = m.quad_y(j), lx = m.quad_x(j);
+      const int y = min(my * 16 + ly, h - 1), yc = min(2 * cyc + (ly & 1), h - 1), x = min(mx * 16 + lx, w - 1);
+      size_t o = (size_t)y * w + x;
+      int r = jpeg_u8(ps[o]), g = jpeg_u8(ps[plane + o]), bl = jpeg_u8(ps[2 * plane + o]);
+      blk[McuLane::luma_block(ly, lx) * kJpgBlock + (ly & 7) * kJpgPitch + (lx & 7)] = ((19595 * r + 38470 * g + 7471 * bl + 32768) >> 16) - 128;
+      if (yc != y) {                     // below the last chroma row: its samples repeat that row's
+        o = (size_t)yc * w + x;
+        r = jpeg_u8(ps[o]); g = jpeg_u8(ps[plane + o]); bl = jpeg_u8(ps[2 * plane + o]);
       }
+      cbs += (-11059 * r - 21709 * g + 32768 * bl + (128 << 16) + 32767) >> 16;
+      crs += (32768 * r - 27439 * g - 5329 * bl + (128 << 16) + 32767) >> 16;
     }
     const int bias = 1 + (qx & 1);
     blk[4 * kJpgBlock + qy * kJpgPitch + qx] = ((cbs + bias) >> 2) - 128;
@@ -172,10 +193,10 @@ __global__ __launch_bounds__(64 * kJpgWaves) void jpeg_mcu_kernel(const float* _
   __syncthreads();
   if (live) {
     const int hp = mcus_y * 16, wp = mcus_x * 16;
-    unsigned char* base = ws + (size_t)img * per_img * kJpgMcuBytes;
+    unsigned char* base = ws + (size_t)m.img * m.per_img * kJpgMcuBytes;
     {                                    // Y: lane -> row lane / 4, columns 4 * (lane % 4) ..: one 4-byte store
       const int ly = lane >> 2, lx = (lane & 3) * 4;
-      const int* p = blk + ((ly >> 3) * 2 + (lx >> 3)) * kJpgBlock + (ly & 7) * kJpgPitch + (lx & 7);
+      const int* p = blk + McuLane::luma_block(ly, lx) * kJpgBlock + (ly & 7) * kJpgPitch + (lx & 7);
       const unsigned v = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24);
       *(unsigned*)(base + (size_t)(my * 16 + ly) * wp + mx * 16 + lx) = v;
     }
@@ -252,11 +273,169 @@ extern "C" int srganfd_jpeg_roundtrip(const float* src, int32_t b, int32_t c, in
   const int mcus_x = ceil_div(w, 16), mcus_y = ceil_div(h, 16);
   const long long total = (long long)b * mcus_x * mcus_y;
   if ((total + kJpgWaves - 1) / kJpgWaves > 0x7fffffffLL) return set_err(SRGANFD_EINVAL, "jpeg_roundtrip: %lld MCUs exceed the grid", total);
-  const size_t pixels = (size_t)b * h * w, blocks = (pixels + 255) / 256;
   SRGANFD_LAUNCH(jpeg_mcu_kernel, dim3((unsigned)((total + kJpgWaves - 1) / kJpgWaves)), dim3(64 * kJpgWaves), 0, s, src, b, h, w, mcus_x, mcus_y,
                  quality, (unsigned char*)workspace);
-  SRGANFD_LAUNCH(jpeg_finish_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, src, b, h, w, mcus_x, mcus_y, quality,
+  SRGANFD_LAUNCH(jpeg_finish_kernel, dim3(grid_for((size_t)b * h * w, 256, 65536)), dim3(256), 0, s, src, b, h, w, mcus_x, mcus_y, quality,
                  (const unsigned char*)workspace, dst);
+  SRGANFD_HIP_CHECK(hipGetLastError());
+  return SRGANFD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// DiffJPEG (imgproc.py:1198-1497): x255, RGB -> YCbCr, 2x2 chroma average, per 8x8 block DCT -> divide by
+// table * factor -> round (or the cubic "differentiable" rounding, :1183-1195) -> multiply back -> inverse DCT, chroma
+// repeat, YCbCr -> RGB, clamp to [0, 255], /255; the image is zero-padded to multiples of 16 and cropped back
+// (:1482-1495).  The wavefront owns its MCU from load to store; nothing but the RGB input and output touches HBM.
+// The 4-D cosine tensors are the reference's fp32 products (:1250-1252, :1366-1368), summed over all 64 terms like its tensordot.
+// tables: [dct 4096 | idct 4096 | dct scale 64 | idct alpha 64 | y_table 64 | c_table 64] floats.
+// ---------------------------------------------------------------------------------------------------------------
+static constexpr int kJpegTableFloats = 4096 * 2 + 64 * 4;
+extern "C" int32_t srganfd_diff_jpeg_table_floats(void) { return kJpegTableFloats; }
+
+static void diff_jpeg_tables_host(float* t) {
+  const double pi = 3.14159265358979323846;
+  float* dct = t;
+  float* idct = t + 4096;
+  float* scale = t + 8192;
+  float* alpha = scale + 64;
+  float* ytab = alpha + 64;
+  float* ctab = ytab + 64;
+  for (int x = 0; x < 8; ++x)
+    for (int y = 0; y < 8; ++y)
+      for (int u = 0; u < 8; ++u)
+        for (int v = 0; v < 8; ++v) {
+          dct[((x * 8 + y) * 8 + u) * 8 + v] = (float)(cos((2 * x + 1) * u * pi / 16) * cos((2 * y + 1) * v * pi / 16));
+          idct[((x * 8 + y) * 8 + u) * 8 + v] = (float)(cos((2 * u + 1) * x * pi / 16) * cos((2 * v + 1) * y * pi / 16));
+        }
+  for (int u = 0; u < 8; ++u)
+    for (int v = 0; v < 8; ++v) {
+      const double au = u == 0 ? 1.0 / sqrt(2.0) : 1.0, av = v == 0 ? 1.0 / sqrt(2.0) : 1.0;
+      scale[u * 8 + v] = (float)(au * av * 0.25);
+      alpha[u * 8 + v] = (float)(au * av);
+      ytab[u * 8 + v] = kJpgLuma[v * 8 + u];                                 // the reference transposes the standard tables (:43-48)
+      ctab[u * 8 + v] = kJpgChroma[v * 8 + u];
+    }
+}
+extern "C" int srganfd_diff_jpeg_tables(float* host_out) {
+  if (!host_out) return set_err(SRGANFD_EINVAL, "diff_jpeg_tables: null output");
+  diff_jpeg_tables_host(host_out);
+  return SRGANFD_OK;
+}
+
+__global__ __launch_bounds__(64 * kJpgWaves) void diff_jpeg_kernel(const float* __restrict__ src, int b, int h, int w, int mcus_x, int mcus_y,
+                                                                   const float* __restrict__ factor, int differentiable,
+                                                                   const float* __restrict__ tables, float* __restrict__ dst) {
+  __shared__ float sp_all[kJpgWaves][384], cf_all[kJpgWaves][384];
+  const McuLane m(b, mcus_x, mcus_y);
+  const int lane = m.lane, qy = m.qy, qx = m.qx;
+  float* sp = sp_all[m.wave];
+  float* cf = cf_all[m.wave];
+  const float* dct = tables;
+  const float* idct = tables + 4096;
+  const float* scale = tables + 8192;
+  const float* alpha = scale + 64;
+  const float* ytab = alpha + 64;
+  const float* ctab = ytab + 64;
+  const size_t plane = (size_t)h * w;
+  const float* ps = src + (size_t)m.img * 3 * plane;
+  // ---- load the quad, x255, RGB -> YCbCr (tensordot with the transposed matrix + shift, :1201-1212), chroma average (:1219-1226)
+  {
+    float cbs = 0.f, crs = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int ly = m.quad_y(j), lx = m.quad_x(j), y = m.my * 16 + ly, x = m.mx * 16 + lx;
+      float r = 0.f, g = 0.f, bl = 0.f;
+      if (m.live && y < h && x < w) {
+        const size_t o = (size_t)y * w + x;
+        r = ps[o] * 255.f; g = ps[plane + o] * 255.f; bl = ps[2 * plane + o] * 255.f;
+      }
+      float yy = r * 0.299f; yy = fmaf(g, 0.587f, yy); yy = fmaf(bl, 0.114f, yy);
+      float cb = r * -0.168736f; cb = fmaf(g, -0.331264f, cb); cb = fmaf(bl, 0.5f, cb); cb += 128.f;
+      float cr = r * 0.5f; cr = fmaf(g, -0.418688f, cr); cr = fmaf(bl, -0.081312f, cr); cr += 128.f;
+      sp[ly * 16 + lx] = yy;
+      cbs += cb; crs += cr;
+    }
+    sp[256 + qy * 8 + qx] = cbs * 0.25f;
+    sp[320 + qy * 8 + qx] = crs * 0.25f;
+  }
+  __syncthreads();
+  const float f = m.live ? factor[m.img] : 1.f;
+  // ---- forward DCT of the six blocks, quantise, round, de-quantise, x alpha (:1254-1259, :1270-1278, :1183-1195, :1333-1340, :1371)
+  {
+#pragma unroll 1
+    for (int blk = 0; blk < 6; ++blk) {
+      const float* xb = blk < 4 ? sp + ((blk >> 1) * 8) * 16 + (blk & 1) * 8 : sp + 256 + (blk - 4) * 64;
+      const int pitch = blk < 4 ? 16 : 8;
+      float acc = 0.f;
+#pragma unroll
+      for (int x = 0; x < 8; ++x)
+#pragma unroll
+        for (int y = 0; y < 8; ++y) acc = fmaf(xb[x * pitch + y] - 128.f, dct[(x * 8 + y) * 64 + lane], acc);
+      const float coef = scale[lane] * acc;
+      const float tab = (blk < 4 ? ytab[lane] : ctab[lane]) * f;
+      const float q = coef / tab;
+      float rq = rintf(q);                                        // torch.round: half to even
+      if (differentiable) { const float d = q - rq; rq = rq + d * d * d; }
+      cf[blk * 64 + qy * 8 + qx] = (rq * tab) * alpha[lane];
+    }
+  }
+  __syncthreads();
+  // ---- inverse DCT (:1370-1374): pixel (qy, qx) of each block = 0.25 * sum_uv X[u,v] * idct[u,v,qy,qx] + 128
+  {
+#pragma unroll 1
+    for (int blk = 0; blk < 6; ++blk) {
+      const float* xb = cf + blk * 64;
+      float acc = 0.f;
+#pragma unroll
+      for (int i = 0; i < 64; ++i) acc = fmaf(xb[i], idct[i * 64 + lane], acc);
+      const float pv = 0.25f * acc + 128.f;
+      if (blk < 4) sp[((blk >> 1) * 8 + qy) * 16 + (blk & 1) * 8 + qx] = pv;
+      else sp[256 + (blk - 4) * 64 + qy * 8 + qx] = pv;
+    }
+  }
+  __syncthreads();
+  // ---- chroma repeat (:1396-1407), YCbCr -> RGB (:1414-1424), clamp and /255 (:1459-1460), crop (:1495)
+  if (m.live) {
+    const float cb = sp[256 + qy * 8 + qx] - 128.f, cr = sp[320 + qy * 8 + qx] - 128.f;
+    float* pd = dst + (size_t)m.img * 3 * plane;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int ly = m.quad_y(j), lx = m.quad_x(j), y = m.my * 16 + ly, x = m.mx * 16 + lx;
+      if (y < h && x < w) {
+        const float yy = sp[ly * 16 + lx];
+        float r = yy * 1.f; r = fmaf(cb, 0.f, r); r = fmaf(cr, 1.402f, r);
+        float g = yy * 1.f; g = fmaf(cb, -0.344136f, g); g = fmaf(cr, -0.714136f, g);
+        float bl = yy * 1.f; bl = fmaf(cb, 1.772f, bl); bl = fmaf(cr, 0.f, bl);
+        const size_t o = (size_t)y * w + x;
+        pd[o] = fminf(255.f, fmaxf(0.f, r)) / 255.f;
+        pd[plane + o] = fminf(255.f, fmaxf(0.f, g)) / 255.f;
+        pd[2 * plane + o] = fminf(255.f, fmaxf(0.f, bl)) / 255.f;
+      }
+    }
+  }
+}
+
+// quality -> factor in place, as DiffJPEG.forward does on the tensor it is given (:1476-1480, :1127-1144)
+__global__ void jpeg_quality_factor_kernel(float* q, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const float v = q[i];
+    const float t = v < 50.f ? 5000.f / v : 200.f - v * 2.f;
+    q[i] = t / 100.f;
+  }
+}
+
+extern "C" int srganfd_diff_jpeg(const float* src, int32_t b, int32_t c, int32_t h, int32_t w, float* quality, int32_t quality_is_factor,
+                                 int32_t differentiable, const float* tables, float* dst, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
+  if (!src || !dst || !quality || !tables || b <= 0 || h <= 0 || w <= 0) return refuse_empty("diff_jpeg");
+  if (c != 3) return set_err(SRGANFD_EINVAL, "diff_jpeg: needs 3-channel RGB input, got %d channels", c);
+  const int mcus_x = ceil_div(w, 16), mcus_y = ceil_div(h, 16);
+  const long long total = (long long)b * mcus_x * mcus_y;
+  if (total > (1ll << 32)) return set_err(SRGANFD_EINVAL, "diff_jpeg: too many blocks");
+  if (!quality_is_factor) SRGANFD_LAUNCH(jpeg_quality_factor_kernel, dim3(ceil_div(b, 256)), dim3(256), 0, s, quality, b);
+  SRGANFD_LAUNCH(diff_jpeg_kernel, dim3((unsigned)((total + kJpgWaves - 1) / kJpgWaves)), dim3(64 * kJpgWaves), 0, s, src, b, h, w, mcus_x, mcus_y,
+                 (const float*)quality, differentiable, tables, dst);
   SRGANFD_HIP_CHECK(hipGetLastError());
   return SRGANFD_OK;
 }

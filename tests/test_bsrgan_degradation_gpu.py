@@ -1,4 +1,4 @@
-"""BSRGAN's blind degradation on the GPU (sr_gan_fd_amd/csrc/jpeg.hip, blur_f64.hip, imgproc.degradation_process_bsrgan and the prefetcher's
+"""BSRGAN's blind degradation on the GPU (sr_gan_fd_amd/csrc/jpeg.hip, filter2d.hip, imgproc.degradation_process_bsrgan and the prefetcher's
 ``synthesize_lr_bsrgan``) against the reference's recorded results (tests/golden/bsrgan_degradation.npz) and the numpy oracles of
 tests/jpeg_oracle.py and tests/bsrgan_degradation_oracle.py.  Needs numpy and the fixture only.
 

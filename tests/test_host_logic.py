@@ -445,6 +445,24 @@ def test_validation_side_argument_checks():
         A.set_dry_run(False)
 
 
+def test_diff_jpeg_tables_are_the_oracles_standard_tables_transposed():
+    """csrc/jpeg.hip keeps one copy of the standard quantisation tables for both round trips: what srganfd_diff_jpeg_tables derives from it
+    for DiffJPEG (the reference transposes them) is tests/jpeg_oracle.py's copy, which the integer round trip is tested against"""
+    import numpy as np
+    from sr_gan_fd_amd import _abi as A
+    from tests import jpeg_oracle as JO
+    A.set_dry_run(True)
+    try:
+        L = A.lib()
+        t = np.zeros(L.srganfd_diff_jpeg_table_floats(), dtype=np.float32)
+        assert L.srganfd_diff_jpeg_tables(t.ctypes.data) == 0
+        y, c = t[8192 + 128:8192 + 192].reshape(8, 8), t[8192 + 192:8192 + 256].reshape(8, 8)
+        assert np.array_equal(y, JO.LUMA.T.astype(np.float32)) and np.array_equal(c, JO.CHROMA.T.astype(np.float32))
+        assert L.srganfd_diff_jpeg_tables(None) != 0
+    finally:
+        A.set_dry_run(False)
+
+
 def test_modules_deepcopy_and_pickle_like_the_train_scripts_do():
     """AveragedModel deep-copies the generator (train_bsrgan.py:291) and mlflow.pytorch.log_model pickles both networks
     (:203-213): copies must carry the same state_dict, own their parameters, and still run"""

@@ -5,6 +5,8 @@ the comparison is bench.py's cpu_baseline leg of `--workload realesrgan_gan`; th
 
     python tools/degrade_bench.py [--batch 48] [--size 256] [--iters 20]
     python tools/degrade_bench.py --bsrgan [--batch 32] [--size 512] [--iters 20]
+    python tools/degrade_bench.py --digest      one sha1 per entry point on seeded inputs; run once per build (SRGANFD_LIB=<other build>, a fresh
+                                                process each) and compare the lines: equal bits iff all agree
 
 --bsrgan: BSRGAN's blind degradation (imgproc.degradation_process_bsrgan) at the headline shape (batch 32, 3x512x512 GT, factor 4): the
 whole call on fresh draws (host clock around a device synchronise: the draws and the kernel synthesis on the host are part of it), its two
@@ -131,13 +133,86 @@ def bsrgan(a):
          "ms per batch": round(t_cpu * b * 1e3, 1), "host / device": round(t_cpu * b / t_all, 1)})
 
 
+def digests():
+    """one sha1 per entry point of csrc/filter2d.hip, jpeg.hip and degrade.hip on seeded inputs, at every size where a kernel takes another
+    path (ragged tiles, the mirror limit, a dead wave, a copied-through image): two builds compute the same bits iff every line agrees"""
+    from tools.ewbench import digest
+    imgproc = importlib.import_module("sr_gan_fd_amd.imgproc")
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0)
+    rand = lambda *s, dtype=torch.float32: torch.rand(*s, device="cuda", generator=gen, dtype=dtype)
+    randn = lambda *s: torch.randn(*s, device="cuda", generator=gen)
+
+    def row(name, *outs):
+        torch.cuda.synchronize()
+        print(f"{name:58s} " + " ".join(digest(o) for o in outs), flush=True)
+
+    def kernels(n, k, dtype=torch.float32):
+        kk = rand(n, k, k, dtype=dtype)
+        return kk / kk.sum(dim=(1, 2), keepdim=True)
+    for h, w, ks in ((32, 64, (3, 21, 51)), (33, 65, (3, 21, 51)), (100, 130, (3, 21, 51)), (27, 26, (51,))):
+        x = rand(2, 3, h, w)
+        for k in ks:
+            row(f"filter2d {h}x{w} k={k} shared / per-image", imgproc.filter2d_torch(x, kernels(1, k)), imgproc.filter2d_torch(x, kernels(2, k)))
+    x, taps = rand(2, 3, 50, 90), rand(2, 18)
+    out = torch.empty_like(x)
+    A = importlib.import_module("sr_gan_fd_amd._abi")
+    A.check(A.lib().srganfd_filter2d_separable(x.data_ptr(), taps.data_ptr(), 2, 2, 3, 50, 90, 9, out.data_ptr(), A.stream_ptr()), "filter2d_separable")
+    row("filter2d_separable 50x90 per-image 9 taps", out)
+    usm, usm_full = imgproc.USMSharp().cuda(), imgproc.USMSharp().cuda()
+    usm_full.kernel.copy_(kernels(1, 51))                                    # not an outer product: the rank-51 path
+    for n in (64, 256):
+        x = rand(2, 3, n, n)
+        row(f"usm_sharp {n}x{n} separable / rank-51", usm(x, 0.5, 10), usm_full(x, 0.5, 10))
+    for h, w in ((33, 65), (512, 512)):
+        k25 = torch.zeros(3, 25, 25, device="cuda", dtype=torch.float64)
+        k25[1, 9:16, 9:16], k25[2] = kernels(1, 7, torch.float64)[0], kernels(1, 25, torch.float64)[0]
+        row(f"filter2d_mirror_f64 {h}x{w} k = 0 / 7 / 25", imgproc.filter2d_mirror_f64(rand(3, 3, h, w), k25, [0, 7, 25]))
+    jpeg, jpeg_d = imgproc.DiffJPEG().cuda(), imgproc.DiffJPEG(differentiable=True).cuda()
+    for b, h, w in ((1, 16, 16), (1, 17, 15), (1, 130, 33), (3, 16, 16), (48, 256, 256)):
+        x = rand(b, 3, h, w)
+        q = rand(b) * 65 + 30
+        row(f"diff_jpeg {b}x3x{h}x{w} round / cubic", jpeg(x, q.clone()), jpeg_d(x, q.clone()))
+        row(f"jpeg_roundtrip {b}x3x{h}x{w} q = 1 / 50 / 100", *[imgproc.jpeg_compression(x, q) for q in (1, 50, 100)])
+        if b == 3:
+            row(f"jpeg_roundtrip {b}x3x{h}x{w} q = 40, 0, 90", imgproc.jpeg_compression(x, [40, 0, 90]))
+    x = rand(4, 3, 100, 130) * 1.2 - 0.1
+    row("quantize_u8", imgproc.quantize_u8(x))
+    for mode in ("area", "bilinear", "bicubic"):
+        row(f"resize {mode} x1.37 / x0.41 / -> 64x48", imgproc.interpolate(x, scale_factor=1.37, mode=mode), imgproc.interpolate(x, scale_factor=0.41, mode=mode),
+            imgproc.interpolate(x, size=(64, 48), mode=mode))
+    sigma, gray = rand(4) * 30, torch.tensor([0., 1., 0., 1.], device="cuda")
+    n_color, n_gray = randn(4, 3, 100, 130), randn(100, 130)
+    row("gaussian_noise colour / grey", imgproc.gaussian_noise_apply(x, n_color, None, sigma, gray, False, False),
+        imgproc.gaussian_noise_apply(x, n_color, n_gray, sigma, gray, False, False))
+    row("gaussian_noise clip x rounds", *[imgproc.gaussian_noise_apply(x, n_color, n_gray, sigma, gray, c, r) for c in (False, True) for r in (False, True)])
+    for want_gray in (False, True):
+        img_q, gray_q, vals, vals_gray = imgproc.poisson_noise_prepare(x, want_gray)
+        row(f"poisson_prepare grey = {want_gray}", *[t for t in (img_q, gray_q, vals, vals_gray) if t is not None])
+        pois = torch.floor(img_q * vals.view(4, 1, 1, 1) + randn(4, 3, 100, 130))             # any draw does: the apply stage is deterministic
+        pois_g = torch.floor(gray_q * vals_gray.view(4, 1, 1, 1) + randn(4, 1, 100, 130)) if want_gray else None
+        row(f"poisson_apply grey = {want_gray} clip x rounds", *[imgproc.poisson_noise_apply(x, img_q, gray_q, pois, pois_g, vals, vals_gray, sigma / 10,
+                                                                                            gray if want_gray else None, c, r) for c in (False, True) for r in (False, True)])
+    sq = rand(2, 3, 96, 96)
+    row("crop_rot_flip ops 0 .. 5", *[imgproc._crop_rot_flip(sq, 5, 7, 64, 64, op) for op in range(6)])
+    gt, k21 = rand(4, 3, 256, 256), kernels(4, 21)
+    torch.manual_seed(0); random.seed(0); np.random.seed(0)
+    imgproc.DRAW_DEVICE = "cpu"                                              # the draws come from the seeded host generators: the same on every build
+    row("degradation_process (seeded draws)", *imgproc.degradation_process(gt, k21, k21, k21, 4, PARAMS, jpeg, usm))
+    draws = imgproc.bsrgan_degradation_draws(4, 4)
+    row("degradation_process_bsrgan (recorded draws)", imgproc.degradation_process_bsrgan(gt, 4, draws=draws))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--size", type=int, default=None)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--bsrgan", action="store_true")
+    ap.add_argument("--digest", action="store_true")
     a = ap.parse_args()
+    if a.digest:
+        return digests()
     if a.bsrgan:
         return bsrgan(a)
     a.batch, a.size = a.batch or 48, a.size or 256

@@ -1,4 +1,4 @@
-"""Device assembly of wgrad.hip, dense_chain.hip, conv_thin.hip, resample.hip or the view kernels' files, one tree against another, per kernel (the method of
+"""Device assembly of wgrad.hip, dense_chain.hip, conv_thin.hip, resample.hip, the view kernels' or the degradation kernels' files, one tree against another, per kernel (the method of
 profiles/conv_igemm_refactor_isa.txt).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I. --offload-device-only -S -o parent.s <parent>/wgrad.hip      (same for the branch)
@@ -8,6 +8,8 @@ profiles/conv_igemm_refactor_isa.txt).
     python tools/wgrad_isa_compare.py --kernel resample parent.s branch.s > profiles/resample_refactor_isa.txt
     cat <parent>/{elementwise,loss,layout,norm,resample}.s > parent.s  (same for the branch)
     python tools/wgrad_isa_compare.py --kernel views parent.s branch.s > profiles/view_kernels_refactor_isa.txt
+    cat <parent>/{degrade,blur_f64,jpeg}.s > parent.s ; cat <branch>/{degrade,filter2d,jpeg}.s > branch.s
+    python tools/wgrad_isa_compare.py --kernel degrade parent.s branch.s > profiles/degrade_refactor_isa.txt
 
 wgrad kernels are matched by template arguments <T, KS, STRIDE, XP, YP, DMA>; a seventh argument (the parent's VAR) is dropped;
 dense-chain kernels by <T, RPW>; the thin-side kernels by <T, MASK, NT> (thin_in) and <T> (thin_out, thin_wgrad), the slab reduction by
@@ -20,6 +22,9 @@ whose labels are those of --kernel resample) matches the scalar / vector pairs o
 x_kernel<T, N>, the three per-pixel RGB kernels to rgb_to_nhwc_kernel<T, CLAMP, WIDE>, the four one-block sums to finish_kernel<E>, and
 every other kernel by name and element type, whatever its arguments became; scalar forms are reported, axpby_kernel<f32, scalar> aside
 (the trainers run it); an s_waitcnt count that moved is listed, and fails only if the waits on vector memory (vmcnt) moved.
+--kernel degrade (degrade.hip, filter2d.hip / blur_f64.hip, jpeg.hip) matches kernels by name and template arguments, which the refactor kept.
+Held per kernel: LDS bytes, no scratch, the counts of global loads, global stores, LDS reads, LDS writes and barriers, the waves-per-SIMD step
+of the VGPR count; scalar loads and s_waitcnt are counted and listed where they moved, not held.
 A working tool, not a test."""
 import collections
 import re
@@ -77,6 +82,11 @@ def views_label(sym):
 TYPES = {"t": "bf16", "DF16_": "f16", "f": "f32"}
 CLASSES = [("mfma", r"v_mfma"), ("lds", r"ds_"), ("global", r"(global|flat|scratch)_"), ("buffer", r"buffer_"), ("s_waitcnt", r"s_waitcnt"),
            ("s_barrier", r"s_barrier")]
+DEGRADE_CLASSES = [("global load", r"(global|flat)_load"), ("global store", r"(global|flat)_store"), ("global atomic", r"(global|flat)_atomic"),
+                   ("lds read", r"ds_read"), ("lds write", r"ds_write"), ("lds other", r"ds_"), ("scratch", r"scratch_"), ("scalar load", r"s_load|s_buffer_load"),
+                   ("s_waitcnt", r"s_waitcnt"), ("s_barrier", r"s_barrier")]
+DEGRADE_NAME = re.compile(r"_ZN7srganfd\d+?([a-z][a-z0-9_]*_kernel)(?:I((?:L[ib]\d+E)+)E)?E")
+LISTED = []                                         # classes that are counted and listed where they moved, not held
 AT_MOST = []                                        # classes whose count may fall but not rise
 WAVE_STEPS = [64, 72, 80, 96, 128, 168, 256, 512]   # VGPRs per lane at which one more wave per SIMD is lost (512 registers, granule 8)
 
@@ -96,6 +106,10 @@ def label(sym):
             return fmt(m.groups()), None
     if VIEWS and views_label(sym):
         return views_label(sym), None
+    if LISTED and DEGRADE_NAME.match(sym):
+        name, args = DEGRADE_NAME.match(sym).groups()
+        vals = ["true" if k == "b" and v == "1" else "false" if k == "b" else v for k, v in re.findall(r"L([ib])(\d+)E", args or "")]
+        return name + ("<%s>" % ", ".join(vals) if vals else ""), None
     m = DC_NAME.search(sym)
     if m:
         return "dense_chain_kernel<%s, RPW=%s>" % (TYPES[m.group(1)], m.group(2)), None
@@ -165,8 +179,11 @@ def main():
         elif argv[1] == "views":
             global VIEWS
             VIEWS = True
+        elif argv[1] == "degrade":
+            CLASSES[:] = DEGRADE_CLASSES
+            LISTED.extend(["scalar load", "s_waitcnt"])
         elif argv[1] not in ("wgrad", "resample"):
-            sys.exit("--kernel: wgrad, dense_chain, thin, resample or views, not %r" % argv[1])
+            sys.exit("--kernel: wgrad, dense_chain, thin, resample, views or degrade, not %r" % argv[1])
         argv = argv[2:]
     P, B = parse(argv[0]), parse(argv[1])
     only_p, only_b = sorted(set(P) - set(B)), sorted(set(B) - set(P))
@@ -196,8 +213,12 @@ def main():
         waits_moved = VIEWS and cp["s_waitcnt"] != cb["s_waitcnt"] and wv[0] == wv[1]      # scalar (kernel-argument) waits alone: listed
         if report_only(n):
             print("    a scalar form: reported, not held to the parent's counts")
-        elif any(cb[k] > cp[k] if k in AT_MOST else cb[k] != cp[k] for k in cp if not (waits_moved and k == "s_waitcnt")):
+        elif any(cb[k] > cp[k] if k in AT_MOST else cb[k] != cp[k] for k in cp if not (waits_moved and k == "s_waitcnt") and k not in LISTED):
             bad.append(n + ": instruction-class counts differ")
+        if LISTED:
+            if p["meta"][".amdhsa_group_segment_fixed_size"] != b["meta"][".amdhsa_group_segment_fixed_size"]:
+                bad.append(n + ": LDS bytes differ")
+            moved.extend("%s: %s %d -> %d" % (n, k, cp[k], cb[k]) for k in LISTED if cp[k] != cb[k])
         if waits_moved and not report_only(n):
             moved.append("%s: s_waitcnt %d -> %d, those on vector memory %d on both sides" % (n, cp["s_waitcnt"], cb["s_waitcnt"], wv[0]))
         if sb > sp:
@@ -215,6 +236,10 @@ def main():
             op, ob = collections.Counter(o.split()[0] for o in p["ops"]), collections.Counter(o.split()[0] for o in b["ops"])
             print("    per opcode (differing only): " + ", ".join("%s %d|%d" % (k, op[k], ob[k]) for k in sorted(set(op) | set(ob)) if op[k] != ob[k]))
     print("# identical streams: %d of %d; identical metadata (kernarg size aside): %d of %d" % (n_same, len(set(P) & set(B)), n_meta, len(set(P) & set(B))))
+    if LISTED:
+        print("# scalar-load and s_waitcnt counts that moved (listed, not held): %d" % len(moved))
+        for x in moved:
+            print("#   " + x)
     if VIEWS:
         print("# s_waitcnt counts that moved with the kernel-argument layout (waits on vector memory equal): %d" % len(moved))
         for x in moved:
