@@ -57,42 +57,34 @@ class AttentionEngine(EngineBase):
         return pb.finish(device)
 
     # ---- per-shape plan: always with its backward list ----
-    def _plan(self, N: int, H: int, W: int, dt, dtc: int, device, pk: dict, train: bool = True) -> _Shape:
-        key = (N, H, W, dtc, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
-        sp = self.shapes.get(key)
-        if sp is not None:
-            return sp
-        sp = _Shape()
-        sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
-        sp.hs, sp.ws = H, W
-        C, L = self.C, H * W
-        V = A.view
-        fptr, wptr, O = self.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
-        P = lambda name: fptr + 4 * self._poff(name)
-        cv = lambda x, y, key, cin, cout, **kw: ops.Conv(ops.conv_args(dtc, V(x), V(y), wptr + O[key], N, H, W, cin, cout, ksize=1, pad=0, **kw))
-        aa = lambda **kw: ops.attn_args(dtc, N, L, self.heads, self.D, qkv=sp.qkv, lse=sp.lse, **kw)
+    always_backward = True
 
-        def new(c, dtype=dt):
-            return torch.empty(N, H, W, c, dtype=dtype, device=device)
-        sp.xin, sp.qkv, sp.att, sp.y = new(C), new(3 * C), new(C), new(C, torch.float32)
-        sp.lse = torch.empty(N, self.heads, L, dtype=torch.float32, device=device)
-        sp.x_in, sp.result, sp.per_call = (V(sp.xin), C), (V(sp.y), A.F32, 0), (N, L, L)
+    def _attn_args(self, sp: _Shape, **kw):
+        return ops.attn_args(sp.dtc, sp.N, sp.H * sp.W, self.heads, self.D, qkv=sp.qkv, lse=sp.lse, **kw)
+
+    def _plan_forward(self, sp: _Shape, b: ops.PlanBuilder, train: bool) -> None:
+        N, H, W, C, V = sp.N, sp.H, sp.W, self.C, A.view
+        sp.hs, sp.ws = H, W
+        one = dict(ksize=1, pad=0)
+        sp.xin, sp.qkv, sp.att, sp.y = b.act(H, W, C), b.act(H, W, 3 * C), b.act(H, W, C), b.act(H, W, C, dtype=torch.float32)
+        sp.lse = b.buf(N, self.heads, H * W, dtype=torch.float32)
+        sp.x_in, sp.result, sp.per_call = (V(sp.xin), C), (V(sp.y), A.F32, 0), (N, H * W, H * W)
         # the weights result is the pass's own tensor: a forward that does not want it skips the launch
-        sp.fw = [cv(sp.xin, sp.qkv, ("f", "in"), C, 3 * C, bias=P(IN_B)), ops.Attention("fwd", aa(out=sp.att)), ops.PerCall(ops.Attention("weights", aa())),
-                 cv(sp.att, sp.y, ("f", "out"), C, C, bias=P(OUT_B), y_f32=True)]
-        # backward
-        sp.dy, sp.datt, sp.dqkv, sp.dxp = new(C), new(C), new(3 * C), new(C, torch.float32)
+        sp.fw = [b.conv(sp.xin, sp.qkv, ("f", "in"), H, W, C, 3 * C, bias=b.P(IN_B), **one), ops.Attention("fwd", self._attn_args(sp, out=sp.att)),
+                 ops.PerCall(ops.Attention("weights", self._attn_args(sp))),
+                 b.conv(sp.att, sp.y, ("f", "out"), H, W, C, C, bias=b.P(OUT_B), y_f32=True, **one)]
+
+    def _plan_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        H, W, C, V = sp.H, sp.W, self.C, A.view
+        one = dict(ksize=1, pad=0)
+        sp.dy, sp.datt, sp.dqkv, sp.dxp = b.act(H, W, C), b.act(H, W, C), b.act(H, W, 3 * C), b.act(H, W, C, dtype=torch.float32)
         sp.dy_in, sp.dx_out = (V(sp.dy), C), (V(sp.dxp), A.F32)
-        wplans = ops.WgradPlans(device, dtc, N)
-        wg = lambda x, dy, cout, w, b: ops.Wgrad(wplans.conv(H, W, C, cout, self._poff(w), self._poff(b), ksize=1, pad=0), V(x), V(dy))
         bwd = dict(out=sp.att, d_out=sp.datt, d_qkv=sp.dqkv)
-        sp.attn_ws = torch.empty(ops.attention_workspace_bytes(aa(**bwd)), dtype=torch.uint8, device=device)
-        sp.bw = [wg(sp.att, sp.dy, C, OUT_W, OUT_B), cv(sp.dy, sp.datt, ("b", "out"), C, C), ops.Attention("bwd", aa(workspace=sp.attn_ws, **bwd)),
-                 wg(sp.xin, sp.dqkv, 3 * C, IN_W, IN_B)]
-        sp.dx_conv = cv(sp.dqkv, sp.dxp, ("b", "in"), 3 * C, C, y_f32=True)
-        sp.wg_ws = wplans.workspace()
-        self.shapes[key] = sp
-        return sp
+        sp.attn_ws = b.buf(ops.attention_workspace_bytes(self._attn_args(sp, **bwd)), dtype=torch.uint8)
+        sp.bw = [b.wgrad(sp.att, sp.dy, H, W, C, C, OUT_W, OUT_B, **one), b.dgrad(sp.dy, sp.datt, ("b", "out"), H, W, C, C, **one),
+                 ops.Attention("bwd", self._attn_args(sp, workspace=sp.attn_ws, **bwd)), b.wgrad(sp.xin, sp.dqkv, H, W, C, 3 * C, IN_W, IN_B, **one)]
+        sp.dx_conv = b.dgrad(sp.dqkv, sp.dxp, ("b", "in"), H, W, 3 * C, C, y_f32=True, **one)
+        sp.wg_ws = b.wplans.workspace()
 
     def forward(self, x: Tensor, need_weights: bool) -> Tuple[Tensor, Optional[Tensor]]:
         """(attn_output (b, c, h, w), attn_output_weights (b, h*w, h*w) or None)"""

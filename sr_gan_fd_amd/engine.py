@@ -193,8 +193,9 @@ class EngineBase:
     dtype (built by the subclass's ``_build_pack``), the token that ties a backward pass to its forward, and the one forward and
     backward pass over a plan's launch lists.
 
-    A subclass describes its network -- ``_build_pack`` and ``_plan(N, H, W, dt, dtc, device, pk, train)`` -- and names its
-    ``what`` (the reference class, for messages), ``in_ch`` and ``out_ch``.  What differs between the engines at the boundary of a
+    A subclass describes its network -- ``_build_pack`` and the two halves of a plan, ``_plan_forward(sp, b, train)`` and
+    ``_plan_backward(sp, b)`` (``b``: the plan's ops.PlanBuilder), which ``_plan`` calls for a shape it has no plan for yet -- and
+    names its ``what`` (the reference class, for messages), ``in_ch`` and ``out_ch``.  What differs between the engines at the boundary of a
     pass is data on the plan ``sp`` (items: ops.py's, each with ``launch(run)``):
       sp.fw                  forward items
       sp.x_in                (view, pitch): where the NCHW input goes as NHWC, in_ch real channels of ``pitch`` written
@@ -214,6 +215,8 @@ class EngineBase:
     what = "engine"
     unshuffle = 1                      # PixelUnshuffle factor in front of the first layer (Real-ESRGAN's generator below x4)
     batch_stats = False                # BatchNorm layers: backward needs the batch statistics of a training-mode forward
+    always_backward = False            # True: every plan carries a backward list, is not keyed on ``train`` and is never pinned
+    conv_batch = None                  # the batch of the plan's conv launches where it is not the plan's N (ops.PlanBuilder's ``n``)
 
     def __init__(self, owner: nn.Module, named_params: Sequence[Tuple[str, nn.Parameter]]):
         self.owner = owner
@@ -241,6 +244,26 @@ class EngineBase:
         if self.fp.stale(pk):
             pk["table"].run(self.fp.flat, pk["buf"])
         return pk
+
+    # -- per-shape plan -----------------------------------------------------------------------
+    def _plan_key(self) -> tuple:
+        """what a plan depends on besides shape, dtype, buffers and ``train``"""
+        return ()
+
+    def _plan(self, N: int, H: int, W: int, dt: torch.dtype, dtc: int, device, pk: dict, train: bool) -> _Shape:
+        train = train or self.always_backward
+        # the launch lists bake absolute pointers into the packed buffer AND the flat parameter buffer (biases): both are in the key
+        key = (N, H, W, dtc) + (() if self.always_backward else (train,)) + (str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr()) + self._plan_key()
+        sp = self.shapes.get(key)
+        if sp is None:
+            sp = _Shape()
+            sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
+            b = ops.PlanBuilder(self, sp, pk, n=self.conv_batch)
+            self._plan_forward(sp, b, train)
+            if train:
+                self._plan_backward(sp, b)
+            self.shapes.put(key, sp, pinned=train and not self.always_backward)
+        return sp
 
     # -- execution ----------------------------------------------------------------------------
     def _check_input(self, x: Tensor) -> Tuple[int, int, int]:
@@ -405,28 +428,16 @@ class TrunkEngine(EngineBase):
         return pb.finish(device)
 
     # -- per-shape plan -----------------------------------------------------------------------
-    def _plan(self, N: int, H: int, W: int, dt: torch.dtype, dtc: int, device, pk: dict, train: bool) -> _Shape:
-        # the launch lists bake absolute pointers into the packed buffer AND the flat parameter buffer (biases): both are in the key
-        key = (N, H, W, dtc, train, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr()) + self._plan_key()
-        sp = self.shapes.get(key)
-        if sp is not None:
-            return sp
-        sp = _Shape()
+    def _plan_forward(self, sp: _Shape, b: ops.PlanBuilder, train: bool) -> None:
+        N, H, W, dtc = sp.N, sp.H, sp.W, sp.dtc
         Cc, G, Ccat, R = self.Cc, self.G, self.Ccat, self.R
-        flat = self.fp.flat
-        fptr = flat.data_ptr()
-        wptr = pk["buf"].data_ptr()
-
-        def new(*shape, dtype=dt):
-            return torch.empty(*shape, dtype=dtype, device=device)
-
         if train:
-            cat = sp.cat = [new(N, H, W, Ccat) for _ in range(R + 1)]
+            cat = sp.cat = [b.act(H, W, Ccat) for _ in range(R + 1)]
             catb = lambda i: cat[i]            # (captures the list, not `sp`: a closure stored on sp that refers to sp is a cycle)
         else:
             # inference: block 0's buffer is kept (conv2 adds out1, model.py:369-370); the rest rotate.
             # block i reads buffer i, writes i+1, and (last block of an RRDB) re-reads i-2: 4 buffers suffice.
-            cat = sp.cat = [new(N, H, W, Ccat) for _ in range(min(R + 1, 5))]
+            cat = sp.cat = [b.act(H, W, Ccat) for _ in range(min(R + 1, 5))]
             catb = lambda i: cat[0] if i == 0 else cat[1 + (i - 1) % 4]
         sp.catb = catb
         V = A.view
@@ -436,9 +447,7 @@ class TrunkEngine(EngineBase):
         # boundary kernels convert NCHW <-> NHWC directly into / out of these buffers).
         sp.planar = 1 if (self.full and os.environ.get("SRGANFD_PLANAR", "1") != "0") else 0
         VC = lambda t, c0=0: A.view(t, c0=c0, planar=sp.planar)
-
-        def bias(name):
-            return fptr + 4 * self._poff(name)
+        lre = dict(act=A.ACT_LRELU, slope=0.2)
 
         fw = []   # forward launch list
         if self.full:
@@ -446,220 +455,205 @@ class TrunkEngine(EngineBase):
             # thin-side kernels (csrc/conv_thin.hip) for conv1 / conv4 in the 16-bit modes: the image side is NHWC with a 4-channel pitch
             sp.thin_i, sp.thin_o = ops.thin_ok(dtc, Cc, self.in_ch), ops.thin_ok(dtc, Cc, self.out_ch)
             cin1 = ops.pad32(self.in_ch)          # 3 -> 32; Real-ESRGAN below x4: 12 -> 32, 48 -> 64 (Real_ESRGAN/model.py:190-201)
-            sp.xin = new(N, H, W, 4 if sp.thin_i else cin1)
-            sp.f0 = new(N, H, W, Cc)
-            sp.ups = [new(N, H << u, W << u, Cc) for u in range(1, self.n_up + 1)]
-            sp.c3 = new(N, H * s, W * s, Cc)
-            sp.srp = new(N, H * s, W * s, 4, dtype=torch.float32)
-            fw.append(ops.image_to_features(dtc, sp.thin_i, sp.xin, VC(catb(0)), bias("conv1.weight"), wptr + pk["offs"][("f", "conv1")], N, H, W,
-                                            self.in_ch, Cc, True, bias=bias("conv1.bias")))
+            sp.xin = b.act(H, W, 4 if sp.thin_i else cin1)
+            sp.f0 = b.act(H, W, Cc)
+            sp.ups = [b.act(H << u, W << u, Cc) for u in range(1, self.n_up + 1)]
+            sp.c3 = b.act(H * s, W * s, Cc)
+            sp.srp = b.act(H * s, W * s, 4, dtype=torch.float32)
+            fw.append(b.image_to_features(sp.thin_i, sp.xin, VC(catb(0)), "conv1", H, W, self.in_ch, Cc, True))
         for i, pre in enumerate(self._rdb_prefix):
             ci = catb(i)
             blk = []
             for k in range(1, 5):
-                blk.append(ops.conv_args(dtc, VC(ci), VC(ci, c0=Cc + (k - 1) * G), wptr + pk["offs"][("f", i, k)], N, H, W, Cc + (k - 1) * G, G,
-                                         bias=bias(f"{pre}conv{k}.bias"), act=A.ACT_LRELU, slope=0.2))
+                blk.append(ops.conv_args(dtc, VC(ci), VC(ci, c0=Cc + (k - 1) * G), b.Wp(("f", i, k)), N, H, W, Cc + (k - 1) * G, G,
+                                         bias=b.P(f"{pre}conv{k}.bias"), **lre))
             last = self.rrdb and i % 3 == 2
             kw = dict(post_scale=0.04, r1=VC(ci), r1_scale=0.2, r2=VC(catb(i - 2)), r2_scale=1.0) if last else \
                 dict(post_scale=0.2, r1=VC(ci), r1_scale=1.0)
-            blk.append(ops.conv_args(dtc, VC(ci), VC(catb(i + 1)), wptr + pk["offs"][("f", i, 5)], N, H, W, Ccat, Cc,
-                                     bias=bias(f"{pre}conv5.bias"), **kw))
+            blk.append(ops.conv_args(dtc, VC(ci), VC(catb(i + 1)), b.Wp(("f", i, 5)), N, H, W, Ccat, Cc, bias=b.P(f"{pre}conv5.bias"), **kw))
             # small batches (the reference's own crop sizes): the five launches as ONE LDS-resident launch (csrc/dense_chain.hip)
-            fw.extend(ops.dense_chain_or_launches(blk, device) if (Cc, G) == (64, 32) else [ops.Conv(a) for a in blk])
+            fw.extend(ops.dense_chain_or_launches(blk, sp.device) if (Cc, G) == (64, 32) else [ops.Conv(a) for a in blk])
         if self.full:
             # what conv2 reads: the trunk's output, or the output of a stage between the two (BSRGANtrans, engine_trans.py)
-            sp.conv2_in = self._stage_forward(sp, pk, fw, VC(catb(R)), N, H, W, dt, dtc, device, train)
-            fw.append(ops.Conv(ops.conv_args(dtc, sp.conv2_in, V(sp.f0), wptr + pk["offs"][("f", "conv2")], N, H, W, Cc, Cc, bias=bias("conv2.bias"),
-                                             r1=VC(catb(0)), r1_scale=1.0)))
+            sp.conv2_in = self._stage_forward(sp, b, fw, VC(catb(R)), train)
+            fw.append(b.conv(sp.conv2_in, sp.f0, ("f", "conv2"), H, W, Cc, Cc, bias=b.P("conv2.bias"), r1=VC(catb(0)), r1_scale=1.0))
             src, h, w = sp.f0, H, W
             for u in range(1, self.n_up + 1):
                 nm = f"upsampling{u}.0"
                 if self._parity(dtc):
-                    fw.extend(self._up_forward(dtc, pk, V(src), V(sp.ups[u - 1]), N, h, w, bias(nm + ".bias"), nm))
+                    fw.extend(self._up_forward(b, V(src), V(sp.ups[u - 1]), h, w, nm))
                 else:
-                    fw.append(ops.Conv(ops.conv_args(dtc, V(src), V(sp.ups[u - 1]), wptr + pk["offs"][("f", nm)], N, h, w, Cc, Cc, up=1,
-                                                     bias=bias(nm + ".bias"), act=A.ACT_LRELU, slope=0.2)))
+                    fw.append(b.conv(src, sp.ups[u - 1], ("f", nm), h, w, Cc, Cc, up=1, bias=b.P(nm + ".bias"), **lre))
                 src, h, w = sp.ups[u - 1], h * 2, w * 2
-            fw.append(ops.Conv(ops.conv_args(dtc, V(src), V(sp.c3), wptr + pk["offs"][("f", "conv3.0")], N, h, w, Cc, Cc, bias=bias("conv3.0.bias"),
-                                             act=A.ACT_LRELU, slope=0.2)))
-            fw.append(ops.features_to_image(dtc, sp.thin_o, V(sp.c3), sp.srp, 4, bias("conv4.weight"), wptr + pk["offs"][("f", "conv4")], N, h, w,
-                                            self.out_ch, Cc, False, bias=bias("conv4.bias")))
+            fw.append(b.conv(src, sp.c3, ("f", "conv3.0"), h, w, Cc, Cc, bias=b.P("conv3.0.bias"), **lre))
+            fw.append(b.features_to_image(sp.thin_o, sp.c3, sp.srp, 4, "conv4", h, w, self.out_ch, Cc, False))
             sp.hs, sp.ws = h, w
             sp.x_in, sp.result = (V(sp.xin), sp.xin.shape[-1]), (V(sp.srp), A.F32, 1)
         else:
             sp.hs, sp.ws = H, W
             sp.x_in, sp.result = (V(catb(0)), Cc), (V(catb(R)), dtc, 0)
         sp.fw = fw
-        sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
-        if train:
-            self._plan_backward(sp, pk)
-        self.shapes.put(key, sp, pinned=train)
-        return sp
 
-    def _up_forward(self, dtc: int, pk: dict, x: A.View, y: A.View, N: int, h: int, w: int, bias: int, nm: str) -> List[ops.Conv]:
+    def _up_forward(self, b: ops.PlanBuilder, x: A.View, y: A.View, h: int, w: int, nm: str) -> List[ops.Conv]:
         """nearest x2 + 3x3 pad-1 conv + LeakyReLU (BSRGAN/model.py:372-374) as its four output-parity classes: 2x2-tap convs over the
         low-res input x (pack codes 14..17), written into the high-res y.  One launch when the library takes the four classes together
         (ops.class4_ok), else one launch per class."""
-        Cc, O = self.Cc, pk["offs"]
-        return ops.parity_class_launches(dtc, x, y, pk["buf"].data_ptr(), [O[("fc", nm, c)] for c in range(4)], N, h, w, Cc, Cc, 2, 1,
-                                         tag=" nearest-x2 fwd", bias=bias, act=A.ACT_LRELU, slope=0.2)      # class (py, px) reads the window at (oy + py - 1, ox + px - 1)
+        Cc = self.Cc
+        return ops.parity_class_launches(b.dtc, x, y, b.wptr, [b.offs[("fc", nm, c)] for c in range(4)], b.N, h, w, Cc, Cc, 2, 1,
+                                         tag=" nearest-x2 fwd", bias=b.P(nm + ".bias"), act=A.ACT_LRELU, slope=0.2)      # class (py, px) reads the window at (oy + py - 1, ox + px - 1)
 
-    def _plan_backward(self, sp: _Shape, pk: dict) -> None:
-        N, H, W, dt, dtc, device = sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device
+    def _block_s5(self, i: int) -> float:
+        """the scale of block i's conv5 output: 0.2, times the RRDB's 0.2 in its last block"""
+        return 0.2 * (0.2 if (self.rrdb and i % 3 == 2) else 1.0)
+
+    def _dense_plan(self, sp: _Shape, b: ops.PlanBuilder, s5: float, splits: int = 0) -> ops.WgradPlan:
+        """a dense block's weight-gradient plan, by (conv5's scale, pixel splits; 0: the library's choice for one block per launch)"""
+        if (s5, splits) not in sp.dense_plans:
+            Cc, G, Ccat = self.Cc, self.G, self.Ccat
+            convs, pre = [], self._rdb_prefix[0]            # the plan's offsets are relative to the block: every block's are block 0's
+            rel = self._poff(pre + "conv1.weight")
+            for k in range(1, 6):
+                cin, cout = Cc + (k - 1) * G, (Cc if k == 5 else G)
+                convs.append(dict(ci_lo=0, cin=cin, co_lo=(0 if k == 5 else Cc + (4 - k) * G), cout=cout,
+                                  dw_off=self._poff(pre + f"conv{k}.weight") - rel, db_off=self._poff(pre + f"conv{k}.bias") - rel,
+                                  co_dst=cout, ci_dst=cin, alpha=(s5 if k == 5 else 1.0)))
+            sp.dense_plans[(s5, splits)] = b.wplans.plan(sp.H, sp.W, Ccat, Ccat, convs, splits=splits)
+        return sp.dense_plans[(s5, splits)]
+
+    def _plan_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        N, H, W, dtc = sp.N, sp.H, sp.W, sp.dtc
         Cc, G, Ccat, R = self.Cc, self.G, self.Ccat, self.R
-        wptr = pk["buf"].data_ptr()
         V = A.view
-        VC = VD = lambda t, c0=0: A.view(t, c0=c0, planar=sp.planar)      # forward dense-block buffers and stacked-gradient buffers (same
-        #                                                                   layout: planar only one of the two measured half the gain each, DESIGN 3)
-
-        def new(*shape, dtype=dt):
-            return torch.empty(*shape, dtype=dtype, device=device)
-
-        wplans = ops.WgradPlans(device, dtc, N)
-        # the dense blocks' weight-gradient plans, by (conv5's scale, pixel splits; 0: the library's choice for one block per launch)
-        plans, rel = {}, self._poff(self._rdb_prefix[0] + "conv1.weight")
-
-        def dense_plan(s5, splits=0):
-            if (s5, splits) not in plans:
-                convs, pre = [], self._rdb_prefix[0]        # the plan's offsets are relative to the block: every block's are block 0's
-                for k in range(1, 6):
-                    cin, cout = Cc + (k - 1) * G, (Cc if k == 5 else G)
-                    convs.append(dict(ci_lo=0, cin=cin, co_lo=(0 if k == 5 else Cc + (4 - k) * G), cout=cout,
-                                      dw_off=self._poff(pre + f"conv{k}.weight") - rel, db_off=self._poff(pre + f"conv{k}.bias") - rel,
-                                      co_dst=cout, ci_dst=cin, alpha=(s5 if k == 5 else 1.0)))
-                plans[(s5, splits)] = wplans.plan(H, W, Ccat, Ccat, convs, splits=splits)
-            return plans[(s5, splits)]
-        block_s5 = lambda i: 0.2 * (0.2 if (self.rrdb and i % 3 == 2) else 1.0)
+        VD = lambda t, c0=0: A.view(t, c0=c0, planar=sp.planar)      # the stacked-gradient buffers: the layout of the forward's dense-block buffers
+        #                                                              (planar only one of the two measured half the gain each, DESIGN 3)
+        sp.dense_plans = {}
         # _BATCH_WGRAD: up to _BATCH_REDUCE blocks' weight gradients as one MFMA launch (batch_wgrads).  "auto": where one block's
         # launch already fills the chip -- at least as many pixel tiles as the device gives it splits -- so that a batch's fewer
         # splits per block lose nothing
-        p0 = dense_plan(block_s5(R - 1))
-        sp.batch_wgrad = _BATCH_REDUCE > 1 and (_BATCH_WGRAD == "1" or (_BATCH_WGRAD == "auto" and p0.ntiles >= max(1, ops.device_cus(device) // p0.ngroups)))
+        p0 = self._dense_plan(sp, b, self._block_s5(R - 1))
+        sp.batch_wgrad = _BATCH_REDUCE > 1 and (_BATCH_WGRAD == "1" or (_BATCH_WGRAD == "auto" and p0.ntiles >= max(1, ops.device_cus(sp.device) // p0.ngroups)))
         # a batch's launch stands at its LAST block and reads every block's stacked-gradient buffer there.  Per-layer data gradients:
         # four rotating buffers hold that long (a block's 192->64 launch, which overwrites the buffer four blocks up, follows its weight
         # gradient; a batch of more than four blocks needs one each).  The dense-block launch takes all five convs before it: one
         # buffer more than a batch has blocks
         chain_form = (Cc, G) == (64, 32) and dtc in (A.F16, A.BF16) and ops.dense_chain_wanted(N, H, W)
         ndy = max(4, _BATCH_REDUCE + (1 if chain_form else 0)) if sp.batch_wgrad else 4
-        sp.dy = [new(N, H, W, Ccat) for _ in range(ndy)]
-        sp.dx0 = new(N, H, W, Cc)           # gradient w.r.t. the trunk input
+        sp.dy = [b.act(H, W, Ccat) for _ in range(ndy)]
+        sp.dx0 = b.act(H, W, Cc)            # gradient w.r.t. the trunk input
         dyb = lambda i: sp.dy[i % ndy]
         if not self.full:
             sp.dy_in, sp.dx_out = (V(dyb(R - 1)), Cc), (V(sp.dx0), dtc)
-        bw = []                              # ops.Conv | Wgrad | ThinLaunch | DenseChain | Call and the bucket markers ops.Ready
-        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
-
+        # ops.Conv | Wgrad | ThinLaunch | DenseChain | Call and the bucket markers ops.Ready
+        bw = self._backward_tail(sp, b, VD(dyb(R - 1))) if self.full else []
+        bw += self._backward_blocks(sp, b, dyb, VD)
         if self.full:
-            s = 1 << self.n_up
-            hs, ws_ = sp.hs, sp.ws
-            sp.dsrp = new(N, hs, ws_, 4 if sp.thin_o else 32)
-            sp.dy_in = (V(sp.dsrp), sp.dsrp.shape[-1])
-            sp.gA = new(N, hs, ws_, Cc)
-            fptr = self.fp.flat.data_ptr()
-            sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device) if (sp.thin_i or sp.thin_o) else None
-            sp.gB = new(N, hs, ws_, Cc)
-            sp.glo = [new(N, H << u, W << u, Cc) for u in range(0, self.n_up)]   # grads at the input res of upsampling u+1
+            bw.append(ops.Call("srganfd_axpby", (V(sp.d_f0), V(sp.dx0), dtc, N * H * W, Cc, 1.0, 1.0), "axpby"))
+            bw.append(b.image_wgrad(sp.thin_i, sp.xin, sp.dx0, "conv1", sp.thin_ws, H, W, self.in_ch, Cc, True))
+        # last bucket: whatever the earlier markers did not cover
+        covered = min([it.lo for it in bw if isinstance(it, ops.Ready)], default=self.fp.total)
+        bw.append(ops.Ready(0, covered))
+        self._finish_backward(sp, b)
+        sp.wg_ws = b.wplans.workspace()
+        sp.bw = self._batch_dense_wgrads(sp, b, bw, p0)
 
-            def one(name, cout, cin, dw_only=False):
-                return [dict(cin=ops.pad32(cin), cout=ops.pad32(cout), dw_off=self._poff(name + ".weight"), db_off=self._poff(name + ".bias"),
-                             co_dst=cout, ci_dst=cin)]
-            # conv4
-            w4 = fptr + 4 * self._poff("conv4.weight")
-            bw.append(ops.image_wgrad(dtc, sp.thin_o, wplans, sp.dsrp, sp.c3, w4, self._poff("conv4.weight"), self._poff("conv4.bias"), sp.thin_ws,
-                                      N, hs, ws_, self.out_ch, Cc, False))
-            bw.append(ops.image_to_features(dtc, sp.thin_o, sp.dsrp, V(sp.gA), w4, wptr + pk["offs"][("b", "conv4")], N, hs, ws_, self.out_ch, Cc, False,
-                                            flip=True, mask=V(sp.c3), mask_slope=0.2))
-            # conv3
-            src3 = sp.ups[-1] if self.n_up else sp.f0
-            bw.append(ops.Wgrad(wplans.plan(hs, ws_, Cc, Cc, one("conv3.0", Cc, Cc)), V(src3), V(sp.gA)))
-            bw.append(cv(V(sp.gA), V(sp.gB), wptr + pk["offs"][("b", "conv3.0")], N, hs, ws_, Cc, Cc, mask=V(src3) if self.n_up else A.NULL_VIEW, mask_slope=0.2))
-            cur, other = sp.gB, sp.gA        # cur = gradient w.r.t. pre-activation of upsampling{n_up} (at its output res)
-            for u in range(self.n_up, 0, -1):
-                nm = f"upsampling{u}.0"
-                hin, win = H << (u - 1), W << (u - 1)
-                xin_t = sp.ups[u - 2] if u >= 2 else sp.f0
-                npx = N * (hin * 2) * (win * 2)
-                cur_v = V(cur.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
-                oth_v = V(other.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
-                bw.append(ops.Wgrad(wplans.plan(hin, win, Cc, Cc, one(nm, Cc, Cc), up=1), V(xin_t), cur_v))
-                glo = sp.glo[u - 1]
-                if self._parity(dtc):
-                    # data gradient, nearest adjoint and (u >= 2: the input is the previous upsampling conv's LeakyReLU output) LeakyReLU' as
-                    # ONE 4x4 stride-2 pad-1 conv over the high-res gradient, written at the low resolution
-                    it = cv(cur_v, V(glo), wptr + pk["offs"][("b4", nm)], N, hin * 2, win * 2, Cc, Cc, ksize=4, stride=2, pad=1,
-                            mask=V(xin_t) if u >= 2 else A.NULL_VIEW, mask_slope=0.2)
-                    it.args._label_tag = " nearest-x2 dgrad"
-                    bw.append(it)
-                else:
-                    bw.append(cv(cur_v, oth_v, wptr + pk["offs"][("b", nm)], N, hin * 2, win * 2, Cc, Cc))
-                    bw.append(ops.Call("srganfd_resample", (0, oth_v, V(glo), dtc, N, hin, win, Cc), "nearest_bwd"))
-                    if u >= 2:   # input of this stage is the LeakyReLU output of the previous upsampling conv
-                        bw.append(ops.Call("srganfd_lrelu_bwd", (V(glo), V(xin_t), A.NULL_VIEW, V(glo), dtc, N * hin * win, Cc, 0.2), "lrelu_bwd"))
-                cur, other = glo, sp.gA      # the next stage works at (hin, win): gA is its scratch, the gradient lives in glo
-            d_f0 = cur if self.n_up else sp.gB
-            sp.d_f0 = d_f0
-            # conv2: f0 = out1 + conv2(trunk_out)
-            bw.append(ops.Wgrad(wplans.plan(H, W, Cc, Cc, one("conv2", Cc, Cc)), sp.conv2_in, V(d_f0)))
-            dst2, epi2 = self._conv2_dgrad_target(sp, VD(dyb(R - 1)))
-            bw.append(cv(V(d_f0), dst2, wptr + pk["offs"][("b", "conv2")], N, H, W, Cc, Cc, **epi2))
-            # gradient buckets for the data-parallel exchange (parallel.BucketReducer): parameters sit in named_parameters() order --
-            # conv1, the dense blocks, conv2 and the tail -- so "everything from conv2 on" is one contiguous range, final here
-            bw.append(ops.Ready(self._poff("conv2.weight"), self.fp.total))
-            # a stage between trunk and conv2: its backward ends in the last dense block's stacked-gradient buffer, its parameters are final
-            bw.extend(self._stage_backward(sp, pk, wplans, VD(dyb(R - 1))))
-        # dense blocks, last to first
-        rdb_names = ["conv%d" % k for k in range(1, 6)]
+    def _backward_tail(self, sp: _Shape, b: ops.PlanBuilder, trunk_grad: A.View) -> list:
+        """the generator's tail, from the image's gradient to ``trunk_grad`` (channels [0, Cc) of the last dense block's stacked-gradient
+        buffer): conv4, conv3, the upsampling stages, conv2, the first gradient bucket and the stage between trunk and conv2"""
+        N, H, W, dtc, Cc, V = sp.N, sp.H, sp.W, sp.dtc, self.Cc, A.view
+        hs, ws_ = sp.hs, sp.ws
+        sp.dsrp = b.act(hs, ws_, 4 if sp.thin_o else 32)
+        sp.dy_in = (V(sp.dsrp), sp.dsrp.shape[-1])
+        sp.gA, sp.gB = b.act(hs, ws_, Cc), b.act(hs, ws_, Cc)
+        sp.thin_ws = b.thin_ws(sp.thin_i, sp.thin_o)
+        sp.glo = [b.act(H << u, W << u, Cc) for u in range(0, self.n_up)]   # grads at the input res of upsampling u+1
+        src3 = sp.ups[-1] if self.n_up else sp.f0
+        bw = [
+            b.image_wgrad(sp.thin_o, sp.dsrp, sp.c3, "conv4", sp.thin_ws, hs, ws_, self.out_ch, Cc, False),
+            b.image_to_features(sp.thin_o, sp.dsrp, sp.gA, "conv4", hs, ws_, self.out_ch, Cc, False, flip=True, mask=V(sp.c3), mask_slope=0.2),
+            b.wgrad(src3, sp.gA, hs, ws_, Cc, Cc, "conv3.0.weight", "conv3.0.bias"),
+            b.dgrad(sp.gA, sp.gB, ("b", "conv3.0"), hs, ws_, Cc, Cc, mask=src3 if self.n_up else None),
+        ]
+        cur, other = sp.gB, sp.gA        # cur = gradient w.r.t. pre-activation of upsampling{n_up} (at its output res)
+        for u in range(self.n_up, 0, -1):
+            nm = f"upsampling{u}.0"
+            hin, win = H << (u - 1), W << (u - 1)
+            xin_t = sp.ups[u - 2] if u >= 2 else sp.f0
+            npx = N * (hin * 2) * (win * 2)
+            cur_v = V(cur.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
+            oth_v = V(other.view(-1)[: npx * Cc].view(N, hin * 2, win * 2, Cc))
+            bw.append(b.wgrad(xin_t, cur_v, hin, win, Cc, Cc, nm + ".weight", nm + ".bias", up=1))
+            glo = sp.glo[u - 1]
+            if self._parity(dtc):
+                # data gradient, nearest adjoint and (u >= 2: the input is the previous upsampling conv's LeakyReLU output) LeakyReLU' as
+                # ONE 4x4 stride-2 pad-1 conv over the high-res gradient, written at the low resolution
+                it = b.dgrad(cur_v, glo, ("b4", nm), hin * 2, win * 2, Cc, Cc, mask=xin_t if u >= 2 else None, ksize=4, stride=2, pad=1)
+                it.args._label_tag = " nearest-x2 dgrad"
+                bw.append(it)
+            else:
+                bw.append(b.dgrad(cur_v, oth_v, ("b", nm), hin * 2, win * 2, Cc, Cc))
+                bw.append(b.resample(0, oth_v, glo, hin, win, Cc, what="nearest_bwd"))
+                if u >= 2:   # input of this stage is the LeakyReLU output of the previous upsampling conv
+                    bw.append(b.lrelu_bwd(glo, xin_t, glo, N * hin * win, Cc))
+            cur, other = glo, sp.gA      # the next stage works at (hin, win): gA is its scratch, the gradient lives in glo
+        d_f0 = sp.d_f0 = cur if self.n_up else sp.gB
+        # conv2: f0 = out1 + conv2(trunk_out)
+        bw.append(b.wgrad(sp.conv2_in, d_f0, H, W, Cc, Cc, "conv2.weight", "conv2.bias"))
+        dst2, epi2 = self._conv2_dgrad_target(sp, trunk_grad)
+        bw.append(b.conv(d_f0, dst2, ("b", "conv2"), H, W, Cc, Cc, **epi2))
+        # gradient buckets for the data-parallel exchange (parallel.BucketReducer): parameters sit in named_parameters() order --
+        # conv1, the dense blocks, conv2 and the tail -- so "everything from conv2 on" is one contiguous range, final here
+        bw.append(ops.Ready(self._poff("conv2.weight"), self.fp.total))
+        # a stage between trunk and conv2: its backward ends in the last dense block's stacked-gradient buffer, its parameters are final
+        bw.extend(self._stage_backward(sp, b, trunk_grad))
+        return bw
+
+    def _backward_blocks(self, sp: _Shape, b: ops.PlanBuilder, dyb, VD) -> list:
+        """the dense blocks, last to first: each block's data gradient (a dense block over its stacked-gradient buffer ``dyb(i)``), its
+        weight gradient, and the marker of the trunk's upper half"""
+        N, H, W, dtc = sp.N, sp.H, sp.W, sp.dtc
+        Cc, G, Ccat, R = self.Cc, self.G, self.Ccat, self.R
+        VC = VD                              # (the forward's dense-block buffers have the stacked-gradient buffers' layout)
+        bw = []
         for i in range(R - 1, -1, -1):
             pre = self._rdb_prefix[i]
             last = self.rrdb and i % 3 == 2
             first = self.rrdb and i % 3 == 0
             s_out = 0.2 if last else 1.0
-            s5 = 0.2 * s_out
             ci, di = sp.catb(i), dyb(i)
             blk = []
             for step in range(4):
                 kdim = Cc + step * G
-                blk.append(ops.conv_args(dtc, VD(di), VD(di, c0=Cc + step * G), wptr + pk["offs"][("b", i, step)], N, H, W, kdim, G,
+                blk.append(ops.conv_args(dtc, VD(di), VD(di, c0=Cc + step * G), b.Wp(("b", i, step)), N, H, W, kdim, G,
                                          mask=VC(ci, c0=Cc + (3 - step) * G), mask_slope=0.2))
-            dst = VD(dyb(i - 1)) if i > 0 else V(sp.dx0)
+            dst = VD(dyb(i - 1)) if i > 0 else A.view(sp.dx0)
             kw = dict(r1=VD(di), r1_scale=s_out)
             if first:
                 kw.update(r2=VD(dyb(i + 2)), r2_scale=1.0)
-            blk.append(ops.conv_args(dtc, VD(di), dst, wptr + pk["offs"][("b", i, 4)], N, H, W, Ccat, Cc, **kw))
+            blk.append(ops.conv_args(dtc, VD(di), dst, b.Wp(("b", i, 4)), N, H, W, Ccat, Cc, **kw))
             chain = ops.dense_chain_or_launches(blk, sp.device) if (Cc, G) == (64, 32) else [ops.Conv(a) for a in blk]
-            wg = ops.Wgrad(dense_plan(s5), VC(ci), VD(di), dw_off=self._poff(pre + "conv1.weight"), block=i)     # the plan's offsets are relative to the block
+            wg = ops.Wgrad(self._dense_plan(sp, b, self._block_s5(i)), VC(ci), VD(di), dw_off=self._poff(pre + "conv1.weight"), block=i)     # the plan's offsets are relative to the block
             ready = [ops.Ready(self._poff(pre + "conv1.weight"), self._trunk_end())] if self.full and R >= 4 and i == R // 2 else []     # upper half of the trunk is final: second bucket
             # the weight gradient reads what the four growth layers of the data gradient wrote and follows them (or the one launch for all five convs)
             bw.extend(chain[:4] + [wg] + ready + chain[4:])
-        if self.full:
-            bw.append(ops.Call("srganfd_axpby", (V(sp.d_f0), V(sp.dx0), dtc, N * H * W, Cc, 1.0, 1.0), "axpby"))
-            bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, sp.xin, sp.dx0, fptr + 4 * self._poff("conv1.weight"), self._poff("conv1.weight"),
-                                      self._poff("conv1.bias"), sp.thin_ws, N, H, W, self.in_ch, Cc, True))
-        # last bucket: whatever the earlier markers did not cover
-        covered = min([it.lo for it in bw if isinstance(it, ops.Ready)], default=self.fp.total)
-        bw.append(ops.Ready(0, covered))
-        self._finish_backward(sp, pk)
-        sp.wg_ws = wplans.workspace()
-        # four more workspaces of the dense-block plan's size for the batched slab reduction (34 MB each at B=32, 128x128)
-        dense_ws = max((p_.workspace_bytes for p_ in plans.values()), default=0)
-        sp.wg_ws4 = [torch.empty(dense_ws, dtype=torch.uint8, device=device) for _ in range(_BATCH_REDUCE)] if (dense_ws and _BATCH_REDUCE > 1) else None
+        return bw
+
+    def _batch_dense_wgrads(self, sp: _Shape, b: ops.PlanBuilder, bw: list, p0: ops.WgradPlan) -> list:
+        """``bw`` with the dense blocks' weight gradients batched as the switches say (batch_wgrads / batch_reductions), and the
+        workspaces that takes: _BATCH_REDUCE more of the dense-block plan's size (34 MB each at B=32, 128x128)"""
+        dense_ws = max((p_.workspace_bytes for p_ in sp.dense_plans.values()), default=0)
+        sp.wg_ws4 = [b.buf(dense_ws, dtype=torch.uint8) for _ in range(_BATCH_REDUCE)] if (dense_ws and _BATCH_REDUCE > 1) else None
         if sp.wg_ws4 is None:
-            sp.bw = bw
-        elif sp.batch_wgrad:
+            return bw
+        if sp.batch_wgrad:
             # a batch of n blocks: plans with 1 / n of one block's pixel splits, so the launch has one block's workgroups
-            sp.bw = batch_wgrads(bw, sp.wg_ws4, lambda wg, n: wg.plan if n == 1 else dense_plan(block_s5(wg.block), max(1, p0.splits // n)))
-        else:
-            sp.bw = batch_reductions(bw, sp.wg_ws4)
+            return batch_wgrads(bw, sp.wg_ws4, lambda wg, n: wg.plan if n == 1 else self._dense_plan(sp, b, self._block_s5(wg.block), max(1, p0.splits // n)))
+        return batch_reductions(bw, sp.wg_ws4)
 
     # -- what a generator with a stage between the trunk and conv2 overrides (engine_trans.py); here: no stage -----------------
-    def _plan_key(self) -> tuple:
-        """what a plan depends on besides shape, dtype, buffers and ``train``"""
-        return ()
-
     def _stage_pack(self, pb: "ops.PackBuilder", dtc: int) -> None:
         """the stage's packed operands"""
 
-    def _stage_forward(self, sp: _Shape, pk: dict, fw: list, trunk_out: A.View, N: int, H: int, W: int, dt, dtc: int, device, train: bool) -> A.View:
+    def _stage_forward(self, sp: _Shape, b: ops.PlanBuilder, fw: list, trunk_out: A.View, train: bool) -> A.View:
         """appends the stage's forward items to ``fw``; returns the view conv2 reads"""
         return trunk_out
 
@@ -667,7 +661,7 @@ class TrunkEngine(EngineBase):
         """(where conv2's data gradient goes, its epilogue keywords)"""
         return trunk_grad, {}
 
-    def _stage_backward(self, sp: _Shape, pk: dict, wplans: "ops.WgradPlans", trunk_grad: A.View) -> list:
+    def _stage_backward(self, sp: _Shape, b: ops.PlanBuilder, trunk_grad: A.View) -> list:
         """the stage's backward items, from conv2's data gradient to channels [0, Cc) of ``trunk_grad``, and their bucket marker"""
         return []
 
@@ -675,7 +669,7 @@ class TrunkEngine(EngineBase):
         """offset of the first parameter behind the trunk's"""
         return self._poff("conv2.weight")
 
-    def _finish_backward(self, sp: _Shape, pk: dict) -> None:
+    def _finish_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
         """last step of _plan_backward, before the workspaces are sized"""
 
     # -- execution ----------------------------------------------------------------------------

@@ -141,229 +141,193 @@ class AesrganDiscriminatorEngine(DiscriminatorEngineCore):
             pb.classes(("b", pre + ".theta"), src, co, ci, 1, 10)      # 2x2 stride-2 data gradient: 4 classes of 1x1 convs
         return pb.finish(device)
 
-    # ---- plan ----
-    def _plan(self, N, H, W, dt, dtc, device, pk, train=True):
-        key = (N, H, W, dtc, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
-        sp = self.shapes.get(key)
-        if sp is not None:
-            return sp
-        if H % 8 or W % 8:
-            raise A.SrganfdError("UNetDiscriminatorAesrgan input height/width must be multiples of 8")
-        sp = _Shape()
-        sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
-        V = A.view
-        fptr, wptr, O = self.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
-        P = lambda name: fptr + 4 * self._poff(name)      # (used while the plan is built only, not stored on it)
-        Wp = lambda *key: wptr + O[key]
-        nf = self.nf
-
-        def new(h, w, c, dtype=dt):
-            return torch.empty(N, h, w, c, dtype=dtype, device=device)
-        R = [(H >> k, W >> k) for k in range(4)]
-        Hg, Wg = R[3][0] + 2, R[3][1] + 2
+    # ---- plan: the buffer tables, the attention gate (forward and backward), the U-Net spine (forward and backward) ----
+    def _forward_buffers(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        """sp.B: the spine's activations by name; sp.attn[k]: gate k's (``dims``: its sizes); R[k]: the size at depth k, Rg: the gating map's"""
+        H, W, nf = sp.H, sp.W, self.nf
+        R = sp.R = [(H >> k, W >> k) for k in range(4)]
+        Hg, Wg = sp.Rg = (R[3][0] + 2, R[3][1] + 2)
         B = sp.B = {}
-        # conv0 (in_ch -> nf) and conv9 (nf -> 1) on the thin-side kernels in the 16-bit modes (csrc/conv_thin.hip): 4-channel pitch
-        sp.thin_i, sp.thin_o = ops.thin_ok(dtc, nf, self.in_ch), ops.thin_ok(dtc, nf, 1)
-        B["xin"] = sp.xin = new(H, W, 4 if sp.thin_i else 32)
-        B["x0"], B["x1"], B["x2"], B["x3"] = new(*R[0], nf), new(*R[1], 2 * nf), new(*R[2], 4 * nf), new(*R[3], 8 * nf)
-        B["gated"] = new(Hg, Wg, 4 * nf)
-        B["cat1"], B["cat2"], B["cat3"] = new(*R[2], 8 * nf), new(*R[1], 4 * nf), new(*R[0], 2 * nf)
-        B["b3"], B["x4"], B["b4"], B["x5"], B["b5"] = new(*R[2], 8 * nf), new(*R[2], 4 * nf), new(*R[1], 4 * nf), new(*R[1], 2 * nf), new(*R[0], 2 * nf)
-        B["x6"], B["c7"], B["c8"] = new(*R[0], nf), new(*R[0], nf), new(*R[0], nf)
-        bn_ws = [torch.empty(2048 * 256 + 3 * 256, dtype=torch.float32, device=device), None]
-        sp.bn = {}
-        lre = dict(act=A.ACT_LRELU, slope=0.2)
-        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
-        rs = lambda op, a, b, h, w, c, dtype=dtc: ops.Call("srganfd_resample", (op, a, b, dtype, N, h, w, c), "resample")
-        fw = [
-            ops.image_to_features(dtc, sp.thin_i, B["xin"], V(B["x0"]), P("conv0.weight"), Wp("f", "conv0"), N, H, W, self.in_ch, nf, True,
-                                  bias=P("conv0.bias"), **lre),
-            cv(V(B["x0"]), V(B["x1"]), Wp("f", "conv1"), N, *R[0], nf, 2 * nf, stride=2, **lre),
-            cv(V(B["x1"]), V(B["x2"]), Wp("f", "conv2"), N, *R[1], 2 * nf, 4 * nf, stride=2, **lre),
-            cv(V(B["x2"]), V(B["x3"]), Wp("f", "conv3"), N, *R[2], 4 * nf, 8 * nf, stride=2, **lre),
-            cv(V(B["x3"]), V(B["gated"]), Wp("f", "gating"), N, *R[3], 8 * nf, 4 * nf, ksize=1, pad=1, **lre),
-        ]
+        B["xin"] = sp.xin = b.act(H, W, 4 if sp.thin_i else 32)
+        B["x0"], B["x1"], B["x2"], B["x3"] = b.act(*R[0], nf), b.act(*R[1], 2 * nf), b.act(*R[2], 4 * nf), b.act(*R[3], 8 * nf)
+        B["gated"] = b.act(Hg, Wg, 4 * nf)
+        B["cat1"], B["cat2"], B["cat3"] = b.act(*R[2], 8 * nf), b.act(*R[1], 4 * nf), b.act(*R[0], 2 * nf)
+        B["b3"], B["x4"], B["b4"], B["x5"], B["b5"] = b.act(*R[2], 8 * nf), b.act(*R[2], 4 * nf), b.act(*R[1], 4 * nf), b.act(*R[1], 2 * nf), b.act(*R[0], 2 * nf)
+        B["x6"], B["c7"], B["c8"] = b.act(*R[0], nf), b.act(*R[0], nf), b.act(*R[0], nf)
         sp.attn = {}
-        for k, xname, cat in ((1, "x2", "cat1"), (2, "x1", "cat2"), (3, "x0", "cat3")):
-            pre = f"attn_{k}"
+        for k, xname in ((1, "x2"), (2, "x1"), (3, "x0")):
             Ck = B[xname].shape[-1]
             h, w = R[3 - k]
             hh, wh = h // 2, w // 2
-            T = {}
-            T["theta"], T["phi"], T["phiup"], T["f"] = new(hh, wh, Ck), new(Hg, Wg, Ck), new(hh, wh, Ck), new(hh, wh, Ck)
-            T["sig"] = torch.empty(N, hh, wh, 1, dtype=torch.float32, device=device)
-            T["sigup"] = torch.empty(N, h, w, 1, dtype=torch.float32, device=device)
-            T["y"], T["wy"] = new(h, w, Ck), new(h, w, Ck)
-            T["save"] = torch.empty(4 * Ck, dtype=torch.float32, device=device)
+            T = sp.attn[k] = {}
+            T["theta"], T["phi"], T["phiup"], T["f"] = b.act(hh, wh, Ck), b.act(Hg, Wg, Ck), b.act(hh, wh, Ck), b.act(hh, wh, Ck)
+            T["sig"], T["sigup"] = b.act(hh, wh, 1, dtype=torch.float32), b.act(h, w, 1, dtype=torch.float32)
+            T["y"], T["wy"] = b.act(h, w, Ck), b.act(h, w, Ck)
+            T["save"] = b.buf(4 * Ck, dtype=torch.float32)
             T["dims"] = (h, w, hh, wh, Ck)
-            sp.attn[k] = T
-            fw += [
-                cv(V(B[xname]), V(T["theta"]), Wp("f", pre + ".theta"), N, h, w, Ck, Ck, ksize=2, stride=2, pad=0),
-                cv(V(B["gated"]), V(T["phi"]), Wp("f", pre + ".phi"), N, Hg, Wg, 4 * nf, Ck, ksize=1, pad=0, bias=P(pre + ".phi.bias")),
-                ops.Call("srganfd_resize_bilinear", (0, V(T["phi"]), V(T["phiup"]), dtc, N, Hg, Wg, hh, wh, Ck), "resize"),
-                ops.Call("srganfd_add_relu", (V(T["theta"]), V(T["phiup"]), V(T["f"]), dtc, N * hh * wh, Ck), "add_relu"),
-                cv(V(T["f"]), V(T["sig"]), Wp("f", pre + ".psi"), N, hh, wh, Ck, 32, ksize=1, pad=0, cout_store=1, bias=P(pre + ".psi.bias"), y_f32=True),
-                ops.Call("srganfd_sigmoid", (T["sig"].data_ptr(), T["sig"].numel()), "sigmoid"),
-                rs(1, V(T["sig"]), V(T["sigup"]), hh, wh, 1, A.F32),
-                ops.Call("srganfd_gate_mul", (0, V(B[xname]), T["sigup"].data_ptr(), V(T["y"]), A.NULL_VIEW, None, dtc, N * h * w, Ck), "gate_mul"),
-                cv(V(T["y"]), V(T["wy"]), Wp("f", pre + ".W.0"), N, h, w, Ck, Ck, ksize=1, pad=0, bias=P(pre + ".W.0.bias")),
-            ]
-            sp.bn[k] = GateBatchNorm(self, V(T["wy"]), V(B[cat]), dtc, N * h * w, Ck, self._poff(pre + ".W.1.weight"), self._poff(pre + ".W.1.bias"),
-                                     _mod(self.owner, pre + ".W.1"), T["save"], bn_ws)
-            fw.append(sp.bn[k])
-        fw += [
-            rs(1, V(B["x3"]), V(B["b3"]), *R[3], 8 * nf),
-            cv(V(B["b3"]), V(B["cat1"], c0=4 * nf), Wp("f", "cat_1.convU"), N, *R[2], 8 * nf, 4 * nf, **lre),
-            cv(V(B["cat1"]), V(B["x4"]), Wp("f", "conv4"), N, *R[2], 8 * nf, 4 * nf, **lre),
-            rs(1, V(B["x4"]), V(B["b4"]), *R[2], 4 * nf),
-            cv(V(B["b4"]), V(B["cat2"], c0=2 * nf), Wp("f", "cat_2.convU"), N, *R[1], 4 * nf, 2 * nf, **lre),
-            cv(V(B["cat2"]), V(B["x5"]), Wp("f", "conv5"), N, *R[1], 4 * nf, 2 * nf, **lre),
-            rs(1, V(B["x5"]), V(B["b5"]), *R[1], 2 * nf),
-            cv(V(B["b5"]), V(B["cat3"], c0=nf), Wp("f", "cat_3.convU"), N, *R[0], 2 * nf, nf, **lre),
-            cv(V(B["cat3"]), V(B["x6"]), Wp("f", "conv6"), N, *R[0], 2 * nf, nf, **lre),
-            cv(V(B["x6"]), V(B["c7"]), Wp("f", "conv7"), N, *R[0], nf, nf, **lre),
-            cv(V(B["c7"]), V(B["c8"]), Wp("f", "conv8"), N, *R[0], nf, nf, **lre),
-        ]
-        # conv9 writes the logits, allocated per forward
-        fw.append(ops.PerCall(ops.features_to_image(dtc, sp.thin_o, V(B["c8"]), 0, 1, P("conv9.weight"), Wp("f", "conv9"), N, H, W, 1, nf, False,
-                                                    bias=P("conv9.bias"))))
-        sp.fw = fw
-        sp.R, sp.Rg = R, (Hg, Wg)
-        self._plan_backward(sp, pk)
-        self.shapes[key] = sp
-        return sp
 
-    def _plan_backward(self, sp, pk):
-        N, H, W, dt, dtc, device = sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device
-        V, B, R, nf = A.view, sp.B, sp.R, self.nf
+    def _backward_buffers(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        """sp.G: the spine's gradients by name; sp.attn[k]["grad"]: gate k's"""
+        H, W, nf, R = sp.H, sp.W, self.nf, sp.R
         Hg, Wg = sp.Rg
-        wptr, O = pk["buf"].data_ptr(), pk["offs"]
-        Wp = lambda *key: wptr + O[key]
-        fptr = self.fp.flat.data_ptr()
-        P = lambda name: fptr + 4 * self.fp.off(name)      # (used while the plan is built only, not stored on it)
-
-        def new(h, w, c, dtype=dt):
-            return torch.empty(N, h, w, c, dtype=dtype, device=device)
-        wplans = ops.WgradPlans(device, dtc, N)
-
-        def wg(name, x, dy, h, w, cin, cout, k=3, s=1, pad=1, sn=False, cin_real=None, cout_real=None, bias=False, dy_c0=0):
-            plan = wplans.conv(h, w, cin, cout, self._poff(name + (".weight_orig" if sn else ".weight")), self._poff(name + ".bias") if bias else -1,
-                               cin_real, cout_real, ksize=k, stride=s, pad=pad)
-            return ops.Wgrad(plan, V(x), V(dy, c0=dy_c0), sn=SN_INDEX[name] if sn else None)
-
-        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
-        rs = lambda op, a, b, h, w, c, dtype=dtc: ops.Call("srganfd_resample", (op, a, b, dtype, N, h, w, c), "resample")
-        lb = lambda dy, act, out, npix, c, slope=0.2: ops.Call("srganfd_lrelu_bwd", (dy, act, A.NULL_VIEW, out, dtc, npix, c, slope), "lrelu_bwd")
-
-        def strided_dgrad(key, ks, dy, dx, hd, wd, cin_op, cout_op, r1=None, r2=None, mask=None):
-            """4 parity classes writing a (2hd x 2wd) image: ks=2 (3x3 s2 conv) or ks=1 (2x2 s2 conv)"""
-            view = lambda t: None if t is None else V(t)
-            return ops.parity_class_launches(      # class_pad 0: every class reads the same window of dy
-                dtc, V(dy), V(dx), wptr, [O[key + (c,)] for c in range(4)], N, hd, wd, cin_op, cout_op, ks, 0,
-                **ops.dgrad_epilogue(view(r1), view(r2), view(mask)))
-
-        sp.dl = new(H, W, 4 if sp.thin_o else 32)
-        sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device) if (sp.thin_i or sp.thin_o) else None
+        sp.dl = b.act(H, W, 4 if sp.thin_o else 32)
+        sp.thin_ws = b.thin_ws(sp.thin_i, sp.thin_o)
         G = sp.G = {}
-        G["g8"], G["g7"], G["g6"] = new(*R[0], nf), new(*R[0], nf), new(*R[0], nf)
-        G["dc3"], G["db5"], G["dx5"] = new(*R[0], 2 * nf), new(*R[0], 2 * nf), new(*R[1], 2 * nf)
-        G["dc2"], G["db4"], G["dx4"] = new(*R[1], 4 * nf), new(*R[1], 4 * nf), new(*R[2], 4 * nf)
-        G["dc1"], G["db3"], G["dx3a"], G["dx3"] = new(*R[2], 8 * nf), new(*R[2], 8 * nf), new(*R[3], 8 * nf), new(*R[3], 8 * nf)
-        G["dx2"], G["dx1"], G["dx0"] = new(*R[2], 4 * nf), new(*R[1], 2 * nf), new(*R[0], nf)
-        G["dgated"] = [new(Hg, Wg, 4 * nf) for _ in range(3)]
-        sp.dxp = new(H, W, 4, dtype=torch.float32)
+        G["g8"], G["g7"], G["g6"] = b.act(*R[0], nf), b.act(*R[0], nf), b.act(*R[0], nf)
+        G["dc3"], G["db5"], G["dx5"] = b.act(*R[0], 2 * nf), b.act(*R[0], 2 * nf), b.act(*R[1], 2 * nf)
+        G["dc2"], G["db4"], G["dx4"] = b.act(*R[1], 4 * nf), b.act(*R[1], 4 * nf), b.act(*R[2], 4 * nf)
+        G["dc1"], G["db3"], G["dx3a"], G["dx3"] = b.act(*R[2], 8 * nf), b.act(*R[2], 8 * nf), b.act(*R[3], 8 * nf), b.act(*R[3], 8 * nf)
+        G["dx2"], G["dx1"], G["dx0"] = b.act(*R[2], 4 * nf), b.act(*R[1], 2 * nf), b.act(*R[0], nf)
+        G["dgated"] = [b.act(Hg, Wg, 4 * nf) for _ in range(3)]
+        sp.dxp = b.act(H, W, 4, dtype=torch.float32)
+        for k in (1, 2, 3):
+            h, w, hh, wh, Ck = sp.attn[k]["dims"]
+            D = sp.attn[k]["grad"] = {}
+            D["dwy"], D["dy"], D["dxg"] = b.act(h, w, Ck), b.act(h, w, Ck), b.act(h, w, Ck)
+            D["dsigup"], D["dsig"] = b.act(h, w, 1, dtype=torch.float32), b.act(hh, wh, 1, dtype=torch.float32)
+            D["dpsip"], D["df"], D["dxt"], D["dphi"] = b.act(hh, wh, 32), b.act(hh, wh, Ck), b.act(h, w, Ck), b.act(Hg, Wg, Ck)
+
+    def _gate_forward(self, sp: _Shape, b: ops.PlanBuilder, k: int, xname: str, cat: str, bn_ws: list) -> list:
+        """attention gate k on the skip B[xname], into channels [0, Ck) of B[cat]"""
+        N, dtc, nf, B, V = sp.N, sp.dtc, self.nf, sp.B, A.view
+        pre, T = f"attn_{k}", sp.attn[k]
+        h, w, hh, wh, Ck = T["dims"]
+        Hg, Wg = sp.Rg
+        one = dict(ksize=1, pad=0)
+        sp.bn[k] = GateBatchNorm(self, V(T["wy"]), V(B[cat]), dtc, N * h * w, Ck, self._poff(pre + ".W.1.weight"), self._poff(pre + ".W.1.bias"),
+                                 _mod(self.owner, pre + ".W.1"), T["save"], bn_ws)
+        return [
+            b.conv(B[xname], T["theta"], ("f", pre + ".theta"), h, w, Ck, Ck, ksize=2, stride=2, pad=0),
+            b.conv(B["gated"], T["phi"], ("f", pre + ".phi"), Hg, Wg, 4 * nf, Ck, bias=b.P(pre + ".phi.bias"), **one),
+            ops.Call("srganfd_resize_bilinear", (0, V(T["phi"]), V(T["phiup"]), dtc, N, Hg, Wg, hh, wh, Ck), "resize"),
+            ops.Call("srganfd_add_relu", (V(T["theta"]), V(T["phiup"]), V(T["f"]), dtc, N * hh * wh, Ck), "add_relu"),
+            b.conv(T["f"], T["sig"], ("f", pre + ".psi"), hh, wh, Ck, 32, cout_store=1, bias=b.P(pre + ".psi.bias"), y_f32=True, **one),
+            ops.Call("srganfd_sigmoid", (T["sig"].data_ptr(), T["sig"].numel()), "sigmoid"),
+            b.resample(1, T["sig"], T["sigup"], hh, wh, 1, A.F32),
+            ops.Call("srganfd_gate_mul", (0, V(B[xname]), T["sigup"].data_ptr(), V(T["y"]), A.NULL_VIEW, None, dtc, N * h * w, Ck), "gate_mul"),
+            b.conv(T["y"], T["wy"], ("f", pre + ".W.0"), h, w, Ck, Ck, bias=b.P(pre + ".W.0.bias"), **one),
+            sp.bn[k],
+        ]
+
+    def _gate_backward(self, sp: _Shape, b: ops.PlanBuilder, k: int, xname: str, dcat, dgated_out, dgated_prev, last: bool) -> list:
+        """gate k from the gradient of its half of the concatenation buffer ``dcat``: its shares of B[xname]'s gradient stay in
+        D["dxg"] and D["dxt"]; the gating map's gradient goes to ``dgated_out``, ``dgated_prev`` added (``last``: and LeakyReLU' of
+        the gating map applied)"""
+        N, dtc, nf, B, V = sp.N, sp.dtc, self.nf, sp.B, A.view
+        pre, T = f"attn_{k}", sp.attn[k]
+        D = T["grad"]
+        h, w, hh, wh, Ck = T["dims"]
+        Hg, Wg = sp.Rg
+        one = dict(ksize=1, pad=0)
+        return [
+            GateBatchNormBwd(sp.bn[k], V(dcat), V(D["dwy"])),
+            b.wgrad(T["y"], D["dwy"], h, w, Ck, Ck, pre + ".W.0.weight", pre + ".W.0.bias", **one),
+            b.dgrad(D["dwy"], D["dy"], ("b", pre + ".W.0"), h, w, Ck, Ck, **one),
+            ops.Call("srganfd_gate_mul", (1, V(B[xname]), T["sigup"].data_ptr(), V(D["dy"]), V(D["dxg"]), D["dsigup"].data_ptr(), dtc, N * h * w, Ck),
+                     "gate_mul_bwd"),
+            b.resample(2, D["dsigup"], D["dsig"], hh, wh, 1, A.F32),
+            ops.Call("srganfd_sigmoid_bwd", (D["dsig"].data_ptr(), T["sig"].data_ptr(), D["dsig"].data_ptr(), D["dsig"].numel()), "sigmoid_bwd"),
+            ops.Call("srganfd_nchw_to_nhwc", (D["dsig"].data_ptr(), N, 1, hh, wh, V(D["dpsip"]), dtc, 32, None, None), "pad32"),
+            b.wgrad(T["f"], D["dpsip"], hh, wh, Ck, 32, pre + ".psi.weight", pre + ".psi.bias", cout_real=1, **one),
+            b.dgrad(D["dpsip"], D["df"], ("b", pre + ".psi"), hh, wh, 32, Ck, mask=T["f"], mask_slope=0.0, **one),
+            b.wgrad(B[xname], D["df"], h, w, Ck, Ck, pre + ".theta.weight", ksize=2, stride=2, pad=0),
+            *b.strided_dgrad(D["df"], D["dxt"], ("b", pre + ".theta"), hh, wh, Ck, Ck, 1, 0),      # 2x2 stride 2: four classes of 1x1 convs
+            ops.Call("srganfd_resize_bilinear", (1, V(D["df"]), V(D["dphi"]), dtc, N, Hg, Wg, hh, wh, Ck), "resize_bwd"),
+            b.wgrad(B["gated"], D["dphi"], Hg, Wg, 4 * nf, Ck, pre + ".phi.weight", pre + ".phi.bias", **one),
+            b.dgrad(D["dphi"], dgated_out, ("b", pre + ".phi"), Hg, Wg, Ck, 4 * nf, r1=dgated_prev, mask=B["gated"] if last else None, **one),
+        ]
+
+    def _plan_forward(self, sp: _Shape, b: ops.PlanBuilder, train: bool) -> None:
+        N, H, W, dtc, nf, V = sp.N, sp.H, sp.W, sp.dtc, self.nf, A.view
+        if H % 8 or W % 8:
+            raise A.SrganfdError("UNetDiscriminatorAesrgan input height/width must be multiples of 8")
+        # conv0 (in_ch -> nf) and conv9 (nf -> 1) on the thin-side kernels in the 16-bit modes (csrc/conv_thin.hip): 4-channel pitch
+        sp.thin_i, sp.thin_o = ops.thin_ok(dtc, nf, self.in_ch), ops.thin_ok(dtc, nf, 1)
+        self._forward_buffers(sp, b)
+        B, R = sp.B, sp.R
+        bn_ws = [b.buf(2048 * 256 + 3 * 256, dtype=torch.float32), None]
+        sp.bn = {}
+        lre = dict(act=A.ACT_LRELU, slope=0.2)
+        fw = [
+            b.image_to_features(sp.thin_i, B["xin"], B["x0"], "conv0", H, W, self.in_ch, nf, True, **lre),
+            b.conv(B["x0"], B["x1"], ("f", "conv1"), *R[0], nf, 2 * nf, stride=2, **lre),
+            b.conv(B["x1"], B["x2"], ("f", "conv2"), *R[1], 2 * nf, 4 * nf, stride=2, **lre),
+            b.conv(B["x2"], B["x3"], ("f", "conv3"), *R[2], 4 * nf, 8 * nf, stride=2, **lre),
+            b.conv(B["x3"], B["gated"], ("f", "gating"), *R[3], 8 * nf, 4 * nf, ksize=1, pad=1, **lre),
+        ]
+        for k, xname, cat in ((1, "x2", "cat1"), (2, "x1", "cat2"), (3, "x0", "cat3")):
+            fw += self._gate_forward(sp, b, k, xname, cat, bn_ws)
+        fw += [
+            b.resample(1, B["x3"], B["b3"], *R[3], 8 * nf),
+            b.conv(B["b3"], V(B["cat1"], c0=4 * nf), ("f", "cat_1.convU"), *R[2], 8 * nf, 4 * nf, **lre),
+            b.conv(B["cat1"], B["x4"], ("f", "conv4"), *R[2], 8 * nf, 4 * nf, **lre),
+            b.resample(1, B["x4"], B["b4"], *R[2], 4 * nf),
+            b.conv(B["b4"], V(B["cat2"], c0=2 * nf), ("f", "cat_2.convU"), *R[1], 4 * nf, 2 * nf, **lre),
+            b.conv(B["cat2"], B["x5"], ("f", "conv5"), *R[1], 4 * nf, 2 * nf, **lre),
+            b.resample(1, B["x5"], B["b5"], *R[1], 2 * nf),
+            b.conv(B["b5"], V(B["cat3"], c0=nf), ("f", "cat_3.convU"), *R[0], 2 * nf, nf, **lre),
+            b.conv(B["cat3"], B["x6"], ("f", "conv6"), *R[0], 2 * nf, nf, **lre),
+            b.conv(B["x6"], B["c7"], ("f", "conv7"), *R[0], nf, nf, **lre),
+            b.conv(B["c7"], B["c8"], ("f", "conv8"), *R[0], nf, nf, **lre),
+            # conv9 writes the logits, allocated per forward
+            ops.PerCall(b.features_to_image(sp.thin_o, B["c8"], 0, 1, "conv9", H, W, 1, nf, False)),
+        ]
+        sp.fw = fw
+
+    def _plan_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        N, H, W, nf, V = sp.N, sp.H, sp.W, self.nf, A.view
+        self._backward_buffers(sp, b)
+        B, G, R = sp.B, sp.G, sp.R
+        Hg, Wg = sp.Rg
         P0 = N * H * W
+        grad = lambda k, name: sp.attn[k]["grad"][name]
 
-        def attn_bwd(k, xname, dcat, dgated_out, dgated_prev, last):
-            pre = f"attn_{k}"
-            T = sp.attn[k]
-            h, w, hh, wh, Ck = T["dims"]
-            D = T["grad"] = {}
-            D["dwy"], D["dy"], D["dxg"] = new(h, w, Ck), new(h, w, Ck), new(h, w, Ck)
-            D["dsigup"] = torch.empty(N, h, w, 1, dtype=torch.float32, device=device)
-            D["dsig"] = torch.empty(N, hh, wh, 1, dtype=torch.float32, device=device)
-            D["dpsip"], D["df"], D["dxt"], D["dphi"] = new(hh, wh, 32), new(hh, wh, Ck), new(h, w, Ck), new(Hg, Wg, Ck)
-            items = [
-                GateBatchNormBwd(sp.bn[k], V(dcat), V(D["dwy"])),
-                wg(pre + ".W.0", T["y"], D["dwy"], h, w, Ck, Ck, k=1, pad=0, bias=True),
-                cv(V(D["dwy"]), V(D["dy"]), Wp("b", pre + ".W.0"), N, h, w, Ck, Ck, ksize=1, pad=0),
-                ops.Call("srganfd_gate_mul", (1, V(B[xname]), T["sigup"].data_ptr(), V(D["dy"]), V(D["dxg"]), D["dsigup"].data_ptr(), dtc, N * h * w, Ck),
-                         "gate_mul_bwd"),
-                rs(2, V(D["dsigup"]), V(D["dsig"]), hh, wh, 1, A.F32),
-                ops.Call("srganfd_sigmoid_bwd", (D["dsig"].data_ptr(), T["sig"].data_ptr(), D["dsig"].data_ptr(), D["dsig"].numel()), "sigmoid_bwd"),
-                ops.Call("srganfd_nchw_to_nhwc", (D["dsig"].data_ptr(), N, 1, hh, wh, V(D["dpsip"]), dtc, 32, None, None), "pad32"),
-                wg(pre + ".psi", T["f"], D["dpsip"], hh, wh, Ck, 32, k=1, pad=0, cout_real=1, bias=True),
-                cv(V(D["dpsip"]), V(D["df"]), Wp("b", pre + ".psi"), N, hh, wh, 32, Ck, ksize=1, pad=0, mask=V(T["f"]), mask_slope=0.0),
-                wg(pre + ".theta", B[xname], D["df"], h, w, Ck, Ck, k=2, s=2, pad=0),
-            ]
-            items += strided_dgrad(("b", pre + ".theta"), 1, D["df"], D["dxt"], hh, wh, Ck, Ck)
-            items += [
-                ops.Call("srganfd_resize_bilinear", (1, V(D["df"]), V(D["dphi"]), dtc, N, Hg, Wg, hh, wh, Ck), "resize_bwd"),
-                wg(pre + ".phi", B["gated"], D["dphi"], Hg, Wg, 4 * nf, Ck, k=1, pad=0, bias=True),
-                cv(V(D["dphi"]), V(dgated_out), Wp("b", pre + ".phi"), N, Hg, Wg, Ck, 4 * nf, ksize=1, pad=0,
-                   r1=V(dgated_prev) if dgated_prev is not None else A.NULL_VIEW, r1_scale=1.0 if dgated_prev is not None else 0.0,
-                   mask=V(B["gated"]) if last else A.NULL_VIEW, mask_slope=0.2),
-            ]
-            return items
+        def sn_wgrad(name, x, dy, h, w, cin, cout, **kw):
+            """weight gradient of a spectral-normalised layer: dL/d(W/sigma) goes to the scratch gradient, SnGradBatch finishes the job"""
+            return b.wgrad(x, dy, h, w, cin, cout, name + ".weight_orig", sn=SN_INDEX[name], **kw)
 
+        def up_block(k, cat, dcat, bprev, dbprev, dxprev, xprev, conv, dx, h, w, c, npix):
+            """conv{4,5,6} over the concatenation buffer ``cat`` and the convU in front of its upper half, down to the LeakyReLU'-masked
+            gradient ``dxprev`` of the layer below (``xprev``, half the size; None: the bottom of the U, which the gating conv masks)"""
+            out = [sn_wgrad(conv, B[cat], G[dx], h, w, 2 * c, c),
+                   b.dgrad(G[dx], G[dcat], ("b", conv), h, w, c, 2 * c),
+                   b.lrelu_bwd(V(G[dcat], c0=c), V(B[cat], c0=c), V(G[dcat], c0=c), npix, c),
+                   sn_wgrad(f"cat_{k}.convU", B[bprev], V(G[dcat], c0=c), h, w, 2 * c, c),
+                   b.dgrad(V(G[dcat], c0=c), G[dbprev], ("b", f"cat_{k}.convU"), h, w, c, 2 * c),
+                   b.resample(2, G[dbprev], G[dxprev], h // 2, w // 2, 2 * c)]
+            if xprev is not None:
+                out.append(b.lrelu_bwd(G[dxprev], B[xprev], G[dxprev], npix // 4, 2 * c))
+            return out
         bw = [
-            ops.image_wgrad(dtc, sp.thin_o, wplans, sp.dl, B["c8"], P("conv9.weight"), self._poff("conv9.weight"), self._poff("conv9.bias"), sp.thin_ws,
-                            N, H, W, 1, nf, False),
-            ops.image_to_features(dtc, sp.thin_o, sp.dl, V(G["g8"]), P("conv9.weight"), Wp("b", "conv9"), N, H, W, 1, nf, False, flip=True,
-                                  mask=V(B["c8"]), mask_slope=0.2),
-            wg("conv8", B["c7"], G["g8"], H, W, nf, nf, sn=True),
-            cv(V(G["g8"]), V(G["g7"]), Wp("b", "conv8"), N, H, W, nf, nf, mask=V(B["c7"]), mask_slope=0.2),
-            wg("conv7", B["x6"], G["g7"], H, W, nf, nf, sn=True),
-            cv(V(G["g7"]), V(G["g6"]), Wp("b", "conv7"), N, H, W, nf, nf, mask=V(B["x6"]), mask_slope=0.2),
-            wg("conv6", B["cat3"], G["g6"], H, W, 2 * nf, nf, sn=True),
-            cv(V(G["g6"]), V(G["dc3"]), Wp("b", "conv6"), N, H, W, nf, 2 * nf),
-            lb(V(G["dc3"], c0=nf), V(B["cat3"], c0=nf), V(G["dc3"], c0=nf), P0, nf),
-            wg("cat_3.convU", B["b5"], G["dc3"], H, W, 2 * nf, nf, sn=True, dy_c0=nf),
-            cv(V(G["dc3"], c0=nf), V(G["db5"]), Wp("b", "cat_3.convU"), N, H, W, nf, 2 * nf),
-            rs(2, V(G["db5"]), V(G["dx5"]), *R[1], 2 * nf),
-            lb(V(G["dx5"]), V(B["x5"]), V(G["dx5"]), P0 // 4, 2 * nf),
+            b.image_wgrad(sp.thin_o, sp.dl, B["c8"], "conv9", sp.thin_ws, H, W, 1, nf, False),
+            b.image_to_features(sp.thin_o, sp.dl, G["g8"], "conv9", H, W, 1, nf, False, flip=True, mask=V(B["c8"]), mask_slope=0.2),
+            sn_wgrad("conv8", B["c7"], G["g8"], H, W, nf, nf),
+            b.dgrad(G["g8"], G["g7"], ("b", "conv8"), H, W, nf, nf, mask=B["c7"]),
+            sn_wgrad("conv7", B["x6"], G["g7"], H, W, nf, nf),
+            b.dgrad(G["g7"], G["g6"], ("b", "conv7"), H, W, nf, nf, mask=B["x6"]),
         ]
-        bw += attn_bwd(3, "x0", G["dc3"], G["dgated"][0], None, False)
-        bw += [
-            wg("conv5", B["cat2"], G["dx5"], *R[1], 4 * nf, 2 * nf, sn=True),
-            cv(V(G["dx5"]), V(G["dc2"]), Wp("b", "conv5"), N, *R[1], 2 * nf, 4 * nf),
-            lb(V(G["dc2"], c0=2 * nf), V(B["cat2"], c0=2 * nf), V(G["dc2"], c0=2 * nf), P0 // 4, 2 * nf),
-            wg("cat_2.convU", B["b4"], G["dc2"], *R[1], 4 * nf, 2 * nf, sn=True, dy_c0=2 * nf),
-            cv(V(G["dc2"], c0=2 * nf), V(G["db4"]), Wp("b", "cat_2.convU"), N, *R[1], 2 * nf, 4 * nf),
-            rs(2, V(G["db4"]), V(G["dx4"]), *R[2], 4 * nf),
-            lb(V(G["dx4"]), V(B["x4"]), V(G["dx4"]), P0 // 16, 4 * nf),
-        ]
-        bw += attn_bwd(2, "x1", G["dc2"], G["dgated"][1], G["dgated"][0], False)
-        bw += [
-            wg("conv4", B["cat1"], G["dx4"], *R[2], 8 * nf, 4 * nf, sn=True),
-            cv(V(G["dx4"]), V(G["dc1"]), Wp("b", "conv4"), N, *R[2], 4 * nf, 8 * nf),
-            lb(V(G["dc1"], c0=4 * nf), V(B["cat1"], c0=4 * nf), V(G["dc1"], c0=4 * nf), P0 // 16, 4 * nf),
-            wg("cat_1.convU", B["b3"], G["dc1"], *R[2], 8 * nf, 4 * nf, sn=True, dy_c0=4 * nf),
-            cv(V(G["dc1"], c0=4 * nf), V(G["db3"]), Wp("b", "cat_1.convU"), N, *R[2], 4 * nf, 8 * nf),
-            rs(2, V(G["db3"]), V(G["dx3a"]), *R[3], 8 * nf),
-        ]
-        bw += attn_bwd(1, "x2", G["dc1"], G["dgated"][2], G["dgated"][1], True)
+        bw += up_block(3, "cat3", "dc3", "b5", "db5", "dx5", "x5", "conv6", "g6", *R[0], nf, P0)
+        bw += self._gate_backward(sp, b, 3, "x0", G["dc3"], G["dgated"][0], None, False)
+        bw += up_block(2, "cat2", "dc2", "b4", "db4", "dx4", "x4", "conv5", "dx5", *R[1], 2 * nf, P0 // 4)
+        bw += self._gate_backward(sp, b, 2, "x1", G["dc2"], G["dgated"][1], G["dgated"][0], False)
+        bw += up_block(1, "cat1", "dc1", "b3", "db3", "dx3a", None, "conv4", "dx4", *R[2], 4 * nf, P0 // 16)
+        bw += self._gate_backward(sp, b, 1, "x2", G["dc1"], G["dgated"][2], G["dgated"][1], True)
         dgated = G["dgated"][2]      # sum of the three gates' gradients, LeakyReLU' of `gated` applied
         bw += [
-            wg("gating", B["x3"], dgated, *R[3], 8 * nf, 4 * nf, k=1, pad=1, sn=True),
-            cv(V(dgated), V(G["dx3"]), Wp("b", "gating"), N, Hg, Wg, 4 * nf, 8 * nf, ksize=1, pad=-1, r1=V(G["dx3a"]), r1_scale=1.0,
-               mask=V(B["x3"]), mask_slope=0.2),
-            wg("conv3", B["x2"], G["dx3"], *R[2], 4 * nf, 8 * nf, s=2, sn=True),
+            sn_wgrad("gating", B["x3"], dgated, *R[3], 8 * nf, 4 * nf, ksize=1, pad=1),
+            b.dgrad(dgated, G["dx3"], ("b", "gating"), Hg, Wg, 4 * nf, 8 * nf, r1=G["dx3a"], mask=B["x3"], ksize=1, pad=-1),
+            sn_wgrad("conv3", B["x2"], G["dx3"], *R[2], 4 * nf, 8 * nf, stride=2),
+            # the 3x3 stride-2 data gradients: 4 parity classes of 2x2-tap convs, each with its gate's two shares of the skip's gradient
+            *b.strided_dgrad(G["dx3"], G["dx2"], ("b", "conv3"), *R[3], 8 * nf, 4 * nf, 2, 0, r1=grad(1, "dxg"), r2=grad(1, "dxt"), mask=B["x2"]),
+            sn_wgrad("conv2", B["x1"], G["dx2"], *R[1], 2 * nf, 4 * nf, stride=2),
+            *b.strided_dgrad(G["dx2"], G["dx1"], ("b", "conv2"), *R[2], 4 * nf, 2 * nf, 2, 0, r1=grad(2, "dxg"), r2=grad(2, "dxt"), mask=B["x1"]),
+            sn_wgrad("conv1", B["x0"], G["dx1"], *R[0], nf, 2 * nf, stride=2),
+            *b.strided_dgrad(G["dx1"], G["dx0"], ("b", "conv1"), *R[1], 2 * nf, nf, 2, 0, r1=grad(3, "dxg"), r2=grad(3, "dxt"), mask=B["x0"]),
+            b.image_wgrad(sp.thin_i, B["xin"], G["dx0"], "conv0", sp.thin_ws, H, W, self.in_ch, nf, True),
         ]
-        bw += strided_dgrad(("b", "conv3"), 2, G["dx3"], G["dx2"], *R[3], 8 * nf, 4 * nf,
-                            r1=sp.attn[1]["grad"]["dxg"], r2=sp.attn[1]["grad"]["dxt"], mask=B["x2"])
-        bw.append(wg("conv2", B["x1"], G["dx2"], *R[1], 2 * nf, 4 * nf, s=2, sn=True))
-        bw += strided_dgrad(("b", "conv2"), 2, G["dx2"], G["dx1"], *R[2], 4 * nf, 2 * nf,
-                            r1=sp.attn[2]["grad"]["dxg"], r2=sp.attn[2]["grad"]["dxt"], mask=B["x1"])
-        bw.append(wg("conv1", B["x0"], G["dx1"], *R[0], nf, 2 * nf, s=2, sn=True))
-        bw += strided_dgrad(("b", "conv1"), 2, G["dx1"], G["dx0"], *R[1], 2 * nf, nf,
-                            r1=sp.attn[3]["grad"]["dxg"], r2=sp.attn[3]["grad"]["dxt"], mask=B["x0"])
-        bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, B["xin"], G["dx0"], P("conv0.weight"), self._poff("conv0.weight"), self._poff("conv0.bias"),
-                                  sp.thin_ws, N, H, W, self.in_ch, nf, True))
-        sp.dx_conv = first_layer_dgrad(ops.features_to_image(dtc, sp.thin_i, V(G["dx0"]), sp.dxp, 4, P("conv0.weight"), Wp("b", "conv0"), N, H, W,
-                                                             self.in_ch, nf, True, flip=True))
+        sp.dx_conv = first_layer_dgrad(b.features_to_image(sp.thin_i, G["dx0"], sp.dxp, 4, "conv0", H, W, self.in_ch, nf, True, flip=True))
         sp.bw = bw
-        self._backward_workspaces(sp, wplans, pk)
+        self._backward_workspaces(sp, b)
 
     # ---- execution: EngineBase's passes; the attention maps of the last forward are kept on the module ----
     def forward(self, x: Tensor, training: bool) -> Tensor:

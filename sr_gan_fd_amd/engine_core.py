@@ -2,7 +2,7 @@
 that runs its power iteration, the last item of their backward lists (SnGradBatch) and the plan data that is the same for all three.
 The passes over the launch lists and the autograd glue are engine.py's (EngineBase).
 
-A subclass describes its network: the layer tables, ``_build_pack``, ``_plan`` / ``_plan_backward`` (the launch lists) and, beside
+A subclass describes its network: the layer tables, ``_build_pack``, ``_plan_forward`` / ``_plan_backward`` (the launch lists) and, beside
 itself, the launch items only it has (BatchNorm).  Its plans always carry a backward list.  Of what EngineBase reads from a plan, a
 subclass sets sp.xin (the NHWC input buffer: 4-channel pitch for the thin kernels, else padded to 32), sp.dl (NHWC buffer of the
 logits' gradient), sp.dxp and sp.dx_conv (the fp32 NHWC4 gradient of the input and the item, ``first_layer_dgrad``, that writes it);
@@ -56,6 +56,7 @@ def first_layer_dgrad(item):
 class DiscriminatorEngineCore(EngineBase):
     what = "discriminator"             # the reference class's name, for messages
     out_ch = 1                         # the logits
+    always_backward = True
 
     def __init__(self, owner: nn.Module, in_ch: int, sn_params: Sequence[str] = ()):
         """sn_params: names of the spectral-normalised weights (``....weight_orig``) in the order of their 1/sigma slots: layer l's
@@ -90,17 +91,17 @@ class DiscriminatorEngineCore(EngineBase):
         pk["table"].run(flat, pk["buf"], pk.get("scalars"))
         return pk
 
-    def _backward_workspaces(self, sp: _Shape, wplans: ops.WgradPlans, pk: dict) -> None:
+    def _backward_workspaces(self, sp: _Shape, b: ops.PlanBuilder) -> None:
         """what every discriminator's plan ends with: where the passes enter and leave it (EngineBase), and the workspaces"""
         sp.x_in, sp.dy_in, sp.dx_out = (A.view(sp.xin), sp.xin.shape[-1]), (A.view(sp.dl), sp.dl.shape[-1]), (A.view(sp.dxp), A.F32)
         sp.hs, sp.ws = sp.dl.shape[1:3]
         sp.per_call = (sp.N, 1, sp.hs, sp.ws)
-        sp.wg_ws = wplans.workspace()
+        sp.wg_ws = b.wplans.workspace()
         # spectral-normalised layers write dL/d(W/sigma) here, each into its own range; passes with frozen parameters also send
         # BatchNorm's dgamma / dbeta here
         sp.gtmp = torch.zeros(self.fp.total, dtype=torch.float32, device=sp.device)
         sn_ws = torch.empty(len(self.sn) * A.SN_GRAD_WS_FLOATS, dtype=torch.float32, device=sp.device)
-        sp.bw.append(SnGradBatch(self, [it.sn for it in sp.bw if isinstance(it, ops.Wgrad) and it.sn is not None], pk.get("scalars"), sn_ws))
+        sp.bw.append(SnGradBatch(self, [it.sn for it in sp.bw if isinstance(it, ops.Wgrad) and it.sn is not None], b.pk.get("scalars"), sn_ws))
 
     def forward(self, x: Tensor, training: bool) -> Tensor:
         """the logits of one forward: always on a plan with a backward list, in the module's mode ``training``"""

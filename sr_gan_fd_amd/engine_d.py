@@ -55,129 +55,85 @@ class DiscriminatorEngine(DiscriminatorEngineCore):
         return pb.finish(device)
 
     # ---- per-shape plan ----
-    def _plan(self, N, S1, S2, dt, dtc, device, pk, train=True) -> _Shape:
-        key = (N, S1, S2, dtc, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
-        sp = self.shapes.get(key)
-        if sp is not None:
-            return sp
-        if S1 % 8 or S2 % 8:
+    def _plan_forward(self, sp: _Shape, b: ops.PlanBuilder, train: bool) -> None:
+        H, W = sp.H, sp.W
+        if H % 8 or W % 8:
             raise A.SrganfdError("DiscriminatorUNet input height/width must be multiples of 8")
-        sp = _Shape()
-        sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, S1, S2, dt, dtc, device
-        V = A.view
-        fptr, wptr = self.fp.flat.data_ptr(), pk["buf"].data_ptr()
-        O = pk["offs"]
-
-        def new(h, w, c, dtype=dt):
-            return torch.empty(N, h, w, c, dtype=dtype, device=device)
-        H, W = S1, S2
         # conv1 (in_ch -> 64) and conv4 (64 -> out_ch) on the thin-side kernels in the 16-bit modes (csrc/conv_thin.hip): 4-channel pitch
-        sp.thin_i, sp.thin_o = ops.thin_ok(dtc, 64, self.in_ch), ops.thin_ok(dtc, 64, self.out_ch)
-        sp.xin = new(H, W, 4 if sp.thin_i else 32)
-        sp.out1 = new(H, W, 64)
-        sp.d1, sp.d2, sp.d3 = new(H // 2, W // 2, 128), new(H // 4, W // 4, 256), new(H // 8, W // 8, 512)
-        sp.b3, sp.u1 = new(H // 4, W // 4, 512), new(H // 4, W // 4, 256)
-        sp.b2, sp.u2 = new(H // 2, W // 2, 256), new(H // 2, W // 2, 128)
-        sp.b1, sp.u3 = new(H, W, 128), new(H, W, 64)
-        sp.c2, sp.c3 = new(H, W, 64), new(H, W, 64)
+        sp.thin_i, sp.thin_o = ops.thin_ok(sp.dtc, 64, self.in_ch), ops.thin_ok(sp.dtc, 64, self.out_ch)
+        sp.xin = b.act(H, W, 4 if sp.thin_i else 32)
+        sp.out1 = b.act(H, W, 64)
+        sp.d1, sp.d2, sp.d3 = b.act(H // 2, W // 2, 128), b.act(H // 4, W // 4, 256), b.act(H // 8, W // 8, 512)
+        sp.b3, sp.u1 = b.act(H // 4, W // 4, 512), b.act(H // 4, W // 4, 256)
+        sp.b2, sp.u2 = b.act(H // 2, W // 2, 256), b.act(H // 2, W // 2, 128)
+        sp.b1, sp.u3 = b.act(H, W, 128), b.act(H, W, 64)
+        sp.c2, sp.c3 = b.act(H, W, 64), b.act(H, W, 64)
         # LeakyReLU outputs before the skip adds (exact derivative sign in backward)
-        sp.a1, sp.a2, sp.a3 = new(H // 4, W // 4, 256), new(H // 2, W // 2, 128), new(H, W, 64)
-        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
-        rs = lambda op, a, b, h, w, c: ops.Call("srganfd_resample", (op, a, b, dtc, N, h, w, c), "resample")
-        lre = dict(act=A.ACT_LRELU, slope=0.2)
-        w1, b1 = fptr + 4 * self._poff("conv1.weight"), fptr + 4 * self._poff("conv1.bias")
-        fw = [
-            ops.image_to_features(dtc, sp.thin_i, sp.xin, V(sp.out1), w1, wptr + O[("f", "conv1")], N, H, W, self.in_ch, 64, True, bias=b1),
-            cv(V(sp.out1), V(sp.d1), wptr + O[("f", "down_block1")], N, H, W, 64, 128, ksize=4, stride=2, **lre),
-            cv(V(sp.d1), V(sp.d2), wptr + O[("f", "down_block2")], N, H // 2, W // 2, 128, 256, ksize=4, stride=2, **lre),
-            cv(V(sp.d2), V(sp.d3), wptr + O[("f", "down_block3")], N, H // 4, W // 4, 256, 512, ksize=4, stride=2, **lre),
-            rs(1, V(sp.d3), V(sp.b3), H // 8, W // 8, 512),
-            cv(V(sp.b3), V(sp.u1), wptr + O[("f", "up_block1")], N, H // 4, W // 4, 512, 256, r1=V(sp.d2), r1_scale=1.0, y2=V(sp.a1), **lre),
-            rs(1, V(sp.u1), V(sp.b2), H // 4, W // 4, 256),
-            cv(V(sp.b2), V(sp.u2), wptr + O[("f", "up_block2")], N, H // 2, W // 2, 256, 128, r1=V(sp.d1), r1_scale=1.0, y2=V(sp.a2), **lre),
-            rs(1, V(sp.u2), V(sp.b1), H // 2, W // 2, 128),
-            cv(V(sp.b1), V(sp.u3), wptr + O[("f", "up_block3")], N, H, W, 128, 64, r1=V(sp.out1), r1_scale=1.0, y2=V(sp.a3), **lre),
-            cv(V(sp.u3), V(sp.c2), wptr + O[("f", "conv2")], N, H, W, 64, 64, **lre),
-            cv(V(sp.c2), V(sp.c3), wptr + O[("f", "conv3")], N, H, W, 64, 64, **lre),
-        ]
-        # conv4 writes the logits, allocated per forward
-        fw.append(ops.PerCall(ops.features_to_image(dtc, sp.thin_o, V(sp.c3), 0, 1, fptr + 4 * self._poff("conv4.weight"), wptr + O[("f", "conv4")],
-                                                    N, H, W, 1, 64, False, bias=fptr + 4 * self._poff("conv4.bias"))))
-        sp.fw = fw
-        self._plan_backward(sp, pk)
-        self.shapes[key] = sp
-        return sp
-
-    def _plan_backward(self, sp: _Shape, pk: dict) -> None:
-        N, H, W, dt, dtc, device = sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device
+        sp.a1, sp.a2, sp.a3 = b.act(H // 4, W // 4, 256), b.act(H // 2, W // 2, 128), b.act(H, W, 64)
         V = A.view
-        wptr, O = pk["buf"].data_ptr(), pk["offs"]
+        lre = dict(act=A.ACT_LRELU, slope=0.2)
+        sp.fw = [
+            b.image_to_features(sp.thin_i, sp.xin, sp.out1, "conv1", H, W, self.in_ch, 64, True),
+            b.conv(sp.out1, sp.d1, ("f", "down_block1"), H, W, 64, 128, ksize=4, stride=2, **lre),
+            b.conv(sp.d1, sp.d2, ("f", "down_block2"), H // 2, W // 2, 128, 256, ksize=4, stride=2, **lre),
+            b.conv(sp.d2, sp.d3, ("f", "down_block3"), H // 4, W // 4, 256, 512, ksize=4, stride=2, **lre),
+            b.resample(1, sp.d3, sp.b3, H // 8, W // 8, 512),
+            b.conv(sp.b3, sp.u1, ("f", "up_block1"), H // 4, W // 4, 512, 256, r1=V(sp.d2), r1_scale=1.0, y2=V(sp.a1), **lre),
+            b.resample(1, sp.u1, sp.b2, H // 4, W // 4, 256),
+            b.conv(sp.b2, sp.u2, ("f", "up_block2"), H // 2, W // 2, 256, 128, r1=V(sp.d1), r1_scale=1.0, y2=V(sp.a2), **lre),
+            b.resample(1, sp.u2, sp.b1, H // 2, W // 2, 128),
+            b.conv(sp.b1, sp.u3, ("f", "up_block3"), H, W, 128, 64, r1=V(sp.out1), r1_scale=1.0, y2=V(sp.a3), **lre),
+            b.conv(sp.u3, sp.c2, ("f", "conv2"), H, W, 64, 64, **lre),
+            b.conv(sp.c2, sp.c3, ("f", "conv3"), H, W, 64, 64, **lre),
+            # conv4 writes the logits, allocated per forward
+            ops.PerCall(b.features_to_image(sp.thin_o, sp.c3, 0, 1, "conv4", H, W, 1, 64, False)),
+        ]
 
-        def new(h, w, c, dtype=dt):
-            return torch.empty(N, h, w, c, dtype=dtype, device=device)
-        sp.dl = new(H, W, 4 if sp.thin_o else 32)
-        fptr = self.fp.flat.data_ptr()
-        sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device) if (sp.thin_i or sp.thin_o) else None
-        gA, gB, gC, gD = new(H, W, 64), new(H, W, 64), new(H, W, 128), new(H, W, 64)
-        h1, h2, h3, h4 = new(H // 2, W // 2, 128), new(H // 2, W // 2, 128), new(H // 2, W // 2, 256), new(H // 2, W // 2, 128)
-        q1, q2, q3, q4 = new(H // 4, W // 4, 256), new(H // 4, W // 4, 256), new(H // 4, W // 4, 512), new(H // 4, W // 4, 256)
-        e1 = new(H // 8, W // 8, 512)
-        sp.dxp = new(H, W, 4, dtype=torch.float32)
+    def _plan_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        H, W = sp.H, sp.W
+        sp.dl = b.act(H, W, 4 if sp.thin_o else 32)
+        sp.thin_ws = b.thin_ws(sp.thin_i, sp.thin_o)
+        gA, gB, gC, gD = b.act(H, W, 64), b.act(H, W, 64), b.act(H, W, 128), b.act(H, W, 64)
+        h1, h2, h3, h4 = b.act(H // 2, W // 2, 128), b.act(H // 2, W // 2, 128), b.act(H // 2, W // 2, 256), b.act(H // 2, W // 2, 128)
+        q1, q2, q3, q4 = b.act(H // 4, W // 4, 256), b.act(H // 4, W // 4, 256), b.act(H // 4, W // 4, 512), b.act(H // 4, W // 4, 256)
+        e1 = b.act(H // 8, W // 8, 512)
+        sp.dxp = b.act(H, W, 4, dtype=torch.float32)
         sp.keep = [gA, gB, gC, gD, h1, h2, h3, h4, q1, q2, q3, q4, e1]
-        wplans = ops.WgradPlans(device, dtc, N)
 
-        def wg(name, x, dy, h, w, cin, cout, sn_index=None, k=3, s=1, cin_real=None, cout_real=None, bias=False):
-            """weight gradient: plain params write straight into the flat gradient; SN layers write
-            dL/d(W/sigma) into the temp buffer and srganfd_spectral_norm_grad finishes the job."""
-            pname = self.sn[sn_index][0] if sn_index is not None else f"{name}.weight"
-            plan = wplans.conv(h, w, cin, cout, self._poff(pname), self._poff(f"{name}.bias") if bias else -1, cin_real, cout_real,
-                               ksize=k, stride=s, pad=1)
-            return ops.Wgrad(plan, V(x), V(dy), sn=sn_index)
-
-        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
-        # bilinear-x2 backward + LeakyReLU' of the upsampled layer in one pass: raw gradient (the skip connection's share) and masked one
-        rsl = lambda dy, raw, act, masked, h, w, c: ops.Call("srganfd_resample_bwd_lrelu", (dy, raw, act, masked, dtc, N, h, w, c, 0.2), "resample_bwd_lrelu")
-
-        def s2_dgrad(name, dy, dx, hd, wd, cout, cin, r1, mask):
-            """data gradient of a 4x4 stride-2 conv: 4 output-parity classes (2x2-tap convs over dy)"""
-            return ops.parity_class_launches(
-                dtc, V(dy), V(dx), wptr, [O[("b", name, c)] for c in range(4)], N, hd, wd, cout, cin, 2, 1,
-                **ops.dgrad_epilogue(r1=None if r1 is None else V(r1), mask=None if mask is None else V(mask)))
-
-        w4raw, w1raw = fptr + 4 * self._poff("conv4.weight"), fptr + 4 * self._poff("conv1.weight")
+        def sn_wgrad(l, x, dy, h, w, cin, cout, **kw):
+            """weight gradient of spectral-normalised layer l: dL/d(W/sigma) goes to the scratch gradient, SnGradBatch finishes the job"""
+            return b.wgrad(x, dy, h, w, cin, cout, self.sn[l][0], sn=l, **kw)
+        down = dict(ksize=4, stride=2, pad=1)
         bw = [
-            ops.image_wgrad(dtc, sp.thin_o, wplans, sp.dl, sp.c3, w4raw, self._poff("conv4.weight"), self._poff("conv4.bias"), sp.thin_ws,
-                            N, H, W, 1, 64, False),
-            ops.image_to_features(dtc, sp.thin_o, sp.dl, V(gA), w4raw, wptr + O[("b", "conv4")], N, H, W, 1, 64, False, flip=True,
-                                  mask=V(sp.c3), mask_slope=0.2),
-            wg("conv3", sp.c2, gA, H, W, 64, 64, sn_index=7),
-            cv(V(gA), V(gB), wptr + O[("b", "conv3")], N, H, W, 64, 64, mask=V(sp.c2), mask_slope=0.2),
-            wg("conv2", sp.u3, gB, H, W, 64, 64, sn_index=6),
+            b.image_wgrad(sp.thin_o, sp.dl, sp.c3, "conv4", sp.thin_ws, H, W, 1, 64, False),
+            b.image_to_features(sp.thin_o, sp.dl, gA, "conv4", H, W, 1, 64, False, flip=True, mask=A.view(sp.c3), mask_slope=0.2),
+            sn_wgrad(7, sp.c2, gA, H, W, 64, 64),
+            b.dgrad(gA, gB, ("b", "conv3"), H, W, 64, 64, mask=sp.c2),
+            sn_wgrad(6, sp.u3, gB, H, W, 64, 64),
             # u3 = lrelu(z3) + out1: the conv's two outputs are d u3 (y2: the skip's share, added into d out1 below) and
             # d z3 = d u3 * lrelu'(a3) (y, after the mask) -- no separate LeakyReLU-backward pass over the 512^2 tensor
-            cv(V(gB), V(gD), wptr + O[("b", "conv2")], N, H, W, 64, 64, y2=V(gA), mask=V(sp.a3), mask_slope=0.2),   # gA = d u3, gD = d z3
-            wg("up_block3", sp.b1, gD, H, W, 128, 64, sn_index=5),
-            cv(V(gD), V(gC), wptr + O[("b", "up_block3")], N, H, W, 64, 128),            # gC = d b1
-            rsl(V(gC), V(h1), V(sp.a2), V(h2), H // 2, W // 2, 128),                     # h1 = d u2, h2 = d z2
-            wg("up_block2", sp.b2, h2, H // 2, W // 2, 256, 128, sn_index=4),
-            cv(V(h2), V(h3), wptr + O[("b", "up_block2")], N, H // 2, W // 2, 128, 256),  # h3 = d b2
-            rsl(V(h3), V(q1), V(sp.a1), V(q2), H // 4, W // 4, 256),                     # q1 = d u1, q2 = d z1
-            wg("up_block1", sp.b3, q2, H // 4, W // 4, 512, 256, sn_index=3),
-            cv(V(q2), V(q3), wptr + O[("b", "up_block1")], N, H // 4, W // 4, 256, 512),  # q3 = d b3
-            rsl(V(q3), A.NULL_VIEW, V(sp.d3), V(e1), H // 8, W // 8, 512),               # e1 = d d3 (pre-activation)
-            wg("down_block3", sp.d2, e1, H // 4, W // 4, 256, 512, sn_index=2, k=4, s=2),
+            b.dgrad(gB, gD, ("b", "conv2"), H, W, 64, 64, mask=sp.a3, y2=A.view(gA)),              # gA = d u3, gD = d z3
+            sn_wgrad(5, sp.b1, gD, H, W, 128, 64),
+            b.dgrad(gD, gC, ("b", "up_block3"), H, W, 64, 128),                                  # gC = d b1
+            b.resample_bwd_lrelu(gC, h1, sp.a2, h2, H // 2, W // 2, 128),                        # h1 = d u2, h2 = d z2
+            sn_wgrad(4, sp.b2, h2, H // 2, W // 2, 256, 128),
+            b.dgrad(h2, h3, ("b", "up_block2"), H // 2, W // 2, 128, 256),                       # h3 = d b2
+            b.resample_bwd_lrelu(h3, q1, sp.a1, q2, H // 4, W // 4, 256),                        # q1 = d u1, q2 = d z1
+            sn_wgrad(3, sp.b3, q2, H // 4, W // 4, 512, 256),
+            b.dgrad(q2, q3, ("b", "up_block1"), H // 4, W // 4, 256, 512),                       # q3 = d b3
+            b.resample_bwd_lrelu(q3, A.NULL_VIEW, sp.d3, e1, H // 8, W // 8, 512),               # e1 = d d3 (pre-activation)
+            sn_wgrad(2, sp.d2, e1, H // 4, W // 4, 256, 512, **down),
         ]
-        bw += s2_dgrad("down_block3", e1, q4, H // 8, W // 8, 512, 256, q1, sp.d2)       # q4 = (d d2 + d u1) * lrelu'(d2)
-        bw.append(wg("down_block2", sp.d1, q4, H // 2, W // 2, 128, 256, sn_index=1, k=4, s=2))
-        bw += s2_dgrad("down_block2", q4, h4, H // 4, W // 4, 256, 128, h1, sp.d1)       # h4 = (d d1 + d u2) * lrelu'(d1)
-        bw.append(wg("down_block1", sp.out1, h4, H, W, 64, 128, sn_index=0, k=4, s=2))
-        bw += s2_dgrad("down_block1", h4, gD, H // 2, W // 2, 128, 64, gA, None)         # gD = d out1 (+ skip d u3)
-        bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, sp.xin, gD, w1raw, self._poff("conv1.weight"), self._poff("conv1.bias"), sp.thin_ws,
-                                  N, H, W, self.in_ch, 64, True))
-        sp.dx_conv = first_layer_dgrad(ops.features_to_image(dtc, sp.thin_i, V(gD), sp.dxp, 4, w1raw, wptr + O[("b", "conv1")], N, H, W, self.in_ch, 64,
-                                                             True, flip=True))
+        # the 4x4 stride-2 data gradients: 4 output-parity classes (2x2-tap convs over dy)
+        bw += b.strided_dgrad(e1, q4, ("b", "down_block3"), H // 8, W // 8, 512, 256, 2, 1, r1=q1, mask=sp.d2)     # q4 = (d d2 + d u1) * lrelu'(d2)
+        bw.append(sn_wgrad(1, sp.d1, q4, H // 2, W // 2, 128, 256, **down))
+        bw += b.strided_dgrad(q4, h4, ("b", "down_block2"), H // 4, W // 4, 256, 128, 2, 1, r1=h1, mask=sp.d1)     # h4 = (d d1 + d u2) * lrelu'(d1)
+        bw.append(sn_wgrad(0, sp.out1, h4, H, W, 64, 128, **down))
+        bw += b.strided_dgrad(h4, gD, ("b", "down_block1"), H // 2, W // 2, 128, 64, 2, 1, r1=gA)                  # gD = d out1 (+ skip d u3)
+        bw.append(b.image_wgrad(sp.thin_i, sp.xin, gD, "conv1", sp.thin_ws, H, W, self.in_ch, 64, True))
+        sp.dx_conv = first_layer_dgrad(b.features_to_image(sp.thin_i, gD, sp.dxp, 4, "conv1", H, W, self.in_ch, 64, True, flip=True))
         sp.bw = bw
-        self._backward_workspaces(sp, wplans, pk)
+        self._backward_workspaces(sp, b)
 
 
 def discriminator_engine(owner: nn.Module) -> DiscriminatorEngine:

@@ -99,110 +99,80 @@ class EsrganDiscriminatorEngine(DiscriminatorEngineCore):
         layer("fc2", self._poff("classifier.2.weight"), 1, self.hid, 1, 1)
         return pb.finish(device)
 
-    # ---- per-shape plan ----
-    def _plan(self, N, H, W, dt, dtc, device, pk, train=True):
+    # ---- per-shape plan: one of a ring of RING per shape, the next one at every forward ----
+    def _plan(self, *args):
         self._fw_count += 1
-        key = (N, H, W, dtc, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr(), self._fw_count % RING)
-        sp = self.shapes.get(key)
-        if sp is not None:
-            return sp
-        sp = _Shape()
-        sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
-        V = A.view
-        fptr, wptr, O = self.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
+        return super()._plan(*args)
 
-        def new(h, w, c, dtype=dt, zero=False):
-            f = torch.zeros if zero else torch.empty
-            return f(N, h, w, c, dtype=dtype, device=device)
-        sp.xin = new(H, W, 32)
+    def _plan_key(self) -> tuple:
+        return (self._fw_count % RING,)
+
+    def _plan_forward(self, sp: _Shape, b: ops.PlanBuilder, train: bool) -> None:
+        N, V = sp.N, A.view
+        lre = dict(act=A.ACT_LRELU, slope=SLOPE)
+        sp.xin = b.act(sp.H, sp.W, 32)
         sp.y, sp.a, sp.save, sp.hw, sp.bn = {}, {}, {}, {}, {}
-        sp.bn_ws = torch.empty(2048 * 256 + 3 * 256, dtype=torch.float32, device=device)
-        h, w = H, W
+        sp.bn_ws = b.buf(2048 * 256 + 3 * 256, dtype=torch.float32)
+        h, w = sp.H, sp.W
         fw = []
-        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
         prev = sp.xin
         for i, (fi, ci, co, ks, st) in enumerate(self.convs):
             ho, wo = h // st, w // st
             sp.hw[i] = (h, w, ho, wo)
-            sp.a[i] = new(ho, wo, co)
+            sp.a[i] = b.act(ho, wo, co)
             if i == 0:
-                fw.append(cv(V(prev), V(sp.a[0]), wptr + O[("f", fi)], N, h, w, 32, co, bias=fptr + 4 * self._poff("features.0.bias"),
-                             act=A.ACT_LRELU, slope=SLOPE))
+                fw.append(b.conv(prev, sp.a[0], ("f", fi), h, w, 32, co, bias=b.P("features.0.bias"), **lre))
             else:
-                sp.y[i] = new(ho, wo, co)
-                sp.save[i] = torch.empty(4 * co, dtype=torch.float32, device=device)
-                fw.append(cv(V(prev), V(sp.y[i]), wptr + O[("f", fi)], N, h, w, ci, co, ksize=ks, stride=st))
-                sp.bn[i] = StageBatchNorm(self, V(sp.y[i]), V(sp.a[i]), dtc, N * ho * wo, co, self._poff(f"features.{fi + 1}.weight"),
+                sp.y[i] = b.act(ho, wo, co)
+                sp.save[i] = b.buf(4 * co, dtype=torch.float32)
+                fw.append(b.conv(prev, sp.y[i], ("f", fi), h, w, ci, co, ksize=ks, stride=st))
+                sp.bn[i] = StageBatchNorm(self, V(sp.y[i]), V(sp.a[i]), sp.dtc, N * ho * wo, co, self._poff(f"features.{fi + 1}.weight"),
                                           self._poff(f"features.{fi + 1}.bias"), self.owner.features[fi + 1], sp.save[i], sp.bn_ws)
                 fw.append(sp.bn[i])
             prev, h, w = sp.a[i], ho, wo
-        sp.f1 = new(1, 1, self.hid_pad, zero=True)          # padded channels stay zero (they meet zero weights in fc2)
-        fw.append(cv(V(sp.a[9]), V(sp.f1), wptr + O[("f", "fc1")], N, 4, 4, 512, self.hid_pad, cout_store=self.hid, ksize=4, stride=2,
-                     pad=0, bias=fptr + 4 * self._poff("classifier.0.bias"), act=A.ACT_LRELU, slope=SLOPE))
+        sp.f1 = torch.zeros(N, 1, 1, self.hid_pad, dtype=sp.dt, device=sp.device)          # padded channels stay zero (they meet zero weights in fc2)
+        fw.append(b.conv(sp.a[9], sp.f1, ("f", "fc1"), 4, 4, 512, self.hid_pad, cout_store=self.hid, ksize=4, stride=2, pad=0,
+                         bias=b.P("classifier.0.bias"), **lre))
         # Linear(100,1) writes the logits, allocated per forward
-        fw.append(ops.PerCall(cv(V(sp.f1), A.View(0, 1, 0), wptr + O[("f", "fc2")], N, 1, 1, self.hid_pad, 32, cout_store=1, ksize=1, pad=0,
-                                 bias=fptr + 4 * self._poff("classifier.2.bias"), y_f32=True)))
+        fw.append(ops.PerCall(b.conv(sp.f1, A.View(0, 1, 0), ("f", "fc2"), 1, 1, self.hid_pad, 32, cout_store=1, ksize=1, pad=0,
+                                     bias=b.P("classifier.2.bias"), y_f32=True)))
         sp.fw = fw
-        self._plan_backward(sp, pk)
-        self.shapes[key] = sp
-        return sp
 
-    def _plan_backward(self, sp, pk):
-        N, dt, dtc, device = sp.N, sp.dt, sp.dtc, sp.device
+    def _plan_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
         V = A.view
-        wptr, O = pk["buf"].data_ptr(), pk["offs"]
-
-        def new(h, w, c, dtype=dt):
-            return torch.empty(N, h, w, c, dtype=dtype, device=device)
-        wplans = ops.WgradPlans(device, dtc, N)
-
-        def wg(pname, bname, x, dy, h, w, cin, cout, k, s, pad, cin_real=None, cout_real=None):
-            plan = wplans.conv(h, w, cin, cout, self._poff(pname), self._poff(bname) if bname else -1, cin_real, cout_real, ksize=k, stride=s, pad=pad)
-            return ops.Wgrad(plan, V(x), V(dy))
-
-        def s2_dgrad(key, dy, dx, hd, wd, cout, cin, mask, pad):
-            """data gradient of a 4x4 stride-2 conv as 4 output-parity classes (2x2-tap convs over dy).  pad = 1: class
-            (py,px) has hd x wd outputs; pad = 0 (the classifier's 4x4 'valid' conv): hd+1 x wd+1 outputs, the tap pairs of
-            the opposite parity and one row/column of zero padding on the low side."""
-            return ops.parity_class_launches(
-                dtc, V(dy), V(dx), wptr, [O[("b", key, c)] for c in range(4)], N, hd, wd, cout, cin, 2, 1, valid=pad == 0,
-                **ops.dgrad_epilogue(mask=None if mask is None else V(mask), mask_slope=SLOPE))
-
-        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
-        sp.dl = new(1, 1, 32)
-        df1 = new(1, 1, self.hid_pad)
+        sp.dl = b.act(1, 1, 32)
+        df1 = b.act(1, 1, self.hid_pad)
         bw = [
-            wg("classifier.2.weight", "classifier.2.bias", sp.f1, sp.dl, 1, 1, self.hid_pad, 32, 1, 1, 0, cin_real=self.hid, cout_real=1),
-            cv(V(sp.dl), V(df1), wptr + O[("b", "fc2")], N, 1, 1, 32, self.hid_pad, ksize=1, pad=0, mask=V(sp.f1), mask_slope=SLOPE),
-            wg("classifier.0.weight", "classifier.0.bias", sp.a[9], df1, 4, 4, 512, self.hid_pad, 4, 2, 0, cout_real=self.hid),
+            b.wgrad(sp.f1, sp.dl, 1, 1, self.hid_pad, 32, "classifier.2.weight", "classifier.2.bias", cin_real=self.hid, cout_real=1, ksize=1, stride=1, pad=0),
+            b.dgrad(sp.dl, df1, ("b", "fc2"), 1, 1, 32, self.hid_pad, mask=sp.f1, mask_slope=SLOPE, ksize=1, pad=0),
+            b.wgrad(sp.a[9], df1, 4, 4, 512, self.hid_pad, "classifier.0.weight", "classifier.0.bias", cout_real=self.hid, ksize=4, stride=2, pad=0),
         ]
-        dA = new(4, 4, 512)                       # gradient w.r.t. a9 (post-activation): the BN backward applies LeakyReLU'
-        bw += s2_dgrad("fc1", df1, dA, 1, 1, self.hid_pad, 512, None, 0)
+        dA = b.act(4, 4, 512)                     # gradient w.r.t. a9 (post-activation): the BN backward applies LeakyReLU'
+        # the classifier's 4x4 'valid' conv as 4 output-parity classes: 2 x 2 outputs each, the tap pairs of the opposite parity
+        bw += b.strided_dgrad(df1, dA, ("b", "fc1"), 1, 1, self.hid_pad, 512, 2, 1, valid=True)
         sp.keep = [df1, dA]
         for i in range(9, 0, -1):
             fi, ci, co, ks, st = self.convs[i]
             h, w, ho, wo = sp.hw[i]
-            dY = new(ho, wo, co)
+            dY = b.act(ho, wo, co)
             bw.append(StageBatchNormBwd(sp.bn[i], V(dA), V(dY)))
-            xprev = sp.a[i - 1]
-            bw.append(wg(f"features.{fi}.weight", None, xprev, dY, h, w, ci, co, ks, st, 1))
-            dAp = new(h, w, ci)
+            bw.append(b.wgrad(sp.a[i - 1], dY, h, w, ci, co, f"features.{fi}.weight", ksize=ks, stride=st, pad=1))
+            dAp = b.act(h, w, ci)
             # below stage 1 sits conv0 + LeakyReLU (no BatchNorm): its activation derivative goes into this epilogue
             mask0 = sp.a[0] if i == 1 else None
             if st == 1:
-                bw.append(cv(V(dY), V(dAp), wptr + O[("b", fi)], N, ho, wo, co, ci, mask=V(mask0) if mask0 is not None else A.NULL_VIEW,
-                             mask_slope=SLOPE))
+                bw.append(b.dgrad(dY, dAp, ("b", fi), ho, wo, co, ci, mask=mask0, mask_slope=SLOPE))
             else:
-                bw += s2_dgrad(fi, dY, dAp, ho, wo, co, ci, mask0, 1)
+                bw += b.strided_dgrad(dY, dAp, ("b", fi), ho, wo, co, ci, 2, 1, mask=mask0)      # 4x4 stride 2 pad 1: 2x2-tap classes over dY
             sp.keep += [dY, dAp]
             dA = dAp
         # dA is now dL/d(conv0 output before LeakyReLU)
-        bw.append(wg("features.0.weight", "features.0.bias", sp.xin, dA, sp.H, sp.W, 32, 64, 3, 1, 1, cin_real=3))
+        bw.append(b.wgrad(sp.xin, dA, sp.H, sp.W, 32, 64, "features.0.weight", "features.0.bias", cin_real=3))
         sp.bw = bw
-        sp.dxp = torch.empty(N, sp.H, sp.W, 4, dtype=torch.float32, device=device)
-        sp.dx_conv = first_layer_dgrad(cv(V(dA), V(sp.dxp), wptr + O[("b", 0)], N, sp.H, sp.W, 64, 32, cout_store=3, y_f32=True))
-        self._backward_workspaces(sp, wplans, pk)
-        sp.per_call = (N, 1)                      # the classifier's logits: no height and width
+        sp.dxp = b.act(sp.H, sp.W, 4, dtype=torch.float32)
+        sp.dx_conv = first_layer_dgrad(b.conv(dA, sp.dxp, ("b", 0), sp.H, sp.W, 64, 32, cout_store=3, y_f32=True))
+        self._backward_workspaces(sp, b)
+        sp.per_call = (sp.N, 1)                   # the classifier's logits: no height and width
 
     # ---- execution: EngineBase's passes ----
     def _check_input(self, x: Tensor):

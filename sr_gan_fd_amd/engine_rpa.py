@@ -94,46 +94,35 @@ class RpaEngine(EngineBase):
         return pb.finish(device)
 
     # ---- per-shape plan ----
-    def _plan(self, N: int, H: int, W: int, dt, dtc: int, device, pk: dict, train: bool) -> _Shape:
-        key = (N, H, W, dtc, train, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
-        sp = self.shapes.get(key)
-        if sp is not None:
-            return sp
-        sp = _Shape()
-        sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, device
-        F, V = self.F, A.view
-        fptr, wptr, O = self.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
-        P = lambda name: fptr + 4 * self._poff(name)
+    def _plan_forward(self, sp: _Shape, b: ops.PlanBuilder, train: bool) -> None:
+        N, H, W, dtc, F, V = sp.N, sp.H, sp.W, sp.dtc, self.F, A.view
         lre = dict(act=A.ACT_LRELU, slope=0.2)
-
-        def new(h, w, c, dtype=dt):
-            return torch.empty(N, h, w, c, dtype=dtype, device=device)
         shared = {}
 
         def act(role, bi, h, w, c):
             """a block's activation buffer: its own when a backward pass will read it; an inference plan shares one per role among the
             blocks (they run one after the other), block outputs alternating between two"""
             if train:
-                return new(h, w, c)
+                return b.act(h, w, c)
             k = (role if role != "y" else "y%d" % (bi & 1), h, w, c)
             if k not in shared:
-                shared[k] = new(h, w, c)
+                shared[k] = b.act(h, w, c)
             return shared[k]
 
-        def cv(x, y, name, h, w, cin, cout, k, **kw):
-            return ops.Conv(ops.conv_args(dtc, V(x), V(y), wptr + O[("f", name)], N, h, w, cin, cout, ksize=k, pad=k // 2, bias=P(name + ".bias"), **kw))
+        def layer(x, y, name, h, w, cin, cout, k, **kw):
+            """conv ``name`` (k x k, 'same' padding) with its bias"""
+            return b.conv(x, y, ("f", name), h, w, cin, cout, ksize=k, pad=k // 2, bias=b.P(name + ".bias"), **kw)
 
-        def gate(h, w, x, a, **kw):
-            return ops.PixelGate(ops.pixel_gate_args(dtc, N * h * w, F, V(x), V(a), **{k: V(t) for k, t in kw.items()}))
+        def gate(h, w, x, a, z):
+            return ops.PixelGate(ops.pixel_gate_args(dtc, N * h * w, F, V(x), V(a), z=V(z)))
         fw = []
         if self.gen:
             sp.thin_i = ops.thin_ok(dtc, F, self.in_ch)
-            sp.xin, sp.z0 = new(H, W, 4 if sp.thin_i else 32), new(H, W, F)
-            fw.append(ops.image_to_features(dtc, sp.thin_i, sp.xin, V(sp.z0), P("conv1.weight"), wptr + O[("f", "conv1")], N, H, W, self.in_ch, F, True,
-                                            bias=P("conv1.bias"), **lre))
+            sp.xin, sp.z0 = b.act(H, W, 4 if sp.thin_i else 32), b.act(H, W, F)
+            fw.append(b.image_to_features(sp.thin_i, sp.xin, sp.z0, "conv1", H, W, self.in_ch, F, True, **lre))
             cur = sp.z0
         else:
-            sp.xin = cur = new(H, W, F)
+            sp.xin = cur = b.act(H, W, F)
         h, w = H, W
         sp.recs = []
         for bi, (kind, pre) in enumerate(self.blocks):
@@ -141,52 +130,41 @@ class RpaEngine(EngineBase):
             r.kind, r.pre, r.h, r.w, r.x = kind, pre, h, w, cur
             if kind == "rpa":
                 r.h1, r.h2, r.a, r.g, r.y = act("h1", bi, h, w, 2 * F), act("h2", bi, h, w, 4 * F), act("a", bi, h, w, F), act("g", bi, h, w, F), act("y", bi, h, w, F)
-                fw += [cv(r.x, r.h1, pre + "conv1", h, w, F, 2 * F, 1, **lre), cv(r.h1, r.h2, pre + "conv2", h, w, 2 * F, 4 * F, 1, **lre),
-                       cv(r.h2, r.a, pre + "conv3", h, w, 4 * F, F, 3), gate(h, w, r.x, r.a, z=r.g)]
+                fw += [layer(r.x, r.h1, pre + "conv1", h, w, F, 2 * F, 1, **lre), layer(r.h1, r.h2, pre + "conv2", h, w, 2 * F, 4 * F, 1, **lre),
+                       layer(r.h2, r.a, pre + "conv3", h, w, 4 * F, F, 3), gate(h, w, r.x, r.a, r.g)]
                 if self.gen and bi == self.n_rpa - 1:
                     # the long skip z + z_ (model.py:170) in the last RPA's conv4: s = z0 + lrelu(...), the LeakyReLU output kept beside it
-                    sp.s = new(h, w, F)
-                    fw.append(cv(r.g, sp.s, pre + "conv4", h, w, F, F, 3, r1=V(sp.z0), r1_scale=1.0, y2=V(r.y), **lre))
+                    sp.s = b.act(h, w, F)
+                    fw.append(layer(r.g, sp.s, pre + "conv4", h, w, F, F, 3, r1=V(sp.z0), r1_scale=1.0, y2=V(r.y), **lre))
                     cur = sp.s
                 else:
-                    fw.append(cv(r.g, r.y, pre + "conv4", h, w, F, F, 3, **lre))
+                    fw.append(layer(r.g, r.y, pre + "conv4", h, w, F, F, 3, **lre))
                     cur = r.y
             else:
                 r.u, r.a, r.g, r.y = act("u", bi, h, w, F), act("a", bi, h, w, F), act("g", bi, h, w, F), act("y", bi, 2 * h, 2 * w, F)
-                fw += [cv(r.x, r.u, pre + "conv1", h, w, F, F, 1, **lre), cv(r.u, r.a, pre + "pa_conv", h, w, F, F, 1), gate(h, w, r.u, r.a, z=r.g),
-                       cv(r.g, r.y, pre + "conv2", h, w, F, F, 3, up=1, **lre)]
+                fw += [layer(r.x, r.u, pre + "conv1", h, w, F, F, 1, **lre), layer(r.u, r.a, pre + "pa_conv", h, w, F, F, 1), gate(h, w, r.u, r.a, r.g),
+                       layer(r.g, r.y, pre + "conv2", h, w, F, F, 3, up=1, **lre)]
                 cur, h, w = r.y, 2 * h, 2 * w
             sp.recs.append(r)
         if self.gen:
-            sp.c2, sp.srp = new(h, w, F // 2), new(h, w, 4, dtype=torch.float32)
-            fw.append(cv(cur, sp.c2, "conv2", h, w, F, F // 2, 3, **lre))
-            fw.append(ops.Conv(ops.conv_args(dtc, V(sp.c2), V(sp.srp), wptr + O[("f", "conv3")], N, h, w, F // 2, 32, cout_store=self.out_ch,
-                                             bias=P("conv3.bias"), y_f32=True)))
+            sp.c2, sp.srp = b.act(h, w, F // 2), b.act(h, w, 4, dtype=torch.float32)
+            fw.append(layer(cur, sp.c2, "conv2", h, w, F, F // 2, 3, **lre))
+            fw.append(b.conv(sp.c2, sp.srp, ("f", "conv3"), h, w, F // 2, 32, cout_store=self.out_ch, bias=b.P("conv3.bias"), y_f32=True))
         sp.fw, sp.last, sp.hs, sp.ws = fw, cur, h, w
         sp.x_in = (V(sp.xin), sp.xin.shape[-1])
         sp.result = (V(sp.srp), A.F32, 0) if self.gen else (V(cur), dtc, 0)      # (a lone block: its stored y, widened)
-        if train:
-            self._plan_backward(sp, pk)
-        self.shapes.put(key, sp, pinned=train)
-        return sp
 
-    def _plan_backward(self, sp: _Shape, pk: dict) -> None:
-        N, H, W, dt, dtc, device, F, V = sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device, self.F, A.view
-        fptr, wptr, O = self.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
-        P = lambda name: fptr + 4 * self._poff(name)
+    def _plan_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        N, H, W, dtc, F, V = sp.N, sp.H, sp.W, sp.dtc, self.F, A.view
         hs, ws = sp.hs, sp.ws
-        wplans = ops.WgradPlans(device, dtc, N)
         pool, turn = {}, [0]
         bw = []
-
-        def new(h, w, c, dtype=dt):
-            return torch.empty(N, h, w, c, dtype=dtype, device=device)
 
         def gb(h, w, c, slot):
             """the blocks run one after the other and share their gradient buffers by role"""
             k = (h, w, c, slot)
             if k not in pool:
-                pool[k] = new(h, w, c)
+                pool[k] = b.act(h, w, c)
             return pool[k]
 
         def pre_buf(h, w):
@@ -194,42 +172,36 @@ class RpaEngine(EngineBase):
             turn[0] ^= 1
             return gb(h, w, F, "pre%d" % turn[0])
 
-        def wg(name, x, dy, h, w, cin, cout, k, **kw):
-            bw.append(ops.Wgrad(wplans.conv(h, w, cin, cout, self._poff(name + ".weight"), self._poff(name + ".bias"), ksize=k, pad=k // 2, **kw), V(x), V(dy)))
-
-        def dg(name, dy, dx, h, w, cout, cin, k, r1=None, r2=None, mask=None, **kw):
-            """data gradient of conv ``name``: reads dy (cout channels), writes dx (cin channels)"""
-            ep = ops.dgrad_epilogue(*(None if t is None else V(t) for t in (r1, r2, mask)))
-            return ops.Conv(ops.conv_args(dtc, V(dy), V(dx), wptr + O[("b", name)], N, h, w, cout, cin, ksize=k, pad=k // 2, **ep, **kw))
+        def layer_bwd(name, x, dy, dx, h, w, cin, cout, k, up=0, **epilogue):
+            """weight gradient of conv ``name`` (x: its input, dy: its pre-activation's gradient at (h << up, w << up)) and its data
+            gradient into dx with ``epilogue`` (PlanBuilder.dgrad's r1 / r2 / mask / y_f32)"""
+            bw.append(b.wgrad(x, dy, h, w, cin, cout, name + ".weight", name + ".bias", ksize=k, pad=k // 2, up=up))
+            return b.dgrad(dy, dx, ("b", name), h << up, w << up, cout, cin, ksize=k, pad=k // 2, **epilogue)
 
         def gate(h, w, x, a, dz, dx):
             return ops.PixelGate(ops.pixel_gate_args(dtc, N * h * w, F, V(x), V(a), dz=V(dz), dx=V(dx), da=V(dz)))       # da over dz, in place
 
-        def lrelu_bwd(dy, act, out, h, w):
-            return ops.Call("srganfd_lrelu_bwd", (V(dy), V(act), A.NULL_VIEW, V(out), dtc, N * h * w, F, 0.2), "lrelu_bwd")
-
         def through_skip():
             """ds is complete: the last RPA's share of it, times the LeakyReLU derivative of that block's output"""
             dpre = pre_buf(H, W)
-            bw.append(lrelu_bwd(sp.ds, sp.recs[self.n_rpa - 1].y, dpre, H, W))
+            bw.append(b.lrelu_bwd(sp.ds, sp.recs[self.n_rpa - 1].y, dpre, N * H * W, F))
             return dpre
         if self.gen:
-            sp.dout = new(hs, ws, 32)
-            sp.ds = new(H, W, F)
+            sp.dout = b.act(hs, ws, 32)
+            sp.ds = b.act(H, W, F)
             dc2 = gb(hs, ws, F // 2, "dc2")
-            bw.append(ops.Wgrad(wplans.conv(hs, ws, F // 2, 32, self._poff("conv3.weight"), self._poff("conv3.bias"), cout_real=self.out_ch), V(sp.c2), V(sp.dout)))
-            bw.append(dg("conv3", sp.dout, dc2, hs, ws, 32, F // 2, 3, mask=sp.c2))
-            wg("conv2", sp.last, dc2, hs, ws, F, F // 2, 3)
+            bw.append(b.wgrad(sp.c2, sp.dout, hs, ws, F // 2, 32, "conv3.weight", "conv3.bias", cout_real=self.out_ch))
+            bw.append(b.dgrad(sp.dout, dc2, ("b", "conv3"), hs, ws, 32, F // 2, mask=sp.c2))
             if self.blocks[-1][0] == "us":
                 dpre = pre_buf(hs, ws)
-                bw.append(dg("conv2", dc2, dpre, hs, ws, F // 2, F, 3, mask=sp.last))
+                bw.append(layer_bwd("conv2", sp.last, dc2, dpre, hs, ws, F, F // 2, 3, mask=sp.last))
             else:
-                bw.append(dg("conv2", dc2, sp.ds, hs, ws, F // 2, F, 3))
+                bw.append(layer_bwd("conv2", sp.last, dc2, sp.ds, hs, ws, F, F // 2, 3))
                 dpre = through_skip()
         else:
-            sp.dout = new(hs, ws, F)
+            sp.dout = b.act(hs, ws, F)
             dpre = pre_buf(hs, ws)
-            bw.append(lrelu_bwd(sp.dout, sp.last, dpre, hs, ws))
+            bw.append(b.lrelu_bwd(sp.dout, sp.last, dpre, N * hs * ws, F))
         sp.dx_conv = None
         for bi in range(len(self.blocks) - 1, -1, -1):
             r = sp.recs[bi]
@@ -237,44 +209,36 @@ class RpaEngine(EngineBase):
             dz, dxg = gb(h, w, F, "dz"), gb(h, w, F, "dxg")
             if kind == "rpa":
                 dh2, dh1 = gb(h, w, 4 * F, "dh2"), gb(h, w, 2 * F, "dh1")
-                wg(pre + "conv4", r.g, dpre, h, w, F, F, 3)
-                bw.append(dg(pre + "conv4", dpre, dz, h, w, F, F, 3))
+                bw.append(layer_bwd(pre + "conv4", r.g, dpre, dz, h, w, F, F, 3))
                 bw.append(gate(h, w, r.x, r.a, dz, dxg))
-                wg(pre + "conv3", r.h2, dz, h, w, 4 * F, F, 3)
-                bw.append(dg(pre + "conv3", dz, dh2, h, w, F, 4 * F, 3, mask=r.h2))
-                wg(pre + "conv2", r.h1, dh2, h, w, 2 * F, 4 * F, 1)
-                bw.append(dg(pre + "conv2", dh2, dh1, h, w, 4 * F, 2 * F, 1, mask=r.h1))
-                wg(pre + "conv1", r.x, dh1, h, w, F, 2 * F, 1)
-                last = dict(name=pre + "conv1", dy=dh1, cout=2 * F, r1=dxg)
+                bw.append(layer_bwd(pre + "conv3", r.h2, dz, dh2, h, w, 4 * F, F, 3, mask=r.h2))
+                bw.append(layer_bwd(pre + "conv2", r.h1, dh2, dh1, h, w, 2 * F, 4 * F, 1, mask=r.h1))
+                first = dict(dy=dh1, cout=2 * F, r1=dxg)
             else:
                 dghi, du = gb(2 * h, 2 * w, F, "dghi"), gb(h, w, F, "du")
-                wg(pre + "conv2", r.g, dpre, h, w, F, F, 3, up=1)
-                bw.append(dg(pre + "conv2", dpre, dghi, 2 * h, 2 * w, F, F, 3))
-                bw.append(ops.Call("srganfd_resample", (0, V(dghi), V(dz), dtc, N, h, w, F), "nearest_bwd"))
+                bw.append(layer_bwd(pre + "conv2", r.g, dpre, dghi, h, w, F, F, 3, up=1))
+                bw.append(b.resample(0, dghi, dz, h, w, F, what="nearest_bwd"))
                 bw.append(gate(h, w, r.u, r.a, dz, dxg))
-                wg(pre + "pa_conv", r.u, dz, h, w, F, F, 1)
-                bw.append(dg(pre + "pa_conv", dz, du, h, w, F, F, 1, r1=dxg, mask=r.u))
-                wg(pre + "conv1", r.x, du, h, w, F, F, 1)
-                last = dict(name=pre + "conv1", dy=du, cout=F, r1=None)
-            # the data gradient of the block's first conv: where it goes and what joins it depends on what the block's input is
+                bw.append(layer_bwd(pre + "pa_conv", r.u, dz, du, h, w, F, F, 1, r1=dxg, mask=r.u))
+                first = dict(dy=du, cout=F, r1=None)
+            # the block's first conv: where its data gradient goes and what joins it depends on what the block's input is
+            conv1 = lambda dx, **epilogue: layer_bwd(pre + "conv1", r.x, first["dy"], dx, h, w, F, first["cout"], 1, r1=first["r1"], **epilogue)
             if not self.gen:                      # a lone block: the module's input, fp32, launched only when its gradient is wanted
-                sp.dxp = new(H, W, F, dtype=torch.float32)
-                sp.dx_conv = dg(last["name"], last["dy"], sp.dxp, h, w, last["cout"], F, 1, r1=last["r1"], y_f32=True)
+                sp.dxp = b.act(H, W, F, dtype=torch.float32)
+                sp.dx_conv = conv1(sp.dxp, y_f32=True)
             elif r.x is sp.s:                     # the sum z0 + y_last: no activation of its own
-                bw.append(dg(last["name"], last["dy"], sp.ds, h, w, last["cout"], F, 1, r1=last["r1"]))
+                bw.append(conv1(sp.ds))
                 dpre = through_skip()
             else:                                 # a LeakyReLU output: the previous block's, or (first RPA) conv1's, which the long skip also reads
                 nxt = pre_buf(h, w)
-                bw.append(dg(last["name"], last["dy"], nxt, h, w, last["cout"], F, 1, r1=last["r1"], r2=sp.ds if bi == 0 else None, mask=r.x))
+                bw.append(conv1(nxt, r2=sp.ds if bi == 0 else None, mask=r.x))
                 dpre = nxt
         if self.gen:
-            sp.thin_ws = torch.empty(ops.thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=device) if sp.thin_i else None
-            bw.append(ops.image_wgrad(dtc, sp.thin_i, wplans, sp.xin, dpre, P("conv1.weight"), self._poff("conv1.weight"), self._poff("conv1.bias"),
-                                      sp.thin_ws, N, H, W, self.in_ch, F, True))
-            sp.dxp = new(H, W, 4, dtype=torch.float32)
-            sp.dx_conv = first_layer_dgrad(ops.features_to_image(dtc, sp.thin_i, V(dpre), sp.dxp, 4, P("conv1.weight"), wptr + O[("b", "conv1")], N, H, W,
-                                                                 self.in_ch, F, True, flip=True))
-        sp.pool, sp.wg_ws, sp.bw = pool, wplans.workspace(), bw
+            sp.thin_ws = b.thin_ws(sp.thin_i)
+            bw.append(b.image_wgrad(sp.thin_i, sp.xin, dpre, "conv1", sp.thin_ws, H, W, self.in_ch, F, True))
+            sp.dxp = b.act(H, W, 4, dtype=torch.float32)
+            sp.dx_conv = first_layer_dgrad(b.features_to_image(sp.thin_i, dpre, sp.dxp, 4, "conv1", H, W, self.in_ch, F, True, flip=True))
+        sp.pool, sp.wg_ws, sp.bw = pool, b.wplans.workspace(), bw
         sp.dy_in, sp.dx_out = (V(sp.dout), sp.dout.shape[-1]), (V(sp.dxp), A.F32)
 
     # ---- execution ----

@@ -116,39 +116,34 @@ class TransGeneratorEngine(TrunkEngine):
         pb.bwd(("b", "conv1"), self._poff("conv1.weight"), Cc, self.in_ch)     # the image's gradient (the padded path; the thin kernels read the raw weight)
 
     # ---- plan ----
-    def _stage_forward(self, sp: _Shape, pk: dict, fw: list, trunk_out: A.View, N: int, H: int, W: int, dt, dtc: int, device, train: bool) -> A.View:
-        Cc, V, O = self.Cc, A.view, pk["offs"]
+    def _stage_forward(self, sp: _Shape, b: ops.PlanBuilder, fw: list, trunk_out: A.View, train: bool) -> A.View:
+        N, H, W, Cc, V = sp.N, sp.H, sp.W, self.Cc, A.view
         h, w = H // 2, W // 2
-        fptr, wptr = self.fp.flat.data_ptr(), pk["buf"].data_ptr()
-        bias = lambda name: fptr + 4 * self._poff(name)
-        new = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=device)
-        sp.ds, sp.ut = new(N, h, w, Cc), new(N, H, W, Cc)
-        fw.append(ops.Conv(ops.conv_args(dtc, trunk_out, V(sp.ds), wptr + O[("f", DS)], N, H, W, Cc, Cc, stride=2, bias=bias(DS + ".bias"),
-                                         act=A.ACT_LRELU, slope=0.2)))
+        lre = dict(act=A.ACT_LRELU, slope=0.2)
+        sp.ds, sp.ut = b.act(h, w, Cc), b.act(H, W, Cc)
+        fw.append(b.conv(trunk_out, sp.ds, ("f", DS), H, W, Cc, Cc, stride=2, bias=b.P(DS + ".bias"), **lre))
         T = N * h * w
-        sp.g_enc = new(N, h, w, Cc) if train else None            # gradient of the stack's result
-        sp.t_wplans = ops.WgradPlans(device, dtc, 1) if train else None
-        sp.ln_ws = torch.empty(ops.add_layernorm_workspace_bytes(T, self.E), dtype=torch.uint8, device=device) if train else None
+        sp.g_enc = b.act(h, w, Cc) if train else None             # gradient of the stack's result
+        tb = ops.PlanBuilder(self, sp, b.pk, n=1)                 # the stack's launches take the T tokens as one image
+        sp.t_wplans = tb.wplans if train else None
+        sp.ln_ws = b.buf(ops.add_layernorm_workspace_bytes(T, self.E), dtype=torch.uint8) if train else None
         kind = {"f": "tf", "b": "tb"}
-        site = StackSite(self._poff, fptr, wptr, lambda d, l, key: O[(kind[d], l, key)], sp.ds.view(T, Cc),
-                         None if sp.g_enc is None else sp.g_enc.view(T, Cc), sp.t_wplans, sp.ln_ws)
-        t_fw, t_bw, out, first_dx = plan_layers(sp, (self.E, self.F, self.heads, self.eps), self.t_prefixes, self._probs, N, h * w, dt, dtc, device, site,
-                                                train=train)
+        site = StackSite(lambda d, l, key: (kind[d], l, key), sp.ds.view(T, Cc), None if sp.g_enc is None else sp.g_enc.view(T, Cc), sp.ln_ws)
+        t_fw, t_bw, out, first_dx = plan_layers(sp, tb, (self.E, self.F, self.heads, self.eps), self.t_prefixes, self._probs, N, h * w, site, train=train)
         if t_fw and t_fw[0].kind == "draw_masks":
             fw.insert(0, t_fw.pop(0))                             # DrawMasks is the first forward item
         fw.extend(t_fw)
         sp.enc_out = out.view(N, h, w, Cc)
         sp.t_len = (len(t_fw), len(t_bw))                         # how many items of each list are the stack's (tests, tools)
         if train:
-            sp.g_ds = new(N, h, w, Cc)                            # gradient of downsamplingTrans's pre-activation
+            sp.g_ds = b.act(h, w, Cc)                             # gradient of downsamplingTrans's pre-activation
             # LeakyReLU' of the stack's input in the epilogue of the first layer's input gradient, after the residual branch's is added
             t_bw.append(first_dx(sp.g_ds.view(T, Cc), mask=V(sp.ds.view(T, Cc)), mask_slope=0.2))
             sp.t_bw = t_bw
-        if self._parity(dtc):
-            fw.extend(self._up_forward(dtc, pk, V(sp.enc_out), V(sp.ut), N, h, w, bias(UT + ".bias"), UT))
+        if self._parity(sp.dtc):
+            fw.extend(self._up_forward(b, V(sp.enc_out), V(sp.ut), h, w, UT))
         else:
-            fw.append(ops.Conv(ops.conv_args(dtc, V(sp.enc_out), V(sp.ut), wptr + O[("f", UT)], N, h, w, Cc, Cc, up=1, bias=bias(UT + ".bias"),
-                                             act=A.ACT_LRELU, slope=0.2)))
+            fw.append(b.conv(sp.enc_out, sp.ut, ("f", UT), h, w, Cc, Cc, up=1, bias=b.P(UT + ".bias"), **lre))
         return V(sp.ut)
 
     def _conv2_dgrad_target(self, sp: _Shape, trunk_grad: A.View) -> Tuple[A.View, dict]:
@@ -156,39 +151,33 @@ class TransGeneratorEngine(TrunkEngine):
         sp.g_ut = torch.empty_like(sp.ut)
         return A.view(sp.g_ut), dict(mask=A.view(sp.ut), mask_slope=0.2)
 
-    def _stage_backward(self, sp: _Shape, pk: dict, wplans: ops.WgradPlans, trunk_grad: A.View) -> list:
-        N, H, W, dtc, Cc, V, O = sp.N, sp.H, sp.W, sp.dtc, self.Cc, A.view, pk["offs"]
+    def _stage_backward(self, sp: _Shape, b: ops.PlanBuilder, trunk_grad: A.View) -> list:
+        N, H, W, Cc = sp.N, sp.H, sp.W, self.Cc
         h, w = H // 2, W // 2
-        wptr = pk["buf"].data_ptr()
-        cv = lambda *a, **k: ops.Conv(ops.conv_args(dtc, *a, **k))
-        one = lambda nm: [dict(cin=Cc, cout=Cc, dw_off=self._poff(nm + ".weight"), db_off=self._poff(nm + ".bias"), co_dst=Cc, ci_dst=Cc)]
-        bw = [ops.Wgrad(wplans.plan(h, w, Cc, Cc, one(UT), up=1), V(sp.enc_out), V(sp.g_ut))]
-        if self._parity(dtc):
-            it = cv(V(sp.g_ut), V(sp.g_enc), wptr + O[("b4", UT)], N, H, W, Cc, Cc, ksize=4, stride=2, pad=1)
+        bw = [b.wgrad(sp.enc_out, sp.g_ut, h, w, Cc, Cc, UT + ".weight", UT + ".bias", up=1)]
+        if self._parity(sp.dtc):
+            it = b.dgrad(sp.g_ut, sp.g_enc, ("b4", UT), H, W, Cc, Cc, ksize=4, stride=2, pad=1)
             it.args._label_tag = " nearest-x2 dgrad"
             bw.append(it)
         else:
             sp.g_tmp = torch.empty_like(sp.ut)
-            bw.append(cv(V(sp.g_ut), V(sp.g_tmp), wptr + O[("b", UT)], N, H, W, Cc, Cc))
-            bw.append(ops.Call("srganfd_resample", (0, V(sp.g_tmp), V(sp.g_enc), dtc, N, h, w, Cc), "nearest_bwd"))
+            bw.append(b.dgrad(sp.g_ut, sp.g_tmp, ("b", UT), H, W, Cc, Cc))
+            bw.append(b.resample(0, sp.g_tmp, sp.g_enc, h, w, Cc, what="nearest_bwd"))
         bw.extend(sp.t_bw)
         del sp.t_bw
-        wplans.ws_bytes = max(wplans.ws_bytes, sp.t_wplans.ws_bytes)       # the stack's weight gradients share the list's workspace
-        bw.append(ops.Wgrad(wplans.plan(H, W, Cc, Cc, one(DS), stride=2), A.view(sp.catb(self.R), planar=sp.planar), V(sp.g_ds)))
-        bw.extend(ops.parity_class_launches(dtc, V(sp.g_ds), trunk_grad, wptr, [O[("b", DS, c)] for c in range(4)], N, h, w, Cc, Cc, 2, 0))
+        b.wplans.ws_bytes = max(b.wplans.ws_bytes, sp.t_wplans.ws_bytes)       # the stack's weight gradients share the list's workspace
+        bw.append(b.wgrad(A.view(sp.catb(self.R), planar=sp.planar), sp.g_ds, H, W, Cc, Cc, DS + ".weight", DS + ".bias", stride=2))
+        bw.extend(b.strided_dgrad(sp.g_ds, trunk_grad, ("b", DS), h, w, Cc, Cc, 2, 0))
         bw.append(ops.Ready(self._trunk_end(), self._poff("conv2.weight")))      # the stage's parameters are final, before the first dense block
         return bw
 
     def _trunk_end(self) -> int:
         return self._poff(DS + ".weight")
 
-    def _finish_backward(self, sp: _Shape, pk: dict) -> None:
+    def _finish_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
         """the image's gradient, for a module-path backward that asks for it: conv1's data gradient, launched only then"""
-        N, H, W, dtc = sp.N, sp.H, sp.W, sp.dtc
-        sp.dxp = torch.empty(N, H, W, 4, dtype=torch.float32, device=sp.device)
-        w1 = self.fp.flat.data_ptr() + 4 * self._poff("conv1.weight")
-        sp.dx_conv = first_layer_dgrad(ops.features_to_image(dtc, sp.thin_i, A.view(sp.dx0), sp.dxp, 4, w1, pk["buf"].data_ptr() + pk["offs"][("b", "conv1")],
-                                                             N, H, W, self.in_ch, self.Cc, True, flip=True))
+        sp.dxp = b.act(sp.H, sp.W, 4, dtype=torch.float32)
+        sp.dx_conv = first_layer_dgrad(b.features_to_image(sp.thin_i, sp.dx0, sp.dxp, 4, "conv1", sp.H, sp.W, self.in_ch, self.Cc, True, flip=True))
         sp.dx_out = (A.view(sp.dxp), A.F32)
 
     # ---- execution ----

@@ -27,10 +27,12 @@ class VggEngineBase(EngineBase):
     """the convs of ``owner.features[:layers]`` as one flat parameter buffer, packed for the forward pass and, with ``dgrad``, for the
     data gradient; the 2N-batch input; the launch of one feature conv"""
     dgrad = False
+    always_backward = True             # (one plan per shape: the differentiable loss's with its backward list, the other's without)
 
     def __init__(self, owner: nn.Module, layers: int):
         self.convs = [(i, m) for i, m in enumerate(owner.features[:layers]) if isinstance(m, nn.Conv2d)]
         super().__init__(owner, [(f"features.{i}.{k}", getattr(m, k)) for i, m in self.convs for k in ("weight", "bias")])
+        self.in_ch = self.convs[0][1].weight.shape[1]
 
     def _fkey(self, i: int):
         """key of features.i's forward operand in the pack record (the forward-only engine has no other operands)"""
@@ -45,11 +47,14 @@ class VggEngineBase(EngineBase):
                 pb.bwd(("b", i), self._poff(f"features.{i}.weight"), co, ci)
         return pb.finish(device)
 
-    def _new_input(self, sp: _Shape, N: int, H: int, W: int, cin: int, dt, dtc: int, device) -> None:
+    def _new_input(self, sp: _Shape, b: ops.PlanBuilder) -> None:
         # features.0 (3 -> 64) on the thin-side kernels in the 16-bit modes (csrc/conv_thin.hip): the normalised image is NHWC with a
         # 4-channel pitch
-        sp.thin = ops.thin_ok(dtc, self.owner.features[0].weight.shape[0], cin)
-        sp.xin = torch.empty(2 * N, H, W, 4 if sp.thin else 32, dtype=dt, device=device)
+        sp.thin = ops.thin_ok(sp.dtc, self.owner.features[0].weight.shape[0], self.in_ch)
+        sp.xin = b.buf(2 * sp.N, sp.H, sp.W, 4 if sp.thin else 32)
+
+    def _plan_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        """(the forward-only loss has none)"""
 
     def _load_input(self, sp: _Shape, sr: Tensor, gt: Tensor, dtc: int, L, st) -> None:
         """SR into the first N images of sp.xin, GT into the other N, normalised with the module's mean / std"""
@@ -61,15 +66,14 @@ class VggEngineBase(EngineBase):
             dst = A.View(sp.xin.data_ptr() + half * N * H * W * cpad * sp.xin.element_size(), cpad, 0)
             A.check(L.srganfd_nchw_to_nhwc(img.data_ptr(), N, cin, H, W, dst, dtc, cpad, mean.data_ptr(), std.data_ptr(), st), "nchw_to_nhwc")
 
-    def _feature_conv(self, sp: _Shape, pk: dict, dtc: int, idx: int, x: Tensor, y: Tensor, cin: int, act: int):
+    def _feature_conv(self, sp: _Shape, b: ops.PlanBuilder, idx: int, x: Tensor, y: Tensor, cin: int, act: int):
         """launch item (ops.Conv or ops.ThinLaunch) of features.idx + activation over the 2N batch: x (its padded channel count is cin) -> y"""
         n, h, w, co = y.shape
-        fptr = self.fp.flat.data_ptr()
-        bias = fptr + 4 * self._poff(f"features.{idx}.bias")
+        bias = b.P(f"features.{idx}.bias")
         if idx == 0 and sp.thin:
-            return ops.ThinLaunch("thin_in", ops.thin_args(dtc, n, h, w, self.convs[0][1].weight.shape[1], fptr + 4 * self._poff("features.0.weight"),
-                                                           A.view(y), w_big_is_cout=True, bias=bias, act=act, thin=sp.xin))
-        return ops.Conv(ops.conv_args(dtc, A.view(x), A.view(y), pk["buf"].data_ptr() + pk["offs"][self._fkey(idx)], n, h, w, cin, co, bias=bias, act=act))
+            return ops.ThinLaunch("thin_in", ops.thin_args(b.dtc, n, h, w, self.in_ch, b.P("features.0.weight"), A.view(y), w_big_is_cout=True, bias=bias,
+                                                           act=act, thin=sp.xin))
+        return ops.Conv(ops.conv_args(b.dtc, A.view(x), A.view(y), b.Wp(self._fkey(idx)), n, h, w, cin, co, bias=bias, act=act))
 
 
 class LossTap:
@@ -93,26 +97,20 @@ class ContentLossEngine(VggEngineBase):
         super().__init__(owner, len(owner.features))
         self.want = [int(n.split(".")[1]) for n in owner.feature_model_extractor_nodes]
 
-    def _plan(self, N, Cin, H, W, dt, dtc, dev, pk):
-        key = (N, H, W, dtc, str(dev), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
-        sp = self.shapes.get(key)
-        if sp is not None:
-            return sp
-        sp = _Shape()
-        self._new_input(sp, N, H, W, Cin, dt, dtc, dev)
+    def _plan_forward(self, sp: _Shape, b: ops.PlanBuilder, train: bool) -> None:
+        N, dtc = sp.N, sp.dtc
+        self._new_input(sp, b)
         sp.bufs = {}
-        sp.ws = torch.empty(A.LOSS_WS_FLOATS, dtype=torch.float32, device=dev)
-        sp.dt, sp.dtc = dt, dtc
+        sp.ws = b.buf(A.LOSS_WS_FLOATS, dtype=torch.float32)
         last = max(self.want)
         post = self.owner.taps_post_relu
-        cur, ch, h, w = sp.xin, 32, H, W
+        cur, ch, h, w = sp.xin, 32, sp.H, sp.W
 
         def buf(tag, hh, ww, cc):
-            b = sp.bufs.get((tag, hh, ww, cc))
-            if b is None:
-                b = torch.empty(2 * N, hh, ww, cc, dtype=dt, device=dev)
-                sp.bufs[(tag, hh, ww, cc)] = b
-            return b
+            """the feature maps alternate between two buffers per size (``tag`` 0 / 1), the pooled ones have their own ("p")"""
+            if (tag, hh, ww, cc) not in sp.bufs:
+                sp.bufs[(tag, hh, ww, cc)] = b.buf(2 * N, hh, ww, cc)
+            return sp.bufs[(tag, hh, ww, cc)]
         fw, flip = [], 0
         for idx in range(last + 1):
             m = self.owner.features[idx]
@@ -123,19 +121,17 @@ class ContentLossEngine(VggEngineBase):
                 tap = idx in self.want
                 # taps are observed after the in-place ReLU unless they are the last requested node
                 relu_in_conv = not (tap and (idx == last or not post))
-                fw.append(self._feature_conv(sp, pk, dtc, idx, cur, out, ch, A.ACT_RELU if relu_in_conv else A.ACT_NONE))
+                fw.append(self._feature_conv(sp, b, idx, cur, out, ch, A.ACT_RELU if relu_in_conv else A.ACT_NONE))
                 if tap:
                     fw.append(LossTap(out, dtc, self.want.index(idx), sp.ws))
                     if not relu_in_conv and idx != last:
-                        fw.append(ops.Call("srganfd_resample", (4, A.view(out), A.view(out), dtc, 2 * N, h, w, co), "relu"))
+                        fw.append(b.resample(4, out, out, h, w, co, n=2 * N, what="relu"))
                 cur, ch = out, co
             elif isinstance(m, nn.MaxPool2d):
                 out = buf("p", h // 2, w // 2, ch)
-                fw.append(ops.Call("srganfd_resample", (3, A.view(cur), A.view(out), dtc, 2 * N, h, w, ch), "maxpool"))
+                fw.append(b.resample(3, cur, out, h, w, ch, n=2 * N, what="maxpool"))
                 cur, h, w = out, h // 2, w // 2
         sp.fw = fw
-        self.shapes[key] = sp
-        return sp
 
     def forward(self, sr: Tensor, gt: Tensor) -> Tensor:
         _require_gpu(sr)
@@ -146,7 +142,7 @@ class ContentLossEngine(VggEngineBase):
         if H < 16 or W < 16:
             raise A.SrganfdError("ContentLoss input height/width must be at least 16 (four 2x2 max-pools; odd sizes floor like torch)")
         L, st = A.lib(), A.stream_ptr()
-        sp = self._last = self._plan(N, Cin, H, W, dt, dtc, dev, pk)
+        sp = self._last = self._plan(N, H, W, dt, dtc, dev, pk, True)
         self._load_input(sp, sr, gt, dtc, L, st)
         losses = torch.zeros(len(self.want), dtype=torch.float32, device=dev)
         ops.run_items(sp.fw, ops.Run("conv2d(vgg)", out=losses.data_ptr()))
@@ -168,18 +164,9 @@ class ContentLossGradEngine(VggEngineBase):
             raise A.SrganfdError("differentiable ContentLoss: the node must be a conv of vgg19.features (esrgan_config uses features.34)")
         super().__init__(owner, self.last + 1)
 
-    def _plan(self, N, H, W, dt, dtc, dev, pk):
-        key = (N, H, W, dtc, str(dev), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
-        sp = self.shapes.get(key)
-        if sp is not None:
-            return sp
-        sp = _Shape()
-        sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = N, H, W, dt, dtc, dev
-        es = torch.empty(0, dtype=dt).element_size()
-        fptr, wptr, O = self.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
-        self._new_input(sp, N, H, W, 3, dt, dtc, dev)      # (thin: features.0's data gradient runs on the thin-side kernel too)
-        half = lambda t: A.View(t.data_ptr(), t.shape[3], 0)                     # SR half (first N images)
-        other = lambda t: A.View(t.data_ptr() + t[:N].numel() * es, t.shape[3], 0)   # GT half
+    def _plan_forward(self, sp: _Shape, b: ops.PlanBuilder, train: bool) -> None:
+        N, H, W, dtc = sp.N, sp.H, sp.W, sp.dtc
+        self._new_input(sp, b)      # (thin: features.0's data gradient runs on the thin-side kernel too)
         fw, chain = [], []          # chain: (layer, index, input, output, h, w, cin, cout) in forward order
         cur, ch, h, w = sp.xin, 32, H, W
         sp.keep = [sp.xin]
@@ -187,45 +174,47 @@ class ContentLossGradEngine(VggEngineBase):
             m = self.owner.features[idx]
             if isinstance(m, nn.Conv2d):
                 co = m.weight.shape[0]
-                out = torch.empty(2 * N, h, w, co, dtype=dt, device=dev)
-                fw.append(self._feature_conv(sp, pk, dtc, idx, cur, out, ch, A.ACT_NONE if idx == self.last else A.ACT_RELU))
+                out = b.buf(2 * N, h, w, co)
+                fw.append(self._feature_conv(sp, b, idx, cur, out, ch, A.ACT_NONE if idx == self.last else A.ACT_RELU))
                 chain.append(("conv", idx, cur, out, h, w, ch, co))
                 cur, ch = out, co
             elif isinstance(m, nn.MaxPool2d):
-                out = torch.empty(2 * N, h // 2, w // 2, ch, dtype=dt, device=dev)
-                fw.append(ops.Call("srganfd_resample", (3, A.view(cur), A.view(out), dtc, 2 * N, h, w, ch), "maxpool"))
+                out = b.buf(2 * N, h // 2, w // 2, ch)
+                fw.append(b.resample(3, cur, out, h, w, ch, n=2 * N, what="maxpool"))
                 chain.append(("pool", idx, cur, out, h, w, ch, ch))
                 cur, h, w = out, h // 2, w // 2
             sp.keep.append(cur)
-        sp.feat, sp.feat_dims = cur, (h, w, ch)
-        sp.loss_views = (half(cur), other(cur))
-        sp.ws = torch.empty(A.LOSS_WS_FLOATS, dtype=torch.float32, device=dev)
+        sp.feat, sp.feat_dims, sp.chain = cur, (h, w, ch), chain
+        sp.ws = b.buf(A.LOSS_WS_FLOATS, dtype=torch.float32)
         fw.append(LossTap(cur, dtc, 0, sp.ws))           # the loss, a one-element vector allocated per forward
         sp.fw = fw
-        # ---- backward launch list (SR half only) ----
+
+    def _plan_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        """the SR half only"""
+        N, dtc = sp.N, sp.dtc
+        half = lambda t: A.View(t.data_ptr(), t.shape[3], 0)                                       # SR half (first N images)
+        other = lambda t: A.View(t.data_ptr() + t[:N].numel() * t.element_size(), t.shape[3], 0)   # GT half
+        sp.loss_views = (half(sp.feat), other(sp.feat))
+        chain = sp.chain
+        del sp.chain
         bw = []
-        g = torch.empty(N, h, w, ch, dtype=dt, device=dev)
-        sp.g_tap = g
+        g = sp.g_tap = b.act(*sp.feat_dims)
         sp.keep.append(g)
-        sp.dxp = torch.empty(N, H, W, 4, dtype=torch.float32, device=dev)
+        sp.dxp = b.act(sp.H, sp.W, 4, dtype=torch.float32)
         for j in range(len(chain) - 1, -1, -1):
             layer, idx, tin, tout, hh, ww, cin, cout = chain[j]
             if idx == 0:
-                bw.append(ops.features_to_image(dtc, sp.thin, A.view(g), sp.dxp, 4, fptr + 4 * self.fp.off("features.0.weight"), wptr + O[("b", 0)],
-                                                N, hh, ww, 3, cout, True, flip=True))
+                bw.append(b.features_to_image(sp.thin, g, sp.dxp, 4, "features.0", hh, ww, 3, cout, True, flip=True, key=("b", 0)))
                 break
-            gin = torch.empty(N, hh, ww, cin, dtype=dt, device=dev)
+            gin = b.act(hh, ww, cin)
             sp.keep.append(gin)
             if layer == "conv":
                 # the conv's input is a ReLU output (mask it here) or a pooled map (the pool's backward applies the ReLU')
-                mask = half(tin) if chain[j - 1][0] == "conv" else A.NULL_VIEW
-                bw.append(ops.Conv(ops.conv_args(dtc, A.view(g), A.view(gin), wptr + O[("b", idx)], N, hh, ww, cout, cin, mask=mask, mask_slope=0.0)))
+                bw.append(b.dgrad(g, gin, ("b", idx), hh, ww, cout, cin, mask=half(tin) if chain[j - 1][0] == "conv" else A.NULL_VIEW, mask_slope=0.0))
             else:
                 bw.append(ops.Call("srganfd_maxpool2_relu_bwd", (half(tin), A.view(g), A.view(gin), dtc, N, hh, ww, cin), "maxpool2_relu_bwd"))
             g = gin
         sp.bw = bw
-        self.shapes[key] = sp
-        return sp
 
     def forward(self, sr: Tensor, gt: Tensor) -> Tensor:
         _require_gpu(sr)
@@ -235,7 +224,7 @@ class ContentLossGradEngine(VggEngineBase):
         N, Cin, H, W = sr.shape
         if Cin != 3 or H % 16 or W % 16:
             raise A.SrganfdError("ContentLoss needs 3-channel inputs with height/width multiples of 16 (four 2x2 max-pools)")
-        sp = self._plan(N, H, W, dt, dtc, dev, pk)
+        sp = self._plan(N, H, W, dt, dtc, dev, pk, True)
         L, st = A.lib(), A.stream_ptr()
         self._load_input(sp, sr, gt, dtc, L, st)
         loss = torch.zeros(1, dtype=torch.float32, device=dev)

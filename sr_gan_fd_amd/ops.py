@@ -653,6 +653,99 @@ class WgradPlans:
         return torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
 
 
+def _view(t) -> A.View:
+    return t if isinstance(t, A.View) else A.view(t)
+
+
+class PlanBuilder:
+    """What the engines' planners share, made once per plan (EngineBase._plan) from the engine, the plan ``sp`` -- its N, dt, dtc and
+    device -- and the packed record ``pk``: the plan's buffers, the addresses of parameters and packed operands, and the launch items
+    the planners put into sp.fw / sp.bw.  Where an item takes ``x`` / ``y`` / ``dy`` / ``mask`` ..., a tensor stands for the view of
+    all its channels.  ``n``: the batch of the conv and weight-gradient launches where it is not the plan's N (the transformer layers
+    run their T tokens as one (S, Nq) image).  ``wplans``: the plan's weight-gradient plans."""
+
+    def __init__(self, eng, sp, pk: dict, n: Optional[int] = None):
+        self.N, self.dt, self.dtc, self.device, self.pk = sp.N if n is None else n, sp.dt, sp.dtc, sp.device, pk
+        self.poff = eng._poff                                  # a parameter's element offset in the flat parameters and the flat gradient
+        self.fptr, self.wptr, self.offs = eng.fp.flat.data_ptr(), pk["buf"].data_ptr(), pk["offs"]
+        self.wplans = WgradPlans(self.device, self.dtc, self.N)
+
+    # ---- buffers ----
+    def buf(self, *shape, dtype=None) -> torch.Tensor:
+        return torch.empty(*shape, dtype=self.dt if dtype is None else dtype, device=self.device)
+
+    def act(self, h: int, w: int, c: int, dtype=None) -> torch.Tensor:
+        """an (N, h, w, c) activation or gradient, in the compute dtype unless ``dtype`` says otherwise"""
+        return self.buf(self.N, h, w, c, dtype=dtype)
+
+    def thin_ws(self, *thin: bool) -> Optional[torch.Tensor]:
+        """the thin weight-gradient workspace, if any of the plan's image-side layers is thin"""
+        return torch.empty(thin_wgrad_workspace_bytes(), dtype=torch.uint8, device=self.device) if any(thin) else None
+
+    # ---- addresses ----
+    def P(self, name: str) -> int:
+        """address of a parameter in the flat buffer"""
+        return self.fptr + 4 * self.poff(name)
+
+    def Wp(self, key) -> int:
+        """address of a packed operand"""
+        return self.wptr + self.offs[key]
+
+    # ---- items ----
+    def conv(self, x, y, key, h: int, w: int, cin: int, cout: int, **kw) -> "Conv":
+        """one conv launch with the packed operand ``key`` over the (N, h, w, cin) input; ``kw``: conv_args' keywords"""
+        return Conv(conv_args(self.dtc, _view(x), _view(y), self.Wp(key), self.N, h, w, cin, cout, **kw))
+
+    def dgrad(self, dy, dx, key, h: int, w: int, cout: int, cin: int, r1=None, r2=None, mask=None, mask_slope: float = 0.2, **kw) -> "Conv":
+        """a stride-1 conv's data gradient: reads dy (cout channels), writes dx (cin channels); ``r1`` / ``r2``: gradients added at
+        scale 1, ``mask``: the activation whose derivative multiplies the sum (dgrad_epilogue)"""
+        ep = dgrad_epilogue(*(None if t is None else _view(t) for t in (r1, r2, mask)), mask_slope)
+        return self.conv(dy, dx, key, h, w, cout, cin, **ep, **kw)
+
+    def strided_dgrad(self, dy, dx, key: tuple, hd: int, wd: int, kdim: int, ndim: int, ksize: int, class_pad: int, r1=None, r2=None, mask=None,
+                      valid: bool = False) -> List["Conv"]:
+        """a stride-2 conv's data gradient as its four output-parity classes (parity_class_launches; the operands under ``key + (class,)``)
+        over the (hd, wd) gradient dy, with dgrad's epilogue"""
+        ep = dgrad_epilogue(*(None if t is None else _view(t) for t in (r1, r2, mask)))
+        return parity_class_launches(self.dtc, _view(dy), _view(dx), self.wptr, [self.offs[key + (c,)] for c in range(4)], self.N, hd, wd, kdim, ndim,
+                                     ksize, class_pad, valid=valid, **ep)
+
+    def wgrad(self, x, dy, h: int, w: int, cin: int, cout: int, weight: str, bias: Optional[str] = None, sn: Optional[int] = None,
+              cin_real: Optional[int] = None, cout_real: Optional[int] = None, **kw) -> "Wgrad":
+        """weight gradient of one conv over the (N, h, w, cin) input x and the gradient dy (cout channels), written at parameter
+        ``weight`` (and ``bias``) of the flat gradient; ``sn``: the layer's spectral-norm slot; ``kw``: ksize / stride / pad / up"""
+        plan = self.wplans.conv(h, w, cin, cout, self.poff(weight), -1 if bias is None else self.poff(bias), cin_real, cout_real, **kw)
+        return Wgrad(plan, _view(x), _view(dy), sn=sn)
+
+    def resample(self, op: int, a, b, h: int, w: int, c: int, dtype: Optional[int] = None, n: Optional[int] = None, what: str = "resample") -> "Call":
+        return Call("srganfd_resample", (op, _view(a), _view(b), self.dtc if dtype is None else dtype, self.N if n is None else n, h, w, c), what)
+
+    def lrelu_bwd(self, dy, act, out, npix: int, c: int, slope: float = 0.2) -> "Call":
+        return Call("srganfd_lrelu_bwd", (_view(dy), _view(act), A.NULL_VIEW, _view(out), self.dtc, npix, c, slope), "lrelu_bwd")
+
+    def resample_bwd_lrelu(self, dy, raw, act, masked, h: int, w: int, c: int, slope: float = 0.2) -> "Call":
+        """bilinear-x2 backward and LeakyReLU' of the upsampled layer in one pass: the raw gradient (a skip connection's share) and the masked one"""
+        return Call("srganfd_resample_bwd_lrelu", (_view(dy), _view(raw), _view(act), _view(masked), self.dtc, self.N, h, w, c, slope), "resample_bwd_lrelu")
+
+    # the image-side layers (image_to_features, features_to_image, image_wgrad) of the layer ``name``: ``cs`` real image channels
+    # against ``big_ch`` features at (h, w); ``first``: the network's first layer (its weight's output channels are the features);
+    # ``flip``: the other layer's data gradient, which takes no bias; ``key``: the packed operand where it is not (direction, name)
+    def image_to_features(self, thin: bool, image, big, name: str, h: int, w: int, cs: int, big_ch: int, first: bool, flip: bool = False, key=None,
+                          **epilogue):
+        bias = {} if flip else dict(bias=self.P(name + ".bias"))
+        return image_to_features(self.dtc, thin, image, _view(big), self.P(name + ".weight"), self.Wp(key or ("b" if flip else "f", name)), self.N, h, w,
+                                 cs, big_ch, first, flip=flip, **bias, **epilogue)
+
+    def features_to_image(self, thin: bool, big, out, out_pitch: int, name: str, h: int, w: int, cs: int, big_ch: int, first: bool, flip: bool = False,
+                          key=None):
+        return features_to_image(self.dtc, thin, _view(big), out, out_pitch, self.P(name + ".weight"), self.Wp(key or ("b" if flip else "f", name)),
+                                 self.N, h, w, cs, big_ch, first, flip=flip, bias=None if flip else self.P(name + ".bias"))
+
+    def image_wgrad(self, thin: bool, image, big, name: str, thin_ws, h: int, w: int, cs: int, big_ch: int, first: bool):
+        return image_wgrad(self.dtc, thin, self.wplans, image, big, self.P(name + ".weight"), self.poff(name + ".weight"), self.poff(name + ".bias"),
+                           thin_ws, self.N, h, w, cs, big_ch, first)
+
+
 # ---- fused multi-head self-attention (csrc/attention.hip) ----
 ATTN_HEAD_DIMS = (16, 32, 64)
 

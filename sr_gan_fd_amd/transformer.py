@@ -90,59 +90,51 @@ class DrawMasks:
 
 
 class StackSite(NamedTuple):
-    """where a stack of layers sits in its engine (plan_layers): ``poff(name)``: element offset of a parameter in the flat buffer at
-    ``fptr`` (and in the flat gradient); ``woff(d, l, key)``: byte offset behind ``wptr`` of layer l's packed operand ``key`` ("in",
+    """where a stack of layers sits in its engine (plan_layers): ``key(d, l, k)``: the pack key of layer l's operand ``k`` ("in",
     "out", "l1", "l2"), forward (d "f") or data-gradient (d "b") orientation; ``x_in`` (T, E): the first layer's input; ``dy`` (T, E):
-    the gradient of the last layer's output; ``wplans`` / ``ln_ws``: the engine's weight-gradient plans and add + LayerNorm workspace
-    (the last three None for an inference plan)"""
-    poff: Callable
-    fptr: int
-    wptr: int
-    woff: Callable
+    the gradient of the last layer's output; ``ln_ws``: the engine's add + LayerNorm workspace (the last two None for an inference
+    plan)"""
+    key: Callable
     x_in: Tensor
     dy: Optional[Tensor]
-    wplans: Optional[ops.WgradPlans]
     ln_ws: Optional[Tensor]
 
 
-def plan_layers(sp: _Shape, dims: tuple, prefixes: Sequence[str], probs: tuple, S: int, Nq: int, dt, dtc: int, device, site: StackSite,
-                train: bool = True):
+def plan_layers(sp: _Shape, pb: ops.PlanBuilder, dims: tuple, prefixes: Sequence[str], probs: tuple, S: int, Nq: int, site: StackSite, train: bool = True):
     """The launch lists of a stack of layers over T = S Nq tokens, for the stand-alone engine below and for the generator that holds
-    the stack between its trunk and its tail (engine_trans.py).  ``dims``: (E, F, heads, eps); ``prefixes``: the layers' parameter
-    prefixes; ``probs``: site_probs'; ``site``: where the stack sits (StackSite).
+    the stack between its trunk and its tail (engine_trans.py).  ``pb``: a plan builder with a batch of 1 -- the tokens are one
+    (S, Nq) image to the 1x1 convs -- whose weight-gradient plans are the stack's; ``dims``: (E, F, heads, eps); ``prefixes``: the
+    layers' parameter prefixes; ``probs``: site_probs'; ``site``: where the stack sits (StackSite).
     Sets sp.layers (the layers' buffers) and sp.masks ({"<prefix><site>": keep-mask}); returns (forward items -- DrawMasks first when
     a site has p > 0 --, backward items without the first layer's input gradient, the buffer of the stack's output, ``first_dx``:
     ``first_dx(y, **epilogue)`` makes the item that writes the first layer's input gradient into ``y``).
     ``train`` False (an inference plan; no site may have p > 0): no backward list, and one set of buffers serves every layer -- the
     kernels' z, mean, rstd and lse outputs, which only a backward pass reads, land in that one set too."""
     E, F, heads, eps = dims
-    poff, fptr, wptr, woff, x_in, dy, wplans, ln_ws = site
+    key, x_in, dy, ln_ws = site
     D, T = E // heads, S * Nq
-    V = A.view
-    cv = lambda x, y, key, cin, cout, **kw: ops.Conv(ops.conv_args(dtc, V(x), V(y), wptr + woff(*key), 1, S, Nq, cin, cout, ksize=1, pad=0, **kw))
-
-    def new(c, dtype=dt):
-        return torch.empty(T, c, dtype=dtype, device=device)
-    stat = lambda: torch.empty(T, dtype=torch.float32, device=device)
+    V, dtc, device = A.view, pb.dtc, pb.device
+    conv1 = lambda x, y, k, cin, cout, **kw: pb.conv(x, y, key(*k), S, Nq, cin, cout, ksize=1, pad=0, **kw)
+    tok = lambda c: pb.buf(T, c)                     # a (T, c) buffer of the stack
+    stat = lambda: pb.buf(T, dtype=torch.float32)
     u8 = lambda *shape: torch.ones(*shape, dtype=torch.uint8, device=device)
     sp.layers, sp.masks = [], {}
     fw, bw, draws = [], [], []
     L = len(prefixes)
-    dxs = [new(E) if (l > 0 and train) else None for l in range(L)]      # the gradient between two layers: layer l's input is layer l - 1's output
+    dxs = [tok(E) if (l > 0 and train) else None for l in range(L)]      # the gradient between two layers: layer l's input is layer l - 1's output
     x_l = x_in                                       # a layer's input
     per_layer_bw, first_dx = [], None
     for l, pre in enumerate(prefixes):
-        P = lambda name: fptr + 4 * poff(pre + name)
-        off = lambda name: poff(pre + name)
+        off = lambda name: pb.poff(pre + name)
         if train or l == 0:
             b = _Shape()                             # the layer's buffers
-            b.qkv, b.att, b.a, b.z1, b.y1, b.hid, b.f, b.z2, b.y2 = new(3 * E), new(E), new(E), new(E), new(E), new(F), new(E), new(E), new(E)
+            b.qkv, b.att, b.a, b.z1, b.y1, b.hid, b.f, b.z2, b.y2 = tok(3 * E), tok(E), tok(E), tok(E), tok(E), tok(F), tok(E), tok(E), tok(E)
             b.lse = torch.empty(Nq, heads, S, dtype=torch.float32, device=device)
             b.mean1, b.rstd1, b.mean2, b.rstd2 = stat(), stat(), stat(), stat()
         else:
             prev, b = b, _Shape()                    # inference: the one set again, the output in the buffer the layer does not read
             b.__dict__.update(prev.__dict__)
-            b.y2 = sp.layers[l - 2].y2 if l >= 2 else new(E)
+            b.y2 = sp.layers[l - 2].y2 if l >= 2 else tok(E)
         sp.layers.append(b)
         shapes = {"attn": (Nq, heads, S, S), "dropout1": (T, E), "dropout": (T, F), "dropout2": (T, E)}
         keep, scale = {}, {}
@@ -155,42 +147,42 @@ def plan_layers(sp: _Shape, dims: tuple, prefixes: Sequence[str], probs: tuple, 
                 draws.append((keep[site], p))
         aa = lambda **kw: ops.seq_attn_args(dtc, S, Nq, heads, D, qkv=b.qkv, out=b.att, lse=b.lse, keep=keep["attn"], keep_scale=scale["attn"], **kw)
         ln = lambda **kw: ops.AddLayerNorm(dtc, T, E, eps=eps, **kw)
-        fw += [cv(x_l, b.qkv, ("f", l, "in"), E, 3 * E, bias=P("self_attn.in_proj_bias")), ops.SeqAttention("fwd", aa()),
-               cv(b.att, b.a, ("f", l, "out"), E, E, bias=P("self_attn.out_proj.bias")),
-               ln(x=x_l, r=b.a, keep=keep["dropout1"], keep_scale=scale["dropout1"], gamma=P("norm1.weight"), beta=P("norm1.bias"), z=b.z1, y=b.y1,
+        fw += [conv1(x_l, b.qkv, ("f", l, "in"), E, 3 * E, bias=pb.P(pre + "self_attn.in_proj_bias")), ops.SeqAttention("fwd", aa()),
+               conv1(b.att, b.a, ("f", l, "out"), E, E, bias=pb.P(pre + "self_attn.out_proj.bias")),
+               ln(x=x_l, r=b.a, keep=keep["dropout1"], keep_scale=scale["dropout1"], gamma=pb.P(pre + "norm1.weight"), beta=pb.P(pre + "norm1.bias"), z=b.z1, y=b.y1,
                   mean=b.mean1, rstd=b.rstd1),
-               cv(b.y1, b.hid, ("f", l, "l1"), E, F, bias=P("linear1.bias"), act=A.ACT_RELU)]
+               conv1(b.y1, b.hid, ("f", l, "l1"), E, F, bias=pb.P(pre + "linear1.bias"), act=A.ACT_RELU)]
         if keep["dropout"] is not None:
             fw.append(ops.DropoutApply(dtc, b.hid, keep["dropout"], scale["dropout"], b.hid, T * F))
-        fw += [cv(b.hid, b.f, ("f", l, "l2"), F, E, bias=P("linear2.bias")),
-               ln(x=b.y1, r=b.f, keep=keep["dropout2"], keep_scale=scale["dropout2"], gamma=P("norm2.weight"), beta=P("norm2.bias"), z=b.z2, y=b.y2,
+        fw += [conv1(b.hid, b.f, ("f", l, "l2"), F, E, bias=pb.P(pre + "linear2.bias")),
+               ln(x=b.y1, r=b.f, keep=keep["dropout2"], keep_scale=scale["dropout2"], gamma=pb.P(pre + "norm2.weight"), beta=pb.P(pre + "norm2.bias"), z=b.z2, y=b.y2,
                   mean=b.mean2, rstd=b.rstd2)]
         x_in_l, x_l = x_l, b.y2
         if not train:
             continue
         # backward of the layer, from dy_l (the gradient of y2) to the gradient of its input
         dy_l = dxs[l + 1] if l + 1 < L else dy       # the gradient of the layer's output
-        b.dz2, b.df, b.dhid, b.dy1, b.dz1, b.da, b.datt, b.dqkv = new(E), new(E), new(F), new(E), new(E), new(E), new(E), new(3 * E)
+        b.dz2, b.df, b.dhid, b.dy1, b.dz1, b.da, b.datt, b.dqkv = tok(E), tok(E), tok(F), tok(E), tok(E), tok(E), tok(E), tok(3 * E)
         b.dx = dxs[l]
-        wg = lambda x, dy, cin, cout, w, bias: ops.Wgrad(wplans.conv(S, Nq, cin, cout, off(w), off(bias), ksize=1, pad=0), V(x), V(dy))
-        lb = [ln(dy=dy_l, z=b.z2, mean=b.mean2, rstd=b.rstd2, gamma=P("norm2.weight"), keep=keep["dropout2"], keep_scale=scale["dropout2"], dx=b.dz2,
+        wg1 = lambda x, dy, cin, cout, w, bias: pb.wgrad(x, dy, S, Nq, cin, cout, pre + w, pre + bias, ksize=1, pad=0)
+        lb = [ln(dy=dy_l, z=b.z2, mean=b.mean2, rstd=b.rstd2, gamma=pb.P(pre + "norm2.weight"), keep=keep["dropout2"], keep_scale=scale["dropout2"], dx=b.dz2,
                  dr=b.df, dg_off=off("norm2.weight"), db_off=off("norm2.bias"), ws=ln_ws),
-              wg(b.hid, b.df, F, E, "linear2.weight", "linear2.bias"),
-              cv(b.df, b.dhid, ("b", l, "l2"), E, F, mask=V(b.hid), mask_slope=0.0)]
+              wg1(b.hid, b.df, F, E, "linear2.weight", "linear2.bias"),
+              conv1(b.df, b.dhid, ("b", l, "l2"), E, F, mask=V(b.hid), mask_slope=0.0)]
         if keep["dropout"] is not None:
             lb.append(ops.DropoutApply(dtc, b.dhid, keep["dropout"], scale["dropout"], b.dhid, T * F))
-        lb += [wg(b.y1, b.dhid, E, F, "linear1.weight", "linear1.bias"),
-               cv(b.dhid, b.dy1, ("b", l, "l1"), F, E, r1=V(b.dz2), r1_scale=1.0),
-               ln(dy=b.dy1, z=b.z1, mean=b.mean1, rstd=b.rstd1, gamma=P("norm1.weight"), keep=keep["dropout1"], keep_scale=scale["dropout1"], dx=b.dz1,
+        lb += [wg1(b.y1, b.dhid, E, F, "linear1.weight", "linear1.bias"),
+               conv1(b.dhid, b.dy1, ("b", l, "l1"), F, E, r1=V(b.dz2), r1_scale=1.0),
+               ln(dy=b.dy1, z=b.z1, mean=b.mean1, rstd=b.rstd1, gamma=pb.P(pre + "norm1.weight"), keep=keep["dropout1"], keep_scale=scale["dropout1"], dx=b.dz1,
                   dr=b.da, dg_off=off("norm1.weight"), db_off=off("norm1.bias"), ws=ln_ws),
-               wg(b.att, b.da, E, E, "self_attn.out_proj.weight", "self_attn.out_proj.bias"),
-               cv(b.da, b.datt, ("b", l, "out"), E, E),
+               wg1(b.att, b.da, E, E, "self_attn.out_proj.weight", "self_attn.out_proj.bias"),
+               conv1(b.da, b.datt, ("b", l, "out"), E, E),
                ops.SeqAttention("bwd", aa(d_out=b.datt, d_qkv=b.dqkv)),
-               wg(x_in_l, b.dqkv, E, 3 * E, "self_attn.in_proj_weight", "self_attn.in_proj_bias")]
+               wg1(x_in_l, b.dqkv, E, 3 * E, "self_attn.in_proj_weight", "self_attn.in_proj_bias")]
         if l > 0:
-            lb.append(cv(b.dqkv, b.dx, ("b", l, "in"), 3 * E, E, r1=V(b.dz1), r1_scale=1.0))
+            lb.append(conv1(b.dqkv, b.dx, ("b", l, "in"), 3 * E, E, r1=V(b.dz1), r1_scale=1.0))
         else:
-            first_dx = lambda y, b=b, **kw: cv(b.dqkv, y, ("b", 0, "in"), 3 * E, E, r1=V(b.dz1), r1_scale=1.0, **kw)
+            first_dx = lambda y, b=b, **kw: conv1(b.dqkv, y, ("b", 0, "in"), 3 * E, E, r1=V(b.dz1), r1_scale=1.0, **kw)
         per_layer_bw.append(lb)
     for lb in reversed(per_layer_bw):
         bw += lb
@@ -238,34 +230,32 @@ class TransformerEngine(EngineBase):
         return pb.finish(device)
 
     # ---- per-shape plan: always with its backward list; T tokens enter as a (T, E, 1, 1) image (see forward) ----
-    def _plan(self, T: int, H: int, W: int, dt, dtc: int, device, pk: dict, train: bool = True) -> _Shape:
+    always_backward = True
+    conv_batch = 1
+
+    def _plan_key(self) -> tuple:
+        return self._call
+
+    def _plan_forward(self, sp: _Shape, b: ops.PlanBuilder, train: bool) -> None:
+        """both halves: plan_layers makes a layer's backward items beside its forward items"""
         S, Nq, probs = self._call
-        assert T == S * Nq and H == W == 1
-        key = (S, Nq, probs, dtc, str(device), pk["buf"].data_ptr(), self.fp.flat.data_ptr())
-        sp = self.shapes.get(key)
-        if sp is not None:
-            return sp
-        sp = _Shape()
-        sp.N, sp.H, sp.W, sp.dt, sp.dtc, sp.device = T, 1, 1, dt, dtc, device
+        T, E, V = sp.N, self.E, A.view
+        assert T == S * Nq and sp.H == sp.W == 1
         sp.hs = sp.ws = 1
         sp.S, sp.Nq = S, Nq
-        E = self.E
-        V = A.view
-        O = pk["offs"]
-        wplans = ops.WgradPlans(device, dtc, 1)
-        sp.ln_ws = torch.empty(ops.add_layernorm_workspace_bytes(T, E), dtype=torch.uint8, device=device)
-        sp.xin = torch.empty(T, E, dtype=dt, device=device)
-        sp.dy = torch.empty(T, E, dtype=dt, device=device)                       # gradient of the stack's result
-        sp.dxp = torch.empty(T, E, dtype=torch.float32, device=device)           # gradient of its input
-        site = StackSite(self._poff, self.fp.flat.data_ptr(), pk["buf"].data_ptr(), lambda d, l, key: O[(d, l, key)], sp.xin, sp.dy, wplans, sp.ln_ws)
-        fw, bw, out, first_dx = plan_layers(sp, (self.E, self.F, self.heads, self.eps), self.prefixes, probs, S, Nq, dt, dtc, device, site)
+        sp.ln_ws = b.buf(ops.add_layernorm_workspace_bytes(T, E), dtype=torch.uint8)
+        sp.xin = b.buf(T, E)
+        sp.dy = b.buf(T, E)                                   # gradient of the stack's result
+        sp.dxp = b.buf(T, E, dtype=torch.float32)             # gradient of its input
+        site = StackSite(lambda d, l, k: (d, l, k), sp.xin, sp.dy, sp.ln_ws)
+        sp.fw, sp.bw, out, first_dx = plan_layers(sp, b, (self.E, self.F, self.heads, self.eps), self.prefixes, probs, S, Nq, site)
         sp.dx_conv = first_dx(sp.dxp, y_f32=True)        # the first layer's: only for a pass that wants d src, fp32
-        sp.fw, sp.bw = fw, bw
-        sp.x_in, sp.result = (V(sp.xin), E), (V(out), dtc, 0)
+        sp.x_in, sp.result = (V(sp.xin), E), (V(out), sp.dtc, 0)
         sp.dy_in, sp.dx_out = (V(sp.dy), E), (V(sp.dxp), A.F32)
-        sp.wg_ws = wplans.workspace()
-        self.shapes[key] = sp
-        return sp
+        sp.wg_ws = b.wplans.workspace()
+
+    def _plan_backward(self, sp: _Shape, b: ops.PlanBuilder) -> None:
+        """(made by _plan_forward)"""
 
     def forward(self, x: Tensor, training: bool) -> Tensor:
         """x (S, N, E); always on a plan with a backward list, in the module's mode ``training``"""

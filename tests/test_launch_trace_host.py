@@ -27,18 +27,31 @@ work figures.  Each scenario runs a second time under a recorder stub that notes
 trace must be the same one (but for the ``srganfd_conv2d_describe`` calls that ask the library for the labels) and the brackets,
 in order, must equal tests/golden/launch_labels.json.gz (``python tests/golden/make_golden_launch_labels.py``, regenerated under
 the same rule as the trace).
+
+Which buffer: a wrong activation or gradient buffer wired into a launch, or two buffers that alias, leaves every ``"p"`` of the trace
+a ``"p"``.  A third fixture, tests/golden/launch_buffers.json.gz (``python tests/golden/make_golden_launch_buffers.py``, same rule),
+holds per launch one entry for every pointer the trace records as ``"p"``, in the order the trace canonicalises them:
+``"a<k>+<byte offset>"`` when the pointer falls inside the storage of a tensor that a cached plan (``eng.shapes``) of an engine alive
+at the time of the call keeps alive, else ``"p"`` (per-call inputs and outputs, flat gradients, what the trainers own).  The plans
+are walked through dicts, lists, tuples, sets and objects with ``__dict__`` or ``__slots__``, stopping at modules, ctypes objects and
+engines; the recorder keeps every storage it has found until the scenario ends, so no later buffer gets a named one's address, and
+``k`` counts the storages in the order in which the scenario's launches first point into them.  The calls that only ask the library
+something (QUERIES) are compared without an order and are not part of this fixture.
 """
+import bisect
 import ctypes as C
 import gzip
 import hashlib
 import json
 import os
+import weakref
 from collections import Counter
 
 import pytest
 import torch
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_trace.json.gz")
+BUFFERS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_buffers.json.gz")
 LABELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_labels.json.gz")
 NODES = ["features.2", "features.7", "features.16", "features.25", "features.34"]
 MEAN, STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
@@ -71,13 +84,51 @@ def _engine_buffers():
     return out
 
 
+def _plan_storages(found):
+    """adds to ``found`` (address -> storage) the storage of every tensor that a cached plan of an engine alive now holds"""
+    from sr_gan_fd_amd import engine as E
+    seen = set()
+    todo = [sp for eng in list(E._ENGINES.values()) for sp, _ in list(eng.shapes.d.values())]
+    while todo:
+        o = todo.pop()
+        if id(o) in seen or type(o) in weakref.ProxyTypes or o is None or isinstance(o, (str, bytes, int, float, torch.dtype, torch.device)):
+            continue
+        seen.add(id(o))
+        if isinstance(o, torch.Tensor):
+            st = o.untyped_storage()
+            if st.nbytes():
+                found.setdefault(st.data_ptr(), st)
+        elif isinstance(o, dict):
+            todo.extend(o.values())
+        elif isinstance(o, (list, tuple, set, frozenset)):
+            todo.extend(o)
+        elif not isinstance(o, (torch.nn.Module, E.EngineBase, C.Structure, C.Union, C.Array, C._SimpleCData, C._Pointer, type)):
+            todo.extend(getattr(o, "__dict__", {}).values())
+            todo.extend(getattr(o, n) for c in type(o).__mro__ for n in getattr(c, "__slots__", ()) if hasattr(o, n))
+
+
 class Recorder:
     """stands in for the CDLL object: records every srganfd_* call, then makes it"""
 
-    def __init__(self, lib):
+    def __init__(self, lib, buffers=False):
         self._lib, self._wrapped = lib, {}
         self.launches, self.queries = [], []
         self._bufs = None
+        # the plan-held buffers (module docstring): storages found so far by address, their sorted addresses, the names given, and per
+        # launch the entries of its "p" pointers
+        self.buffers = [] if buffers else None
+        self._held, self._bases, self._names, self._row = {}, [], {}, None
+
+    def _plan_buffer(self, v):
+        for walked in (False, True):
+            i = bisect.bisect_right(self._bases, v) - 1
+            if i >= 0 and v < self._bases[i] + self._held[self._bases[i]].nbytes():
+                base = self._bases[i]
+                return "a%d+%d" % (self._names.setdefault(base, len(self._names)), v - base)
+            if not walked:                                     # not in a storage found so far: look at the plans as they are now
+                _plan_storages(self._held)
+                self._bases = sorted(self._held)
+        return "p"
 
     def _ptr(self, v):
         if not v:
@@ -87,6 +138,8 @@ class Recorder:
         for base, nbytes, name in self._bufs:
             if base <= v < base + nbytes:
                 return "%s+%d" % (name, v - base)
+        if self._row is not None:
+            self._row.append(self._plan_buffer(v))
         return "p"
 
     def _canon(self, v, ctype=None):
@@ -119,7 +172,11 @@ class Recorder:
 
             def w(*args):
                 self._bufs = None
+                if self.buffers is not None and dest is self.launches:
+                    self._row = []
+                    self.buffers.append(self._row)
                 dest.append([name] + [self._canon(a, types[i] if i < len(types) else None) for i, a in enumerate(args)])
+                self._row = None
                 return fn(*args)
             self._wrapped[name] = w
         return w
@@ -247,6 +304,45 @@ def _self_attention(dt):
     return m,
 
 
+def _bsrgantrans(dt):
+    """the stage between trunk and conv2 (engine_trans.py over transformer.py's layers), dropout sites drawing: in dry-run mode no
+    mask is drawn, so the record does not depend on the random stream"""
+    import contextlib
+    import io
+    from sr_gan_fd_amd import model as M
+    with contextlib.redirect_stdout(io.StringIO()):
+        m, = _pin(dt, M.bsrgantrans_x2(num_rrdb=1).train())
+    _four_ways(m, torch.rand(2, 3, 8, 8, requires_grad=True))
+    return m,
+
+
+def _transformer_encoder(dt):
+    """the shape of tests/test_transformer_host.py::test_module_call_sequence_at_the_consumers_shape, training mode (dropout launches)"""
+    from sr_gan_fd_amd import model as M
+    m, = _pin(dt, M.TransformerEncoder(M.TransformerEncoderLayer(64, 4, 2048, 0.1), 2).train())
+    _four_ways(m, torch.randn(8, 900, 64, requires_grad=True))
+    return m,
+
+
+def _realesrgan_x2(dt):
+    """PixelUnshuffle(2) in front of conv1 (12 channels, padded to 32), through the module path: a training step, then a forward alone"""
+    from sr_gan_fd_amd import model as M
+    g, = _pin(dt, M.RRDBNet(num_rrdb=1, upscale_factor=2))
+    g(torch.rand(2, 3, 12, 20)).sum().backward()
+    with torch.no_grad():
+        g(torch.rand(2, 3, 12, 20))
+    return g,
+
+
+def _trunk_inference(dt):
+    """six dense blocks on an inference plan: block 0's buffer and the four that rotate"""
+    from sr_gan_fd_amd import model as M
+    g, = _pin(dt, M.bsrgan_x4(num_rrdb=2))
+    with torch.no_grad():
+        g(torch.rand(2, 3, 10, 6))
+    return g,
+
+
 SCENARIOS = {
     "gan_unet": lambda dt: _gan(dt, _unet),
     "gan_unet_generator_first": lambda dt: _gan(dt, _unet, True),
@@ -268,6 +364,12 @@ SCENARIOS = {
     "gan_unet_generator_first_no_usm": lambda dt: _gan(dt, _unet, True, usm=False),
     "esrgan_gan_no_content_no_ema": lambda dt: _esrgan(dt, content=False, ema_decay=None),
     "generator_only_no_ema": lambda dt: _g_only(dt, ema_decay=None),
+    # the planners the cases above do not reach: the transformer stage inside the generator and the encoder stack alone, a generator
+    # with PixelUnshuffle in front, and the generator's inference plan with its rotating dense-block buffers
+    "bsrgantrans_x2": _bsrgantrans,
+    "transformer_encoder": _transformer_encoder,
+    "realesrgan_x2_module": _realesrgan_x2,
+    "generator_inference_rrdb2": _trunk_inference,
 }
 CASES = ["%s-%s" % (s, d) for s in SCENARIOS for d in DTYPES]
 
@@ -284,13 +386,14 @@ class Brackets:
         fn()
 
 
-def record(case, profiled=False):
+def record(case, profiled=False, buffers=False):
     """run one scenario under the recorder: {"launches": [...], "queries": [...], "tables": [...]}; ``profiled``: with
-    profiling.REC set -- the label queries are left out of the launches, and "brackets" holds [label, flop, bytes] per bracket"""
+    profiling.REC set -- the label queries are left out of the launches, and "brackets" holds [label, flop, bytes] per bracket;
+    ``buffers``: "buffers" holds, per launch, the entries of the plan-held buffers (module docstring)"""
     from sr_gan_fd_amd import _abi as A, ops, profiling
     name, dt = case.rsplit("-", 1)
     A.set_dry_run(True)
-    rec = Recorder(A.lib())
+    rec = Recorder(A.lib(), buffers)
     ops._DC_WS.clear()                 # the process-wide dense-chain workspace: its size query belongs to the scenario that plans the first chain
     A._lib = rec
     assert profiling.REC is None
@@ -300,6 +403,8 @@ def record(case, profiled=False):
         torch.manual_seed(0)
         keep = SCENARIOS[name](DTYPES[dt])
         out = {"launches": rec.launches, "queries": rec.queries, "tables": rec.tables()}
+        if buffers:
+            out["buffers"] = rec.buffers
         if profiled:
             out["launches"] = [c for c in rec.launches if c[0] != "srganfd_conv2d_describe"]
             out["brackets"] = profiling.REC.items
@@ -341,10 +446,27 @@ def compare(case, want, got):
     return None
 
 
+def compare_buffers(case, want, got):
+    """None, or the description of the first launch whose plan-held buffers differ"""
+    for i, (a, b) in enumerate(zip(want, got["buffers"])):
+        if a != b:
+            return "%s: call %d (%s) takes other plan buffers: recorded %s, now %s" % (case, i, got["launches"][i][0], json.dumps(a), json.dumps(b))
+    if len(want) != len(got["buffers"]):
+        return "%s: buffers of %d calls recorded, %d calls now" % (case, len(want), len(got["buffers"]))
+    return None
+
+
 @pytest.fixture(scope="module")
 def recorded():
     with gzip.open(FIXTURE, "rt") as f:
         return json.load(f)
+
+
+@pytest.fixture(scope="module")
+def now():
+    """case -> its record with the plan-held buffers: each case runs once for the trace test and the buffer test"""
+    done = {}
+    return lambda case: done[case] if case in done else done.setdefault(case, record(case, buffers=True))
 
 
 def test_fixture_covers_every_case(recorded):
@@ -354,8 +476,28 @@ def test_fixture_covers_every_case(recorded):
 
 
 @pytest.mark.parametrize("case", CASES)
-def test_launch_trace_matches_the_recorded_one(case, recorded):
-    msg = compare(case, recorded[case], record(case))
+def test_launch_trace_matches_the_recorded_one(case, recorded, now):
+    msg = compare(case, recorded[case], now(case))
+    assert msg is None, msg
+
+
+@pytest.fixture(scope="module")
+def recorded_buffers():
+    with gzip.open(BUFFERS, "rt") as f:
+        return json.load(f)
+
+
+def test_buffer_fixture_covers_every_case(recorded, recorded_buffers):
+    assert sorted(recorded_buffers) == sorted(CASES)
+    assert all(len(recorded_buffers[c]) == len(recorded[c]["launches"]) for c in CASES)
+    names = [e for rows in recorded_buffers.values() for row in rows for e in row]
+    assert len(names) > 20000 and sum(e != "p" for e in names) > 0.8 * len(names)
+    assert os.path.getsize(BUFFERS) < 1 << 16
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_launches_take_the_recorded_plan_buffers(case, recorded_buffers, now):
+    msg = compare_buffers(case, recorded_buffers[case], now(case))
     assert msg is None, msg
 
 
